@@ -22,16 +22,25 @@ device memory, copies and waits go through libmtscomp_hip.so (mts_dev_alloc / mt
 process, whatever the import order.  `--dist-backend nccl` additionally brings up an RCCL group (init + one all-reduce outside
 the timed region, under a watchdog that exits non-zero if it hangs); the size exchange stays on the host group.
 
-The JSON line carries, next to the contract's keys:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints the line.
+The JSON line carries, next to the contract's keys, what the timed steps themselves give (the library's per-stage event times):
   roofline             the dominant kernel (k_match5): algorithmic bytes (R + C of the batch) / its launch time
   roofline_compress    (R + C) / time of the whole compress direction, roofline_decompress likewise (C + R)
+Everything else runs after the timed region with --full only:
+  byte_identical_chunk0  the device round trip of every rank checked, chunk 0 against zlib level 6 (null without --full)
+  level_curve          --config stress: levels 1 and 9 beside the timed level 6
   cpu_baseline         the reference's ThreadPool path restated (numpy + stdlib zlib: the oracle) on ALL host cores and on 1
   byte_identical_chunks  how many of the recording's chunks are byte for byte what that CPU path produced (+ the .cbin sha1s)
-  extras (N = 1 only, after the timed region; --no-extras skips them)
+  extras (after the timed region; --no-extras skips them)
     file_to_file       the drop-in calls compress() / decompress(out=...) on the 60 s recording as a file on tmpfs (PCIe, SHA-1
                        and file I/O included; check_after_* off like the reference's benchmark.py:29,36), next to the CPU port's
     random_read        BASELINE configs[2]: a 600 s file, 1000 windows of 1 s at splitmix(i) starts through Reader[a:b]
     level_sweep        BASELINE configs[4] shape (1024 ch, 0.25 s chunks) at levels 1, 2, 3, 6, 9: ratio and GB/s
+    in_process_multi_gpu  (N > 1) HipCodec over all N devices from rank 0
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's shard when N > 1) as DIR/<name>.npy, float32 /
+float64, a fixed seeded sample where the whole would not fit in 64 MB (see dump_outputs): the inputs are the seeded synthetic
+recording, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -65,9 +74,14 @@ def parse_args(argv=None):
                    help='headline: 385 ch, 1 s chunks, level 6 (configs[1] / configs[3]); stress: BASELINE configs[4], 1024 ch, 0.25 s chunks, '
                         '600 s over the ranks, timed at level 6, levels 1 and 9 measured beside it')
     p.add_argument('--channels', type=int, default=0, help='default: 385 (headline), 1024 (stress)')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps also check the outputs (device round trip, chunk 0 against zlib) and measure what the headline '
+                        'does not need: the CPU baseline, level_curve (--config stress) and the extras')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write what the last timed step computed (compressed chunks, decompressed rows: seeded samples) as DIR/<name>.npy')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     p.add_argument('--cpu-chunks', type=int, default=0, help='chunks in the all-cores CPU sample (default: one per host cpu)')
-    p.add_argument('--no-extras', action='store_true', help='skip the configs[2] / configs[4] measurements')
+    p.add_argument('--no-extras', action='store_true', help='with --full: skip the configs[2] / configs[4] measurements')
     p.add_argument('--extras-seconds', type=int, default=600, help='length of the random-read file (configs[2])')
     p.add_argument('--dist-backend', default='gloo', choices=('nccl', 'gloo'),
                    help='gloo (default): the host-side size exchange is the path\'s only exchange; nccl: also bring up an RCCL group (init check)')
@@ -76,6 +90,8 @@ def parse_args(argv=None):
                    help='let ranks share devices (rank -> device rank mod visible): smoke test of the N > 1 path on fewer GPUs, not a measurement')
     p.add_argument('--master-port', type=int, default=0, help='rendezvous port of the self-launched ranks (default: a free one)')
     a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error('--steps must be at least 1 and --warmup at least 0')
     resolve_workload(a)
     return a
 
@@ -84,15 +100,16 @@ def resolve_workload(a):
     """Fills in what the flags left open: channels, rows per chunk, chunks per GPU and the sentence that names the workload.
     N = 1: BASELINE configs[1] (60 chunks).  N > 1: every rank owns what a rank of configs[3] owns on 8 GPUs (450 chunks: at N = 8
     the job IS configs[3], 3600 s; at N = 2 / 4 it is 900 / 1800 s: weak scaling, per-GPU work fixed).  --config stress: configs[4],
-    its 2400 chunks dealt over the ranks (one rank alone takes an 8-GPU rank's 300)."""
+    its 2400 chunks dealt over the ranks (one rank alone takes an 8-GPU rank's 300); with --full levels 1 and 9 are measured beside it."""
     n = max(a.gpus, 1)
     if a.config == 'stress':
         a.channels = a.channels or 1024
         a.chunk_rows = STRESS_ROWS
         a.n_chunks = a.seconds or (STRESS_CHUNKS // n if n > 1 else STRESS_CHUNKS // 8)
-        a.levels_beside = (1, 9)
+        a.levels_beside = (1, 9) if a.full else ()
         a.workload = ('%d ch @ 30 kHz, chunk = 0.25 s (%d samples), %d chunks per GPU (%d GPUs: %.0f s of the 600 s of BASELINE configs[4]), '
-                      'timed at zlib level 6; levels 1 and 9 beside it (level_curve)' % (a.channels, STRESS_ROWS, a.n_chunks, n, a.n_chunks * n * 0.25))
+                      'timed at zlib level 6%s' % (a.channels, STRESS_ROWS, a.n_chunks, n, a.n_chunks * n * 0.25,
+                                                   '; levels 1 and 9 beside it (level_curve)' if a.levels_beside else ''))
     else:
         a.channels = a.channels or 385
         a.chunk_rows = RATE
@@ -622,6 +639,57 @@ def extra_in_process_multi_gpu(hip, x, nc, n_dev):
             'path': 'HipCodec(devices=range(N)): host arrays in, bytes out, one host thread per GPU (rank 0 of the bench, the other ranks idle)'}
 
 
+DUMP_SEED = 1234                  # the sample positions of --dump-outputs: fixed, independent of what the build computed
+DUMP_VALUES = 1 << 21             # values per sampled array (8 MB of float32); the decompressed rows take twice that: < 40 MB in all
+
+
+def dump_outputs(out_dir, cbuf, slots, sizes, back, status, n_chunks, rate, nc):
+    """--dump-outputs: what the last timed step handed its caller -- every chunk's zlib stream (cbuf at slots, sizes) and the
+    decompressed recording (back) with its per-chunk status -- as .npy files under `out_dir`; bytes and int16 samples as float32
+    (exact), sizes, positions and status as float64 (exact).  The whole would be GBs, so the streams and rows are sampled at
+    positions drawn from DUMP_SEED alone (a stream's positions are fixed fractions of its length):
+      compressed_sizes     (n_chunks,)        bytes of every chunk's stream
+      compressed_head      (n_chunks, H)      its first H bytes (zlib header, first block header and code lengths), -1 past its end
+      compressed_tail      (n_chunks, T)      its last T bytes (end of the last block, adler32), -1 before its start
+      compressed_sample    (n_chunks, S)      the bytes at floor(u_j * size) for S seeded fractions u_j
+      decompressed_rows    (R,)               R seeded row indices into the shard's n_chunks * rate rows
+      decompressed_sample  (R, nc)            those rows of the decompressed recording
+      chunk_status         (n_chunks,)        the decompress call's status per chunk (0 = fine)
+    Returns the names written."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    per_chunk = max(1, DUMP_VALUES // n_chunks)
+    H, T, S = min(4096, per_chunk), min(64, per_chunk), min(16384, per_chunk)
+    rng = np.random.RandomState(DUMP_SEED)
+    frac = np.sort(rng.random_sample(S))
+    n_rows = n_chunks * rate
+    R = min(n_rows, 2 * DUMP_VALUES // nc)
+    rows = np.sort(rng.choice(n_rows, R, replace=False)) if R < n_rows else np.arange(n_rows)
+    head = np.full((n_chunks, H), -1, dtype=np.float32)
+    tail = np.full((n_chunks, T), -1, dtype=np.float32)
+    sample = np.zeros((n_chunks, S), dtype=np.float32)
+    dec = np.empty((R, nc), dtype=np.float32)
+    chunk_bytes = rate * nc * 2
+    for k in range(n_chunks):
+        n = int(sizes[k])
+        z = cbuf.download(int(slots[k]), n) if n else np.zeros(0, dtype=np.uint8)
+        head[k, :min(H, n)] = z[:H]
+        tail[k, T - min(T, n):] = z[n - min(T, n):]
+        sample[k] = z[np.minimum((frac * n).astype(np.int64), n - 1)] if n else -1
+        sel = np.nonzero((rows >= k * rate) & (rows < (k + 1) * rate))[0]
+        if sel.size:
+            x = back.download(k * chunk_bytes, chunk_bytes, np.int16).reshape(rate, nc)
+            dec[sel] = x[rows[sel] - k * rate]
+    arrays = {'compressed_sizes': np.asarray(sizes, dtype=np.float64), 'compressed_head': head, 'compressed_tail': tail,
+              'compressed_sample': sample, 'decompressed_rows': rows.astype(np.float64), 'decompressed_sample': dec,
+              'chunk_status': np.asarray(status, dtype=np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, 'the dumped outputs would take %d bytes' % total
+    for name, a in arrays.items():
+        np.save(out_dir / (name + '.npy'), a)
+    return sorted(arrays)
+
+
 def init_ranks(args, rank, world, dev):
     """The process groups of a multi-rank run, under a watchdog: a rendezvous or RCCL bring-up that does not finish within
     --init-timeout seconds ends this rank with a message and a non-zero status instead of hanging the node.
@@ -776,18 +844,24 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=host_group)
         elapsed, t_c, t_d = t.tolist()
 
-    # correctness of what was timed (outside the timed region): device round trip on every rank + oracle spot check
-    n_diff, first_diff = back.diff(raw)
-    assert n_diff == 0, 'round trip mismatch: %d bytes differ, the first at %d' % (n_diff, first_diff)
+    # what the last timed step computed, before anything after the timed region touches the buffers
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, cbuf, slots, sizes, back, status, n_chunks, rate, nc)
+
     csize_local = int(sizes.sum())
-    csize = int(offsets[-1]) if args.steps else csize_local
+    csize = int(offsets[-1])
     ok_oracle = None
-    if rank == 0:
-        from oracle import oracle as O
-        first = raw.download(0, chunk_bytes, np.int16).reshape(rate, nc)
-        z0 = cbuf.download(0, int(sizes[0])).tobytes()
-        ok_oracle = z0 == O.ref_compress_chunk(first)
-        assert ok_oracle, 'chunk 0 is not byte-identical to zlib level 6'
+    if args.full:
+        # correctness of what was timed (outside the timed region): device round trip on every rank + oracle spot check
+        n_diff, first_diff = back.diff(raw)
+        assert n_diff == 0, 'round trip mismatch: %d bytes differ, the first at %d' % (n_diff, first_diff)
+        if rank == 0:
+            from oracle import oracle as O
+            first = raw.download(0, chunk_bytes, np.int16).reshape(rate, nc)
+            z0 = cbuf.download(0, int(sizes[0])).tobytes()
+            ok_oracle = z0 == O.ref_compress_chunk(first)
+            assert ok_oracle, 'chunk 0 is not byte-identical to zlib level 6'
 
     # --config stress: levels 1 and 9 beside the timed level 6 (BASELINE configs[4]: "levels {1,6,9} sweep -- ratio vs GB/s curve"):
     # one warm-up and one timed pass per level on every rank, the slowest rank's time, the ratio over all ranks' chunks; after the
@@ -854,7 +928,7 @@ def main(argv=None):
             'metric': 'compress + decompress GB/s (raw int16)', 'value': total_raw / elapsed / 1e9, 'unit': 'GB/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_step,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'int16',
-            'data': 'synthetic',
+            'data': 'synthetic', 'full': bool(args.full), 'dumped_outputs': dumped,
             'config': {'workload': args.workload,
                        'n_channels': nc, 'chunks_per_gpu': n_chunks, 'chunk_rows': rate, 'chunk_bytes': chunk_bytes,
                        'sharding': 'chunk i -> rank i mod N (round robin), no collective on the data path; the compressed sizes are '
@@ -880,9 +954,11 @@ def main(argv=None):
         x_host = None
         cpu_chunks = None
         headline = args.config == 'headline'
-        if (not args.no_cpu_baseline or not args.no_extras) and world == 1 and headline:
+        cpu_leg = args.full and not args.no_cpu_baseline
+        extras_leg = args.full and not args.no_extras
+        if (cpu_leg or extras_leg) and world == 1 and headline:
             x_host = raw.download(dtype=np.int16).reshape(n_chunks * rate, nc)
-        if not args.no_cpu_baseline and world == 1 and headline:             # (the CPU comparison is taken once, at N = 1)
+        if cpu_leg and world == 1 and headline:             # (the CPU comparison is taken once, at N = 1)
             try:
                 res['cpu_baseline'], cpu_chunks = cpu_baseline(x_host, nc, n_chunks, args.cpu_chunks)
             except Exception as e:  # noqa: BLE001  -- the headline line must come out whatever happens here
@@ -898,7 +974,7 @@ def main(argv=None):
             res['cbin_sha1_cpu'] = hashlib.sha1(b''.join(cpu_chunks)).hexdigest()
             del host, mine_c
             assert all(same), 'chunks %s differ from zlib level 6' % [i for i, ok in enumerate(same) if not ok][:8]
-        if not args.no_extras and world == 1 and headline:
+        if extras_leg and world == 1 and headline:
             for b in (back, cbuf, raw):             # (room for the extras' buffers)
                 b.free()
             extras = {}
@@ -913,7 +989,7 @@ def main(argv=None):
                     extras[name] = {'error': repr(e)}
                 extras[name]['wall_s'] = time.perf_counter() - t1
             res['extras'] = extras
-        if not args.no_extras and world > 1 and not args.oversubscribe and headline:
+        if extras_leg and world > 1 and not args.oversubscribe and headline:
             t1 = time.perf_counter()
             try:
                 n_take = min(n_chunks, 64)                       # (host arrays through PCIe: a sample of the shard is enough to see every lane work)

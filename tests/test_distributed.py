@@ -64,9 +64,9 @@ def test_default_workloads_land_on_baseline_configs():
         assert owners == list(range(450 * n))
     a = bench.parse_args(['--gpus', '8'])
     assert 'configs[3]: 3600 s over 8 GPUs' in a.workload and a.n_chunks * 8 == 3600
-    a = bench.parse_args(['--gpus', '8', '--config', 'stress'])
+    a = bench.parse_args(['--gpus', '8', '--config', 'stress', '--full'])
     assert (a.n_chunks * 8, a.channels, a.chunk_rows, a.levels_beside) == (2400, 1024, 7500, (1, 9)) and 'configs[4]' in a.workload
     a = bench.parse_args(['--config', 'stress'])
-    assert (a.n_chunks, a.channels, a.chunk_rows) == (300, 1024, 7500)
+    assert (a.n_chunks, a.channels, a.chunk_rows, a.levels_beside) == (300, 1024, 7500, ())      # (a plain run times level 6 alone)
     a = bench.parse_args(['--gpus', '2', '--seconds', '2'])          # (the smoke test's size: flags still win)
     assert a.n_chunks == 2

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything profiles/ holds for one round, from a 1-GPU box:  tools/profile_round.sh r1
-#   <tag>_bench_default.jsonl      the default bench line
+#   <tag>_bench_default.jsonl      the bench line with --full (checks, CPU baseline, extras)
 #   <tag>_bench_kernel_stats.csv   rocprofv3 --kernel-trace --stats of the same command (per-kernel totals / averages)
 #   <tag>_bench_pmc_hbm_bytes.csv  FETCH_SIZE / WRITE_SIZE per kernel (two separate --pmc passes, no trace domains)
 #   <tag>_traffic.json             HBM bytes per launch of the dominant kernel, read by bench.py
@@ -12,7 +12,7 @@ out=$R/gpurun_out/profile_$tag
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 cd $R
-python3 bench.py > $out/${tag}_bench_default.jsonl 2> $out/bench_stderr.txt
+python3 bench.py --full > $out/${tag}_bench_default.jsonl 2> $out/bench_stderr.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --no-cpu-baseline --no-extras > $out/stats_stdout.txt 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 bench.py --no-cpu-baseline --no-extras --steps 1 --warmup 0 > $out/pmc_fetch_stdout.txt 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 bench.py --no-cpu-baseline --no-extras --steps 1 --warmup 0 > $out/pmc_write_stdout.txt 2>&1
