@@ -45,6 +45,7 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats / mts_dev_window_stats only; the codec does not care) */
 
 int mts_version(void);
 int mts_device_count(void);                 /* number of gfx950 devices visible; 0 if none */
@@ -146,6 +147,40 @@ int mts_cache_read_slices_leading(long cache_id, int n_chunks, const long *chunk
                                   int itemsize, int flags, int n_leading, int n_requests, const long *requests,
                                   void *out, const long *out_offsets, long out_bytes, int *chunk_status);
 
+/*
+ * Per-window, per-channel statistics of decoded chunks (an extension: the reference has no such call; its users reduce
+ * Reader[...] with numpy).  Only the results cross the bus.
+ *   windows        [row_begin + w * window_rows, min(row_begin + (w + 1) * window_rows, row_end)) for
+ *                  w < ceil((row_end - row_begin) / window_rows), in absolute file rows
+ *   chunks         chunk i holds file rows [chunk_row0[i], chunk_row0[i] + n_rows[i]); ascending, not overlapping, not
+ *                  necessarily adjacent (a lane of a multi-device caller gets every G-th chunk); every chunk must hold a row of
+ *                  [row_begin, row_end).  A call reduces the rows of its chunks only.
+ *   cols           n_cols >= 1 channel indices, any order, repeats allowed
+ *   flags          as everywhere; MTS_FLAG_FLOAT for float items, MTS_FLAG_UNSIGNED for unsigned integers (signed otherwise)
+ *   outputs        (n_windows, n_cols) C order:
+ *                    out_min / out_max  the item type; floats propagate NaN like np.min / np.max
+ *                    out_sum            int64 (x.astype(int64).sum(0), two's-complement wrap) for integers, double for floats
+ *                    out_sumsq          uint64 -- the EXACT sum of squares -- for 1- and 2-byte integers (windows of up to 2^31 rows);
+ *                                       double accumulation for 4/8-byte integers and floats.  A caller combining several calls
+ *                                       adds the uint64 sums and converts once.
+ *                    out_count          (n_windows) rows of the window held by the chunks that decoded
+ *                  A window with no row in these chunks gets the identities: type max / +inf, type min / -inf, 0, 0, count 0.
+ *                  Nothing is atomic: the double sums are the same from run to run.
+ *   chunk_status   MTS_CHUNK_* per chunk as in mts_decompress_chunks; the rows of a failed chunk count nowhere
+ * mts_window_stats: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated (whole chunks, adler32 checked) and
+ * reduced piece by piece in a transient workspace, the compressed bytes of the next piece crossing the bus beside the kernels; they
+ * are NOT inserted into the cache.  Outputs are host memory.
+ * mts_dev_window_stats: device d_cdata and d_* outputs on `device`, count and chunk_status on the host; no cache.
+ * MTS_E_ARG before anything is launched: window_rows < 1, n_cols < 1, a column outside [0, n_channels), chunks out of order or
+ * outside the range, an empty chunk, or a window of more than 2^31 rows on the exact (1/2-byte integer) path.
+ */
+int mts_window_stats(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0,
+                     const unsigned char *cdata, const long *c_offsets, const long *c_lengths, const long *n_rows,
+                     int n_channels, int itemsize, int flags, long row_begin, long row_end, long window_rows, int n_cols,
+                     const int *cols, void *out_min, void *out_max, void *out_sum, void *out_sumsq, long *out_count,
+                     int *chunk_status);
+
 /* ---------------------------------------------------------------------------------------------
  * Device-resident variants (inputs and outputs already in HBM; used by bench.py and by callers that
  * keep recordings on the GPU).  Pointers are device pointers on `device`; `stream` is a hipStream_t
@@ -159,6 +194,11 @@ int mts_dev_decompress_chunks(int device, void *stream, const unsigned char *d_c
                               const long *c_offsets, const long *c_lengths, const long *n_rows,
                               int n_chunks, int n_channels, int itemsize, int flags, void *d_out,
                               const long *out_offsets, int *chunk_status /* host */);
+int mts_dev_window_stats(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets,
+                         const long *c_lengths, const long *chunk_row0, const long *n_rows, int n_chunks,
+                         int n_channels, int itemsize, int flags, long row_begin, long row_end, long window_rows,
+                         int n_cols, const int *cols, void *d_min, void *d_max, void *d_sum, void *d_sumsq,
+                         long *count /* host */, int *chunk_status /* host */);
 /* integer-exact synthetic recording, rows [t0, t1) of n_channels int16, on device */
 int mts_dev_synth_int16(int device, void *stream, void *d_out, long t0, long t1, int n_channels,
                         long seed);

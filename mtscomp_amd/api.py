@@ -61,6 +61,8 @@ DEVICE_CACHE_MAX_CHUNKS = 8     # longer slices are streamed through the host pa
 READ_AHEAD_MAX = int(os.environ.get('MTSCOMP_READ_AHEAD', 4))   # chunks a cold slice may decode ahead of itself into the device cache (0 = off)
 MAP_CDATA = os.environ.get('MTSCOMP_MAP_CDATA', '1') not in ('', '0')      # slices read their compressed bytes out of a mapping of the .cbin (0: preadv into page-locked memory)
 PREAD_THREADS = int(os.environ.get('MTSCOMP_PREAD_THREADS', 8))      # threads that read the compressed bytes of a slice's missing chunks (a few MB and more)
+WINDOW_STATS_CALL_BYTES = 1 << 30      # Reader.window_stats: compressed bytes per device call (a longer range is split on chunk boundaries)
+WINDOW_STATS_SLAB_BYTES = 1 << 30      # ... and partial results per call on the device (one per column and tile of <= 512 rows of a window)
 
 logger = logging.getLogger('mtscomp_amd')
 logger.setLevel(logging.INFO)
@@ -252,6 +254,16 @@ class HipCodec:
     host_buffer = staticmethod(hip.HostBuffer)
     host_buffer_take = staticmethod(hip.pinned_pool.take)
     host_buffer_give = staticmethod(hip.pinned_pool.give)
+
+    def window_stats(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols,
+                     lane=None):
+        """Per-window statistics of the chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])) on one device (`lane` modulo the
+        devices, default the first): mts_window_stats.  cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0
+        are read there.  -> (status list, dict min/max/sum/sumsq/count): the partials of these chunks, identities for windows they
+        do not touch (Reader.window_stats combines the lanes)."""
+        device = self.devices[(lane or 0) % len(self.devices)]
+        return hip.window_stats(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end,
+                                window_rows, cols, device=device)
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1075,6 +1087,134 @@ class Reader:
                 if e.code != hip.E_MISS or attempt:
                     raise
                 present = [False] * len(keys)                  # dropped since the query (or a prefix fell short): send everything
+
+    # -- per-window statistics on the device (an extension: the reference's users reduce Reader[...] with numpy)
+    def _stats_channels(self, channels):
+        """(column indices as an int array, squeeze) for an int, a slice with step >= 1 or a 1-D sequence of ints."""
+        nc = self.n_channels
+        if isinstance(channels, (int, np.integer)):
+            c = int(channels)
+            if not -nc <= c < nc:
+                raise IndexError("channel %d is out of bounds for %d channels" % (c, nc))
+            return np.array([c % nc], dtype=np.int64), True
+        if isinstance(channels, slice):
+            c0, c1, cs = channels.indices(nc)
+            if cs < 1:
+                raise ValueError("window_stats: a channel slice needs a step >= 1")
+            return np.arange(c0, c1, cs, dtype=np.int64), False
+        cols = np.asarray(channels)
+        if cols.ndim != 1 or (cols.size and cols.dtype.kind not in 'iu'):
+            raise IndexError("window_stats: channels must be an int, a slice or a 1-D sequence of ints")
+        cols = cols.astype(np.int64)
+        if cols.size and (cols.min() < -nc or cols.max() >= nc):
+            raise IndexError("channel index out of bounds for %d channels" % nc)
+        return cols % nc if cols.size else cols, False
+
+    def window_stats(self, window, start=0, stop=None, channels=slice(None)):
+        """Per-window, per-channel statistics of rows [start, stop) computed on the device: only the results cross the bus.
+        Windows are [start + w * window, min(start + (w + 1) * window, stop)); window=None is one window over the range.
+        start / stop follow Reader[...] (None, negative, clipped).  channels: an int (the arrays are then 1-D), a slice with
+        step >= 1, or a sequence of ints.  Returns a Bunch: count (n_windows,) int64; min, max in the recording's dtype (NaN
+        propagates like np.min / np.max); sum (int64 with numpy's wrap for integers, float64 for floats); sumsq (float64; exact
+        for 1/2-byte integers); mean = sum / count and rms = sqrt(sumsq / count) in float64; start, stop, window, channels.
+        Chunks resident in the device cache are read where they lie; the others are decoded in a transient workspace and NOT
+        kept.  A damaged chunk raises the IOError of Reader[...]."""
+        if not callable(getattr(self.codec, 'window_stats', None)):
+            raise NotImplementedError("window_stats needs a codec that reduces on the device (HipCodec); %r has none"
+                                      % getattr(self.codec, 'name', self.codec))
+        i0 = self._validate_index(start, 0)
+        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        if window is None:
+            window = max(i1 - i0, 1)
+        if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1:
+            raise ValueError("window must be an int >= 1 or None, got %r" % (window,))
+        window = int(window)
+        cols, squeeze = self._stats_channels(channels)
+        n_win = -(-(i1 - i0) // window)
+        t_dt, s_dt, q_dt = hip.stats_dtypes(self.dtype)
+        shape = (n_win, cols.size)
+        fi = np.finfo if self.dtype.kind == 'f' else np.iinfo
+        mn = np.full(shape, np.inf if self.dtype.kind == 'f' else fi(self.dtype).max, dtype=t_dt)
+        mx = np.full(shape, -np.inf if self.dtype.kind == 'f' else fi(self.dtype).min, dtype=t_dt)
+        sm, sq, cnt = np.zeros(shape, s_dt), np.zeros(shape, q_dt), np.zeros(n_win, np.int64)
+        first = bisect.bisect_right(self.chunk_bounds, i0) - 1
+        last = bisect.bisect_left(self.chunk_bounds, i1) - 1
+        chunks = [k for k in range(max(first, 0), min(last, self.n_chunks - 1) + 1)
+                  if self.chunk_bounds[k + 1] > max(i0, self.chunk_bounds[k]) and self.chunk_bounds[k] < i1] if n_win and cols.size else []
+        # calls: runs of chunks whose compressed bytes and partial results fit one device call
+        calls, run, nbytes, slab = [], [], 0, 0
+        tile_rows = min(window, 512)
+        for k in chunks:
+            b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
+            t = (-(-(self.chunk_bounds[k + 1] - self.chunk_bounds[k]) // tile_rows) + 1) * cols.size * 32
+            if run and (nbytes + b > WINDOW_STATS_CALL_BYTES or slab + t > WINDOW_STATS_SLAB_BYTES):
+                calls.append(run)
+                run, nbytes, slab = [], 0, 0
+            run.append(k)
+            nbytes, slab = nbytes + b, slab + t
+        if run:
+            calls.append(run)
+        lanes = self._n_lanes()
+        use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
+        status = {}
+        for run in calls:
+            lo, hi = max(i0, self.chunk_bounds[run[0]]), min(i1, self.chunk_bounds[run[-1] + 1])
+            w0, w1 = (lo - i0) // window, -(-(hi - i0) // window)
+            rb, re = i0 + w0 * window, min(i1, i0 + w1 * window)
+            owners = sorted({k % lanes for k in run})
+            parts = [None] * len(owners)
+
+            def one(j, run=run, rb=rb, re=re, owners=owners, parts=parts):
+                g = owners[j]
+                keys = [k for k in run if k % lanes == g]
+                cache = self._cache_for(g) if use_cache else 0
+                st, res = self._lane_window_stats(cache, keys, rb, re, window, cols, g)
+                parts[j] = (keys, st, res)
+            self.codec.run_lanes(one, len(owners))
+            for keys, st, res in parts:                             # lanes in order: the float sums are the same every time
+                status.update(zip(keys, st))
+                sl = slice(w0, w1)
+                mn[sl] = np.minimum(mn[sl], res['min'])
+                mx[sl] = np.maximum(mx[sl], res['max'])
+                sm[sl] += res['sum']
+                sq[sl] += res['sumsq']
+                cnt[sl] += res['count']
+        self._raise_for(status)
+        if not cols.size:                                           # (no columns: nothing to read, the rows are counted here)
+            cnt[:] = np.minimum(window, i1 - i0 - window * np.arange(n_win))
+        sumsq = sq.astype(np.float64)                               # (the exact sums of squares: converted once, here)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            mean = sm.astype(np.float64) / cnt[:, None]
+            rms = np.sqrt(sumsq / cnt[:, None])
+        out = Bunch(count=cnt, min=mn, max=mx, sum=sm, sumsq=sumsq, mean=mean, rms=rms, start=i0, stop=i1, window=window, channels=cols)
+        if squeeze:
+            for key in ('min', 'max', 'sum', 'sumsq', 'mean', 'rms'):
+                out[key] = out[key][:, 0]
+        return out
+
+    def _lane_window_stats(self, cache, keys, row_begin, row_end, window, cols, lane):
+        """One codec.window_stats call for the chunks `keys` of one lane: chunks resident in its cache go without bytes, the
+        others' compressed bytes come from a mapping of the file (or one read); sent whole once more if an entry was dropped
+        between the query and the call.  -> (status list, partials)."""
+        row0 = [self.chunk_bounds[k] for k in keys]
+        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
+        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
+        for attempt in range(2):
+            need = [k for k, p in zip(keys, present) if not p]
+            base = self.chunk_offsets[need[0]] if need else 0
+            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
+            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
+            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
+            buf = self._map_range(nbytes, base) if need else b''
+            if buf is None:
+                buf = self._pread(nbytes, base)
+            try:
+                return self.codec.window_stats(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(),
+                                               row_begin, row_end, window, cols, lane=lane)
+            except hip.HipError as e:
+                if e.code != hip.E_MISS or attempt:
+                    raise
+                present = [False] * len(keys)                       # dropped since the query: send everything
 
     def _read_range(self, b0, b1):
         """The compressed bytes of chunks b0 .. b1-1 in one read."""

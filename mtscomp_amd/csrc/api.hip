@@ -143,6 +143,8 @@ struct Engine {
     } stg[2];                                            // [0]: host -> device, [1]: device -> host
     // inflate workspace
     DBuf inf_scratch, inf_desc, segsums;
+    // window statistics: tile descriptors, the partial slab, the outputs of the host entry point
+    DBuf stats;
     // geometry of the last compress batch whose per-segment / per-block / per-tile descriptors are on the device (a recording is
     // compressed batch after batch of the same shape: the 10 MB of index arrays need not be rebuilt and copied every call)
     // (valid while the three buffers are the allocations the arrays were copied into: DBuf::gen, not the address -- a buffer
@@ -192,7 +194,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();
@@ -1620,6 +1622,245 @@ int mts_debug_inflate(int device, const unsigned char *zbytes, long zlen, unsign
     if (rc) return rc;
     if (out_len) *out_len = *status == MTS_CHUNK_OK ? out_cap : 0;
     return MTS_OK;
+}
+
+// ---- per-window statistics (mts_window_stats, mts_dev_window_stats) ---------------------------------
+// The rows of every (chunk ∩ window) segment are cut into tiles of STAT_TILE_ROWS rows, in row order (stats.hip).  Resident chunks
+// are reduced first, where they lie; the others piece by piece (pipe_pieces): inflate into the piece workspace (E.h_out), reduce,
+// and the next piece's compressed bytes cross the bus on a helper thread meanwhile.  One combine launch at the end.
+static int window_stats_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device,
+                            const long *c_off, const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz,
+                            int flags, long row_begin, long row_end, long window_rows, int n_cols, const int *cols, void *o_min,
+                            void *o_max, void *o_sum, void *o_sq, bool out_on_host, long *count, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
+    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    if (nc <= 0 || n_chunks < 0 || n_cols < 1 || !cols) { set_error("window stats: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
+    if (window_rows < 1) { set_error("window_rows %ld < 1", window_rows); return MTS_E_ARG; }
+    if (row_begin < 0 || row_end < row_begin) { set_error("row range [%ld, %ld) invalid", row_begin, row_end); return MTS_E_ARG; }
+    for (int j = 0; j < n_cols; j++)
+        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
+    const bool exact = !(flags & MTS_FLAG_FLOAT) && sz <= 2;
+    const long span = row_end - row_begin;
+    if (exact && (window_rows < span ? window_rows : span) > (1l << 31)) { set_error("windows of more than 2^31 rows on the exact path"); return MTS_E_ARG; }
+    for (int i = 0; i < n_chunks; i++) {
+        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
+        if (i && row0[i] < row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: rows out of order or overlapping", i); return MTS_E_ARG; }
+        if (row0[i] >= row_end || row0[i] + n_rows[i] <= row_begin) { set_error("chunk %d holds no row of [%ld, %ld)", i, row_begin, row_end); return MTS_E_ARG; }
+        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
+        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
+    }
+    const long n_win = (span + window_rows - 1) / window_rows;
+    if (n_win && (!o_min || !o_max || !o_sum || !o_sq || !count)) return MTS_E_ARG;
+    for (long w = 0; w < n_win; w++) count[w] = 0;
+    if (n_win == 0) return MTS_OK;                           // (no chunk can hold a row of an empty range: n_chunks is 0)
+
+    // ---- tiles, in row order; the tiles of window w are [win_tiles[w], win_tiles[w + 1])
+    std::vector<StatTile> tiles;
+    std::vector<long> tile_win, chunk_tile0(n_chunks + 1);
+    for (int i = 0; i < n_chunks; i++) {
+        chunk_tile0[i] = (long)tiles.size();
+        const long a = row0[i] > row_begin ? row0[i] : row_begin, b = row0[i] + n_rows[i] < row_end ? row0[i] + n_rows[i] : row_end;
+        for (long r = a; r < b;) {
+            const long w = (r - row_begin) / window_rows, wend = row_begin + (w + 1) * window_rows, e = b < wend ? b : wend;
+            for (long q = r; q < e; q += STAT_TILE_ROWS) {
+                StatTile t;
+                t.base = nullptr; t.row_lo = q - row0[i]; t.n_rows = (e - q) < STAT_TILE_ROWS ? (e - q) : STAT_TILE_ROWS; t.chunk = i; t.pad = 0;
+                tiles.push_back(t);
+                tile_win.push_back(w);
+            }
+            r = e;
+        }
+    }
+    chunk_tile0[n_chunks] = (long)tiles.size();
+    const long n_tiles = (long)tiles.size();
+    std::vector<long> win_tiles(n_win + 1, 0);
+    for (long t = 0; t < n_tiles; t++) win_tiles[tile_win[t] + 1]++;
+    for (long w = 0; w < n_win; w++) win_tiles[w + 1] += win_tiles[w];
+
+    // ---- which chunks are resident (whole rows), which are decoded here, in which pieces
+    auto entry_of = [&](int i) -> const CacheEntry * {
+        if (!cache) return nullptr;
+        auto it = cache->map.find(keys[i]);
+        if (it == cache->map.end()) return nullptr;
+        const CacheEntry &e = it->second;
+        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
+    };
+    std::vector<int> miss;
+    for (int i = 0; i < n_chunks; i++) {
+        if (entry_of(i)) continue;
+        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+        miss.push_back(i);
+    }
+    const int m = (int)miss.size();
+    const u64 row_bytes = (u64)nc * sz;
+    std::vector<long> mrows(m), mcoff(m), mclen(m), mooff(m);
+    for (int k = 0; k < m; k++) { mrows[k] = n_rows[miss[k]]; mclen[k] = c_len[miss[k]]; }
+    // (device input: nothing to copy beside the kernels -- one piece, one decode batch; smaller batches inflate slower)
+    const std::vector<int> pb = cdata_on_device ? std::vector<int>{0, m} : pipe_pieces(mrows.data(), false, m, row_bytes);
+    const int np = (int)pb.size() - 1;
+    u64 piece_cap = 0;
+    for (int k = 0; k < np; k++) {
+        u64 o = 0;
+        for (int q = pb[k]; q < pb[k + 1]; q++) { mooff[q] = (long)o; o += align_up((u64)mrows[q] * row_bytes, 256); }
+        if (o > piece_cap) piece_cap = o;
+    }
+    u64 ctot = 0;
+    if (!cdata_on_device) {
+        // (chunks that lie back to back in the caller's buffer keep their distances: one staged copy per run)
+        for (int k = 0; k < m; k++) {
+            const int i = miss[k];
+            const bool joins = k > 0 && c_off[i] == c_off[miss[k - 1]] + mclen[k - 1];
+            if (!joins) ctot = align_up(ctot + (k ? 16 : 0), 16);
+            mcoff[k] = (long)ctot; ctot += (u64)mclen[k];
+        }
+        ctot += 16;
+    } else {
+        for (int k = 0; k < m; k++) mcoff[k] = c_off[miss[k]];
+    }
+
+    // ---- workspace: every allocation of the call comes BEFORE the resident entries are looked at (a workspace allocation that
+    //      fails drops this device's decoded chunks, DBuf::ensure)
+    const u64 plane = (u64)n_tiles * n_cols * 8;
+    const size_t o_tiles = 0, o_ids = align_up(sizeof(StatTile) * (n_tiles + 1), 256), o_ok = o_ids + align_up(4 * (u64)(n_tiles + 1), 256),
+                 o_cols = o_ok + align_up(4 * (u64)(n_chunks + 1), 256), o_wt = o_cols + align_up(4 * (u64)n_cols, 256),
+                 o_slab = o_wt + align_up(8 * (u64)(n_win + 1), 256), o_out = o_slab + align_up(4 * plane, 256);
+    const u64 n_items = (u64)n_win * n_cols;
+    const size_t o_omin = o_out, o_omax = o_omin + align_up(n_items * sz, 256), o_osum = o_omax + align_up(n_items * sz, 256),
+                 o_osq = o_osum + align_up(n_items * 8, 256), o_end = out_on_host ? o_osq + align_up(n_items * 8, 256) : o_out;
+    int rc;
+    if ((rc = E.stats.ensure(o_end + 256))) return rc;
+    if (m && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
+    if (m && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
+    if (cache) {
+        for (int i = 0; i < n_chunks; i++)                   // (the allocations above may have emptied the cache)
+            if (c_len[i] == 0 && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+    }
+    u8 *ws = E.stats.as<u8>();
+    StatTile *d_tiles = (StatTile *)(ws + o_tiles);
+    int *d_ids = (int *)(ws + o_ids), *d_ok = (int *)(ws + o_ok), *d_cols = (int *)(ws + o_cols);
+    long *d_wt = (long *)(ws + o_wt);
+    u8 *d_slab = ws + o_slab;
+    // tile pointers and the order of the launches: resident chunks first, then piece after piece
+    std::vector<int> ok(n_chunks + 1, 0), ids;
+    std::vector<long> launch0;                               // [0]: the resident tiles, [1 + k]: piece k's
+    std::vector<char> decoded(n_chunks, 0);
+    for (int k = 0; k < m; k++) decoded[miss[k]] = 1;
+    launch0.push_back(0);
+    for (int i = 0; i < n_chunks; i++) {
+        if (decoded[i]) continue;
+        const CacheEntry *e = entry_of(i);
+        for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = e->d; ids.push_back((int)t); }
+        ok[i] = 1;
+        status[i] = MTS_CHUNK_OK;
+    }
+    for (int k = 0; k < np; k++) {
+        launch0.push_back((long)ids.size());
+        for (int q = pb[k]; q < pb[k + 1]; q++) {
+            const int i = miss[q];
+            for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = E.h_out.as<u8>() + mooff[q]; ids.push_back((int)t); }
+        }
+    }
+    launch0.push_back((long)ids.size());
+    // (pageable sources: hipMemcpyAsync has staged them when it returns; the vectors live to the end of the call anyway)
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(StatTile) * n_tiles, hipMemcpyHostToDevice, st));
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_ids, ids.data(), 4 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_ok, ok.data(), 4 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_wt, win_tiles.data(), 8 * (size_t)(n_win + 1), hipMemcpyHostToDevice, st));
+    const int dflags = flags & ~MTS_FLAG_UNSIGNED;           // (the decoder compares the transform flags as a whole)
+    // resident chunks: reduced and waited for before any decode (whose workspace allocations could drop cache entries)
+    if (launch0[1] > 0) {
+        if ((rc = launch_stats_tiles(st, sz, flags, d_tiles, d_ids, (int)launch0[1], d_ok, d_cols, n_cols, nc, d_slab, n_tiles))) return rc;
+        MTS_HIP(hipStreamSynchronize(st));
+    }
+    // ---- the other chunks, piece by piece
+    const int dev = E.dev;
+    auto copy_in = [&](int k) -> int {
+        if (cdata_on_device) return MTS_OK;
+        MTS_HIP(hipSetDevice(dev));
+        for (int q = pb[k]; q < pb[k + 1];) {
+            int e = q + 1;
+            while (e < pb[k + 1] && c_off[miss[e]] == c_off[miss[e - 1]] + mclen[e - 1] && mcoff[e] == mcoff[e - 1] + mclen[e - 1]) e++;
+            u64 len = 0;
+            for (int z = q; z < e; z++) len += (u64)mclen[z];
+            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[q], cdata + c_off[miss[q]], (size_t)len); if (rc1) return rc1; }
+            q = e;
+        }
+        return MTS_OK;
+    };
+    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
+    std::vector<int> mst(m > 0 ? m : 1, MTS_CHUNK_CORRUPT);
+    if (np > 0 && m > 0 && (rc = copy_in(0))) return rc;
+    for (int k = 0; k < np && m > 0; k++) {
+        std::future<int> f_in;
+        if (k + 1 < np) f_in = copy_beside(copy_in, k + 1);
+        const int q0 = pb[k], nq = pb[k + 1] - pb[k];
+        rc = dev_decompress(E, st, d_src, mcoff.data() + q0, mclen.data() + q0, mrows.data() + q0, nq, nc, sz, dflags, E.h_out.as<u8>(),
+                            mooff.data() + q0, mst.data() + q0, 0, k > 0);
+        if (!rc) {
+            for (int q = q0; q < q0 + nq; q++) { status[miss[q]] = mst[q]; ok[miss[q]] = mst[q] == MTS_CHUNK_OK; }
+            hipError_t e = hipMemcpyAsync(d_ok, ok.data(), 4 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); rc = MTS_E_HIP; }
+        }
+        if (!rc) rc = launch_stats_tiles(st, sz, flags, d_tiles, d_ids + launch0[1 + k], (int)(launch0[2 + k] - launch0[1 + k]), d_ok, d_cols,
+                                         n_cols, nc, d_slab, n_tiles);
+        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;      // (always joined: it holds references to this frame)
+        if (rc || rc_in) return rc ? rc : rc_in;
+    }
+    // ---- windows: the tiles in order
+    void *c_min = out_on_host ? (void *)(ws + o_omin) : o_min, *c_max = out_on_host ? (void *)(ws + o_omax) : o_max;
+    void *c_sum = out_on_host ? (void *)(ws + o_osum) : o_sum, *c_sq = out_on_host ? (void *)(ws + o_osq) : o_sq;
+    if ((rc = launch_stats_combine(st, sz, flags, d_slab, n_tiles, d_wt, n_win, n_cols, c_min, c_max, c_sum, c_sq))) return rc;
+    if (out_on_host) {                                        // the results, and nothing else, cross the bus
+        MTS_HIP(hipMemcpyAsync(o_min, c_min, n_items * sz, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(o_max, c_max, n_items * sz, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(o_sum, c_sum, n_items * 8, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(o_sq, c_sq, n_items * 8, hipMemcpyDeviceToHost, st));
+    }
+    MTS_HIP(hipStreamSynchronize(st));
+    for (long t = 0; t < n_tiles; t++) if (ok[tiles[t].chunk]) count[tile_win[t]] += tiles[t].n_rows;
+    return MTS_OK;
+}
+
+int mts_window_stats(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                     const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
+                     long row_end, long window_rows, int n_cols, const int *cols, void *out_min, void *out_max, void *out_sum, void *out_sumsq,
+                     long *out_count, int *chunk_status)
+{
+    DevCache *c = nullptr;
+    if (cache_id) {
+        int cdev = 0;
+        c = find_cache(cache_id, &cdev);
+        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
+    }
+    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;      // (destroyed while this call waited for the engine)
+    MTS_HIP(hipSetDevice(E->dev));
+    return window_stats_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize,
+                            flags, row_begin, row_end, window_rows, n_cols, cols, out_min, out_max, out_sum, out_sumsq, true, out_count,
+                            chunk_status);
+}
+
+int mts_dev_window_stats(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                         const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin,
+                         long row_end, long window_rows, int n_cols, const int *cols, void *d_min, void *d_max, void *d_sum, void *d_sumsq,
+                         long *count, int *chunk_status)
+{
+    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    MTS_HIP(hipSetDevice(E->dev));
+    return window_stats_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
+                            n_channels, itemsize, flags, row_begin, row_end, window_rows, n_cols, cols, d_min, d_max, d_sum, d_sumsq, false,
+                            count, chunk_status);
 }
 
 // ---- debug taps ---------------------------------------------------------------------------------

@@ -148,6 +148,17 @@ struct GatherReq { long rb, rs, cb, cs, nr, ncol, out_off; };           // rows 
 int launch_gather_slices(hipStream_t st, const GatherChunk *d_chunks, int n_chunks, const GatherReq *d_req, int n_req, u64 max_items,
                          int n_channels, int itemsize, u8 *d_out);
 
+// stats.hip: per-window statistics of decoded chunks (mts_window_stats)
+constexpr int STAT_TILE_ROWS = 512;                                     // rows of a tile: one workgroup, one partial per column
+struct StatTile { const u8 *base; long row_lo, n_rows; int chunk, pad; };   // base: row 0 of the decoded chunk (n_channels items per row)
+// one partial per (tile, column) into the slab -- four planes of n_tiles * n_cols 8-byte entries: min, max, sum, sum of squares
+int launch_stats_tiles(hipStream_t st, int itemsize, int flags, const StatTile *d_tiles, const int *d_ids /* the tiles of this launch */,
+                       int n_launch, const int *d_ok /* per chunk: 0 = failed, its tiles are identities */, const int *d_cols, int n_cols,
+                       int n_channels, u8 *d_slab, long n_tiles);
+// windows w < n_windows: tiles [win_tiles[w], win_tiles[w + 1]) of the slab, in order, into the (n_windows, n_cols) outputs
+int launch_stats_combine(hipStream_t st, int itemsize, int flags, const u8 *d_slab, long n_tiles, const long *d_win_tiles, long n_windows,
+                         int n_cols, void *d_min, void *d_max, void *d_sum, void *d_sumsq);
+
 // deflate.hip
 size_t hash_sort_ws_bytes(int n_tiles);                            // the one-pass sort's per-tile records
 int launch_hash_sort(hipStream_t st, const u8 *d_stream, const TileDesc *d_tiles, int n_tiles, u32 *d_tmp, u32 *d_sorted,

@@ -22,6 +22,7 @@ FLAG_TIME_DIFF = 1
 FLAG_SPATIAL_DIFF = 2
 FLAG_ORDER_F = 4
 FLAG_FLOAT = 8
+FLAG_UNSIGNED = 16          # integer items are unsigned (window statistics only)
 
 CHUNK_OK = 0
 CHUNK_CORRUPT = -1
@@ -95,6 +96,10 @@ def lib():
                                         C.c_long, ip]
     L.mts_cache_read_slices_leading.argtypes = [C.c_long, C.c_int, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, lp, vp, lp,
                                                 C.c_long, ip]
+    L.mts_window_stats.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long,
+                                   C.c_long, C.c_int, ip, vp, vp, vp, vp, lp, ip]
+    L.mts_dev_window_stats.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
+                                       C.c_int, ip, vp, vp, vp, vp, lp, ip]
     L.mts_release.restype = None
     _lib = L
     return L
@@ -106,7 +111,8 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_host_alloc', 'mts_host_free', 'mts_dev_alloc', 'mts_dev_free', 'mts_dev_copy', 'mts_dev_sync', 'mts_dev_compare',
            'mts_last_stage_times', 'mts_debug_match_tables', 'mts_debug_tokens', 'mts_debug_deflate',
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
-           'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading']
+           'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
+           'mts_window_stats', 'mts_dev_window_stats']
 
 
 def _check(rc, what):
@@ -311,6 +317,80 @@ def cache_read_slices(cache_id, keys, cdata, offs, lens, n_rows, n_channels, dty
            'mts_cache_read_slices_leading')
     arrays = [out[int(o):int(o) + a * b * dtype.itemsize].view(dtype).reshape(a, b) for o, (a, b) in zip(out_offs, shapes)]
     return [int(x) for x in status[:n]], arrays
+
+
+# ------------------------------------------------------------------------------------------------
+# per-window statistics (an extension: the reference has no such call)
+# ------------------------------------------------------------------------------------------------
+def stats_flags(flags, dtype):
+    """flags as mts_window_stats wants them: the float bit and the unsigned bit come from the dtype."""
+    return _dflags(flags, dtype) | (FLAG_UNSIGNED if np.dtype(dtype).kind == 'u' else 0)
+
+
+def stats_exact(dtype):
+    """1- and 2-byte integers: the sum of squares is the exact uint64 sum (converted to float64 once, by the caller)."""
+    dtype = np.dtype(dtype)
+    return dtype.kind in 'iu' and dtype.itemsize <= 2
+
+
+def stats_dtypes(dtype):
+    """(min/max, sum, sumsq) dtypes of the partial results of one call."""
+    dtype = np.dtype(dtype)
+    return dtype, np.dtype(np.float64 if dtype.kind == 'f' else np.int64), np.dtype(np.uint64 if stats_exact(dtype) else np.float64)
+
+
+def _stats_outputs(n_windows, n_cols, dtype):
+    t, s, q = stats_dtypes(dtype)
+    shape = (int(n_windows), int(n_cols))
+    return np.empty(shape, t), np.empty(shape, t), np.empty(shape, s), np.empty(shape, q), np.zeros(max(int(n_windows), 1), np.int64)
+
+
+def _n_windows(row_begin, row_end, window_rows):
+    return max(0, -(-(int(row_end) - int(row_begin)) // int(window_rows))) if int(window_rows) >= 1 else 0
+
+
+def window_stats(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, device=0):
+    """mts_window_stats: per-window statistics of the chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])).  cache_id 0: no cache,
+    every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list,
+    Bunch-like dict min, max, sum, sumsq, count) -- the partials of these chunks: sumsq is uint64 for 1/2-byte integers."""
+    dtype = check_dtype(dtype)
+    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    n = int(rows.size)
+    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
+    assert not n or int((offs + lens).max()) <= cdata.size        # (only the chunks' own bytes are copied: no padding needed here)
+    nw = _n_windows(row_begin, row_end, window_rows)
+    mn, mx, sm, sq, cnt = _stats_outputs(nw, cols.size, dtype)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    _check(lib().mts_window_stats(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows),
+                                  int(n_channels), dtype.itemsize, stats_flags(flags, dtype), int(row_begin), int(row_end), int(window_rows),
+                                  int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)), _ptr(mn), _ptr(mx), _ptr(sm), _ptr(sq), _lp(cnt),
+                                  status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_window_stats')
+    return [int(x) for x in status[:n]], dict(min=mn, max=mx, sum=sm, sumsq=sq, count=cnt[:nw])
+
+
+def dev_window_stats(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, out=None):
+    """mts_dev_window_stats on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the four result arrays
+    (made when None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, dict of numpy
+    arrays as window_stats, out)."""
+    dtype = check_dtype(dtype)
+    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    nw = _n_windows(row_begin, row_end, window_rows)
+    mn, mx, sm, sq, cnt = _stats_outputs(nw, cols.size, dtype)
+    parts = [a.nbytes for a in (mn, mx, sm, sq)]
+    at = np.concatenate(([0], np.cumsum([(b + 255) // 256 * 256 for b in parts])))
+    if out is None or out.nbytes < int(at[-1]) + 256:
+        out = DevBuffer(int(at[-1]) + 256, device=cbuf.device)
+    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
+    _check(lib().mts_dev_window_stats(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
+                                      dtype.itemsize, stats_flags(flags, dtype), int(row_begin), int(row_end), int(window_rows), int(cols.size),
+                                      cols.ctypes.data_as(C.POINTER(C.c_int)), out.at(int(at[0])), out.at(int(at[1])), out.at(int(at[2])),
+                                      out.at(int(at[3])), _lp(cnt), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_window_stats')
+    for a, o in zip((mn, mx, sm, sq), at[:4]):
+        if a.nbytes:
+            _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(int(o)), a.nbytes, 1), 'mts_dev_copy')
+    return [int(x) for x in status[:rows.size]], dict(min=mn, max=mx, sum=sm, sumsq=sq, count=cnt[:nw]), out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,0 +1,131 @@
+"""Test-only helpers for Reader.window_stats: the numpy definition of the statistics, and a lane codec that restates
+mts_window_stats in numpy (so that the CPU suite drives the Python layer: argument handling, lanes, cache use, errors)."""
+import numpy as np
+
+from tests.codec_oracle import LaneOracleCodec
+
+
+def exact_sumsq(dtype):
+    dtype = np.dtype(dtype)
+    return dtype.kind in 'iu' and dtype.itemsize <= 2
+
+
+def _identity(n_windows, n_cols, dtype):
+    dtype = np.dtype(dtype)
+    shape = (n_windows, n_cols)
+    if dtype.kind == 'f':
+        mn, mx = np.full(shape, np.inf, dtype), np.full(shape, -np.inf, dtype)
+    else:
+        mn, mx = np.full(shape, np.iinfo(dtype).max, dtype), np.full(shape, np.iinfo(dtype).min, dtype)
+    s = np.zeros(shape, np.float64 if dtype.kind == 'f' else np.int64)
+    q = np.zeros(shape, np.uint64 if exact_sumsq(dtype) else np.float64)
+    return mn, mx, s, q
+
+
+def segment_stats(x):
+    """min, max, sum, sumsq of the rows of x (2-D) as the C ABI returns them (sumsq uint64 for 1/2-byte integers)."""
+    if x.dtype.kind == 'f':
+        return x.min(0), x.max(0), x.astype(np.float64).sum(0), (x.astype(np.float64) ** 2).sum(0)
+    s = x.astype(np.int64).sum(0)
+    if exact_sumsq(x.dtype):
+        return x.min(0), x.max(0), s, (x.astype(np.int64) ** 2).sum(0).astype(np.uint64)
+    return x.min(0), x.max(0), s, (x.astype(np.float64) ** 2).sum(0)
+
+
+def numpy_window_stats(arr, window, start, stop, cols):
+    """The contract: numpy over rows [start, stop) (already normalised) of the decoded array, columns `cols`.  `abssum`: the sum of
+    |x| per window and column, the scale of the float tolerance."""
+    cols = np.asarray(cols, dtype=np.int64)
+    x = arr[start:stop][:, cols]
+    n = stop - start
+    nw = -(-n // window) if n > 0 else 0
+    mn, mx, s, q = _identity(nw, cols.size, arr.dtype)
+    cnt = np.zeros(nw, np.int64)
+    abssum = np.zeros((nw, cols.size))
+    for w in range(nw):
+        seg = x[w * window:(w + 1) * window]
+        cnt[w] = seg.shape[0]
+        if cols.size:
+            mn[w], mx[w], s[w], q[w] = segment_stats(seg)
+            abssum[w] = np.abs(seg.astype(np.float64)).sum(0)
+    sumsq = q.astype(np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean = s.astype(np.float64) / cnt[:, None]
+        rms = np.sqrt(sumsq / cnt[:, None])
+    return dict(count=cnt, min=mn, max=mx, sum=s, sumsq=sumsq, mean=mean, rms=rms, abssum=abssum)
+
+
+def assert_stats_equal(got, want, dtype, squeeze=False):
+    """min / max exactly (NaN where numpy has NaN; -0.0 == 0.0); integer sums and means bit for bit, the sums of squares too for
+    1/2-byte integers; float64 accumulations within 1e-12 of the sum of |x| (resp. of x^2), NaN and +-inf where numpy has them."""
+    dtype = np.dtype(dtype)
+    assert got['count'].dtype == np.int64 and np.array_equal(got['count'], want['count'])
+    exact = {'min', 'max'} | ({'sum', 'mean'} if dtype.kind != 'f' else set()) | ({'sumsq', 'rms'} if exact_sumsq(dtype) else set())
+    cnt = np.maximum(want['count'], 1)[:, None]
+    scale = dict(sum=want['abssum'], mean=want['abssum'] / cnt, sumsq=want['sumsq'], rms=want['rms'])
+    for key in ('min', 'max', 'sum', 'sumsq', 'mean', 'rms'):
+        g, w = np.asarray(got[key]), np.asarray(want[key])
+        sc = scale.get(key)
+        if squeeze:
+            w, sc = w[:, 0], (sc[:, 0] if sc is not None else None)
+        assert g.shape == w.shape, (key, g.shape, w.shape)
+        want_dt = dtype if key in ('min', 'max') else np.int64 if key == 'sum' and dtype.kind != 'f' else np.float64
+        assert g.dtype == want_dt, (key, g.dtype, want_dt)
+        if key in exact:
+            assert np.array_equal(g, w, equal_nan=True), key
+            continue
+        assert np.array_equal(np.isnan(g), np.isnan(w)), key
+        inf = np.isinf(w)
+        assert np.array_equal(g[inf], w[inf]), key
+        fin = np.isfinite(w)
+        assert np.all(np.abs(g[fin] - w[fin]) <= 1e-12 * np.abs(sc[fin]) + 1e-300), key
+
+
+class StatsOracleCodec(LaneOracleCodec):
+    """LaneOracleCodec + window_stats restated in numpy: the partials of the given chunks (identities for windows they do not
+    touch), resident chunks read from the lane's cache dict (E_MISS when a chunk without bytes is not there), the others
+    decoded and NOT inserted.  Records (lane, keys, lens) of every call."""
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.stats_calls = []
+
+    def window_stats(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end,
+                     window_rows, cols, lane=None):
+        from mtscomp_amd import hip
+        dtype = np.dtype(dtype)
+        self.stats_calls.append((lane, [int(k) for k in keys], [int(n) for n in lens]))
+        cache = self.caches.get(cache_id, {}) if cache_id else {}
+        cols = np.asarray(cols, dtype=np.int64)
+        assert window_rows >= 1 and cols.size and (cols >= 0).all() and (cols < n_channels).all()
+        status, arrays = [], []
+        for k, o, n, nr in zip(keys, offs, lens, n_rows):
+            if not n:
+                if k not in cache:
+                    raise hip.HipError(hip.E_MISS, 'mts_window_stats', 'chunk key %d is not resident' % k)
+                status.append(0)
+                arrays.append(cache[k])
+                continue
+            st, arrs = super(LaneOracleCodec, self).decompress([bytes(memoryview(cdata)[o:o + n])], [nr], n_channels, dtype, flags)
+            self.calls.pop()
+            status.append(st[0])
+            arrays.append(arrs[0])
+        nw = -(-(row_end - row_begin) // window_rows) if row_end > row_begin else 0
+        mn, mx, s, q = _identity(nw, cols.size, dtype)
+        cnt = np.zeros(nw, np.int64)
+        for r0, nr, st, a in zip(row0, n_rows, status, arrays):
+            assert r0 < row_end and r0 + nr > row_begin
+            if st != 0:
+                continue
+            lo, hi = max(r0, row_begin), min(r0 + nr, row_end)
+            r = lo
+            while r < hi:
+                w = (r - row_begin) // window_rows
+                e = min(hi, row_begin + (w + 1) * window_rows)
+                a_mn, a_mx, a_s, a_q = segment_stats(a[r - r0:e - r0][:, cols])
+                mn[w], mx[w] = np.minimum(mn[w], a_mn), np.maximum(mx[w], a_mx)
+                s[w] += a_s
+                q[w] += a_q
+                cnt[w] += e - r
+                r = e
+        return status, dict(min=mn, max=mx, sum=s, sumsq=q, count=cnt)
