@@ -45,7 +45,8 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats / mts_dev_window_stats only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate and their device variants only; the codec does not care) */
+#define MTS_DECIMATE_MAX_TAPS 8192
 
 int mts_version(void);
 int mts_device_count(void);                 /* number of gfx950 devices visible; 0 if none */
@@ -181,6 +182,36 @@ int mts_window_stats(int device, long cache_id, int n_chunks, const long *chunk_
                      const int *cols, void *out_min, void *out_max, void *out_sum, void *out_sumsq, long *out_count,
                      int *chunk_status);
 
+/*
+ * FIR low-pass and decimation of decoded chunks (an extension: the reference has no such call; its users filter Reader[...] on
+ * the host, e.g. with scipy.signal.decimate).  Only the outputs cross the bus.
+ *   outputs        y[k, c] = sum_{j=0..n_taps-1} taps[j] * x[first_row + k * q - j, cols[c]] for k < n_out, in absolute file rows;
+ *                  x is 0 outside [valid_begin, valid_end).  (n_out, n_cols) C order, float (out_itemsize 4) or double (8).
+ *                  Items and taps are converted to that type with round-to-nearest; every output is acc = 0, then
+ *                  acc = acc + taps[j] * x for j = 0, 1, .. in that type, product and sum each rounded (no fused multiply-add):
+ *                  the same bits whatever the call, its pieces or the device.  Zero taps are not skipped (inf * 0 is NaN).
+ *   q, taps        q >= 1; 1 <= n_taps <= MTS_DECIMATE_MAX_TAPS finite doubles on the host, not normalised
+ *   chunks         chunk i holds file rows [chunk_row0[i], chunk_row0[i] + n_rows[i]); adjacent and ascending; together they
+ *                  must cover the rows the outputs read: [first_row - n_taps + 1, first_row + (n_out - 1) * q] ∩ [valid_begin,
+ *                  valid_end)
+ *   cols           n_cols >= 1 channel indices, any order, repeats allowed
+ *   flags          as everywhere; MTS_FLAG_FLOAT for float items, MTS_FLAG_UNSIGNED for unsigned integers (signed otherwise)
+ *   chunk_status   MTS_CHUNK_* per chunk as in mts_decompress_chunks; the outputs that read a failed chunk are undefined
+ * mts_decimate: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated (whole chunks, adler32 checked) piece
+ * by piece (MTS_PIPE_BYTES) in a transient workspace, the compressed bytes of the next piece crossing the bus beside the kernels;
+ * a chunk below a piece boundary that outputs of both pieces read is inflated in both.  They are NOT inserted into the cache.
+ * `out` is host memory.
+ * mts_dev_decimate: device d_cdata and d_out on `device`, chunk_status on the host; no cache.
+ * MTS_E_ARG before anything is launched: q < 1, n_taps outside [1, MTS_DECIMATE_MAX_TAPS], a tap that is not finite, out_itemsize
+ * not 4 or 8, n_cols < 1, a column outside [0, n_channels), chunks not adjacent or not covering the rows read, an empty chunk.
+ */
+int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0,
+                 const unsigned char *cdata, const long *c_offsets, const long *c_lengths, const long *n_rows,
+                 int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row, long n_out,
+                 int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols, void *out,
+                 int *chunk_status);
+
 /* ---------------------------------------------------------------------------------------------
  * Device-resident variants (inputs and outputs already in HBM; used by bench.py and by callers that
  * keep recordings on the GPU).  Pointers are device pointers on `device`; `stream` is a hipStream_t
@@ -199,6 +230,11 @@ int mts_dev_window_stats(int device, void *stream, const unsigned char *d_cdata,
                          int n_channels, int itemsize, int flags, long row_begin, long row_end, long window_rows,
                          int n_cols, const int *cols, void *d_min, void *d_max, void *d_sum, void *d_sumsq,
                          long *count /* host */, int *chunk_status /* host */);
+int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets,
+                     const long *c_lengths, const long *chunk_row0, const long *n_rows, int n_chunks,
+                     int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row,
+                     long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols,
+                     const int *cols, void *d_out, int *chunk_status /* host */);
 /* integer-exact synthetic recording, rows [t0, t1) of n_channels int16, on device */
 int mts_dev_synth_int16(int device, void *stream, void *d_out, long t0, long t1, int n_channels,
                         long seed);

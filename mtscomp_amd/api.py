@@ -63,6 +63,7 @@ MAP_CDATA = os.environ.get('MTSCOMP_MAP_CDATA', '1') not in ('', '0')      # sli
 PREAD_THREADS = int(os.environ.get('MTSCOMP_PREAD_THREADS', 8))      # threads that read the compressed bytes of a slice's missing chunks (a few MB and more)
 WINDOW_STATS_CALL_BYTES = 1 << 30      # Reader.window_stats: compressed bytes per device call (a longer range is split on chunk boundaries)
 WINDOW_STATS_SLAB_BYTES = 1 << 30      # ... and partial results per call on the device (one per column and tile of <= 512 rows of a window)
+DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per device call (a longer range is split at output-row boundaries)
 
 logger = logging.getLogger('mtscomp_amd')
 logger.setLevel(logging.INFO)
@@ -170,6 +171,19 @@ def _one_block(chunks):
     return np.concatenate(chunks, axis=0)
 
 
+def decimate_taps(q):
+    """scipy.signal.decimate's default FIR for factor q: firwin(20 * q + 1, 1 / q, window='hamming'), restated in numpy (a windowed
+    sinc with cutoff 1/q of Nyquist, scaled to unit gain at DC)."""
+    if not isinstance(q, (int, np.integer)) or isinstance(q, bool) or q < 2:
+        raise ValueError("decimate_taps needs an int q >= 2, got %r" % (q,))
+    n = 20 * int(q) + 1
+    f = 1.0 / int(q)
+    m = np.arange(n) - (n - 1) / 2.0
+    h = f * np.sinc(f * m)
+    h *= 0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(n) / (n - 1))
+    return h / h.sum()
+
+
 class HipCodec:
     """Per-chunk codec on MI355X.  ``devices``: list of device indices (default: all visible)."""
 
@@ -264,6 +278,15 @@ class HipCodec:
         device = self.devices[(lane or 0) % len(self.devices)]
         return hip.window_stats(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end,
                                 window_rows, cols, device=device)
+
+    def decimate(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row, n_out, q,
+                 taps, out_dtype, cols, lane=None):
+        """FIR + decimation of the adjacent chunks `keys` on one device (`lane` modulo the devices, default the first): mts_decimate.
+        cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0 are read there.  -> (status list, (n_out, n_cols)
+        out_dtype)."""
+        device = self.devices[(lane or 0) % len(self.devices)]
+        return hip.decimate(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row,
+                            n_out, q, taps, out_dtype, cols, device=device)
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1211,6 +1234,125 @@ class Reader:
             try:
                 return self.codec.window_stats(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(),
                                                row_begin, row_end, window, cols, lane=lane)
+            except hip.HipError as e:
+                if e.code != hip.E_MISS or attempt:
+                    raise
+                present = [False] * len(keys)                       # dropped since the query: send everything
+
+    # -- FIR low-pass + decimation on the device (an extension: the reference's users filter Reader[...] on the host)
+    def decimate(self, q, start=0, stop=None, channels=slice(None), taps=None, edge='zeros', dtype=np.float32):
+        """Low-pass filter rows [start, stop) along time and keep every q-th row, on the device: only the output crosses the bus.
+        y[k, c] = sum_{j < L} taps[j] * x[start + k * q + half - j, cols[c]] for k < ceil((stop - start) / q), half = (L - 1) // 2,
+        computed in `dtype` (float32 or float64): items and taps rounded to it, then acc = acc + taps[j] * x for j = 0 .. L-1 with
+        each product and sum rounded -- the same bits whatever the lanes, calls or pieces.  x is 0 outside [start, stop) for
+        edge='zeros' (scipy.signal.decimate(x, q, ftype='fir', zero_phase=True, axis=0) when taps is None; resample_poly(x, 1, q,
+        window=taps) otherwise) and outside the recording for edge='recording' (pieces then stitch: decimate(q, a, b) followed by
+        decimate(q, b, c) is decimate(q, a, c) when (b - a) % q == 0).  taps=None: decimate_taps(q) (q == 1 needs taps); 1 to 8192
+        finite taps, used as given.  start / stop follow Reader[...]; channels: an int (the result is then 1-D), a slice with step
+        >= 1, or a sequence of ints.  No IIR filters, no rational resampling, no other edge modes.  Chunks resident in the device
+        cache are read where they lie; the others are decoded in a transient workspace and NOT kept.  A damaged chunk in the
+        support raises the IOError of Reader[...]."""
+        if not callable(getattr(self.codec, 'decimate', None)):
+            raise NotImplementedError("decimate needs a codec that filters on the device (HipCodec); %r has none"
+                                      % getattr(self.codec, 'name', self.codec))
+        if not isinstance(q, (int, np.integer)) or isinstance(q, bool) or q < 1:
+            raise ValueError("q must be an int >= 1, got %r" % (q,))
+        q = int(q)
+        if taps is None:
+            if q == 1:
+                raise ValueError("decimate(1) needs explicit taps")
+            taps = decimate_taps(q)
+        taps = np.asarray(taps, dtype=np.float64)
+        if taps.ndim != 1 or not 1 <= taps.size <= hip.DECIMATE_MAX_TAPS or not np.isfinite(taps).all():
+            raise ValueError("taps must be a 1-D sequence of 1 to %d finite numbers" % hip.DECIMATE_MAX_TAPS)
+        try:
+            out_dtype = np.dtype(dtype)
+        except TypeError:
+            raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
+        if out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
+        if edge not in ('zeros', 'recording'):
+            raise ValueError("edge must be 'zeros' or 'recording', got %r" % (edge,))
+        i0 = self._validate_index(start, 0)
+        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        cols, squeeze = self._stats_channels(channels)
+        n_taps = int(taps.size)
+        n_out = -(-(i1 - i0) // q)
+        first_row = i0 + (n_taps - 1) // 2
+        vb, ve = (i0, i1) if edge == 'zeros' else (0, self.n_samples)
+        out = np.zeros((n_out, cols.size), out_dtype)
+        lo, hi = max(vb, first_row - (n_taps - 1)), min(ve, first_row + (n_out - 1) * q + 1)
+        if n_out and cols.size and lo < hi:
+            # calls: cut the outputs where the compressed bytes of the chunks their newest rows lie in pass DECIMATE_CALL_BYTES
+            first = bisect.bisect_right(self.chunk_bounds, lo) - 1
+            last = bisect.bisect_right(self.chunk_bounds, hi - 1) - 1
+            cuts, acc = [0], 0
+            for k in range(first, last + 1):
+                b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
+                if acc and acc + b > DECIMATE_CALL_BYTES:
+                    r = self.chunk_bounds[k] - first_row
+                    kc = min(n_out, max(0, -(-r // q)))
+                    if kc > cuts[-1]:
+                        cuts.append(kc)
+                        acc = 0
+                acc += b
+            cuts.append(n_out)
+            lanes = self._n_lanes()
+            use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
+            status = {}
+            for ka, kb in zip(cuts[:-1], cuts[1:]):
+                if kb <= ka:
+                    continue
+                # lanes: contiguous parts of the call's outputs (a part's halo is decoded by that part alone)
+                nl = max(1, min(lanes, kb - ka))
+                parts = [ka + (kb - ka) * g // nl for g in range(nl + 1)]
+                res = [None] * nl
+
+                def one(g, parts=parts, res=res):
+                    a, b = parts[g], parts[g + 1]
+                    if b <= a:
+                        return
+                    fr = first_row + a * q
+                    plo, phi = max(vb, fr - (n_taps - 1)), min(ve, fr + (b - a - 1) * q + 1)
+                    if plo >= phi:
+                        res[g] = ([], [], np.zeros((b - a, cols.size), out_dtype))
+                        return
+                    c0 = bisect.bisect_right(self.chunk_bounds, plo) - 1
+                    c1 = bisect.bisect_right(self.chunk_bounds, phi - 1) - 1
+                    keys = list(range(c0, c1 + 1))
+                    cache = self._cache_for(g) if use_cache else 0
+                    st, y = self._lane_decimate(cache, keys, vb, ve, fr, b - a, q, taps, out_dtype, cols, g)
+                    res[g] = (keys, st, y)
+                self.codec.run_lanes(one, nl)
+                for g in range(nl):
+                    if res[g] is None:
+                        continue
+                    keys, st, y = res[g]
+                    for k, v in zip(keys, st):
+                        if v != hip.CHUNK_OK or k not in status:
+                            status[k] = v
+                    out[parts[g]:parts[g + 1]] = y
+            self._raise_for(status)
+        return out[:, 0] if squeeze else out
+
+    def _lane_decimate(self, cache, keys, vb, ve, first_row, n_out, q, taps, out_dtype, cols, lane):
+        """One codec.decimate call on one lane: chunks resident in its cache go without bytes, the others' compressed bytes come
+        from a mapping of the file (or one read); sent whole once more if an entry was dropped between the query and the call."""
+        row0 = [self.chunk_bounds[k] for k in keys]
+        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
+        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
+        for attempt in range(2):
+            need = [k for k, p in zip(keys, present) if not p]
+            base = self.chunk_offsets[need[0]] if need else 0
+            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
+            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
+            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
+            buf = self._map_range(nbytes, base) if need else b''
+            if buf is None:
+                buf = self._pread(nbytes, base)
+            try:
+                return self.codec.decimate(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), vb, ve,
+                                           first_row, n_out, q, taps, out_dtype, cols, lane=lane)
             except hip.HipError as e:
                 if e.code != hip.E_MISS or attempt:
                     raise

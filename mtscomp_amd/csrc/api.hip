@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <future>
 #include <mutex>
@@ -145,6 +146,8 @@ struct Engine {
     DBuf inf_scratch, inf_desc, segsums;
     // window statistics: tile descriptors, the partial slab, the outputs of the host entry point
     DBuf stats;
+    // decimation: taps, columns, segment tables, the output of the host entry point
+    DBuf dec;
     // geometry of the last compress batch whose per-segment / per-block / per-tile descriptors are on the device (a recording is
     // compressed batch after batch of the same shape: the 10 MB of index arrays need not be rebuilt and copied every call)
     // (valid while the three buffers are the allocations the arrays were copied into: DBuf::gen, not the address -- a buffer
@@ -194,7 +197,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();
@@ -1824,6 +1827,225 @@ static int window_stats_run(Engine &E, hipStream_t st, DevCache *cache, const lo
     return MTS_OK;
 }
 
+// ---- decimation (mts_decimate, mts_dev_decimate) ---------------------------------------------------------------------------
+// The chunks of a call are cut into pieces of MTS_PIPE_BYTES of decoded bytes to decode (pipe_pieces; resident chunks weigh
+// nothing).  Piece p owns the outputs whose newest row (first_row + k * q) lies in its chunks; their support reaches L - 1 rows
+// further down, so a group decodes its own missing chunks and those of the halo below (a boundary chunk is decoded in both
+// pieces).  Every output is computed once, from the same rows, in the same order: the result does not depend on the pieces.
+// While piece p is decoded and filtered, the compressed bytes of piece p + 1 cross the bus on a helper thread.
+static int decimate_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device, const long *c_off,
+                        const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz, int flags, long vb, long ve,
+                        long first_row, long n_out, int q, int n_taps, const double *taps, int osz, int n_cols, const int *cols, void *out,
+                        bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
+    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    if (nc <= 0 || n_chunks < 0 || n_cols < 1 || n_cols > 64 * 65535 || !cols) { set_error("decimate: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
+    if (q < 1) { set_error("decimate: q %d < 1", q); return MTS_E_ARG; }
+    if (n_taps < 1 || n_taps > MTS_DECIMATE_MAX_TAPS || !taps) { set_error("decimate: %d taps (1 .. %d)", n_taps, MTS_DECIMATE_MAX_TAPS); return MTS_E_ARG; }
+    for (int j = 0; j < n_taps; j++)
+        if (!std::isfinite(taps[j])) { set_error("decimate: tap %d is not finite", j); return MTS_E_ARG; }
+    if (osz != 4 && osz != 8) { set_error("decimate: output itemsize %d (4 or 8)", osz); return MTS_E_ARG; }
+    if (vb < 0 || ve < vb || n_out < 0 || n_out > (1l << 40) || first_row < -(1l << 60) || first_row > (1l << 60)) {
+        set_error("decimate: rows or outputs invalid"); return MTS_E_ARG;
+    }
+    if (n_out && !out) { set_error("decimate: no output buffer"); return MTS_E_ARG; }
+    for (int j = 0; j < n_cols; j++)
+        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
+    for (int i = 0; i < n_chunks; i++) {
+        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
+        if (i && row0[i] != row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: chunks must be adjacent", i); return MTS_E_ARG; }
+        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
+        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
+    }
+    // the rows the outputs read: support ∩ valid range; the chunks must cover them
+    const long need_lo = n_out ? std::max(vb, first_row - (n_taps - 1)) : 0, need_hi = n_out ? std::min(ve, first_row + (n_out - 1) * q + 1) : 0;
+    if (need_lo < need_hi) {
+        if (n_chunks == 0 || row0[0] > need_lo || row0[n_chunks - 1] + n_rows[n_chunks - 1] < need_hi) {
+            set_error("decimate: the chunks do not cover rows [%ld, %ld)", need_lo, need_hi); return MTS_E_ARG;
+        }
+    }
+    for (int i = 0; i < n_chunks; i++) status[i] = MTS_CHUNK_OK;
+    if (n_out == 0) return MTS_OK;
+
+    // ---- which chunks are resident (whole rows), which are decoded here
+    auto entry_of = [&](int i) -> const CacheEntry * {
+        if (!cache) return nullptr;
+        auto it = cache->map.find(keys[i]);
+        if (it == cache->map.end()) return nullptr;
+        const CacheEntry &e = it->second;
+        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
+    };
+    std::vector<char> resident(n_chunks, 0);
+    std::vector<long> weight(n_chunks, 0);
+    for (int i = 0; i < n_chunks; i++) {
+        if (entry_of(i)) { resident[i] = 1; continue; }
+        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+        weight[i] = n_rows[i];
+    }
+    const u64 row_bytes = (u64)nc * sz;
+    // ---- groups of outputs: [gk[g], gk[g + 1]) reads chunks [gc0[g], gc1[g]]
+    std::vector<int> pb = cdata_on_device ? std::vector<int>{0, n_chunks} : pipe_pieces(weight.data(), false, n_chunks, row_bytes);
+    const int np = (int)pb.size() - 1;
+    std::vector<long> gk;
+    gk.push_back(0);
+    for (int p = 1; p < np; p++) {
+        const long r = row0[pb[p]] - first_row;                  // the first output whose newest row is in piece p
+        long k = r <= 0 ? 0 : (r + q - 1) / q;
+        if (k > n_out) k = n_out;
+        gk.push_back(std::max(k, gk.back()));
+    }
+    gk.push_back(n_out);
+    auto chunk_of = [&](long row) -> int {                     // the chunk holding `row` (clamped to the chunks)
+        int lo = 0, hi = n_chunks - 1;
+        while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row0[mid] <= row) lo = mid; else hi = mid - 1; }
+        return lo;
+    };
+    struct Group { long k0, k1; int c0, c1; std::vector<int> miss; std::vector<long> ooff; u64 ws = 0; };
+    std::vector<Group> groups;
+    u64 piece_cap = 0;
+    for (int g = 0; g < np; g++) {
+        if (gk[g + 1] <= gk[g]) continue;
+        Group G;
+        G.k0 = gk[g]; G.k1 = gk[g + 1];
+        const long lo = std::max(vb, first_row + G.k0 * q - (n_taps - 1)), hi = std::min(ve, first_row + (G.k1 - 1) * q + 1);
+        if (lo < hi && n_chunks) {
+            G.c0 = chunk_of(lo); G.c1 = chunk_of(hi - 1);
+            for (int i = G.c0; i <= G.c1; i++)
+                if (!resident[i]) { G.miss.push_back(i); G.ooff.push_back((long)G.ws); G.ws += align_up((u64)n_rows[i] * row_bytes, 256); }
+        } else {
+            G.c0 = 0; G.c1 = -1;                                 // (nothing valid to read: every row is 0)
+        }
+        piece_cap = std::max(piece_cap, G.ws);
+        groups.push_back(std::move(G));
+    }
+    // compressed bytes of every chunk decoded here, once (chunks back to back in the caller's buffer keep their distances)
+    std::vector<long> mcoff(n_chunks, 0);
+    u64 ctot = 0;
+    bool any_miss = false;
+    {
+        int prev = -1;
+        for (int i = 0; i < n_chunks; i++) {
+            if (resident[i]) continue;
+            any_miss = true;
+            if (cdata_on_device) { mcoff[i] = c_off[i]; continue; }
+            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
+            if (!joins) ctot = align_up(ctot + (prev >= 0 ? 16 : 0), 16);
+            mcoff[i] = (long)ctot; ctot += (u64)c_len[i];
+            prev = i;
+        }
+        ctot += 16;
+    }
+    // segment tables, one after the other: per group (c1 - c0 + 1) bases, then (c1 - c0 + 2) first rows
+    std::vector<long> seg_at(groups.size() + 1, 0);
+    for (size_t g = 0; g < groups.size(); g++) seg_at[g + 1] = seg_at[g] + 2l * (groups[g].c1 - groups[g].c0 + 1) + 1;
+    const u64 n_items = (u64)n_out * n_cols;
+    const size_t o_taps = 0, o_cols = align_up(8 * (u64)n_taps, 256), o_seg = o_cols + align_up(4 * (u64)n_cols, 256),
+                 o_out = o_seg + align_up(8 * (u64)(seg_at.back() + 1), 256), o_end = out_on_host ? o_out + align_up(n_items * osz, 256) : o_out;
+    // ---- workspace: these allocations come BEFORE the resident entries are looked at.  The decode of each group allocates
+    //      again (decompress_batch's DBuf::ensure), and an allocation that fails there drops this device's decoded chunks: the
+    //      resident entries of a group are therefore checked once more after its decode and before its launch (below)
+    int rc;
+    if ((rc = E.dec.ensure(o_end + 256))) return rc;
+    if (any_miss && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
+    if (piece_cap && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
+    if (cache) {
+        for (int i = 0; i < n_chunks; i++)                       // (the allocations above may have emptied the cache)
+            if (resident[i] && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+    }
+    u8 *ws = E.dec.as<u8>();
+    std::vector<u8> h_taps(8 * (size_t)n_taps);
+    for (int j = 0; j < n_taps; j++) {
+        if (osz == 4) { const float f = (float)taps[j]; memcpy(h_taps.data() + 4 * j, &f, 4); }
+        else memcpy(h_taps.data() + 8 * j, &taps[j], 8);
+    }
+    std::vector<long> seg(seg_at.back() + 1, 0);
+    std::vector<const u8 *> res_ptr(n_chunks, nullptr);       // the address of each resident entry the tables hold
+    for (int i = 0; i < n_chunks; i++) if (resident[i]) res_ptr[i] = entry_of(i)->d;
+    for (size_t g = 0; g < groups.size(); g++) {
+        const Group &G = groups[g];
+        long *b = seg.data() + seg_at[g], *r = b + (G.c1 - G.c0 + 1);
+        size_t m = 0;
+        for (int i = G.c0; i <= G.c1; i++) {
+            const u8 *base;
+            if (resident[i]) base = res_ptr[i];
+            else base = E.h_out.as<u8>() + G.ooff[m++];
+            b[i - G.c0] = (long)(uintptr_t)base;
+            r[i - G.c0] = row0[i];
+        }
+        r[G.c1 - G.c0 + 1] = G.c1 >= G.c0 ? row0[G.c1] + n_rows[G.c1] : 0;
+    }
+    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), (size_t)osz * n_taps, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_seg, seg.data(), 8 * seg.size(), hipMemcpyHostToDevice, st));
+    void *d_out = out_on_host ? (void *)(ws + o_out) : out;
+    const int dflags = flags & ~MTS_FLAG_UNSIGNED;           // (the decoder compares the transform flags as a whole)
+    const int dev = E.dev;
+    std::vector<char> copied(n_chunks, 0);
+    auto copy_in = [&](int g) -> int {
+        if (cdata_on_device) return MTS_OK;
+        MTS_HIP(hipSetDevice(dev));
+        const std::vector<int> &mi = groups[g].miss;
+        for (size_t a = 0; a < mi.size();) {
+            if (copied[mi[a]]) { a++; continue; }
+            size_t e = a + 1;                                     // a run of chunks back to back here and in the caller's buffer
+            while (e < mi.size() && !copied[mi[e]] && mi[e] == mi[e - 1] + 1 && c_off[mi[e]] == c_off[mi[e - 1]] + c_len[mi[e - 1]] &&
+                   mcoff[mi[e]] == mcoff[mi[e - 1]] + c_len[mi[e - 1]]) e++;
+            u64 len = 0;
+            for (size_t z = a; z < e; z++) { len += (u64)c_len[mi[z]]; copied[mi[z]] = 1; }
+            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[mi[a]], cdata + c_off[mi[a]], (size_t)len); if (rc1) return rc1; }
+            a = e;
+        }
+        return MTS_OK;
+    };
+    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
+    const int ng = (int)groups.size();
+    if (ng > 0 && (rc = copy_in(0))) return rc;
+    bool first_decode = true;
+    for (int g = 0; g < ng; g++) {
+        std::future<int> f_in;
+        if (g + 1 < ng) f_in = copy_beside(copy_in, g + 1);
+        const Group &G = groups[g];
+        const int nm = (int)G.miss.size();
+        if (nm) {
+            std::vector<long> co(nm), cl(nm), nr(nm);
+            std::vector<int> mst(nm, MTS_CHUNK_CORRUPT);
+            for (int z = 0; z < nm; z++) { co[z] = mcoff[G.miss[z]]; cl[z] = c_len[G.miss[z]]; nr[z] = n_rows[G.miss[z]]; }
+            rc = dev_decompress(E, st, d_src, co.data(), cl.data(), nr.data(), nm, nc, sz, dflags, E.h_out.as<u8>(), G.ooff.data(), mst.data(), 0,
+                                !first_decode);
+            first_decode = false;
+            if (!rc) for (int z = 0; z < nm; z++) if (mst[z] != MTS_CHUNK_OK) status[G.miss[z]] = mst[z];
+        }
+        if (!rc && cache) {
+            // a decode allocation that failed drops the decoded chunks (drop_device_caches: hipFree, which waits for the kernels
+            // already launched on the device -- the earlier groups' reads are done).  The tables of this group must not point at a
+            // freed entry: every resident chunk it reads is still in the cache at the same address, or the call ends with
+            // MTS_E_MISS (the Reader sends every chunk's bytes again), before this group's kernel is launched.
+            for (int i = G.c0; i <= G.c1 && !rc; i++) {
+                if (!resident[i]) continue;
+                const CacheEntry *e = entry_of(i);
+                if (!e || e->d != res_ptr[i]) {
+                    set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i);
+                    rc = MTS_E_MISS;
+                }
+            }
+        }
+        if (!rc) {
+            const long *sb = (const long *)(ws + o_seg) + seg_at[g];
+            const int ns = G.c1 - G.c0 + 1;
+            rc = launch_decimate(st, sz, flags, osz, (const u8 *const *)sb, sb + (ns > 0 ? ns : 0), ns > 0 ? ns : 0, nc, (const int *)(ws + o_cols), n_cols,
+                                 ws + o_taps, n_taps, q, first_row, G.k0, G.k1, ns > 0 ? vb : 0, ns > 0 ? ve : 0,
+                                 (u8 *)d_out + (u64)G.k0 * n_cols * osz);
+        }
+        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;      // (always joined: it holds references to this frame)
+        if (rc || rc_in) return rc ? rc : rc_in;
+    }
+    if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, n_items * osz, hipMemcpyDeviceToHost, st));
+    MTS_HIP(hipStreamSynchronize(st));
+    return MTS_OK;
+}
+
 int mts_window_stats(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
                      const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
                      long row_end, long window_rows, int n_cols, const int *cols, void *out_min, void *out_max, void *out_sum, void *out_sumsq,
@@ -1861,6 +2083,44 @@ int mts_dev_window_stats(int device, void *stream, const unsigned char *d_cdata,
     return window_stats_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
                             n_channels, itemsize, flags, row_begin, row_end, window_rows, n_cols, cols, d_min, d_max, d_sum, d_sumsq, false,
                             count, chunk_status);
+}
+
+int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                 const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                 long valid_end, long first_row, long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols,
+                 void *out, int *chunk_status)
+{
+    DevCache *c = nullptr;
+    if (cache_id) {
+        int cdev = 0;
+        c = find_cache(cache_id, &cdev);
+        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
+    }
+    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;      // (destroyed while this call waited for the engine)
+    MTS_HIP(hipSetDevice(E->dev));
+    return decimate_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
+                        valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols, out, true, chunk_status);
+}
+
+int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
+                     const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row,
+                     long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols, void *d_out,
+                     int *chunk_status)
+{
+    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    MTS_HIP(hipSetDevice(E->dev));
+    return decimate_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
+                        itemsize, flags, valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols, d_out, false,
+                        chunk_status);
 }
 
 // ---- debug taps ---------------------------------------------------------------------------------

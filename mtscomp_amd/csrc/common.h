@@ -159,6 +159,14 @@ int launch_stats_tiles(hipStream_t st, int itemsize, int flags, const StatTile *
 int launch_stats_combine(hipStream_t st, int itemsize, int flags, const u8 *d_slab, long n_tiles, const long *d_win_tiles, long n_windows,
                          int n_cols, void *d_min, void *d_max, void *d_sum, void *d_sumsq);
 
+// decimate.hip: FIR + keep every q-th row of decoded chunks (mts_decimate).  Outputs k in [k_begin, k_end) of the call:
+// out[(k - k_begin) * n_cols + c] = sum_j taps[j] * x[first_row + k * q - j, cols[c]] in the out_itemsize float type, j ascending,
+// x = 0 outside [valid_begin, valid_end) and outside the segments; segment s holds file rows [seg_row0[s], seg_row0[s + 1]) at
+// d_seg_base[s] (n_channels items per row); d_taps: n_taps values of the output type
+int launch_decimate(hipStream_t st, int itemsize, int flags, int out_itemsize, const u8 *const *d_seg_base, const long *d_seg_row0, int n_segs,
+                    int n_channels, const int *d_cols, int n_cols, const void *d_taps, int n_taps, int q, long first_row, long k_begin,
+                    long k_end, long valid_begin, long valid_end, void *d_out);
+
 // deflate.hip
 size_t hash_sort_ws_bytes(int n_tiles);                            // the one-pass sort's per-tile records
 int launch_hash_sort(hipStream_t st, const u8 *d_stream, const TileDesc *d_tiles, int n_tiles, u32 *d_tmp, u32 *d_sorted,

@@ -100,6 +100,11 @@ def lib():
                                    C.c_long, C.c_int, ip, vp, vp, vp, vp, lp, ip]
     L.mts_dev_window_stats.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
                                        C.c_int, ip, vp, vp, vp, vp, lp, ip]
+    dp = C.POINTER(C.c_double)
+    L.mts_decimate.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
+                               C.c_long, C.c_int, C.c_int, dp, C.c_int, C.c_int, ip, vp, ip]
+    L.mts_dev_decimate.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
+                                   C.c_int, C.c_int, dp, C.c_int, C.c_int, ip, vp, ip]
     L.mts_release.restype = None
     _lib = L
     return L
@@ -112,7 +117,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_last_stage_times', 'mts_debug_match_tables', 'mts_debug_tokens', 'mts_debug_deflate',
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
-           'mts_window_stats', 'mts_dev_window_stats']
+           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate']
 
 
 def _check(rc, what):
@@ -391,6 +396,62 @@ def dev_window_stats(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, r
         if a.nbytes:
             _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(int(o)), a.nbytes, 1), 'mts_dev_copy')
     return [int(x) for x in status[:rows.size]], dict(min=mn, max=mx, sum=sm, sumsq=sq, count=cnt[:nw]), out
+
+
+# ------------------------------------------------------------------------------------------------
+# FIR low-pass + decimation (an extension: the reference has no such call)
+# ------------------------------------------------------------------------------------------------
+DECIMATE_MAX_TAPS = 8192
+
+
+def _dec_args(taps, out_dtype, cols):
+    taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).ravel())
+    out_dtype = np.dtype(out_dtype)
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    return taps, out_dtype, cols
+
+
+def decimate(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row, n_out, q, taps,
+             out_dtype, cols, device=0):
+    """mts_decimate: y[k, c] = sum_j taps[j] * x[first_row + k * q - j, cols[c]] (x = 0 outside [valid_begin, valid_end)) for k < n_out,
+    from the adjacent chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])).  cache_id 0: no cache, every chunk comes with its
+    bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, (n_out, n_cols) out_dtype)."""
+    dtype = check_dtype(dtype)
+    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
+    taps, out_dtype, cols = _dec_args(taps, out_dtype, cols)
+    n = int(rows.size)
+    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
+    assert not n or int((offs + lens).max()) <= cdata.size
+    out = np.empty((max(int(n_out), 0), cols.size), out_dtype)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    _check(lib().mts_decimate(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
+                              dtype.itemsize, stats_flags(flags, dtype), int(valid_begin), int(valid_end), int(first_row), int(n_out), int(q),
+                              int(taps.size), taps.ctypes.data_as(C.POINTER(C.c_double)), out_dtype.itemsize, int(cols.size),
+                              cols.ctypes.data_as(C.POINTER(C.c_int)), _ptr(out), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_decimate')
+    return [int(x) for x in status[:n]], out
+
+
+def dev_decimate(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row, n_out, q, taps, out_dtype, cols,
+                 out=None, download=True):
+    """mts_dev_decimate on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the result (made when None;
+    returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
+    dtype = check_dtype(dtype)
+    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
+    taps, out_dtype, cols = _dec_args(taps, out_dtype, cols)
+    nbytes = max(int(n_out), 0) * cols.size * out_dtype.itemsize
+    if out is None or out.nbytes < nbytes + 256:
+        out = DevBuffer(nbytes + 256, device=cbuf.device)
+    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
+    _check(lib().mts_dev_decimate(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
+                                  dtype.itemsize, stats_flags(flags, dtype), int(valid_begin), int(valid_end), int(first_row), int(n_out), int(q),
+                                  int(taps.size), taps.ctypes.data_as(C.POINTER(C.c_double)), out_dtype.itemsize, int(cols.size),
+                                  cols.ctypes.data_as(C.POINTER(C.c_int)), out.at(), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_decimate')
+    res = None
+    if download:
+        res = np.empty((max(int(n_out), 0), cols.size), out_dtype)
+        if res.nbytes:
+            _check(lib().mts_dev_copy(out.device, None, _ptr(res), out.at(), res.nbytes, 1), 'mts_dev_copy')
+    return [int(x) for x in status[:rows.size]], res, out
 
 
 # ------------------------------------------------------------------------------------------------
