@@ -1,5 +1,7 @@
 """Test-only helpers for Reader.window_stats: the numpy definition of the statistics, and a lane codec that restates
 mts_window_stats in numpy (so that the CPU suite drives the Python layer: argument handling, lanes, cache use, errors)."""
+import math
+
 import numpy as np
 
 from tests.codec_oracle import LaneOracleCodec
@@ -129,3 +131,111 @@ class StatsOracleCodec(LaneOracleCodec):
                 cnt[w] += e - r
                 r = e
         return status, dict(min=mn, max=mx, sum=s, sumsq=q, count=cnt)
+
+
+# ---- exact references: what the kernels' sums must come within a stated bound of -----------------------------------------------
+STAT_TILE_ROWS = 512                     # api.hip: rows per tile of one (chunk ∩ window) segment
+STAT_WAVES = 4                           # stats.hip: waves per tile, each taking every 4th row
+U = 2.0 ** -53                           # unit roundoff of float64
+
+
+def stat_tiles_per_window(chunk_bounds, start, stop, window):
+    """(tiles of each window, rows of its largest tile): the tiling of api.hip's window_stats_run -- every (chunk ∩ window)
+    segment of [start, stop) cut into STAT_TILE_ROWS-row tiles."""
+    n = stop - start
+    nw = -(-n // window) if n > 0 else 0
+    tiles, big = np.zeros(nw, np.int64), np.zeros(nw, np.int64)
+    b = np.asarray(chunk_bounds, np.int64)
+    for i in range(b.size - 1):
+        lo, hi = max(int(b[i]), start), min(int(b[i + 1]), stop)
+        r = lo
+        while r < hi:
+            w = (r - start) // window
+            e = min(hi, start + (w + 1) * window)
+            tiles[w] += -(-(e - r) // STAT_TILE_ROWS)
+            big[w] = max(big[w], min(e - r, STAT_TILE_ROWS))
+            r = e
+    return tiles, big
+
+
+def stats_depth(chunk_bounds, start, stop, window, parts=1):
+    """m per window: the longest chain of rounded float64 additions (and the rounded square) behind one result of a window.
+    stats.hip:84-100 (k_stats_tiles): a lane adds every 4th row of its tile to an accumulator that starts at 0 -- at most
+    ceil(min(tile rows, 512) / 4) additions -- and wave 0 then adds the 4 wave partials to 0 in wave order: 4 more.
+    stats.hip:119-121 (k_stats_combine): the window's tile partials are added to 0 in tile order: one per tile.  A float64 item
+    is squared with one rounding: 1 more.  `parts`: the partial results of lanes / device calls Reader.window_stats adds on the
+    host (one addition each)."""
+    tiles, big = stat_tiles_per_window(chunk_bounds, start, stop, window)
+    return -(-big // STAT_WAVES) + STAT_WAVES + tiles + 1 + parts
+
+
+def gamma(m):
+    """gamma_m = m u / (1 - m u): |fl(sum) - sum| <= gamma_m * sum|terms| for any order of m - 1 rounded additions (Higham,
+    Accuracy and Stability of Numerical Algorithms, 2nd ed., (3.4) and Lemma 3.1)."""
+    mu = np.asarray(m, np.float64) * U
+    return mu / (1 - mu)
+
+
+def _exact_sum(terms):
+    """(value, sum of |terms|): math.fsum's correctly rounded sum where every term is finite and the sum stays in range; else the
+    IEEE result of any order (NaN when a NaN or both infinities are there, the infinity otherwise; +-inf on overflow)."""
+    t = np.asarray(terms, np.float64)
+    a = float(np.abs(t).sum()) if t.size else 0.0
+    if not np.isfinite(t).all():
+        with np.errstate(invalid='ignore'):
+            return float(t.sum()), a
+    try:
+        return math.fsum(t.tolist()), a
+    except OverflowError:
+        return (math.inf if t.sum() > 0 else -math.inf), a
+
+
+def assert_stats_exact_bound(got, x, chunk_bounds, start, stop, window, cols, parts=1, squeeze=False):
+    """got (Reader.window_stats / the C ABI's dict) against the exact sums of rows [start, stop) of x (the oracle's decode):
+      floats:          |sum - fsum(x)| <= gamma_m * sum|x| and |sumsq - fsum(x^2)| <= gamma_m * sum x^2 with m = stats_depth (x^2
+                       of a float32 item is exact in float64; of a float64 item it is rounded once, which m counts); NaN and
+                       +-inf exactly where the terms make the exact sums NaN / +-inf; no bound where sum|terms| itself
+                       overflows (then some partial sum overflows in almost any order: assert_stats_equal checks numpy's);
+      4/8-byte ints:   sum == the Python-int sum wrapped to int64, bit for bit; |sumsq - sum x^2| <= (m + 3) u sum x^2 (the
+                       exact Python-int sum of squares: each item converted to float64 (one rounding), squared (one), summed);
+      1/2-byte ints:   sum and sumsq (uint64) exactly the Python-int sums.
+    Returns the number of (window, column) results checked."""
+    x = np.asarray(x)
+    dtype = x.dtype
+    cols = [int(c) for c in cols]
+    m = stats_depth(chunk_bounds, start, stop, window, parts)
+    s_got, q_got = np.asarray(got['sum']), np.asarray(got['sumsq'])
+    if squeeze:
+        s_got, q_got = s_got[:, None], q_got[:, None]
+    nw = m.size
+    assert s_got.shape == q_got.shape == (nw, len(cols)), (s_got.shape, nw, len(cols))
+    for w in range(nw):
+        seg = x[start + w * window:min(stop, start + (w + 1) * window)]
+        for jc, c in enumerate(cols):
+            col = seg[:, c]
+            gs, gq = s_got[w, jc], q_got[w, jc]
+            where = (w, jc, c)
+            if dtype.kind == 'f':
+                x64 = col.astype(np.float64)
+                with np.errstate(over='ignore'):
+                    sq = x64 * x64
+                for name, g, terms in (('sum', gs, x64), ('sumsq', gq, sq)):
+                    e, a = _exact_sum(terms)
+                    if not np.isfinite(terms).all():
+                        assert (math.isnan(g) and math.isnan(e)) or g == e, (name, where, g, e)
+                        continue
+                    if not math.isfinite(a):         # (sum |x| beyond float64: a partial sum may overflow in any order; no bound)
+                        continue
+                    assert math.isfinite(g) and abs(float(g) - e) <= float(gamma(m[w])) * a, (name, where, float(g), e, a, int(m[w]))
+                continue
+            ints = [int(v) for v in col.tolist()]
+            s_exact = sum(ints)
+            s_wrap = (s_exact + (1 << 63)) % (1 << 64) - (1 << 63)
+            assert int(gs) == s_wrap, ('sum', where, int(gs), s_wrap)
+            q_exact = sum(v * v for v in ints)
+            if exact_sumsq(dtype):                       # (uint64 from the C ABI; Reader converts it to float64 once)
+                want_q = q_exact if q_got.dtype == np.uint64 else float(q_exact)
+                assert (int(gq) if q_got.dtype == np.uint64 else float(gq)) == want_q, ('sumsq', where, gq, q_exact)
+            else:
+                assert abs(float(gq) - q_exact) <= float(m[w] + 3) * U * q_exact, ('sumsq', where, float(gq), q_exact, int(m[w]))
+    return nw * len(cols)

@@ -1,4 +1,4 @@
-"""Randomised parity under -m gpu: the three fuzzers of tools/ (which found both real bugs of rounds 3-4: the host copy
+"""Randomised parity under -m gpu: the four fuzzers of tools/ (which found both real bugs of rounds 3-4: the host copy
 shares, k_match6's look-back race) run for a fixed budget each, with seeds that CHANGE from day to day and are printed, so
 that the driver's GPU run sees fresh cases every round and a failure can be replayed:
 
@@ -14,6 +14,10 @@ What is compared (all through the C ABI, mtscomp_amd/hip.py):
   * fuzz_reader_gpu.py   files written by compress(), read back through Reader[...] with random slices, steps and column
                          picks, cache on / tiny / off: equal to numpy indexing of the raw array (the reference's own randomised
                          round trips: tests.py:212-243, 381-410)
+  * fuzz_reduce_gpu.py   files of all ten item types written by compress(), reduced through Reader.window_stats and
+                         Reader.decimate with random windows, ranges, channels, q, taps, edges, output types, cache states and
+                         lanes: against references over the oracle's decode (numpy, the exact fsum / Python-int bound, the numpy
+                         restatement of the FIR bit for bit, the integer FIR where the inputs are exactly representable)
 """
 import datetime
 import os
@@ -36,6 +40,7 @@ CASES = [
     ('codec_levels1to9', 'fuzz_gpu.py', 2, {'FUZZ_LEVELS': '2'}),
     ('inflate_verdicts', 'fuzz_inflate_gpu.py', 3, {}),
     ('reader_slices', 'fuzz_reader_gpu.py', 4, {}),
+    ('reduce_extensions', 'fuzz_reduce_gpu.py', 5, {}),
 ]
 
 

@@ -16,7 +16,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from mtscomp_amd import hip  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
-DTYPES = ['uint8', 'int8', 'int16', 'uint16', 'int32', 'int64', 'float32', 'float64']
+DTYPES = ['uint8', 'int8', 'int16', 'uint16', 'int32', 'uint32', 'int64', 'uint64', 'float32', 'float64']
 
 
 def content(r, kind, nt, nc):
