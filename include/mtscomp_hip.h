@@ -45,8 +45,11 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_welch and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
+#define MTS_WELCH_MAX_NPERSEG 16384
+#define MTS_WELCH_BLOCK_SEGMENTS 32   /* mts_welch: segments per block (B), summed in order on the device */
+#define MTS_WELCH_GROUP_ROWS (1l << 20) /* a group is the smallest multiple G of B segments with G * step >= this many rows */
 
 int mts_version(void);
 int mts_device_count(void);                 /* number of gfx950 devices visible; 0 if none */
@@ -212,6 +215,39 @@ int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys
                  int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols, void *out,
                  int *chunk_status);
 
+/*
+ * Per-channel power spectral density, Welch's method (an extension: the reference has no such call; its users run
+ * scipy.signal.welch on Reader[...] on the host).  Only one float64 partial per (group, bin, column) crosses the bus.
+ *   segments       segment s covers file rows [row_seg0 + s * step, row_seg0 + s * step + nperseg); the call computes segments
+ *                  [seg_begin, seg_end): seg_begin is a multiple of the group size G, seg_end a multiple of G or the end of the
+ *                  caller's range (the last group may then be short; not checked)
+ *   nperseg, step  nperseg a power of two in [16, MTS_WELCH_MAX_NPERSEG]; 1 <= step <= nperseg
+ *   taper          nperseg finite doubles on the host, rounded to the compute type
+ *   detrend        1: subtract the segment's mean first (float64: integers' exact sum rounded once, floats' pairwise tree
+ *                  v = v[0::2] + v[1::2]); 0: none
+ *   csize          the FFT's compute type: 4 float, 8 double
+ *   per segment and column: y[n] = F(double(x[n]) - mean) * F(taper[n]), X = real FFT of y in F (radix-4/2 Stockham passes
+ *   over nperseg / 2 complex points, twiddles rounded once to F), P[k] = double(Re X[k])^2 + double(Im X[k])^2, k <= nperseg / 2.
+ *   Blocks of B = MTS_WELCH_BLOCK_SEGMENTS segments are summed in segment order, groups of G segments (smallest multiple of B with
+ *   G * step >= MTS_WELCH_GROUP_ROWS) in block order from +0, all in float64: the same bits whatever the call, its pieces, the
+ *   launches or the device.  No scaling, no one-sided doubling, no division by the number of segments: the caller does that.
+ *   out            (n_groups, nperseg / 2 + 1, n_cols) float64, C order, n_groups = ceil((seg_end - seg_begin) / G)
+ *   chunks         as mts_decimate: adjacent, ascending, covering the rows of the segments; cols: n_cols >= 1, repeats allowed
+ *   chunk_status   MTS_CHUNK_* per chunk; the partials of a segment that reads a failed chunk are undefined
+ * mts_welch: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated piece by piece (MTS_PIPE_BYTES) in a
+ * transient workspace and NOT inserted; pieces are cut at block boundaries, a chunk that blocks of two pieces read is inflated in
+ * both, and the group sums are carried on the device from piece to piece.  `out` is host memory.
+ * mts_dev_welch: device d_cdata and d_out on `device`, chunk_status on the host; no cache.
+ * MTS_E_ARG before anything is launched: nperseg not a power of two in range, step outside [1, nperseg], a taper value that is not
+ * finite, csize not 4 or 8, n_cols < 1, a column outside [0, n_channels), chunks not adjacent or not covering the rows read,
+ * seg_begin not a multiple of G, seg_end <= seg_begin.
+ */
+int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+              const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_seg0,
+              long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,
+              const int *cols, double *out, int *chunk_status);
+
 /* ---------------------------------------------------------------------------------------------
  * Device-resident variants (inputs and outputs already in HBM; used by bench.py and by callers that
  * keep recordings on the GPU).  Pointers are device pointers on `device`; `stream` is a hipStream_t
@@ -235,6 +271,10 @@ int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, con
                      int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row,
                      long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols,
                      const int *cols, void *d_out, int *chunk_status /* host */);
+int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                  const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0,
+                  long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,
+                  const int *cols, double *d_out, int *chunk_status /* host */);
 /* integer-exact synthetic recording, rows [t0, t1) of n_channels int16, on device */
 int mts_dev_synth_int16(int device, void *stream, void *d_out, long t0, long t1, int n_channels,
                         long seed);

@@ -64,6 +64,7 @@ PREAD_THREADS = int(os.environ.get('MTSCOMP_PREAD_THREADS', 8))      # threads t
 WINDOW_STATS_CALL_BYTES = 1 << 30      # Reader.window_stats: compressed bytes per device call (a longer range is split on chunk boundaries)
 WINDOW_STATS_SLAB_BYTES = 1 << 30      # ... and partial results per call on the device (one per column and tile of <= 512 rows of a window)
 DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per device call (a longer range is split at output-row boundaries)
+WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
 
 logger = logging.getLogger('mtscomp_amd')
 logger.setLevel(logging.INFO)
@@ -184,6 +185,24 @@ def decimate_taps(q):
     return h / h.sum()
 
 
+def welch_window(window, nperseg):
+    """The taper of Reader.welch: 'hann', 'hamming' or 'boxcar' as the periodic windows of scipy.signal.get_window(window, nperseg)
+    (restated in numpy), or a 1-D array of nperseg finite numbers, as float64."""
+    if isinstance(window, str):
+        n = np.arange(nperseg)
+        if window == 'hann':
+            return 0.5 - 0.5 * np.cos(2.0 * np.pi * n / nperseg)
+        if window == 'hamming':
+            return 0.54 - 0.46 * np.cos(2.0 * np.pi * n / nperseg)
+        if window == 'boxcar':
+            return np.ones(nperseg)
+        raise ValueError("window must be 'hann', 'hamming', 'boxcar' or an array, got %r" % (window,))
+    w = np.asarray(window, dtype=np.float64)
+    if w.ndim != 1 or w.size != nperseg or not np.isfinite(w).all():
+        raise ValueError("a window array must hold nperseg = %d finite numbers" % nperseg)
+    return w
+
+
 class HipCodec:
     """Per-chunk codec on MI355X.  ``devices``: list of device indices (default: all visible)."""
 
@@ -287,6 +306,15 @@ class HipCodec:
         device = self.devices[(lane or 0) % len(self.devices)]
         return hip.decimate(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row,
                             n_out, q, taps, out_dtype, cols, device=device)
+
+    def welch(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg, step,
+              taper, detrend, compute_dtype, cols, lane=None):
+        """Welch group sums of the adjacent chunks `keys` on one device (`lane` modulo the devices, default the first): mts_welch.
+        cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0 are read there.  -> (status list, (n_groups,
+        nperseg // 2 + 1, n_cols) float64)."""
+        device = self.devices[(lane or 0) % len(self.devices)]
+        return hip.welch(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg,
+                         step, taper, detrend, compute_dtype, cols, device=device)
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1353,6 +1381,144 @@ class Reader:
             try:
                 return self.codec.decimate(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), vb, ve,
                                            first_row, n_out, q, taps, out_dtype, cols, lane=lane)
+            except hip.HipError as e:
+                if e.code != hip.E_MISS or attempt:
+                    raise
+                present = [False] * len(keys)                       # dropped since the query: send everything
+
+    # -- power spectral density on the device (an extension: the reference's users run scipy.signal.welch on Reader[...])
+    def welch(self, nperseg=256, start=0, stop=None, channels=slice(None), noverlap=None, window='hann', detrend='constant',
+              scaling='density', dtype=np.float32):
+        """Per-channel power spectral density of rows [start, stop) by Welch's method, on the device: only the partial sums cross
+        the bus.  Returns (f, psd): f = np.fft.rfftfreq(nperseg, 1 / sample_rate), psd float64 of shape (nperseg // 2 + 1, n_cols)
+        (1-D when channels is an int).  With the defaults this is scipy.signal.welch(self[start:stop, channels], fs=sample_rate,
+        nperseg=nperseg, axis=0) up to rounding; so it is for the other noverlap, window, detrend and scaling values.
+        nperseg: a power of two in [16, 16384] (the FFT length; no nfft).  noverlap: None (nperseg // 2) or 0 <= noverlap < nperseg;
+        segment k covers rows [start + k * step, + nperseg), step = nperseg - noverlap, for k < (n - nperseg) // step + 1 (n = stop -
+        start; rows after the last whole segment are not used).  window: 'hann', 'hamming', 'boxcar' (scipy's periodic windows) or
+        nperseg finite numbers.  detrend: 'constant' (the segment's mean, in float64) or False.  scaling: 'density' (1 / (fs *
+        sum w^2)) or 'spectrum' (1 / (sum w)^2); bins other than 0 and nperseg / 2 are doubled.  dtype: the FFT's compute type,
+        float32 or float64.  start / stop follow Reader[...]; channels: an int, a slice with step >= 1, or a sequence of ints
+        (repeats allowed).  Unlike scipy, a range shorter than nperseg is a ValueError (scipy shrinks nperseg).  The result of a
+        column does not depend on the lanes, calls, pieces, cache residency or the other columns (the summation tree depends on
+        (nperseg, step, dtype) only).  Chunks resident in the device cache are read where they lie; the others are decoded in a
+        transient workspace and NOT kept.  A damaged chunk among the rows read raises the IOError of Reader[...]."""
+        if not callable(getattr(self.codec, 'welch', None)):
+            raise NotImplementedError("welch needs a codec that computes spectra on the device (HipCodec); %r has none"
+                                      % getattr(self.codec, 'name', self.codec))
+        if (not isinstance(nperseg, (int, np.integer)) or isinstance(nperseg, bool) or not 16 <= nperseg <= hip.WELCH_MAX_NPERSEG
+                or nperseg & (nperseg - 1)):
+            raise ValueError("nperseg must be a power of two in [16, %d], got %r" % (hip.WELCH_MAX_NPERSEG, nperseg))
+        nperseg = int(nperseg)
+        if noverlap is None:
+            noverlap = nperseg // 2
+        if not isinstance(noverlap, (int, np.integer)) or isinstance(noverlap, bool) or not 0 <= noverlap < nperseg:
+            raise ValueError("noverlap must be None or an int in [0, nperseg), got %r" % (noverlap,))
+        step = nperseg - int(noverlap)
+        taper = welch_window(window, nperseg)
+        if detrend is False:
+            dt = False
+        elif isinstance(detrend, str) and detrend == 'constant':
+            dt = True
+        else:
+            raise ValueError("detrend must be 'constant' or False, got %r" % (detrend,))
+        if scaling == 'density':
+            scale = 1.0 / (self.sample_rate * float((taper * taper).sum()))
+        elif scaling == 'spectrum':
+            scale = 1.0 / float(taper.sum()) ** 2
+        else:
+            raise ValueError("scaling must be 'density' or 'spectrum', got %r" % (scaling,))
+        try:
+            cdt = np.dtype(dtype)
+        except TypeError:
+            raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
+        if cdt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
+        i0 = self._validate_index(start, 0)
+        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        if i1 - i0 < nperseg:
+            raise ValueError("welch: rows [%d, %d) hold fewer than nperseg = %d rows" % (i0, i1, nperseg))
+        cols, squeeze = self._stats_channels(channels)
+        f = np.fft.rfftfreq(nperseg, 1.0 / self.sample_rate)
+        nb = nperseg // 2 + 1
+        n_seg = (i1 - i0 - nperseg) // step + 1
+        total = np.zeros((nb, cols.size))
+        if cols.size:
+            G = hip.welch_group_segments(step)
+            n_groups = -(-n_seg // G)
+
+            def group_rows(g0, g1):                                  # rows read by groups [g0, g1)
+                return i0 + g0 * G * step, i0 + (min(g1 * G, n_seg) - 1) * step + nperseg
+
+            def chunk_span(g0, g1):
+                lo, hi = group_rows(g0, g1)
+                return bisect.bisect_right(self.chunk_bounds, lo) - 1, bisect.bisect_right(self.chunk_bounds, hi - 1) - 1
+
+            # calls: whole groups, cut where the compressed bytes of their chunks pass WELCH_CALL_BYTES
+            cuts, acc = [0], 0
+            for g in range(n_groups):
+                c0, c1 = chunk_span(g, g + 1)
+                b = self.chunk_offsets[c1 + 1] - self.chunk_offsets[c0]
+                if acc and acc + b > WELCH_CALL_BYTES:
+                    cuts.append(g)
+                    acc = 0
+                acc += b
+            cuts.append(n_groups)
+            lanes = self._n_lanes()
+            use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
+            status = {}
+            parts_by_group = [None] * n_groups
+            for ga, gb in zip(cuts[:-1], cuts[1:]):
+                # lanes: contiguous runs of the call's groups
+                nl = max(1, min(lanes, gb - ga))
+                runs = [ga + (gb - ga) * g // nl for g in range(nl + 1)]
+                res = [None] * nl
+
+                def one(g, runs=runs, res=res):
+                    a, b = runs[g], runs[g + 1]
+                    if b <= a:
+                        return
+                    c0, c1 = chunk_span(a, b)
+                    keys = list(range(c0, c1 + 1))
+                    cache = self._cache_for(g) if use_cache else 0
+                    st, part = self._lane_welch(cache, keys, i0, a * G, min(b * G, n_seg), nperseg, step, taper, dt, cdt, cols, g)
+                    res[g] = (keys, st, part)
+                self.codec.run_lanes(one, nl)
+                for g in range(nl):
+                    if res[g] is None:
+                        continue
+                    keys, st, part = res[g]
+                    for k, v in zip(keys, st):
+                        if v != hip.CHUNK_OK or k not in status:
+                            status[k] = v
+                    for j in range(runs[g + 1] - runs[g]):
+                        parts_by_group[runs[g] + j] = part[j]
+            self._raise_for(status)
+            for part in parts_by_group:                              # the range: groups in order, float64, from +0
+                total = total + part
+        psd = total * scale
+        psd[1:-1] *= 2.0
+        psd /= n_seg
+        return f, (psd[:, 0] if squeeze else psd)
+
+    def _lane_welch(self, cache, keys, row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, compute_dtype, cols, lane):
+        """One codec.welch call on one lane: chunks resident in its cache go without bytes, the others' compressed bytes come from a
+        mapping of the file (or one read); sent whole once more if an entry was dropped between the query and the call."""
+        row0 = [self.chunk_bounds[k] for k in keys]
+        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
+        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
+        for attempt in range(2):
+            need = [k for k, p in zip(keys, present) if not p]
+            base = self.chunk_offsets[need[0]] if need else 0
+            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
+            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
+            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
+            buf = self._map_range(nbytes, base) if need else b''
+            if buf is None:
+                buf = self._pread(nbytes, base)
+            try:
+                return self.codec.welch(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), row_seg0,
+                                        seg_begin, seg_end, nperseg, step, taper, detrend, compute_dtype, cols, lane=lane)
             except hip.HipError as e:
                 if e.code != hip.E_MISS or attempt:
                     raise

@@ -148,6 +148,8 @@ struct Engine {
     DBuf stats;
     // decimation: taps, columns, segment tables, the output of the host entry point
     DBuf dec;
+    // Welch PSD: taper, twiddles, columns, segment tables, block partials, group sums
+    DBuf welch;
     // geometry of the last compress batch whose per-segment / per-block / per-tile descriptors are on the device (a recording is
     // compressed batch after batch of the same shape: the 10 MB of index arrays need not be rebuilt and copied every call)
     // (valid while the three buffers are the allocations the arrays were copied into: DBuf::gen, not the address -- a buffer
@@ -197,7 +199,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &welch};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();
@@ -2046,6 +2048,267 @@ static int decimate_run(Engine &E, hipStream_t st, DevCache *cache, const long *
     return MTS_OK;
 }
 
+// ---- Welch PSD (mts_welch, mts_dev_welch) ------------------------------------------------------------------------------------
+// The call's segments are cut into blocks of B (WELCH_BLOCK_SEGMENTS) and groups of G; the chunks into pieces of MTS_PIPE_BYTES of
+// decoded bytes to decode (pipe_pieces; resident chunks weigh nothing).  Piece p owns the blocks whose first row lies in its chunks
+// and decodes the missing chunks those blocks read (a chunk read by blocks of two pieces is decoded in both).  A piece's blocks are
+// launched in runs that keep the partial slab <= WELCH_SLAB_BYTES, each followed by the combine that adds them to their groups'
+// sums in block order: every group sum is the same sequence of additions whatever the pieces and runs.
+static const u64 WELCH_SLAB_BYTES = 256ull << 20;
+
+// exp(-2 pi i q / n) for q < n: the first octant in extended precision, the rest by exact symmetries (q = 0 gives exactly 1)
+static void welch_twiddle(long q, long n, long double *re, long double *im)
+{
+    const long n4 = n / 4, quad = q / n4;
+    long r = q % n4;
+    const bool flip = 2 * r > n4;                                // cos(pi/2 - a) = sin(a)
+    if (flip) r = n4 - r;
+    const long double a = 2.0L * 3.14159265358979323846264338327950288L * (long double)r / (long double)n;
+    long double c = r ? cosl(a) : 1.0L, s = r ? sinl(a) : 0.0L;
+    if (flip) std::swap(c, s);
+    long double cr, sr;                                          // cos, sin of the whole angle
+    switch (quad) {
+    case 0: cr = c; sr = s; break;
+    case 1: cr = -s; sr = c; break;
+    case 2: cr = -c; sr = -s; break;
+    default: cr = s; sr = -c; break;
+    }
+    *re = cr; *im = -sr;
+}
+
+static int welch_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device, const long *c_off,
+                     const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz, int flags, long row_seg0, long seg_begin,
+                     long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols, const int *cols, double *out,
+                     bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
+    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    if (nc <= 0 || n_chunks < 0 || n_cols < 1 || n_cols > (1 << 24) || !cols) { set_error("welch: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
+    if (nperseg < 16 || nperseg > MTS_WELCH_MAX_NPERSEG || (nperseg & (nperseg - 1))) {
+        set_error("welch: nperseg %d is not a power of two in [16, %d]", nperseg, MTS_WELCH_MAX_NPERSEG); return MTS_E_ARG;
+    }
+    if (step < 1 || step > nperseg) { set_error("welch: step %ld outside [1, %d]", step, nperseg); return MTS_E_ARG; }
+    if (!taper) { set_error("welch: no taper"); return MTS_E_ARG; }
+    for (int j = 0; j < nperseg; j++)
+        if (!std::isfinite(taper[j])) { set_error("welch: taper value %d is not finite", j); return MTS_E_ARG; }
+    if (csize != 4 && csize != 8) { set_error("welch: compute itemsize %d (4 or 8)", csize); return MTS_E_ARG; }
+    const long B = WELCH_BLOCK_SEGMENTS, GR = WELCH_GROUP_ROWS;
+    const long G = B * ((GR + step * B - 1) / (step * B));         // segments per group
+    if (seg_begin < 0 || seg_end <= seg_begin || seg_end - seg_begin > (1l << 40) || seg_begin % G || row_seg0 < 0 || row_seg0 > (1l << 60)) {
+        set_error("welch: segments [%ld, %ld) invalid or not aligned to groups of %ld", seg_begin, seg_end, G); return MTS_E_ARG;
+    }
+    if (!out) { set_error("welch: no output buffer"); return MTS_E_ARG; }
+    for (int j = 0; j < n_cols; j++)
+        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
+    for (int i = 0; i < n_chunks; i++) {
+        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
+        if (i && row0[i] != row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: chunks must be adjacent", i); return MTS_E_ARG; }
+        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
+        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
+    }
+    // the rows the segments read; the chunks must cover them
+    const long need_lo = row_seg0 + seg_begin * step, need_hi = row_seg0 + (seg_end - 1) * step + nperseg;
+    if (n_chunks == 0 || row0[0] > need_lo || row0[n_chunks - 1] + n_rows[n_chunks - 1] < need_hi) {
+        set_error("welch: the chunks do not cover rows [%ld, %ld)", need_lo, need_hi); return MTS_E_ARG;
+    }
+    for (int i = 0; i < n_chunks; i++) status[i] = MTS_CHUNK_OK;
+    int log2n = 0;
+    while ((1 << log2n) < nperseg) log2n++;
+    const long n_seg = seg_end - seg_begin, n_blocks = (n_seg + B - 1) / B, GB = G / B, n_groups = (n_seg + G - 1) / G;
+    const long b_first = seg_begin / B;                              // the call's block 0 (absolute)
+    const long n_elems = (long)(nperseg / 2 + 1) * n_cols;
+
+    // ---- which chunks are resident (whole rows), which are decoded here
+    auto entry_of = [&](int i) -> const CacheEntry * {
+        if (!cache) return nullptr;
+        auto it = cache->map.find(keys[i]);
+        if (it == cache->map.end()) return nullptr;
+        const CacheEntry &e = it->second;
+        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
+    };
+    std::vector<char> resident(n_chunks, 0);
+    std::vector<long> weight(n_chunks, 0);
+    for (int i = 0; i < n_chunks; i++) {
+        if (entry_of(i)) { resident[i] = 1; continue; }
+        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+        weight[i] = n_rows[i];
+    }
+    const u64 row_bytes = (u64)nc * sz;
+    // ---- pieces of blocks: [gb[p], gb[p + 1]) (call-local block indices) read chunks [c0, c1]
+    std::vector<int> pb = cdata_on_device ? std::vector<int>{0, n_chunks} : pipe_pieces(weight.data(), false, n_chunks, row_bytes);
+    const int np = (int)pb.size() - 1;
+    const long block_rows = step * B, row_b0 = row_seg0 + seg_begin * step; // first row of call block 0
+    std::vector<long> gb;
+    gb.push_back(0);
+    for (int p = 1; p < np; p++) {
+        const long r = row0[pb[p]] - row_b0;                        // the first block whose first row is in piece p
+        long k = r <= 0 ? 0 : (r + block_rows - 1) / block_rows;
+        if (k > n_blocks) k = n_blocks;
+        gb.push_back(std::max(k, gb.back()));
+    }
+    gb.push_back(n_blocks);
+    auto chunk_of = [&](long row) -> int {
+        int lo = 0, hi = n_chunks - 1;
+        while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row0[mid] <= row) lo = mid; else hi = mid - 1; }
+        return lo;
+    };
+    struct Piece { long b0, b1; int c0, c1; std::vector<int> miss; std::vector<long> ooff; u64 ws = 0; };
+    std::vector<Piece> pieces;
+    u64 piece_cap = 0;
+    for (int p = 0; p < np; p++) {
+        if (gb[p + 1] <= gb[p]) continue;
+        Piece Pc;
+        Pc.b0 = gb[p]; Pc.b1 = gb[p + 1];
+        const long s_lo = seg_begin + Pc.b0 * B, s_hi = std::min(seg_end, seg_begin + Pc.b1 * B);
+        Pc.c0 = chunk_of(row_seg0 + s_lo * step);
+        Pc.c1 = chunk_of(row_seg0 + (s_hi - 1) * step + nperseg - 1);
+        for (int i = Pc.c0; i <= Pc.c1; i++)
+            if (!resident[i]) { Pc.miss.push_back(i); Pc.ooff.push_back((long)Pc.ws); Pc.ws += align_up((u64)n_rows[i] * row_bytes, 256); }
+        piece_cap = std::max(piece_cap, Pc.ws);
+        pieces.push_back(std::move(Pc));
+    }
+    // compressed bytes of every chunk decoded here, once
+    std::vector<long> mcoff(n_chunks, 0);
+    u64 ctot = 0;
+    bool any_miss = false;
+    {
+        int prev = -1;
+        for (int i = 0; i < n_chunks; i++) {
+            if (resident[i]) continue;
+            any_miss = true;
+            if (cdata_on_device) { mcoff[i] = c_off[i]; continue; }
+            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
+            if (!joins) ctot = align_up(ctot + (prev >= 0 ? 16 : 0), 16);
+            mcoff[i] = (long)ctot; ctot += (u64)c_len[i];
+            prev = i;
+        }
+        ctot += 16;
+    }
+    // segment tables, one per piece: (c1 - c0 + 1) bases, then (c1 - c0 + 2) first rows
+    std::vector<long> seg_at(pieces.size() + 1, 0);
+    for (size_t g = 0; g < pieces.size(); g++) seg_at[g + 1] = seg_at[g] + 2l * (pieces[g].c1 - pieces[g].c0 + 1) + 1;
+    // blocks per launch: the slab of partials stays <= WELCH_SLAB_BYTES (at least one block)
+    const u64 blk_bytes = 8 * (u64)n_elems;
+    long run_blocks = (long)std::max<u64>(1, WELCH_SLAB_BYTES / blk_bytes);
+    run_blocks = std::min(run_blocks, std::min(n_blocks, 65535l));
+    const size_t o_taper = 0, o_tw = align_up((u64)csize * nperseg, 256), o_cols = o_tw + align_up(2 * (u64)csize * nperseg, 256),
+                 o_seg = o_cols + align_up(4 * (u64)n_cols, 256), o_part = o_seg + align_up(8 * (u64)(seg_at.back() + 1), 256),
+                 o_acc = o_part + align_up(blk_bytes * run_blocks, 256),
+                 o_end = out_on_host ? o_acc + align_up(8 * (u64)n_groups * n_elems, 256) : o_acc;
+    // ---- workspace: allocated BEFORE the resident entries are looked at (see decimate_run)
+    int rc;
+    if ((rc = E.welch.ensure(o_end + 256))) return rc;
+    if (any_miss && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
+    if (piece_cap && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
+    if (cache) {
+        for (int i = 0; i < n_chunks; i++)
+            if (resident[i] && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+    }
+    u8 *ws = E.welch.as<u8>();
+    // taper and twiddles, rounded once to the compute type
+    std::vector<u8> h_tt((size_t)csize * 3 * nperseg);
+    for (int j = 0; j < nperseg; j++) {
+        long double re, im;
+        welch_twiddle(j, nperseg, &re, &im);
+        if (csize == 4) {
+            const float w = (float)taper[j], tr = (float)re, ti = (float)im;
+            memcpy(h_tt.data() + 4 * j, &w, 4);
+            memcpy(h_tt.data() + 4 * nperseg + 8 * j, &tr, 4);
+            memcpy(h_tt.data() + 4 * nperseg + 8 * j + 4, &ti, 4);
+        } else {
+            const double tr = (double)re, ti = (double)im;
+            memcpy(h_tt.data() + 8 * j, &taper[j], 8);
+            memcpy(h_tt.data() + 8 * nperseg + 16 * j, &tr, 8);
+            memcpy(h_tt.data() + 8 * nperseg + 16 * j + 8, &ti, 8);
+        }
+    }
+    std::vector<long> seg(seg_at.back() + 1, 0);
+    std::vector<const u8 *> res_ptr(n_chunks, nullptr);
+    for (int i = 0; i < n_chunks; i++) if (resident[i]) res_ptr[i] = entry_of(i)->d;
+    for (size_t g = 0; g < pieces.size(); g++) {
+        const Piece &Pc = pieces[g];
+        long *b = seg.data() + seg_at[g], *r = b + (Pc.c1 - Pc.c0 + 1);
+        size_t m = 0;
+        for (int i = Pc.c0; i <= Pc.c1; i++) {
+            const u8 *base = resident[i] ? res_ptr[i] : E.h_out.as<u8>() + Pc.ooff[m++];
+            b[i - Pc.c0] = (long)(uintptr_t)base;
+            r[i - Pc.c0] = row0[i];
+        }
+        r[Pc.c1 - Pc.c0 + 1] = row0[Pc.c1] + n_rows[Pc.c1];
+    }
+    MTS_HIP(hipMemcpyAsync(ws + o_taper, h_tt.data(), (size_t)csize * nperseg, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_tw, h_tt.data() + (size_t)csize * nperseg, 2 * (size_t)csize * nperseg, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_seg, seg.data(), 8 * seg.size(), hipMemcpyHostToDevice, st));
+    double *d_acc = out_on_host ? (double *)(ws + o_acc) : out;
+    MTS_HIP(hipMemsetAsync(d_acc, 0, 8 * (size_t)n_groups * n_elems, st));
+    double *d_part = (double *)(ws + o_part);
+    const int dflags = flags & ~MTS_FLAG_UNSIGNED;
+    const int dev = E.dev;
+    std::vector<char> copied(n_chunks, 0);
+    auto copy_in = [&](int g) -> int {
+        if (cdata_on_device) return MTS_OK;
+        MTS_HIP(hipSetDevice(dev));
+        const std::vector<int> &mi = pieces[g].miss;
+        for (size_t a = 0; a < mi.size();) {
+            if (copied[mi[a]]) { a++; continue; }
+            size_t e = a + 1;
+            while (e < mi.size() && !copied[mi[e]] && mi[e] == mi[e - 1] + 1 && c_off[mi[e]] == c_off[mi[e - 1]] + c_len[mi[e - 1]] &&
+                   mcoff[mi[e]] == mcoff[mi[e - 1]] + c_len[mi[e - 1]]) e++;
+            u64 len = 0;
+            for (size_t z = a; z < e; z++) { len += (u64)c_len[mi[z]]; copied[mi[z]] = 1; }
+            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[mi[a]], cdata + c_off[mi[a]], (size_t)len); if (rc1) return rc1; }
+            a = e;
+        }
+        return MTS_OK;
+    };
+    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
+    const int ng = (int)pieces.size();
+    if (ng > 0 && (rc = copy_in(0))) return rc;
+    bool first_decode = true;
+    for (int g = 0; g < ng; g++) {
+        std::future<int> f_in;
+        if (g + 1 < ng) f_in = copy_beside(copy_in, g + 1);
+        const Piece &Pc = pieces[g];
+        const int nm = (int)Pc.miss.size();
+        if (nm) {
+            std::vector<long> co(nm), cl(nm), nr(nm);
+            std::vector<int> mst(nm, MTS_CHUNK_CORRUPT);
+            for (int z = 0; z < nm; z++) { co[z] = mcoff[Pc.miss[z]]; cl[z] = c_len[Pc.miss[z]]; nr[z] = n_rows[Pc.miss[z]]; }
+            rc = dev_decompress(E, st, d_src, co.data(), cl.data(), nr.data(), nm, nc, sz, dflags, E.h_out.as<u8>(), Pc.ooff.data(), mst.data(), 0,
+                                !first_decode);
+            first_decode = false;
+            if (!rc) for (int z = 0; z < nm; z++) if (mst[z] != MTS_CHUNK_OK) status[Pc.miss[z]] = mst[z];
+        }
+        if (!rc && cache) {
+            // (as in decimate_run: a decode allocation that failed drops the decoded chunks; this piece's tables must not point at a
+            // freed entry)
+            for (int i = Pc.c0; i <= Pc.c1 && !rc; i++) {
+                if (!resident[i]) continue;
+                const CacheEntry *e = entry_of(i);
+                if (!e || e->d != res_ptr[i]) {
+                    set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i);
+                    rc = MTS_E_MISS;
+                }
+            }
+        }
+        const long *sb = (const long *)(ws + o_seg) + seg_at[g];
+        const int ns = Pc.c1 - Pc.c0 + 1;
+        for (long lb = Pc.b0; !rc && lb < Pc.b1; lb += run_blocks) {
+            const long lb1 = std::min(Pc.b1, lb + run_blocks);
+            rc = launch_welch(st, sz, flags, csize, log2n, (const u8 *const *)sb, sb + ns, ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taper,
+                              ws + o_tw, row_seg0, step, seg_end, b_first + lb, lb1 - lb, detrend ? 1 : 0, d_part);
+            if (!rc) rc = launch_welch_combine(st, d_part, lb, lb1, GB, n_elems, d_acc);
+        }
+        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;
+        if (rc || rc_in) return rc ? rc : rc_in;
+    }
+    if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_acc, 8 * (size_t)n_groups * n_elems, hipMemcpyDeviceToHost, st));
+    MTS_HIP(hipStreamSynchronize(st));
+    return MTS_OK;
+}
+
 int mts_window_stats(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
                      const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
                      long row_end, long window_rows, int n_cols, const int *cols, void *out_min, void *out_max, void *out_sum, void *out_sumsq,
@@ -2121,6 +2384,44 @@ int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, con
     return decimate_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
                         itemsize, flags, valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols, d_out, false,
                         chunk_status);
+}
+
+int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+              const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_seg0,
+              long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,
+              const int *cols, double *out, int *chunk_status)
+{
+    DevCache *c = nullptr;
+    if (cache_id) {
+        int cdev = 0;
+        c = find_cache(cache_id, &cdev);
+        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
+    }
+    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;
+    MTS_HIP(hipSetDevice(E->dev));
+    return welch_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
+                     row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, csize, n_cols, cols, out, true, chunk_status);
+}
+
+int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
+                  const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0, long seg_begin, long seg_end,
+                  int nperseg, long step, const double *taper, int detrend, int csize, int n_cols, const int *cols, double *d_out,
+                  int *chunk_status)
+{
+    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    MTS_HIP(hipSetDevice(E->dev));
+    return welch_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
+                     itemsize, flags, row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, csize, n_cols, cols, d_out, false,
+                     chunk_status);
 }
 
 // ---- debug taps ---------------------------------------------------------------------------------

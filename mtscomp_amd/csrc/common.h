@@ -167,6 +167,19 @@ int launch_decimate(hipStream_t st, int itemsize, int flags, int out_itemsize, c
                     int n_channels, const int *d_cols, int n_cols, const void *d_taps, int n_taps, int q, long first_row, long k_begin,
                     long k_end, long valid_begin, long valid_end, void *d_out);
 
+// welch.hip: Welch PSD partials (mts_welch).  Segments s of blocks [block0, block0 + n_blocks) (block b: segments [b * B, (b + 1) * B)
+// ∩ [.., seg_end)) start at file row row_seg0 + s * step; d_part[(b - block0), k, c] = sum over the block's segments, in order, of
+// |X_k|^2 of column cols[c] (float64; X in the csize float type).  d_taper: 2^log2n values, d_tw: 2^log2n complex values
+// exp(-2 pi i q / 2^log2n), both in the compute type.  The combine adds the partials of call blocks [lb0, lb1) to the accumulators of
+// their groups (group_blocks blocks each; acc: (groups of the call, n_elems)) in block order.
+#define WELCH_BLOCK_SEGMENTS MTS_WELCH_BLOCK_SEGMENTS   // B and G: include/mtscomp_hip.h
+#define WELCH_GROUP_ROWS MTS_WELCH_GROUP_ROWS
+int welch_tile_columns(int csize, int log2n);
+int launch_welch(hipStream_t st, int itemsize, int flags, int csize, int log2n, const u8 *const *d_seg_base, const long *d_seg_row0, int n_segs,
+                 int n_channels, const int *d_cols, int n_cols, const void *d_taper, const void *d_tw, long row_seg0, long step, long seg_end,
+                 long block0, long n_blocks, int detrend, double *d_part);
+int launch_welch_combine(hipStream_t st, const double *d_part, long lb0, long lb1, long group_blocks, long n_elems, double *d_acc);
+
 // deflate.hip
 size_t hash_sort_ws_bytes(int n_tiles);                            // the one-pass sort's per-tile records
 int launch_hash_sort(hipStream_t st, const u8 *d_stream, const TileDesc *d_tiles, int n_tiles, u32 *d_tmp, u32 *d_sorted,

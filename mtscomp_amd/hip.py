@@ -105,6 +105,10 @@ def lib():
                                C.c_long, C.c_int, C.c_int, dp, C.c_int, C.c_int, ip, vp, ip]
     L.mts_dev_decimate.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
                                    C.c_int, C.c_int, dp, C.c_int, C.c_int, ip, vp, ip]
+    L.mts_welch.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int,
+                            C.c_long, dp, C.c_int, C.c_int, C.c_int, ip, vp, ip]
+    L.mts_dev_welch.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int,
+                                C.c_long, dp, C.c_int, C.c_int, C.c_int, ip, vp, ip]
     L.mts_release.restype = None
     _lib = L
     return L
@@ -117,7 +121,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_last_stage_times', 'mts_debug_match_tables', 'mts_debug_tokens', 'mts_debug_deflate',
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
-           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate']
+           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_welch', 'mts_dev_welch']
 
 
 def _check(rc, what):
@@ -449,6 +453,76 @@ def dev_decimate(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid
     res = None
     if download:
         res = np.empty((max(int(n_out), 0), cols.size), out_dtype)
+        if res.nbytes:
+            _check(lib().mts_dev_copy(out.device, None, _ptr(res), out.at(), res.nbytes, 1), 'mts_dev_copy')
+    return [int(x) for x in status[:rows.size]], res, out
+
+
+# ------------------------------------------------------------------------------------------------
+# Welch power spectral density (an extension: the reference has no such call)
+# ------------------------------------------------------------------------------------------------
+WELCH_MAX_NPERSEG = 16384
+WELCH_BLOCK_SEGMENTS = 32              # B: segments summed in order on the device (MTS_WELCH_BLOCK_SEGMENTS)
+WELCH_GROUP_ROWS = 1 << 20             # G: the smallest multiple of B segments with G * step >= this (MTS_WELCH_GROUP_ROWS)
+
+
+def welch_group_segments(step):
+    """G for a step: the smallest multiple of WELCH_BLOCK_SEGMENTS with G * step >= WELCH_GROUP_ROWS."""
+    b = WELCH_BLOCK_SEGMENTS
+    return b * -(-WELCH_GROUP_ROWS // (int(step) * b))
+
+
+def _welch_args(taper, compute_dtype, cols):
+    taper = np.ascontiguousarray(np.asarray(taper, dtype=np.float64).ravel())
+    csize = np.dtype(compute_dtype).itemsize
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    return taper, csize, cols
+
+
+def _welch_groups(seg_begin, seg_end, step):
+    return -(-(int(seg_end) - int(seg_begin)) // welch_group_segments(step))
+
+
+def welch(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg, step, taper,
+          detrend, compute_dtype, cols, device=0):
+    """mts_welch: the group sums of |X_k|^2 (float64, (n_groups, nperseg // 2 + 1, n_cols)) of segments [seg_begin, seg_end), segment s
+    covering file rows [row_seg0 + s * step, + nperseg), from the adjacent chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])).
+    cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).
+    Returns (status list, partials)."""
+    dtype = check_dtype(dtype)
+    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
+    taper, csize, cols = _welch_args(taper, compute_dtype, cols)
+    n = int(rows.size)
+    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
+    assert not n or int((offs + lens).max()) <= cdata.size
+    out = np.empty((max(_welch_groups(seg_begin, seg_end, step), 0), int(nperseg) // 2 + 1, cols.size), np.float64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    _check(lib().mts_welch(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
+                           dtype.itemsize, stats_flags(flags, dtype), int(row_seg0), int(seg_begin), int(seg_end), int(nperseg), int(step),
+                           taper.ctypes.data_as(C.POINTER(C.c_double)), int(bool(detrend)), csize, int(cols.size),
+                           cols.ctypes.data_as(C.POINTER(C.c_int)), _ptr(out), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_welch')
+    return [int(x) for x in status[:n]], out
+
+
+def dev_welch(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend,
+              compute_dtype, cols, out=None, download=True):
+    """mts_dev_welch on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the partials (made when None;
+    returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
+    dtype = check_dtype(dtype)
+    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
+    taper, csize, cols = _welch_args(taper, compute_dtype, cols)
+    shape = (max(_welch_groups(seg_begin, seg_end, step), 0), int(nperseg) // 2 + 1, cols.size)
+    nbytes = 8 * shape[0] * shape[1] * shape[2]
+    if out is None or out.nbytes < nbytes + 256:
+        out = DevBuffer(nbytes + 256, device=cbuf.device)
+    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
+    _check(lib().mts_dev_welch(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
+                               dtype.itemsize, stats_flags(flags, dtype), int(row_seg0), int(seg_begin), int(seg_end), int(nperseg), int(step),
+                               taper.ctypes.data_as(C.POINTER(C.c_double)), int(bool(detrend)), csize, int(cols.size),
+                               cols.ctypes.data_as(C.POINTER(C.c_int)), out.at(), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_welch')
+    res = None
+    if download:
+        res = np.empty(shape, np.float64)
         if res.nbytes:
             _check(lib().mts_dev_copy(out.device, None, _ptr(res), out.at(), res.nbytes, 1), 'mts_dev_copy')
     return [int(x) for x in status[:rows.size]], res, out
