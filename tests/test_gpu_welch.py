@@ -1,5 +1,5 @@
 """Reader.welch and mts_welch / mts_dev_welch on the MI355X: the FFT kernel against a float64 reference (welch_f64) within the
-derived bound (welch_bound) over the oracle's decode of every golden file and all ten item types at every nperseg, exact cases,
+derived per-bin bound (welch_bound_bins) over the oracle's decode of every golden file and all ten item types at every nperseg, exact cases,
 bit-identity across lanes, pieces, cache residency, repeats and columns, the two entry points, argument errors, a damaged chunk,
 special float values and the configs[1] recording in HBM."""
 import ctypes as C
@@ -14,7 +14,7 @@ import mtscomp_amd
 from mtscomp_amd import api, hip
 from tests.codec_oracle import OracleCodec
 from tests.test_gpu_window_stats import GOLDEN, CASES, _golden_reader, _hbm_recording, _oracle_decode
-from tests.welch_oracle import assert_welch_close, psd_scale, welch_bound, welch_f64
+from tests.welch_oracle import assert_welch_close, psd_scale, welch_bound_bins, welch_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,7 @@ def tmp_cfg(tmp_path, monkeypatch):
 
 def _check(r, dec, nperseg, start=0, stop=None, channels=slice(None), noverlap=None, window='hann', detrend='constant',
            scaling='density', dtype=np.float32):
-    """Reader.welch against welch_f64 over `dec` (the oracle's decode) within welch_bound; returns the largest error / bound."""
+    """Reader.welch against welch_f64 over `dec` (the oracle's decode) within welch_bound_bins; returns the largest error / bound."""
     f, got = r.welch(nperseg, start, stop, channels=channels, noverlap=noverlap, window=window, detrend=detrend, scaling=scaling, dtype=dtype)
     n, nc = dec.shape
     i0 = r._validate_index(start, 0)
@@ -41,10 +41,10 @@ def _check(r, dec, nperseg, start=0, stop=None, channels=slice(None), noverlap=N
         [int(c) % nc for c in channels]
     step = nperseg - (nperseg // 2 if noverlap is None else noverlap)
     taper = api.welch_window(window, nperseg)
-    tot, energy, n_seg = welch_f64(dec[:, cols], i0, i1, nperseg, step, taper, detrend == 'constant')
+    tot, _, n_seg, first = welch_f64(dec[:, cols], i0, i1, nperseg, step, taper, detrend == 'constant', dtype)
     k = psd_scale(nperseg, taper, scaling, r.sample_rate, n_seg)[:, None]
     assert got.dtype == np.float64 and f.shape == (nperseg // 2 + 1,)
-    return assert_welch_close(got.reshape(tot.shape), tot * k, welch_bound(nperseg, dtype, energy, n_seg)[None, :] * k)
+    return assert_welch_close(got.reshape(tot.shape), tot * k, welch_bound_bins(tot, first, n_seg) * k)
 
 
 def _file(tmp, x, rate=RATE, chunk_duration=1., **kw):
@@ -241,9 +241,10 @@ def test_groups_split_over_lanes_and_calls(tmp_cfg, monkeypatch):
         assert len(calls) == -(-n_seg // G) and sorted(s0 for _, s0, _ in calls) == list(range(0, n_seg, G))
         if nperseg >= 1024:
             taper = api.welch_window('hann', nperseg)
-            tot, energy, _ = welch_f64(x[:, [1]], 5, rows, nperseg, step, taper, True)
+            tot, _, _, first = welch_f64(x[:, [1]], 5, rows, nperseg, step, taper, True, dtype)
             k = psd_scale(nperseg, taper, 'density', RATE, n_seg)[:, None]
-            assert_welch_close(a[:, [1]], tot * k, welch_bound(nperseg, dtype, energy, n_seg)[None, :] * k)
+            print('%d %s: largest error / bound %.3g' % (nperseg, np.dtype(dtype).name,
+                                                         assert_welch_close(a[:, [1]], tot * k, welch_bound_bins(tot, first, n_seg) * k)))
     one.close()
     two.close()
 
@@ -299,8 +300,8 @@ def test_dev_entry_equals_host_entry_and_errors(tmp_cfg):
                           512, taper, True, np.float32, cols)
     assert st2 == [0] * len(rows)
     assert dev.tobytes() == host.tobytes()
-    tot, energy, _ = welch_f64(x, 0, n, 1024, 512, taper, True)
-    assert_welch_close(dev.sum(axis=0), tot, welch_bound(1024, np.float32, energy, n_seg)[None, :])
+    tot, _, _, first = welch_f64(x, 0, n, 1024, 512, taper, True, np.float32)
+    print('largest error / bound %.3g' % assert_welch_close(dev.sum(axis=0), tot, welch_bound_bins(tot, first, n_seg)))
     # MTS_E_ARG before anything runs, both entries
     L = hip.lib()
     lp = [np.ascontiguousarray(a, dtype=np.int64) for a in (slots, sizes, bounds[:-1], rows)]
@@ -375,7 +376,7 @@ def test_config1_in_hbm():
         assert st == [0] * len(keys)
         assert h1[0].tobytes() == got[1].tobytes()
     cols = np.arange(0, nc, 16)
-    tot, energy, _ = welch_f64(x[:, cols], 0, n, 1024, 512, taper, True)
     for cdt, got in zip((np.float32, np.float64), res):
+        tot, _, _, first = welch_f64(x[:, cols], 0, n, 1024, 512, taper, True, cdt)
         print('configs[1] %s: largest error / bound %.3g' % (np.dtype(cdt).name,
-                                                              assert_welch_close(got[:, cols], tot, welch_bound(1024, cdt, energy, n_seg)[None, :])))
+                                                              assert_welch_close(got[:, cols], tot, welch_bound_bins(tot, first, n_seg))))

@@ -1,5 +1,5 @@
 """Randomised parity of Reader.welch under -m gpu: tools/fuzz_welch_gpu.py for MTS_FUZZ_SECONDS (default 30) with a fixed seed
-(MTS_FUZZ_SEED overrides it; the seed is printed), every result against welch_f64 within welch_bound.  Replay a failure with
+(MTS_FUZZ_SEED overrides it; the seed is printed), every result against welch_f64 within welch_bound_bins.  Replay a failure with
     MTS_FUZZ_SEED=<seed> MTS_FUZZ_SECONDS=30 python -m pytest tests/test_gpu_welch_fuzz.py -m gpu -s
 """
 import os

@@ -6,7 +6,7 @@ import pytest
 import mtscomp_amd
 from mtscomp_amd import api, hip
 from tests.codec_oracle import OracleCodec
-from tests.welch_oracle import WelchOracleCodec, assert_welch_close, psd_scale, welch_bound, welch_f64
+from tests.welch_oracle import WelchOracleCodec, assert_welch_close, psd_scale, welch_bound_bins, welch_f64
 
 
 @pytest.fixture
@@ -51,9 +51,9 @@ def _check_scipy(r, x, nperseg, start, stop, channels, noverlap, window, detrend
     assert got.dtype == np.float64
     step = nperseg - (nperseg // 2 if noverlap is None else noverlap)
     taper = api.welch_window(window, nperseg)
-    _, energy, n_seg = welch_f64(x[:, cols], i0, i1, nperseg, step, taper, bool(detrend))
+    tot, _, n_seg, first = welch_f64(x[:, cols], i0, i1, nperseg, step, taper, bool(detrend), dtype)
     k = psd_scale(nperseg, taper, scaling, r.sample_rate, n_seg)
-    bound = k[:, None] * welch_bound(nperseg, dtype, energy, n_seg)[None, :]
+    bound = k[:, None] * welch_bound_bins(tot, first, n_seg)
     got2 = got.reshape(want.shape)
     assert_welch_close(got2, want, bound * 1.01 + 1e-12 * np.abs(want))   # (scipy's own float64 rounding: below 1e-12 relative)
     return got
@@ -101,7 +101,7 @@ def test_float64_restatement_matches_scipy():
     x = _recording(rows=5000, nc=3, seed=3).astype(np.float64)
     for nperseg, step, detrend in [(256, 128, True), (64, 64, False), (1024, 1000, True)]:
         taper = api.welch_window('hann', nperseg)
-        tot, energy, n_seg = welch_f64(x, 0, 5000, nperseg, step, taper, detrend)
+        tot, energy, n_seg, _ = welch_f64(x, 0, 5000, nperseg, step, taper, detrend)
         _, want = signal.welch(x, fs=1.0, nperseg=nperseg, noverlap=nperseg - step, detrend='constant' if detrend else False,
                                scaling='spectrum', axis=0)
         got = tot * psd_scale(nperseg, taper, 'spectrum', 1.0, n_seg)[:, None]
