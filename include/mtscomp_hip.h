@@ -45,11 +45,14 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_welch and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_welch, mts_gram and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
 #define MTS_WELCH_MAX_NPERSEG 16384
 #define MTS_WELCH_BLOCK_SEGMENTS 32   /* mts_welch: segments per block (B), summed in order on the device */
 #define MTS_WELCH_GROUP_ROWS (1l << 20) /* a group is the smallest multiple G of B segments with G * step >= this many rows */
+#define MTS_GRAM_GROUP_ROWS (1l << 20)  /* mts_gram: rows per group of a window (aligned to the window's start; the last may be short) */
+#define MTS_GRAM_SLAB_ROWS 4096         /* mts_gram: rows per slab of a group (aligned to the group's start; the last may be short) */
+#define MTS_GRAM_MAX_COLS 16384
 
 int mts_version(void);
 int mts_device_count(void);                 /* number of gfx950 devices visible; 0 if none */
@@ -248,6 +251,42 @@ int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, c
               long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,
               const int *cols, double *out, int *chunk_status);
 
+/*
+ * Channel x channel Gram matrices and column sums per window (an extension: the reference has no such call; its users form
+ * x.T @ x of Reader[...] on the host).  Only one partial per (group, column pair) crosses the bus.
+ *   grid           the range [range_begin, range_end) in windows [range_begin + w * window_rows, min(.. + window_rows, range_end));
+ *                  window w in groups of MTS_GRAM_GROUP_ROWS rows aligned to its start (the last may be short).  Groups are numbered
+ *                  window after window: with K = ceil(window_rows / MTS_GRAM_GROUP_ROWS), group g is group g % K of window g / K.
+ *                  The call computes groups [group_begin, group_end).
+ *   the tree       a group is cut into slabs of MTS_GRAM_SLAB_ROWS rows aligned to its start (the last may be short).  Items are
+ *                  converted to double once (exact but for 8-byte integers, which are rounded).  A slab's entry (i, j) is the chain of
+ *                  v_mfma_f64_16x16x4_f64 steps over its rows 4 at a time in row order, from +0 (rows past the slab's end read as 0);
+ *                  a group's entry is its slabs' entries added in slab order from +0, in double.  G[i, j] and G[j, i] are the same
+ *                  value (one triangle, mirrored).  Nothing depends on chunks, calls, pieces, lanes, cache residency or the other
+ *                  columns.  For an error bound: a product of a row goes through at most h = min(rows, SLAB) + slabs - 1 roundings
+ *                  inside its group (a 4-row step rounds a term at most 4 times), plus the groups of the window on the host.
+ *                  Column sums: per slab, the items added in row order from 0 (integers: int64 modulo 2^64; floats: double from +0),
+ *                  slabs in slab order.
+ *   out_gram       (group_end - group_begin, n_cols, n_cols): int64 for 1- and 2-byte integers (exact: a group's sum of products is
+ *                  an integer below 2^52), float64 for every other type
+ *   out_sum        (group_end - group_begin, n_cols): int64 for every integer type (numpy's wrap modulo 2^64, so that the host's
+ *                  sums equal np.sum(x, dtype=np.int64)), float64 for floats
+ *   chunks         as mts_decimate: adjacent, ascending, covering the groups' rows; cols: 1 <= n_cols <= MTS_GRAM_MAX_COLS, repeats
+ *                  allowed
+ *   chunk_status   MTS_CHUNK_* per chunk; the partials of a group that reads a failed chunk are undefined
+ * mts_gram: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated piece by piece (MTS_PIPE_BYTES) in a
+ * transient workspace and NOT inserted; pieces are cut at group boundaries, a chunk that groups of two pieces read is inflated in both.
+ * out_gram / out_sum are host memory.
+ * mts_dev_gram: device d_cdata, d_gram and d_sum on `device`, chunk_status on the host; no cache.
+ * MTS_E_ARG before anything is launched: n_cols < 1 or too many, a column outside [0, n_channels), window_rows < 1, an empty or
+ * negative range, a group run that is empty or outside the range, chunks not adjacent, empty or not covering the groups' rows.
+ */
+int mts_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+             const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long range_begin,
+             long range_end, long window_rows, long group_begin, long group_end, int n_cols, const int *cols, void *out_gram, void *out_sum,
+             int *chunk_status);
+
 /* ---------------------------------------------------------------------------------------------
  * Device-resident variants (inputs and outputs already in HBM; used by bench.py and by callers that
  * keep recordings on the GPU).  Pointers are device pointers on `device`; `stream` is a hipStream_t
@@ -275,6 +314,9 @@ int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const 
                   const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0,
                   long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,
                   const int *cols, double *d_out, int *chunk_status /* host */);
+int mts_dev_gram(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
+                 const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long range_begin, long range_end, long window_rows,
+                 long group_begin, long group_end, int n_cols, const int *cols, void *d_gram, void *d_sum, int *chunk_status /* host */);
 /* integer-exact synthetic recording, rows [t0, t1) of n_channels int16, on device */
 int mts_dev_synth_int16(int device, void *stream, void *d_out, long t0, long t1, int n_channels,
                         long seed);

@@ -65,6 +65,8 @@ WINDOW_STATS_CALL_BYTES = 1 << 30      # Reader.window_stats: compressed bytes p
 WINDOW_STATS_SLAB_BYTES = 1 << 30      # ... and partial results per call on the device (one per column and tile of <= 512 rows of a window)
 DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per device call (a longer range is split at output-row boundaries)
 WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
+GRAM_CALL_BYTES = 1 << 30              # Reader.cov: compressed bytes per device call (a longer range is split at group boundaries)
+GRAM_SLAB_BYTES = 1 << 30              # ... and partial results per call (one Gram matrix and one row of sums per group)
 
 logger = logging.getLogger('mtscomp_amd')
 logger.setLevel(logging.INFO)
@@ -315,6 +317,15 @@ class HipCodec:
         device = self.devices[(lane or 0) % len(self.devices)]
         return hip.welch(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg,
                          step, taper, detrend, compute_dtype, cols, device=device)
+
+    def gram(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows, group_begin,
+             group_end, cols, lane=None):
+        """Gram entries and column sums of groups [group_begin, group_end) of the grid (range, window_rows) from the adjacent chunks
+        `keys` on one device (`lane` modulo the devices, default the first): mts_gram.  cache_id: the lane's decoded-chunk cache (0:
+        none); chunks with lens[i] == 0 are read there.  -> (status list, gram (n_groups, n_cols, n_cols), sum (n_groups, n_cols))."""
+        device = self.devices[(lane or 0) % len(self.devices)]
+        return hip.gram(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows,
+                        group_begin, group_end, cols, device=device)
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1519,6 +1530,123 @@ class Reader:
             try:
                 return self.codec.welch(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), row_seg0,
                                         seg_begin, seg_end, nperseg, step, taper, detrend, compute_dtype, cols, lane=lane)
+            except hip.HipError as e:
+                if e.code != hip.E_MISS or attempt:
+                    raise
+                present = [False] * len(keys)                       # dropped since the query: send everything
+
+    # -- channel covariance on the device (an extension: the reference's users form x.T @ x of Reader[...] on the host)
+    def cov(self, start=0, stop=None, channels=slice(None), window=None, ddof=1):
+        """Per-window channel x channel covariance of rows [start, stop), on the device: only one Gram matrix and one row of sums per
+        group of rows cross the bus.  Per window this is np.cov(self[w0:w1, channels], rowvar=False, ddof=ddof) up to rounding.
+        Windows are [start + w * window, min(start + (w + 1) * window, stop)); window=None is one window over the range.  start / stop
+        follow Reader[...]; channels: an int (C = 1: nothing is squeezed), a slice with step >= 1, or a sequence of ints in any order,
+        repeats allowed.  ddof: an int >= 0.  Returns a Bunch: count (n_windows,) int64; sum (n_windows, C): int64 with numpy's wrap
+        for integer dtypes, float64 for floats; gram (n_windows, C, C) = sum over rows of x[t, i] * x[t, j]: int64 and exact (numpy's
+        wrap included) for 1- and 2-byte integers, else float64 with the items converted to float64 once (8-byte integers rounded);
+        mean = sum / count; cov = (float64(gram) - np.outer(float64(sum), mean)) / (count - ddof), NaN where count - ddof <= 0; start,
+        stop, window, channels.  The summation tree (include/mtscomp_hip.h, mts_gram) depends on the rows' offsets in their window
+        only: the same bits whatever the lanes, calls, cache residency, column set or order; G[i, j] and G[j, i] are equal.  The
+        raw-moment formula loses relative accuracy on float data whose mean is large compared with its spread (no centred two-pass
+        form).  Chunks resident in the device cache are read where they lie; the others are decoded in a transient workspace and NOT
+        kept.  A damaged chunk raises the IOError of Reader[...]."""
+        if not callable(getattr(self.codec, 'gram', None)):
+            raise NotImplementedError("cov needs a codec that forms Gram matrices on the device (HipCodec); %r has none"
+                                      % getattr(self.codec, 'name', self.codec))
+        i0 = self._validate_index(start, 0)
+        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        if window is None:
+            window = max(i1 - i0, 1)
+        if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1:
+            raise ValueError("window must be an int >= 1 or None, got %r" % (window,))
+        window = int(window)
+        if not isinstance(ddof, (int, np.integer)) or isinstance(ddof, bool) or ddof < 0:
+            raise ValueError("ddof must be an int >= 0, got %r" % (ddof,))
+        ddof = int(ddof)
+        cols, _ = self._stats_channels(channels)
+        nc = int(cols.size)
+        n_win = -(-(i1 - i0) // window)
+        g_dt, s_dt = hip.gram_dtypes(self.dtype)
+        gram = np.zeros((n_win, nc, nc), g_dt)
+        sm = np.zeros((n_win, nc), s_dt)
+        cnt = np.minimum(window, i1 - i0 - window * np.arange(n_win, dtype=np.int64)).astype(np.int64)
+        if n_win and nc:
+            K = -(-window // hip.GRAM_GROUP_ROWS)
+            n_groups = hip.gram_groups(i0, i1, window)
+            g = np.arange(n_groups, dtype=np.int64)
+            w0 = i0 + (g // K) * window
+            glo = w0 + (g % K) * hip.GRAM_GROUP_ROWS
+            ghi = np.minimum(np.minimum(glo + hip.GRAM_GROUP_ROWS, w0 + window), i1)
+            bounds, offsets = np.asarray(self.chunk_bounds, np.int64), np.asarray(self.chunk_offsets, np.int64)
+            gc0 = np.searchsorted(bounds, glo, 'right') - 1
+            gc1 = np.searchsorted(bounds, ghi - 1, 'right') - 1
+            # calls: whole groups, cut where the compressed bytes of their chunks pass GRAM_CALL_BYTES or their results GRAM_SLAB_BYTES
+            cum = np.concatenate(([0], np.cumsum(offsets[gc1 + 1] - offsets[gc0])))
+            per_call = max(1, GRAM_SLAB_BYTES // (8 * (nc * nc + nc)))
+            cuts = [0]
+            while cuts[-1] < n_groups:
+                a = cuts[-1]
+                b = int(np.searchsorted(cum, cum[a] + GRAM_CALL_BYTES, 'right')) - 1
+                cuts.append(min(n_groups, a + per_call, max(b, a + 1)))
+            lanes = self._n_lanes()
+            use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
+            status = {}
+            for ga, gb in zip(cuts[:-1], cuts[1:]):
+                # lanes: contiguous runs of the call's groups
+                nl = max(1, min(lanes, gb - ga))
+                runs = [ga + (gb - ga) * j // nl for j in range(nl + 1)]
+                res = [None] * nl
+
+                def one(j, runs=runs, res=res):
+                    a, b = runs[j], runs[j + 1]
+                    if b <= a:
+                        return
+                    keys = list(range(int(gc0[a]), int(gc1[b - 1]) + 1))
+                    cache = self._cache_for(j) if use_cache else 0
+                    res[j] = (keys,) + tuple(self._lane_gram(cache, keys, i0, i1, window, a, b, cols, j))
+                self.codec.run_lanes(one, nl)
+                for j in range(nl):                                 # groups in order: the float sums are the same every time
+                    if res[j] is None:
+                        continue
+                    keys, st, gp, sp = res[j]
+                    for k, v in zip(keys, st):
+                        if v != hip.CHUNK_OK or k not in status:
+                            status[k] = v
+                    a, b = runs[j], runs[j + 1]
+                    if K == 1:
+                        gram[a:b] += gp
+                        sm[a:b] += sp
+                    else:
+                        for z in range(b - a):
+                            gram[(a + z) // K] += gp[z]
+                            sm[(a + z) // K] += sp[z]
+            self._raise_for(status)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            sf = sm.astype(np.float64)
+            mean = sf / cnt[:, None]
+            denom = cnt - ddof
+            cov = (gram.astype(np.float64) - sf[:, :, None] * mean[:, None, :]) / denom[:, None, None]
+        cov[denom <= 0] = np.nan
+        return Bunch(count=cnt, sum=sm, gram=gram, mean=mean, cov=cov, start=i0, stop=i1, window=window, channels=cols)
+
+    def _lane_gram(self, cache, keys, range_begin, range_end, window, group_begin, group_end, cols, lane):
+        """One codec.gram call on one lane: chunks resident in its cache go without bytes, the others' compressed bytes come from a
+        mapping of the file (or one read); sent whole once more if an entry was dropped between the query and the call."""
+        row0 = [self.chunk_bounds[k] for k in keys]
+        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
+        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
+        for attempt in range(2):
+            need = [k for k, p in zip(keys, present) if not p]
+            base = self.chunk_offsets[need[0]] if need else 0
+            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
+            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
+            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
+            buf = self._map_range(nbytes, base) if need else b''
+            if buf is None:
+                buf = self._pread(nbytes, base)
+            try:
+                return self.codec.gram(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), range_begin,
+                                       range_end, window, group_begin, group_end, cols, lane=lane)
             except hip.HipError as e:
                 if e.code != hip.E_MISS or attempt:
                     raise

@@ -150,6 +150,8 @@ struct Engine {
     DBuf dec;
     // Welch PSD: taper, twiddles, columns, segment tables, block partials, group sums
     DBuf welch;
+    // Gram matrices: columns, slab and group tables, slab partials, the accumulators of the host entry point
+    DBuf gram;
     // geometry of the last compress batch whose per-segment / per-block / per-tile descriptors are on the device (a recording is
     // compressed batch after batch of the same shape: the 10 MB of index arrays need not be rebuilt and copied every call)
     // (valid while the three buffers are the allocations the arrays were copied into: DBuf::gen, not the address -- a buffer
@@ -199,7 +201,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &welch};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &welch, &gram};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();
@@ -2422,6 +2424,301 @@ int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const 
     return welch_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
                      itemsize, flags, row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, csize, n_cols, cols, d_out, false,
                      chunk_status);
+}
+
+// ---- Gram matrices (mts_gram, mts_dev_gram) ----------------------------------------------------------------------------------
+// The call's groups are cut into slabs of GRAM_SLAB_ROWS rows; the chunks into pieces of MTS_PIPE_BYTES of decoded bytes to decode
+// (pipe_pieces; resident chunks weigh nothing).  Piece p owns the groups whose first row lies in its chunks and decodes the missing
+// chunks those groups read (a chunk read by groups of two pieces is decoded in both).  A piece's slabs are launched in runs that keep
+// the partial slab <= GRAM_SLAB_BYTES, each followed by the combine that adds them to their groups' accumulators in slab order: every
+// group sum is the same sequence of additions whatever the pieces and runs.
+static const u64 GRAM_SLAB_BYTES = 256ull << 20;
+
+static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device, const long *c_off,
+                    const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz, int flags, long range_begin,
+                    long range_end, long window_rows, long group_begin, long group_end, int n_cols, const int *cols, void *out_gram, void *out_sum,
+                    bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
+    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    if (nc <= 0 || n_chunks < 0 || n_cols < 1 || n_cols > MTS_GRAM_MAX_COLS || !cols) {
+        set_error("gram: n_channels, n_chunks or columns invalid (1 <= n_cols <= %d)", MTS_GRAM_MAX_COLS); return MTS_E_ARG;
+    }
+    if (window_rows < 1) { set_error("gram: window_rows %ld < 1", window_rows); return MTS_E_ARG; }
+    if (range_begin < 0 || range_end <= range_begin || range_end > (1l << 60)) { set_error("gram: range [%ld, %ld) invalid", range_begin, range_end); return MTS_E_ARG; }
+    const long GR = GRAM_GROUP_ROWS, SR = GRAM_SLAB_ROWS;
+    const long K = (window_rows + GR - 1) / GR;                   // groups per whole window
+    const long n_range = range_end - range_begin, n_full = n_range / window_rows, tail = n_range % window_rows;
+    const long total_groups = n_full * K + (tail + GR - 1) / GR;
+    if (group_begin < 0 || group_end <= group_begin || group_end > total_groups) {
+        set_error("gram: groups [%ld, %ld) empty or outside the %ld groups of the range", group_begin, group_end, total_groups); return MTS_E_ARG;
+    }
+    if (!out_gram || !out_sum) { set_error("gram: no output buffer"); return MTS_E_ARG; }
+    for (int j = 0; j < n_cols; j++)
+        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
+    for (int i = 0; i < n_chunks; i++) {
+        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
+        if (i && row0[i] != row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: chunks must be adjacent", i); return MTS_E_ARG; }
+        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
+        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
+    }
+    // the groups' rows: group g -> [grow[g], grow_end(g))
+    const long n_groups = group_end - group_begin;
+    if (n_groups > (1l << 31)) { set_error("gram: too many groups in one call"); return MTS_E_ARG; }
+    auto group_rows = [&](long g, long *lo, long *hi) {
+        const long w = g / K, k = g % K, w0 = range_begin + w * window_rows;
+        const long w1 = std::min(w0 + window_rows, range_end);
+        *lo = w0 + k * GR;
+        *hi = std::min(*lo + GR, w1);
+    };
+    long need_lo, need_hi, tmp;
+    group_rows(group_begin, &need_lo, &tmp);
+    group_rows(group_end - 1, &tmp, &need_hi);
+    if (n_chunks == 0 || row0[0] > need_lo || row0[n_chunks - 1] + n_rows[n_chunks - 1] < need_hi) {
+        set_error("gram: the chunks do not cover rows [%ld, %ld)", need_lo, need_hi); return MTS_E_ARG;
+    }
+    for (int i = 0; i < n_chunks; i++) status[i] = MTS_CHUNK_OK;
+    // slabs of the call: slab_rows (2 per slab), gfirst[g] the first slab of call group g
+    std::vector<long> gfirst(n_groups + 1, 0), glo(n_groups);
+    long n_slabs = 0;
+    for (long g = 0; g < n_groups; g++) {
+        long lo, hi;
+        group_rows(group_begin + g, &lo, &hi);
+        glo[g] = lo;
+        gfirst[g] = n_slabs;
+        n_slabs += (hi - lo + SR - 1) / SR;
+    }
+    gfirst[n_groups] = n_slabs;
+    std::vector<long> slab_rows(2 * (size_t)n_slabs);
+    for (long g = 0; g < n_groups; g++) {
+        long lo, hi;
+        group_rows(group_begin + g, &lo, &hi);
+        for (long s = gfirst[g], r = lo; s < gfirst[g + 1]; s++, r += SR) { slab_rows[2 * s] = r; slab_rows[2 * s + 1] = std::min(r + SR, hi); }
+    }
+
+    // ---- which chunks are resident (whole rows), which are decoded here
+    auto entry_of = [&](int i) -> const CacheEntry * {
+        if (!cache) return nullptr;
+        auto it = cache->map.find(keys[i]);
+        if (it == cache->map.end()) return nullptr;
+        const CacheEntry &e = it->second;
+        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
+    };
+    std::vector<char> resident(n_chunks, 0);
+    std::vector<long> weight(n_chunks, 0);
+    for (int i = 0; i < n_chunks; i++) {
+        if (entry_of(i)) { resident[i] = 1; continue; }
+        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+        weight[i] = n_rows[i];
+    }
+    const u64 row_bytes = (u64)nc * sz;
+    // ---- pieces of groups: [gp[p], gp[p + 1]) (call-local group indices) read chunks [c0, c1]
+    std::vector<int> pb = cdata_on_device ? std::vector<int>{0, n_chunks} : pipe_pieces(weight.data(), false, n_chunks, row_bytes);
+    const int np = (int)pb.size() - 1;
+    std::vector<long> gp;
+    gp.push_back(0);
+    for (int p = 1; p < np; p++) {
+        const long r = row0[pb[p]];                                     // the first group whose first row is in piece p
+        const long k = std::lower_bound(glo.begin(), glo.end(), r) - glo.begin();
+        gp.push_back(std::max(k, gp.back()));
+    }
+    gp.push_back(n_groups);
+    auto chunk_of = [&](long row) -> int {
+        int lo = 0, hi = n_chunks - 1;
+        while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row0[mid] <= row) lo = mid; else hi = mid - 1; }
+        return lo;
+    };
+    struct Piece { long g0, g1; int c0, c1; std::vector<int> miss; std::vector<long> ooff; u64 ws = 0; };
+    std::vector<Piece> pieces;
+    u64 piece_cap = 0;
+    for (int p = 0; p < np; p++) {
+        if (gp[p + 1] <= gp[p]) continue;
+        Piece Pc;
+        Pc.g0 = gp[p]; Pc.g1 = gp[p + 1];
+        Pc.c0 = chunk_of(slab_rows[2 * gfirst[Pc.g0]]);
+        Pc.c1 = chunk_of(slab_rows[2 * gfirst[Pc.g1] - 1] - 1);
+        for (int i = Pc.c0; i <= Pc.c1; i++)
+            if (!resident[i]) { Pc.miss.push_back(i); Pc.ooff.push_back((long)Pc.ws); Pc.ws += align_up((u64)n_rows[i] * row_bytes, 256); }
+        piece_cap = std::max(piece_cap, Pc.ws);
+        pieces.push_back(std::move(Pc));
+    }
+    // compressed bytes of every chunk decoded here, once
+    std::vector<long> mcoff(n_chunks, 0);
+    u64 ctot = 0;
+    bool any_miss = false;
+    {
+        int prev = -1;
+        for (int i = 0; i < n_chunks; i++) {
+            if (resident[i]) continue;
+            any_miss = true;
+            if (cdata_on_device) { mcoff[i] = c_off[i]; continue; }
+            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
+            if (!joins) ctot = align_up(ctot + (prev >= 0 ? 16 : 0), 16);
+            mcoff[i] = (long)ctot; ctot += (u64)c_len[i];
+            prev = i;
+        }
+        ctot += 16;
+    }
+    // segment tables, one per piece: (c1 - c0 + 1) bases, then (c1 - c0 + 2) first rows
+    std::vector<long> seg_at(pieces.size() + 1, 0);
+    for (size_t g = 0; g < pieces.size(); g++) seg_at[g + 1] = seg_at[g] + 2l * (pieces[g].c1 - pieces[g].c0 + 1) + 1;
+    // slabs per launch: the partials stay <= GRAM_SLAB_BYTES (at least one slab)
+    const u64 slab_bytes = (u64)gram_slab_bytes(n_cols);
+    long run_slabs = (long)std::max<u64>(1, GRAM_SLAB_BYTES / slab_bytes);
+    run_slabs = std::min(run_slabs, std::min(n_slabs, 65535l));
+    const u64 nn = (u64)n_cols * n_cols;
+    const size_t o_cols = 0, o_slab = align_up(4 * (u64)n_cols, 256), o_gf = o_slab + align_up(16 * (u64)n_slabs, 256),
+                 o_seg = o_gf + align_up(8 * (u64)(n_groups + 1), 256), o_part = o_seg + align_up(8 * (u64)(seg_at.back() + 1), 256),
+                 o_psum = o_part + align_up((u64)run_slabs * gram_pairs(n_cols) * 64 * 64 * 8, 256),
+                 o_acc = o_psum + align_up((u64)run_slabs * 8 * n_cols, 256),
+                 o_accs = o_acc + (out_on_host ? align_up(8 * (u64)n_groups * nn, 256) : 0),
+                 o_end = o_accs + (out_on_host ? align_up(8 * (u64)n_groups * n_cols, 256) : 0);
+    // ---- workspace: allocated BEFORE the resident entries are looked at (see decimate_run)
+    int rc;
+    if ((rc = E.gram.ensure(o_end + 256))) return rc;
+    if (any_miss && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
+    if (piece_cap && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
+    if (cache) {
+        for (int i = 0; i < n_chunks; i++)
+            if (resident[i] && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+    }
+    u8 *ws = E.gram.as<u8>();
+    std::vector<long> seg(seg_at.back() + 1, 0);
+    std::vector<const u8 *> res_ptr(n_chunks, nullptr);
+    for (int i = 0; i < n_chunks; i++) if (resident[i]) res_ptr[i] = entry_of(i)->d;
+    for (size_t g = 0; g < pieces.size(); g++) {
+        const Piece &Pc = pieces[g];
+        long *b = seg.data() + seg_at[g], *r = b + (Pc.c1 - Pc.c0 + 1);
+        size_t m = 0;
+        for (int i = Pc.c0; i <= Pc.c1; i++) {
+            const u8 *base = resident[i] ? res_ptr[i] : E.h_out.as<u8>() + Pc.ooff[m++];
+            b[i - Pc.c0] = (long)(uintptr_t)base;
+            r[i - Pc.c0] = row0[i];
+        }
+        r[Pc.c1 - Pc.c0 + 1] = row0[Pc.c1] + n_rows[Pc.c1];
+    }
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_slab, slab_rows.data(), 16 * (size_t)n_slabs, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_gf, gfirst.data(), 8 * (size_t)(n_groups + 1), hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_seg, seg.data(), 8 * seg.size(), hipMemcpyHostToDevice, st));
+    double *d_gram = out_on_host ? (double *)(ws + o_acc) : (double *)out_gram;
+    u64 *d_sum = out_on_host ? (u64 *)(ws + o_accs) : (u64 *)out_sum;
+    MTS_HIP(hipMemsetAsync(d_gram, 0, 8 * (size_t)n_groups * nn, st));
+    MTS_HIP(hipMemsetAsync(d_sum, 0, 8 * (size_t)n_groups * n_cols, st));
+    double *d_part = (double *)(ws + o_part);
+    u64 *d_psum = (u64 *)(ws + o_psum);
+    const long *d_slab = (const long *)(ws + o_slab), *d_gf = (const long *)(ws + o_gf);
+    const bool exact = !(flags & MTS_FLAG_FLOAT) && sz <= 2;
+    const int float_sum = (flags & MTS_FLAG_FLOAT) ? 1 : 0;
+    const int dflags = flags & ~MTS_FLAG_UNSIGNED;
+    const int dev = E.dev;
+    std::vector<char> copied(n_chunks, 0);
+    auto copy_in = [&](int g) -> int {
+        if (cdata_on_device) return MTS_OK;
+        MTS_HIP(hipSetDevice(dev));
+        const std::vector<int> &mi = pieces[g].miss;
+        for (size_t a = 0; a < mi.size();) {
+            if (copied[mi[a]]) { a++; continue; }
+            size_t e = a + 1;
+            while (e < mi.size() && !copied[mi[e]] && mi[e] == mi[e - 1] + 1 && c_off[mi[e]] == c_off[mi[e - 1]] + c_len[mi[e - 1]] &&
+                   mcoff[mi[e]] == mcoff[mi[e - 1]] + c_len[mi[e - 1]]) e++;
+            u64 len = 0;
+            for (size_t z = a; z < e; z++) { len += (u64)c_len[mi[z]]; copied[mi[z]] = 1; }
+            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[mi[a]], cdata + c_off[mi[a]], (size_t)len); if (rc1) return rc1; }
+            a = e;
+        }
+        return MTS_OK;
+    };
+    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
+    const int ng = (int)pieces.size();
+    if (ng > 0 && (rc = copy_in(0))) return rc;
+    bool first_decode = true;
+    for (int g = 0; g < ng; g++) {
+        std::future<int> f_in;
+        if (g + 1 < ng) f_in = copy_beside(copy_in, g + 1);
+        const Piece &Pc = pieces[g];
+        const int nm = (int)Pc.miss.size();
+        if (nm) {
+            std::vector<long> co(nm), cl(nm), nr(nm);
+            std::vector<int> mst(nm, MTS_CHUNK_CORRUPT);
+            for (int z = 0; z < nm; z++) { co[z] = mcoff[Pc.miss[z]]; cl[z] = c_len[Pc.miss[z]]; nr[z] = n_rows[Pc.miss[z]]; }
+            rc = dev_decompress(E, st, d_src, co.data(), cl.data(), nr.data(), nm, nc, sz, dflags, E.h_out.as<u8>(), Pc.ooff.data(), mst.data(), 0,
+                                !first_decode);
+            first_decode = false;
+            if (!rc) for (int z = 0; z < nm; z++) if (mst[z] != MTS_CHUNK_OK) status[Pc.miss[z]] = mst[z];
+        }
+        if (!rc && cache) {
+            // (as in decimate_run: a decode allocation that failed drops the decoded chunks; this piece's tables must not point at a
+            // freed entry)
+            for (int i = Pc.c0; i <= Pc.c1 && !rc; i++) {
+                if (!resident[i]) continue;
+                const CacheEntry *e = entry_of(i);
+                if (!e || e->d != res_ptr[i]) {
+                    set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i);
+                    rc = MTS_E_MISS;
+                }
+            }
+        }
+        const long *sb = (const long *)(ws + o_seg) + seg_at[g];
+        const int ns = Pc.c1 - Pc.c0 + 1;
+        const long p_s0 = gfirst[Pc.g0], p_s1 = gfirst[Pc.g1];
+        for (long s = p_s0; !rc && s < p_s1; s += run_slabs) {
+            const long s1 = std::min(p_s1, s + run_slabs);
+            rc = launch_gram(st, sz, flags, (const u8 *const *)sb, sb + ns, ns, nc, (const int *)(ws + o_cols), n_cols, d_slab, s, s1 - s, d_part, d_psum);
+            // the groups the slabs [s, s1) belong to
+            const long g0 = std::upper_bound(gfirst.begin(), gfirst.end(), s) - gfirst.begin() - 1;
+            const long g1 = std::lower_bound(gfirst.begin(), gfirst.end(), s1) - gfirst.begin();
+            for (long ga = g0; !rc && ga < g1; ga += 65535)
+                rc = launch_gram_combine(st, d_part, d_psum, s, s1, ga, std::min(g1, ga + 65535), d_gf, n_cols, float_sum, d_gram, d_sum);
+        }
+        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;
+        if (rc || rc_in) return rc ? rc : rc_in;
+    }
+    if (exact && (rc = launch_gram_finish(st, d_gram, n_groups * (long)nn))) return rc;
+    if (out_on_host) {
+        MTS_HIP(hipMemcpyAsync(out_gram, d_gram, 8 * (size_t)n_groups * nn, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_sum, d_sum, 8 * (size_t)n_groups * n_cols, hipMemcpyDeviceToHost, st));
+    }
+    MTS_HIP(hipStreamSynchronize(st));
+    return MTS_OK;
+}
+
+int mts_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+             const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long range_begin,
+             long range_end, long window_rows, long group_begin, long group_end, int n_cols, const int *cols, void *out_gram, void *out_sum,
+             int *chunk_status)
+{
+    DevCache *c = nullptr;
+    if (cache_id) {
+        int cdev = 0;
+        c = find_cache(cache_id, &cdev);
+        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
+    }
+    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;
+    MTS_HIP(hipSetDevice(E->dev));
+    return gram_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
+                    range_begin, range_end, window_rows, group_begin, group_end, n_cols, cols, out_gram, out_sum, true, chunk_status);
+}
+
+int mts_dev_gram(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
+                 const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long range_begin, long range_end, long window_rows,
+                 long group_begin, long group_end, int n_cols, const int *cols, void *d_gram, void *d_sum, int *chunk_status)
+{
+    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    MTS_HIP(hipSetDevice(E->dev));
+    return gram_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
+                    itemsize, flags, range_begin, range_end, window_rows, group_begin, group_end, n_cols, cols, d_gram, d_sum, false,
+                    chunk_status);
 }
 
 // ---- debug taps ---------------------------------------------------------------------------------

@@ -180,6 +180,24 @@ int launch_welch(hipStream_t st, int itemsize, int flags, int csize, int log2n, 
                  long block0, long n_blocks, int detrend, double *d_part);
 int launch_welch_combine(hipStream_t st, const double *d_part, long lb0, long lb1, long group_blocks, long n_elems, double *d_acc);
 
+// gram.hip: Gram partials (mts_gram).  Slab s of the call covers file rows [slab_rows[2 s], slab_rows[2 s + 1]) (GRAM_SLAB_ROWS rows of
+// a group at most, aligned to its start).  launch_gram: for the call's slabs [slab0, slab0 + n_slabs), d_part[s - slab0][pair][64][64]
+// double (pair: super tiles si <= sj of 64 columns, gram_pairs of them) and d_psum[s - slab0][c] (u64: integers modulo 2^64, floats as
+// double bits).  launch_gram_combine adds the slabs [s0, s1) (partials at d_part / d_psum) to the accumulators of their groups [g0, g1)
+// (d_gfirst[g]: the first slab of the call's group g) in slab order: d_gram (groups, n_cols, n_cols) double, d_sum (groups, n_cols).
+// launch_gram_finish turns n doubles holding integers into int64 in place.
+#define GRAM_GROUP_ROWS MTS_GRAM_GROUP_ROWS            // include/mtscomp_hip.h
+#define GRAM_SLAB_ROWS MTS_GRAM_SLAB_ROWS
+constexpr int GRAM_STEP_ROWS = 32;                    // rows staged in LDS per step of k_gram (a multiple of 4)
+static_assert(GRAM_SLAB_ROWS % GRAM_STEP_ROWS == 0, "slabs are whole steps");
+long gram_pairs(int n_cols);
+long gram_slab_bytes(int n_cols);                     // partial bytes per slab
+int launch_gram(hipStream_t st, int itemsize, int flags, const u8 *const *d_seg_base, const long *d_seg_row0, int n_segs, int n_channels,
+                const int *d_cols, int n_cols, const long *d_slab_rows, long slab0, long n_slabs, double *d_part, u64 *d_psum);
+int launch_gram_combine(hipStream_t st, const double *d_part, const u64 *d_psum, long s0, long s1, long g0, long g1, const long *d_gfirst, int n_cols,
+                        int float_sum, double *d_gram, u64 *d_sum);
+int launch_gram_finish(hipStream_t st, double *d_gram, long n);
+
 // deflate.hip
 size_t hash_sort_ws_bytes(int n_tiles);                            // the one-pass sort's per-tile records
 int launch_hash_sort(hipStream_t st, const u8 *d_stream, const TileDesc *d_tiles, int n_tiles, u32 *d_tmp, u32 *d_sorted,

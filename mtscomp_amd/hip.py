@@ -109,6 +109,10 @@ def lib():
                             C.c_long, dp, C.c_int, C.c_int, C.c_int, ip, vp, ip]
     L.mts_dev_welch.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int,
                                 C.c_long, dp, C.c_int, C.c_int, C.c_int, ip, vp, ip]
+    L.mts_gram.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
+                           C.c_long, C.c_int, ip, vp, vp, ip]
+    L.mts_dev_gram.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
+                               C.c_long, C.c_int, ip, vp, vp, ip]
     L.mts_release.restype = None
     _lib = L
     return L
@@ -121,7 +125,8 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_last_stage_times', 'mts_debug_match_tables', 'mts_debug_tokens', 'mts_debug_deflate',
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
-           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_welch', 'mts_dev_welch']
+           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_welch', 'mts_dev_welch',
+           'mts_gram', 'mts_dev_gram']
 
 
 def _check(rc, what):
@@ -526,6 +531,99 @@ def dev_welch(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_seg0
         if res.nbytes:
             _check(lib().mts_dev_copy(out.device, None, _ptr(res), out.at(), res.nbytes, 1), 'mts_dev_copy')
     return [int(x) for x in status[:rows.size]], res, out
+
+
+# ------------------------------------------------------------------------------------------------
+# channel x channel Gram matrices (an extension: the reference has no such call)
+# ------------------------------------------------------------------------------------------------
+GRAM_GROUP_ROWS = 1 << 20              # rows per group of a window, aligned to its start (MTS_GRAM_GROUP_ROWS)
+GRAM_SLAB_ROWS = 4096                  # rows per slab of a group, aligned to its start (MTS_GRAM_SLAB_ROWS)
+GRAM_MAX_COLS = 16384                  # MTS_GRAM_MAX_COLS
+
+
+def gram_exact(dtype):
+    """1- and 2-byte integers: a group's Gram entries are exact int64 (every partial sum is an integer below 2^52)."""
+    dtype = np.dtype(dtype)
+    return dtype.kind in 'iu' and dtype.itemsize <= 2
+
+
+def gram_dtypes(dtype):
+    """(gram, sum) dtypes of the partial results of one call: int64 Gram entries for 1- and 2-byte integers, float64 otherwise;
+    int64 sums (modulo 2^64) for every integer type, float64 for floats."""
+    dtype = np.dtype(dtype)
+    return np.dtype(np.int64 if gram_exact(dtype) else np.float64), np.dtype(np.float64 if dtype.kind == 'f' else np.int64)
+
+
+def gram_groups(range_begin, range_end, window_rows):
+    """The number of groups of the grid: windows of window_rows rows over [range_begin, range_end), each cut into groups of
+    GRAM_GROUP_ROWS rows aligned to its start."""
+    n, w = int(range_end) - int(range_begin), int(window_rows)
+    k = -(-w // GRAM_GROUP_ROWS)
+    return (n // w) * k + -(-(n % w) // GRAM_GROUP_ROWS)
+
+
+def gram_group_rows(range_begin, range_end, window_rows, g):
+    """File rows [lo, hi) of group g of the grid (group g % K of window g // K, K = ceil(window_rows / GRAM_GROUP_ROWS))."""
+    w = int(window_rows)
+    k = -(-w // GRAM_GROUP_ROWS)
+    w0 = int(range_begin) + (g // k) * w
+    lo = w0 + (g % k) * GRAM_GROUP_ROWS
+    return lo, min(lo + GRAM_GROUP_ROWS, w0 + w, int(range_end))
+
+
+def _gram_out(n_groups, n_cols, dtype, alloc=np.empty):
+    g_dt, s_dt = gram_dtypes(dtype)
+    return alloc((max(int(n_groups), 0), int(n_cols), int(n_cols)), g_dt), alloc((max(int(n_groups), 0), int(n_cols)), s_dt)
+
+
+def gram(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows, group_begin, group_end,
+         cols, device=0):
+    """mts_gram: the Gram entries and column sums of groups [group_begin, group_end) of the grid (range, window_rows), from the
+    adjacent chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])).  cache_id 0: no cache, every chunk comes with its bytes; else
+    chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, gram (n_groups, n_cols, n_cols), sum (n_groups,
+    n_cols)) in the gram_dtypes of the recording's dtype."""
+    dtype = check_dtype(dtype)
+    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    n = int(rows.size)
+    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
+    assert not n or int((offs + lens).max()) <= cdata.size
+    g, s = _gram_out(int(group_end) - int(group_begin), cols.size, dtype)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    _check(lib().mts_gram(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
+                          dtype.itemsize, stats_flags(flags, dtype), int(range_begin), int(range_end), int(window_rows), int(group_begin),
+                          int(group_end), int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)), _ptr(g), _ptr(s),
+                          status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_gram')
+    return [int(x) for x in status[:n]], g, s
+
+
+def dev_gram(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows, group_begin, group_end, cols,
+             out=None, download=True):
+    """mts_dev_gram on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for both results (Gram entries, then
+    the sums at a 256-byte aligned offset; made when None, returned so that a caller timing repeated calls can pass it again).
+    Returns (status list, gram or None, sum or None, out)."""
+    dtype = check_dtype(dtype)
+    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    ng = max(int(group_end) - int(group_begin), 0)
+    g_dt, s_dt = gram_dtypes(dtype)
+    g_bytes, s_bytes = 8 * ng * cols.size * cols.size, 8 * ng * cols.size
+    s_off = -(-g_bytes // 256) * 256
+    if out is None or out.nbytes < s_off + s_bytes + 256:
+        out = DevBuffer(s_off + s_bytes + 256, device=cbuf.device)
+    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
+    _check(lib().mts_dev_gram(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
+                              dtype.itemsize, stats_flags(flags, dtype), int(range_begin), int(range_end), int(window_rows), int(group_begin),
+                              int(group_end), int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)), out.at(), out.at(s_off),
+                              status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_gram')
+    g = s = None
+    if download:
+        g, s = _gram_out(ng, cols.size, dtype)
+        if g.nbytes:
+            _check(lib().mts_dev_copy(out.device, None, _ptr(g), out.at(), g.nbytes, 1), 'mts_dev_copy')
+        if s.nbytes:
+            _check(lib().mts_dev_copy(out.device, None, _ptr(s), out.at(s_off), s.nbytes, 1), 'mts_dev_copy')
+    return [int(x) for x in status[:rows.size]], g, s, out
 
 
 # ------------------------------------------------------------------------------------------------
