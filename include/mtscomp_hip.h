@@ -287,6 +287,49 @@ int mts_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, co
              long range_end, long window_rows, long group_begin, long group_end, int n_cols, const int *cols, void *out_gram, void *out_sum,
              int *chunk_status);
 
+/*
+ * One round of a radix select over the windows of mts_window_stats (an extension: the reference has no such call; its users sort
+ * Reader[...] on the host).  Order statistics do not combine across chunks; digit histograms of candidates do.  Only the histograms
+ * cross the bus.  The range, the windows, the chunks (ascending, not necessarily adjacent), cols, flags and chunk_status are those of
+ * mts_window_stats.
+ *   order key      a u64 with key_bits significant bits whose unsigned order is np.sort's order of the items:
+ *                    mode 0  the item in its own type, key_bits = 8 * itemsize.  Unsigned integers: the value.  Signed integers: the
+ *                            two's-complement pattern with the sign bit flipped.  Floats: with b the bit pattern and SIGN its top bit,
+ *                            a NaN of either sign -> all ones; -0 and +0 -> SIGN (one key); b & SIGN ? ~b : b | SIGN otherwise.
+ *                            All ones is the key of a NaN and of nothing else (+inf is below it).
+ *                    mode 1  the double d = double(x) - center[w, j] (one IEEE subtraction), mapped as a float; key_bits = 64
+ *                    mode 2  the double |d|, mapped the same way; key_bits = 64
+ *                  center: (n_windows, n_cols) doubles on the host, read in modes 1 and 2 only (may be NaN or infinite)
+ *   digits         MTS_RANK_BITS = 8 bits wide
+ *   selectors      MTS_RANK_SELECTORS = 2 per (window, column) cell: sel_shift (n_windows, 2, n_cols) ints and sel_prefix of the same
+ *                  shape, u64, on the host.  shift < 0: the selector is inactive.  Otherwise 0 <= shift <= key_bits - 8, and the
+ *                  selector's candidates are the cell's items with key >> (shift + 8) == prefix (every item when shift + 8 ==
+ *                  key_bits: the prefix must then be 0; a prefix must fit the key_bits - shift - 8 bits above the digit).  The two
+ *                  selectors of a cell are counted independently; a caller that wants every item counted once keeps their
+ *                  candidate sets disjoint.
+ *   outputs        hist  (n_windows, 2, 256, n_cols) u32: the number of candidates with (key >> shift) & 255 == digit (exact while a
+ *                        window has fewer than 2^32 rows)
+ *                  kmin, kmax  (n_windows, 2, n_cols) u64: the smallest and the largest candidate key; all ones and 0 when there
+ *                        is no candidate (and for an inactive selector)
+ *                  count (n_windows) rows of the window held by the chunks that decoded
+ *                  All of them are integers accumulated with integer atomics: counts add, kmin / kmax combine with min / max.  A
+ *                  caller that splits a window over calls, pieces or lanes combines the outputs in any order and gets the same bits.
+ * mts_rank_hist: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated (whole chunks, adler32 checked) and
+ * counted piece by piece in a transient workspace, the compressed bytes of the next piece crossing the bus beside the kernels; they
+ * are NOT inserted into the cache.  Outputs are host memory.
+ * mts_dev_rank_hist: device d_cdata and d_* outputs on `device`; selectors, center, count and chunk_status on the host; no cache.
+ * MTS_E_ARG before anything is launched: what mts_window_stats refuses, a mode outside 0..2, no center in modes 1 and 2, a shift
+ * above key_bits - 8, or a prefix that does not fit.
+ */
+#define MTS_RANK_BITS 8
+#define MTS_RANK_SELECTORS 2
+int mts_rank_hist(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                  const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
+                  long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
+                  const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *out_hist, unsigned long long *out_kmin,
+                  unsigned long long *out_kmax, long *out_count, int *chunk_status);
+
 /* ---------------------------------------------------------------------------------------------
  * Device-resident variants (inputs and outputs already in HBM; used by bench.py and by callers that
  * keep recordings on the GPU).  Pointers are device pointers on `device`; `stream` is a hipStream_t
@@ -317,6 +360,11 @@ int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const 
 int mts_dev_gram(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
                  const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long range_begin, long range_end, long window_rows,
                  long group_begin, long group_end, int n_cols, const int *cols, void *d_gram, void *d_sum, int *chunk_status /* host */);
+int mts_dev_rank_hist(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                      const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin,
+                      long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center /* host */,
+                      const unsigned long long *sel_prefix /* host */, const int *sel_shift /* host */, unsigned int *d_hist,
+                      unsigned long long *d_kmin, unsigned long long *d_kmax, long *count /* host */, int *chunk_status /* host */);
 /* integer-exact synthetic recording, rows [t0, t1) of n_channels int16, on device */
 int mts_dev_synth_int16(int device, void *stream, void *d_out, long t0, long t1, int n_channels,
                         long seed);

@@ -23,6 +23,7 @@ import os
 import threading
 import os.path as op
 from collections import OrderedDict
+from fractions import Fraction
 from multiprocessing.dummy import Pool as ThreadPool
 from pathlib import Path
 from threading import Lock
@@ -67,6 +68,9 @@ DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per d
 WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
 GRAM_CALL_BYTES = 1 << 30              # Reader.cov: compressed bytes per device call (a longer range is split at group boundaries)
 GRAM_SLAB_BYTES = 1 << 30              # ... and partial results per call (one Gram matrix and one row of sums per group)
+QUANTILE_CALL_BYTES = 1 << 30          # Reader.quantile / median / mad: compressed bytes per device call (split on chunk boundaries)
+QUANTILE_SLAB_BYTES = 1 << 30          # ... and histogram bytes per call (2 KiB per window and column): the windows are scanned in runs
+QUANTILE_METHODS = ('linear', 'lower', 'higher', 'nearest', 'midpoint')
 
 logger = logging.getLogger('mtscomp_amd')
 logger.setLevel(logging.INFO)
@@ -326,6 +330,15 @@ class HipCodec:
         device = self.devices[(lane or 0) % len(self.devices)]
         return hip.gram(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows,
                         group_begin, group_end, cols, device=device)
+
+    def rank_hist(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, mode,
+                  center, sel_prefix, sel_shift, lane=None):
+        """One round of the radix select over the chunks `keys` on one device (`lane` modulo the devices, default the first):
+        mts_rank_hist.  cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0 are read there.  -> (status list,
+        dict hist/kmin/kmax/count): the partials of these chunks, all integers (Reader.quantile combines the lanes in any order)."""
+        device = self.devices[(lane or 0) % len(self.devices)]
+        return hip.rank_hist(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows,
+                             cols, mode, center, sel_prefix, sel_shift, device=device)
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1277,6 +1290,322 @@ class Reader:
                 if e.code != hip.E_MISS or attempt:
                     raise
                 present = [False] * len(keys)                       # dropped since the query: send everything
+
+    # -- exact order statistics on the device (an extension: the reference's users sort Reader[...] on the host)
+    def _rank_setup(self, what, start, stop, window, channels):
+        if not callable(getattr(self.codec, 'rank_hist', None)):
+            raise NotImplementedError("%s needs a codec that selects on the device (HipCodec); %r has none"
+                                      % (what, getattr(self.codec, 'name', self.codec)))
+        i0 = self._validate_index(start, 0)
+        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        if window is None:
+            window = max(i1 - i0, 1)
+        if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1:
+            raise ValueError("window must be an int >= 1 or None, got %r" % (window,))
+        window = int(window)
+        if min(window, i1 - i0) >= 1 << 32:
+            raise ValueError("windows of 2^32 rows or more are not supported")
+        cols, squeeze = self._stats_channels(channels)
+        n_win = -(-(i1 - i0) // window)
+        count = np.minimum(window, i1 - i0 - window * np.arange(n_win, dtype=np.int64)).astype(np.int64)
+        return i0, i1, window, cols, squeeze, count
+
+    def _rank_center(self, center, n_win, n_cols):
+        c = np.asarray(0.0 if center is None else center)
+        if c.dtype.kind not in 'fiub':
+            raise ValueError("center must be None or an array of numbers")
+        try:
+            return np.ascontiguousarray(np.broadcast_to(c.astype(np.float64), (n_win, n_cols)))
+        except ValueError:
+            raise ValueError("center of shape %r does not broadcast to (n_windows, n_channels) = %r" % (c.shape, (n_win, n_cols))) from None
+
+    def _rank_scan(self, i0, i1, window, cols, ranks, mode=0, center=None):
+        """The order statistics `ranks` (n_windows, R) int64, 0 <= rank < rows of the window, of every (window, column) cell of the
+        grid: a most-significant-digit radix select whose rounds are mts_rank_hist calls.  -> (keys (n_windows, R, C) uint64 --
+        hip.rank_values turns them into items --, has_nan (n_windows, C), rounds: the mts_rank_hist passes made).  The windows are scanned in runs whose histograms fit
+        QUANTILE_SLAB_BYTES, RANK_SELECTORS ranks at a time; a run is at most ceil(key_bits / 8) rounds, each one pass over its
+        chunks."""
+        n_win, R = ranks.shape
+        S, nb = hip.RANK_SELECTORS, 1 << hip.RANK_BITS
+        out = np.zeros((n_win, R, cols.size), np.uint64)
+        has_nan = np.zeros((n_win, cols.size), bool)
+        rounds = 0
+        if not n_win or not cols.size or not R:
+            return out, has_nan, rounds
+        nan_key = hip.rank_key_nan(self.dtype, mode)
+        floats = bool(mode) or self.dtype.kind == 'f'
+        per_win = S * (4 * nb + 16) * cols.size
+        run_wins = max(1, QUANTILE_SLAB_BYTES // per_win)
+        status = {}
+        for ws in range(0, n_win, run_wins):
+            we = min(n_win, ws + run_wins)
+            rb, re = i0 + ws * window, min(i1, i0 + we * window)
+            first = bisect.bisect_right(self.chunk_bounds, rb) - 1
+            last = bisect.bisect_left(self.chunk_bounds, re) - 1
+            chunks = [k for k in range(max(first, 0), min(last, self.n_chunks - 1) + 1)
+                      if self.chunk_bounds[k + 1] > max(rb, self.chunk_bounds[k]) and self.chunk_bounds[k] < re]
+            calls, run, nbytes = [], [], 0
+            for k in chunks:
+                b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
+                if run and nbytes + b > QUANTILE_CALL_BYTES:
+                    calls.append(run)
+                    run, nbytes = [], 0
+                run.append(k)
+                nbytes += b
+            if run:
+                calls.append(run)
+            cen = center[ws:we] if mode else None
+            for r0 in range(0, R, S):
+                rk = ranks[ws:we, r0:r0 + S]
+                got = rk.shape[1]
+                if got < S:                                         # (an odd rank out: the second selector repeats it and shares its histogram)
+                    rk = np.concatenate([rk] + [rk[:, -1:]] * (S - got), axis=1)
+                keys, kmax0, n_rounds = self._rank_rounds(calls, rb, re, window, cols, mode, cen, rk, status)
+                rounds += n_rounds
+                out[ws:we, r0:r0 + got] = keys[:, :got]
+                if r0 == 0 and floats:
+                    has_nan[ws:we] = kmax0 == nan_key
+        return out, has_nan, rounds
+
+    def _rank_rounds(self, calls, rb, re, window, cols, mode, center, ranks, status):
+        """The rounds of one run of windows [rb, re) for RANK_SELECTORS ranks per cell.  State per (window, selector, column): the
+        candidates are the items with key >> (shift + 8) == pref, the rank `rel` counts among them.  A round's histogram picks the
+        digit; the candidates' kmin / kmax (known one round late) tell down to which bit they all agree (bit_length(kmin ^ kmax)): the next digit
+        starts there, and kmin == kmax ends the scan.  The
+        two ranks of a cell share ONE selector while their candidates are the same set, so that the candidate sets of a cell's
+        selectors are always disjoint.  -> (keys (n_windows, S, C) uint64, kmax of the first, prefix-free round (n_windows, C), the rounds made)."""
+        S, B = hip.RANK_SELECTORS, hip.RANK_BITS
+        nw, C = ranks.shape[0], cols.size
+        kb = hip.rank_key_bits(self.dtype, mode)
+        u64 = np.uint64
+        rel = np.repeat(ranks[:, :, None].astype(np.int64), C, axis=2)
+        shift = np.full((nw, S, C), kb - B, u64)
+        pref = np.zeros((nw, S, C), u64)
+        ubits = np.full((nw, S, C), B, u64)          # < 8 on a last round whose digit still holds known bits: only digits that agree with `kdig` there count
+        kdig = np.zeros((nw, S, C), u64)
+        done = np.zeros((nw, S, C), bool)
+        val = np.zeros((nw, S, C), u64)
+        kmax0 = None
+        max_rounds = -(-kb // B)
+        digits = np.arange(1 << B, dtype=u64)[None, :, None]
+        rnd = 0
+        while not done.all():
+            assert rnd < max_rounds, 'radix select: more than %d rounds' % max_rounds
+            share = ~done[:, 0] & ~done[:, 1] & (pref[:, 0] == pref[:, 1]) & (shift[:, 0] == shift[:, 1])
+            sel_shift = np.where(done, -1, shift.astype(np.int64)).astype(np.int32)
+            sel_shift[:, 1][share] = -1
+            hist, kmin, kmax = self._rank_call(calls, rb, re, window, cols, mode, center, pref, sel_shift, status)
+            if rnd == 0:
+                kmax0 = kmax[:, 0].copy()
+            for s in range(S):
+                if s and not share.any():
+                    h, kmn, kmx = hist[:, s], kmin[:, s], kmax[:, s]
+                elif s and not share.all():
+                    h = np.where(share[:, None, :], hist[:, 0], hist[:, s])
+                    kmn, kmx = np.where(share, kmin[:, 0], kmin[:, s]), np.where(share, kmax[:, 0], kmax[:, s])
+                else:                                               # (selector 1 shares selector 0's candidates)
+                    h, kmn, kmx = hist[:, 0], kmin[:, 0], kmax[:, 0]
+                act = ~done[:, s]
+                if (ubits[:, s] < B).any():                         # (a last round whose digit still holds known bits)
+                    ub = ubits[:, s][:, None, :]
+                    h = np.where((digits >> ub) == (kdig[:, s][:, None, :] >> ub), h, 0)
+                cum = np.cumsum(h, axis=1, dtype=np.int64)
+                r = rel[:, s]
+                if not (r[act] < cum[:, -1][act]).all():
+                    raise RuntimeError("radix select: a rank beyond the rows counted (rows were not counted)")
+                dig = np.minimum((cum <= r[:, None, :]).sum(axis=1), (1 << B) - 1)
+                below = np.take_along_axis(cum, dig[:, None, :], axis=1)[:, 0] - np.take_along_axis(h, dig[:, None, :], axis=1)[:, 0]
+                sh = shift[:, s]
+                known = ((pref[:, s] << u64(B)) | dig.astype(u64)) << sh         # every bit from `sh` up
+                d = hip.rank_bit_length(kmn ^ kmx)                                         # the candidates of this round agree above bit d
+                u = np.minimum(sh, d)
+                low = (u64(1) << sh) - u64(1)
+                known |= kmn & low & ~((u64(1) << u) - u64(1))
+                fin = act & (u == 0)
+                val[:, s] = np.where(fin, known, val[:, s])
+                go = act & ~fin
+                nsh = np.where(u >= B, u - u64(B), u64(0)).astype(u64)
+                shift[:, s] = np.where(go, nsh, sh)
+                pref[:, s] = np.where(go, known >> (nsh + u64(B)), pref[:, s])
+                ubits[:, s] = np.where(go, np.minimum(u, u64(B)), ubits[:, s])
+                kdig[:, s] = np.where(go & (u < B), known & u64((1 << B) - 1), u64(0))
+                rel[:, s] = np.where(go, r - below, r)
+                done[:, s] |= fin
+            rnd += 1
+        return val, kmax0, rnd
+
+    def _rank_call(self, calls, rb, re, window, cols, mode, center, pref, sel_shift, status):
+        """One round over the chunks of `calls` (lists of chunk indices): every call's chunks on their owner lanes, the integer
+        partials added (the order does not matter).  A chunk that did not decode raises the error of Reader[...]."""
+        S, nb = hip.RANK_SELECTORS, 1 << hip.RANK_BITS
+        nw, C = pref.shape[0], cols.size
+        hist = np.zeros((nw, S, nb, C), np.uint32)
+        kmin = np.full((nw, S, C), hip.RANK_KEY_NONE, np.uint64)
+        kmax = np.zeros((nw, S, C), np.uint64)
+        lanes = self._n_lanes()
+        use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
+        for run in calls:
+            lo, hi = max(rb, self.chunk_bounds[run[0]]), min(re, self.chunk_bounds[run[-1] + 1])
+            w0, w1 = (lo - rb) // window, -(-(hi - rb) // window)
+            cb, ce = rb + w0 * window, min(re, rb + w1 * window)
+            owners = sorted({k % lanes for k in run})
+            parts = [None] * len(owners)
+            sl = slice(w0, w1)
+            cen = None if center is None else np.ascontiguousarray(center[sl])
+            pre, shf = np.ascontiguousarray(pref[sl]), np.ascontiguousarray(sel_shift[sl])
+
+            def one(j, run=run, owners=owners, parts=parts, cb=cb, ce=ce, cen=cen, pre=pre, shf=shf):
+                g = owners[j]
+                keys = [k for k in run if k % lanes == g]
+                cache = self._cache_for(g) if use_cache else 0
+                st, res = self._lane_rank_hist(cache, keys, cb, ce, window, cols, mode, cen, pre, shf, g)
+                parts[j] = (keys, st, res)
+            self.codec.run_lanes(one, len(owners))
+            for keys, st, res in parts:
+                status.update(zip(keys, st))
+                hist[sl] += res['hist']
+                kmin[sl] = np.minimum(kmin[sl], res['kmin'])
+                kmax[sl] = np.maximum(kmax[sl], res['kmax'])
+        self._raise_for(status)
+        return hist, kmin, kmax
+
+    def _lane_rank_hist(self, cache, keys, row_begin, row_end, window, cols, mode, center, pref, sel_shift, lane):
+        """One codec.rank_hist call for the chunks `keys` of one lane: chunks resident in its cache go without bytes, the others'
+        compressed bytes come from a mapping of the file (or one read); sent whole once more if an entry was dropped between the
+        query and the call.  -> (status list, partials)."""
+        row0 = [self.chunk_bounds[k] for k in keys]
+        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
+        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
+        for attempt in range(2):
+            need = [k for k, p in zip(keys, present) if not p]
+            base = self.chunk_offsets[need[0]] if need else 0
+            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
+            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
+            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
+            buf = self._map_range(nbytes, base) if need else b''
+            if buf is None:
+                buf = self._pread(nbytes, base)
+            try:
+                return self.codec.rank_hist(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), row_begin,
+                                            row_end, window, cols, mode, center, pref, sel_shift, lane=lane)
+            except hip.HipError as e:
+                if e.code != hip.E_MISS or attempt:
+                    raise
+                present = [False] * len(keys)                       # dropped since the query: send everything
+
+    def quantile(self, q, start=0, stop=None, channels=slice(None), window=None, method='linear', center=None, absolute=False):
+        """Exact per-window, per-channel quantiles of rows [start, stop), selected on the device: only digit histograms cross the
+        bus.  start / stop / window / channels as window_stats (window=None: one window over the range).  q: a float or a 1-D
+        sequence of floats in [0, 1].  For a window of n rows the position v = q * (n - 1) is computed exactly (as a fraction), index
+        = floor(v), frac = v - index; the device delivers the order statistics lower = sort(x)[index] and upper = sort(x)[min(index + 1,
+        n - 1)], and the result is formed in float64 from lo = float64(lower), hi = float64(upper) -- 'linear': lo + (hi - lo) * frac;
+        'lower': lo; 'higher': hi if frac > 0 else lo; 'midpoint': (lo + hi) / 2 if frac > 0 else lo; 'nearest': lo below a half, hi
+        above, the even index at exactly a half (numpy's rule).
+        center / absolute change what is ordered: float64(x) - c[w, j], or its absolute value; c broadcasts to (n_windows, n_channels),
+        None is 0.  lower / upper are then float64, otherwise they are in the recording's dtype.
+        Ordering: as np.sort; every NaN, of either sign, sorts last; -0.0 and +0.0 are one key and come back as +0.0 (compare by
+        value); a window that holds a NaN gives a NaN quantile, as np.quantile does, while lower / upper still hold the order
+        statistics; integers are ordered in their own type, 8-byte ones exactly.
+        Returns a Bunch: count (n_windows,); q (n_q,); quantile (n_windows, n_q, C) float64; lower, upper of that shape; index
+        (n_windows, n_q) int64 and frac float64; start, stop, window, channels, method; rounds, the passes over the chunks the call made
+        (mts_rank_hist rounds: what a cold scan decodes).  A scalar q drops the n_q axis, an int channel
+        the C axis.  Chunks resident in the device cache are read where they lie; the others are decoded in a transient workspace
+        and NOT kept.  Every window costs a histogram however few rows it has: small windows are correct, not fast.  A damaged chunk
+        raises the IOError of Reader[...]."""
+        if method not in QUANTILE_METHODS:
+            raise ValueError("method must be one of %r, got %r" % (QUANTILE_METHODS, method))
+        try:
+            qa = np.asarray(q, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("q must be a float or a 1-D sequence of floats in [0, 1]") from None
+        q_scalar = qa.ndim == 0
+        qa = qa.reshape(-1) if qa.ndim <= 1 else qa
+        if qa.ndim != 1 or np.asarray(q).dtype.kind not in 'fiu' or not ((qa >= 0) & (qa <= 1)).all():
+            raise ValueError("q must be a float or a 1-D sequence of floats in [0, 1], got %r" % (q,))
+        i0, i1, window, cols, squeeze, count = self._rank_setup('quantile', start, stop, window, channels)
+        n_win, nq = count.size, qa.size
+        mode = 2 if absolute else 1 if center is not None else 0
+        cen = self._rank_center(center, n_win, cols.size) if mode else None
+        index = np.zeros((n_win, nq), np.int64)
+        frac = np.zeros((n_win, nq), np.float64)
+        lengths = sorted(set(count.tolist()))                      # (two values at most: the window and the rest)
+        uniq = {}
+        for n in lengths:
+            rows = count == n
+            for k, qv in enumerate(qa.tolist()):
+                v = Fraction(qv) * (n - 1)
+                j = v.numerator // v.denominator
+                index[rows, k], frac[rows, k] = j, float(v - j)
+            w = int(np.argmax(rows))
+            uniq[n] = np.unique(np.concatenate((index[w], np.minimum(index[w] + 1, n - 1))))      # the distinct ranks of such a window
+        upper_i = np.minimum(index + 1, count[:, None] - 1)
+        R = max((u.size for u in uniq.values()), default=0)
+        rk = np.zeros((n_win, R), np.int64)
+        pos_lo, pos_hi = np.zeros((n_win, nq), np.int64), np.zeros((n_win, nq), np.int64)
+        for n in lengths:                                           # (windows of one length share their ranks; padded with the last)
+            rows, u = count == n, uniq[n]
+            w = int(np.argmax(rows))
+            rk[rows] = np.concatenate((u, np.repeat(u[-1:], R - u.size)))
+            pos_lo[rows], pos_hi[rows] = np.searchsorted(u, index[w]), np.searchsorted(u, upper_i[w])
+        keys, has_nan, rounds = self._rank_scan(i0, i1, window, cols, rk, mode, cen)
+        vals = hip.rank_values(keys, self.dtype, mode)              # (n_win, R, C)
+        if n_win:
+            lower, upper = np.take_along_axis(vals, pos_lo[:, :, None], axis=1), np.take_along_axis(vals, pos_hi[:, :, None], axis=1)
+        else:
+            lower = upper = np.zeros((0, nq, cols.size), vals.dtype)
+        lo, hi, g = lower.astype(np.float64), upper.astype(np.float64), frac[:, :, None]
+        with np.errstate(invalid='ignore', over='ignore'):
+            if method == 'linear':
+                res = lo + (hi - lo) * g
+            elif method == 'lower':
+                res = lo.copy()
+            elif method == 'higher':
+                res = np.where(g > 0, hi, lo)
+            elif method == 'midpoint':
+                res = np.where(g > 0, (lo + hi) / 2, lo)
+            else:
+                even = (index % 2 == 0)[:, :, None]
+                res = np.where(g < 0.5, lo, np.where(g > 0.5, hi, np.where(even, lo, hi)))
+        res = np.where(has_nan[:, None, :], np.nan, res)
+        out = Bunch(count=count, q=qa, quantile=res, lower=lower, upper=upper, index=index, frac=frac, start=i0, stop=i1, window=window,
+                    channels=cols, method=method, rounds=rounds)
+        if squeeze:
+            for key in ('quantile', 'lower', 'upper'):
+                out[key] = out[key][:, :, 0]
+        if q_scalar:
+            for key in ('quantile', 'lower', 'upper', 'index', 'frac'):
+                out[key] = out[key][:, 0]
+        return out
+
+    def median(self, start=0, stop=None, channels=slice(None), window=None):
+        """Per-window, per-channel median of rows [start, stop) as float64, (n_windows, C) (an int channel drops C): quantile(0.5)
+        with method='midpoint' -- (float64(lower) + float64(upper)) / 2 over the two middle order statistics of a window of an even
+        number of rows, the middle one of an odd number --, the value of np.median(r[w0:w1, channels].astype(np.float64), axis=0),
+        NaN for a window that holds one.  Ordering rules, cache use and errors as quantile."""
+        return self.quantile(0.5, start, stop, channels=channels, window=window, method='midpoint').quantile
+
+    def mad(self, start=0, stop=None, channels=slice(None), window=None, center='median'):
+        """Per-window, per-channel median absolute deviation median(|float64(x) - center|) of rows [start, stop): two scans on the
+        device, the median, then the median of the absolute deviations from it.  center: 'median', or an array that broadcasts to
+        (n_windows, C) (zeros: the spike-band noise estimate median(|x|); divide by 0.6745 for a standard deviation).  Returns a
+        Bunch: count, center, mad (n_windows, C) float64 (an int channel drops C), start, stop, window, channels, rounds (the passes
+        over the chunks of both scans).  Per window it
+        equals scipy.stats.median_abs_deviation(x.astype(np.float64), axis=0), NaN for a window that holds one.  Ordering rules,
+        cache use and errors as quantile."""
+        i0, i1, window, cols, squeeze, count = self._rank_setup('mad', start, stop, window, channels)
+        if isinstance(center, str):
+            if center != 'median':
+                raise ValueError("center must be 'median' or an array, got %r" % (center,))
+            med = self.quantile(0.5, i0, i1, channels=cols, window=window, method='midpoint')
+            cen, rounds = med.quantile.reshape(count.size, cols.size), med.rounds
+        else:
+            cen, rounds = self._rank_center(center, count.size, cols.size), 0
+        res = self.quantile(0.5, i0, i1, channels=cols, window=window, method='midpoint', center=cen, absolute=True)
+        dev = res.quantile
+        out = Bunch(count=count, center=cen, mad=dev, start=i0, stop=i1, window=window, channels=cols, rounds=rounds + res.rounds)
+        if squeeze:
+            out.center, out.mad = cen[:, 0], dev[:, 0]
+        return out
 
     # -- FIR low-pass + decimation on the device (an extension: the reference's users filter Reader[...] on the host)
     def decimate(self, q, start=0, stop=None, channels=slice(None), taps=None, edge='zeros', dtype=np.float32):

@@ -1831,6 +1831,216 @@ static int window_stats_run(Engine &E, hipStream_t st, DevCache *cache, const lo
     return MTS_OK;
 }
 
+// ---- one round of a radix select (mts_rank_hist, mts_dev_rank_hist) ---------------------------------
+// The tiles, the residency rules and the pieces of window_stats_run, with tiles of SEL_TILE_ROWS rows and no combine launch: every
+// tile adds its counts to the histograms of its window with integer atomics (select.hip), so the outputs are the same whatever the
+// order of the launches.
+static int rank_hist_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device,
+                         const long *c_off, const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz, int flags,
+                         long row_begin, long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
+                         const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *o_hist, unsigned long long *o_kmin,
+                         unsigned long long *o_kmax, bool out_on_host, long *count, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
+    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    if (nc <= 0 || n_chunks < 0 || n_cols < 1 || !cols) { set_error("rank hist: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
+    if (window_rows < 1) { set_error("window_rows %ld < 1", window_rows); return MTS_E_ARG; }
+    if (row_begin < 0 || row_end < row_begin) { set_error("row range [%ld, %ld) invalid", row_begin, row_end); return MTS_E_ARG; }
+    if (mode < 0 || mode > 2) { set_error("rank hist: mode %d (0, 1 or 2)", mode); return MTS_E_ARG; }
+    for (int j = 0; j < n_cols; j++)
+        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
+    const long span = row_end - row_begin;
+    if ((window_rows < span ? window_rows : span) >= (1l << 32)) { set_error("windows of 2^32 rows or more"); return MTS_E_ARG; }
+    for (int i = 0; i < n_chunks; i++) {
+        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
+        if (i && row0[i] < row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: rows out of order or overlapping", i); return MTS_E_ARG; }
+        if (row0[i] >= row_end || row0[i] + n_rows[i] <= row_begin) { set_error("chunk %d holds no row of [%ld, %ld)", i, row_begin, row_end); return MTS_E_ARG; }
+        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
+        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
+    }
+    const long n_win = (span + window_rows - 1) / window_rows;
+    if (n_win && (!o_hist || !o_kmin || !o_kmax || !count || !sel_prefix || !sel_shift || (mode && !center))) {
+        set_error("rank hist: selectors, center or outputs missing"); return MTS_E_ARG;
+    }
+    const int key_bits = mode ? 64 : 8 * sz;
+    const u64 n_sel = (u64)n_win * MTS_RANK_SELECTORS * n_cols;
+    for (u64 e = 0; e < n_sel; e++) {
+        const int sh = sel_shift[e];
+        if (sh < 0) continue;
+        const int above = key_bits - sh - MTS_RANK_BITS;     // bits of the key above the digit
+        if (above < 0) { set_error("rank hist: shift %d above key_bits - %d", sh, MTS_RANK_BITS); return MTS_E_ARG; }
+        if (above < 64 && (sel_prefix[e] >> above)) { set_error("rank hist: a prefix of more than %d bits at shift %d", above, sh); return MTS_E_ARG; }
+    }
+    for (long w = 0; w < n_win; w++) count[w] = 0;
+    if (n_win == 0) return MTS_OK;                           // (no chunk can hold a row of an empty range: n_chunks is 0)
+
+    // ---- tiles, in row order
+    std::vector<StatTile> tiles;
+    std::vector<long> tile_win, chunk_tile0(n_chunks + 1);
+    for (int i = 0; i < n_chunks; i++) {
+        chunk_tile0[i] = (long)tiles.size();
+        const long a = row0[i] > row_begin ? row0[i] : row_begin, b = row0[i] + n_rows[i] < row_end ? row0[i] + n_rows[i] : row_end;
+        for (long r = a; r < b;) {
+            const long w = (r - row_begin) / window_rows, wend = row_begin + (w + 1) * window_rows, e = b < wend ? b : wend;
+            for (long q = r; q < e; q += SEL_TILE_ROWS) {
+                StatTile t;
+                t.base = nullptr; t.row_lo = q - row0[i]; t.n_rows = (e - q) < SEL_TILE_ROWS ? (e - q) : SEL_TILE_ROWS; t.chunk = i; t.pad = 0;
+                tiles.push_back(t);
+                tile_win.push_back(w);
+            }
+            r = e;
+        }
+    }
+    chunk_tile0[n_chunks] = (long)tiles.size();
+    const long n_tiles = (long)tiles.size();
+
+    // ---- which chunks are resident (whole rows), which are decoded here, in which pieces
+    auto entry_of = [&](int i) -> const CacheEntry * {
+        if (!cache) return nullptr;
+        auto it = cache->map.find(keys[i]);
+        if (it == cache->map.end()) return nullptr;
+        const CacheEntry &e = it->second;
+        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
+    };
+    std::vector<int> miss;
+    for (int i = 0; i < n_chunks; i++) {
+        if (entry_of(i)) continue;
+        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+        miss.push_back(i);
+    }
+    const int m = (int)miss.size();
+    const u64 row_bytes = (u64)nc * sz;
+    std::vector<long> mrows(m), mcoff(m), mclen(m), mooff(m);
+    for (int k = 0; k < m; k++) { mrows[k] = n_rows[miss[k]]; mclen[k] = c_len[miss[k]]; }
+    const std::vector<int> pb = cdata_on_device ? std::vector<int>{0, m} : pipe_pieces(mrows.data(), false, m, row_bytes);
+    const int np = (int)pb.size() - 1;
+    u64 piece_cap = 0;
+    for (int k = 0; k < np; k++) {
+        u64 o = 0;
+        for (int q = pb[k]; q < pb[k + 1]; q++) { mooff[q] = (long)o; o += align_up((u64)mrows[q] * row_bytes, 256); }
+        if (o > piece_cap) piece_cap = o;
+    }
+    u64 ctot = 0;
+    if (!cdata_on_device) {
+        for (int k = 0; k < m; k++) {
+            const int i = miss[k];
+            const bool joins = k > 0 && c_off[i] == c_off[miss[k - 1]] + mclen[k - 1];
+            if (!joins) ctot = align_up(ctot + (k ? 16 : 0), 16);
+            mcoff[k] = (long)ctot; ctot += (u64)mclen[k];
+        }
+        ctot += 16;
+    } else {
+        for (int k = 0; k < m; k++) mcoff[k] = c_off[miss[k]];
+    }
+
+    // ---- workspace: every allocation of the call comes BEFORE the resident entries are looked at
+    const u64 n_cells = (u64)n_win * n_cols, hist_bytes = n_sel * (4ull << MTS_RANK_BITS), k_bytes = n_sel * 8;
+    const size_t o_tiles = 0, o_tw = align_up(sizeof(StatTile) * (n_tiles + 1), 256), o_ids = o_tw + align_up(8 * (u64)(n_tiles + 1), 256),
+                 o_ok = o_ids + align_up(4 * (u64)(n_tiles + 1), 256), o_cols = o_ok + align_up(4 * (u64)(n_chunks + 1), 256),
+                 o_cen = o_cols + align_up(4 * (u64)n_cols, 256), o_pre = o_cen + align_up(mode ? 8 * n_cells : 0, 256),
+                 o_shf = o_pre + align_up(k_bytes, 256), o_out = o_shf + align_up(n_sel * 4, 256);
+    const size_t w_hist = o_out, w_kmin = w_hist + align_up(hist_bytes, 256), w_kmax = w_kmin + align_up(k_bytes, 256),
+                 o_end = out_on_host ? w_kmax + align_up(k_bytes, 256) : o_out;
+    int rc;
+    if ((rc = E.stats.ensure(o_end + 256))) return rc;
+    if (m && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
+    if (m && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
+    if (cache) {
+        for (int i = 0; i < n_chunks; i++)                   // (the allocations above may have emptied the cache)
+            if (c_len[i] == 0 && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
+    }
+    u8 *ws = E.stats.as<u8>();
+    StatTile *d_tiles = (StatTile *)(ws + o_tiles);
+    long *d_tw = (long *)(ws + o_tw);
+    int *d_ids = (int *)(ws + o_ids), *d_ok = (int *)(ws + o_ok), *d_cols = (int *)(ws + o_cols), *d_shf = (int *)(ws + o_shf);
+    double *d_cen = (double *)(ws + o_cen);
+    u64 *d_pre = (u64 *)(ws + o_pre);
+    u32 *d_hist = out_on_host ? (u32 *)(ws + w_hist) : (u32 *)o_hist;
+    u64 *d_kmin = out_on_host ? (u64 *)(ws + w_kmin) : (u64 *)o_kmin, *d_kmax = out_on_host ? (u64 *)(ws + w_kmax) : (u64 *)o_kmax;
+    // tile pointers and the order of the launches: resident chunks first, then piece after piece
+    std::vector<int> ok(n_chunks + 1, 0), ids;
+    std::vector<long> launch0;
+    std::vector<char> decoded(n_chunks, 0);
+    for (int k = 0; k < m; k++) decoded[miss[k]] = 1;
+    launch0.push_back(0);
+    for (int i = 0; i < n_chunks; i++) {
+        if (decoded[i]) continue;
+        const CacheEntry *e = entry_of(i);
+        for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = e->d; ids.push_back((int)t); }
+        ok[i] = 1;
+        status[i] = MTS_CHUNK_OK;
+    }
+    for (int k = 0; k < np; k++) {
+        launch0.push_back((long)ids.size());
+        for (int q = pb[k]; q < pb[k + 1]; q++) {
+            const int i = miss[q];
+            for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = E.h_out.as<u8>() + mooff[q]; ids.push_back((int)t); }
+        }
+    }
+    launch0.push_back((long)ids.size());
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(StatTile) * n_tiles, hipMemcpyHostToDevice, st));
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tw, tile_win.data(), 8 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_ids, ids.data(), 4 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_ok, ok.data(), 4 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    if (mode) MTS_HIP(hipMemcpyAsync(d_cen, center, 8 * (size_t)n_cells, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_pre, sel_prefix, (size_t)k_bytes, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_shf, sel_shift, 4 * (size_t)n_sel, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemsetAsync(d_hist, 0, (size_t)hist_bytes, st));
+    MTS_HIP(hipMemsetAsync(d_kmin, 0xff, (size_t)k_bytes, st));
+    MTS_HIP(hipMemsetAsync(d_kmax, 0, (size_t)k_bytes, st));
+    const int dflags = flags & ~MTS_FLAG_UNSIGNED;           // (the decoder compares the transform flags as a whole)
+    // resident chunks: counted and waited for before any decode (whose workspace allocations could drop cache entries)
+    if (launch0[1] > 0) {
+        if ((rc = launch_rank_hist(st, sz, flags, mode, d_tiles, d_tw, d_ids, (int)launch0[1], d_ok, d_cols, n_cols, nc, d_cen, d_pre, d_shf,
+                                   d_hist, d_kmin, d_kmax))) return rc;
+        MTS_HIP(hipStreamSynchronize(st));
+    }
+    // ---- the other chunks, piece by piece
+    const int dev = E.dev;
+    auto copy_in = [&](int k) -> int {
+        if (cdata_on_device) return MTS_OK;
+        MTS_HIP(hipSetDevice(dev));
+        for (int q = pb[k]; q < pb[k + 1];) {
+            int e = q + 1;
+            while (e < pb[k + 1] && c_off[miss[e]] == c_off[miss[e - 1]] + mclen[e - 1] && mcoff[e] == mcoff[e - 1] + mclen[e - 1]) e++;
+            u64 len = 0;
+            for (int z = q; z < e; z++) len += (u64)mclen[z];
+            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[q], cdata + c_off[miss[q]], (size_t)len); if (rc1) return rc1; }
+            q = e;
+        }
+        return MTS_OK;
+    };
+    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
+    std::vector<int> mst(m > 0 ? m : 1, MTS_CHUNK_CORRUPT);
+    if (np > 0 && m > 0 && (rc = copy_in(0))) return rc;
+    for (int k = 0; k < np && m > 0; k++) {
+        std::future<int> f_in;
+        if (k + 1 < np) f_in = copy_beside(copy_in, k + 1);
+        const int q0 = pb[k], nq = pb[k + 1] - pb[k];
+        rc = dev_decompress(E, st, d_src, mcoff.data() + q0, mclen.data() + q0, mrows.data() + q0, nq, nc, sz, dflags, E.h_out.as<u8>(),
+                            mooff.data() + q0, mst.data() + q0, 0, k > 0);
+        if (!rc) {
+            for (int q = q0; q < q0 + nq; q++) { status[miss[q]] = mst[q]; ok[miss[q]] = mst[q] == MTS_CHUNK_OK; }
+            hipError_t e = hipMemcpyAsync(d_ok, ok.data(), 4 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); rc = MTS_E_HIP; }
+        }
+        if (!rc) rc = launch_rank_hist(st, sz, flags, mode, d_tiles, d_tw, d_ids + launch0[1 + k], (int)(launch0[2 + k] - launch0[1 + k]), d_ok,
+                                       d_cols, n_cols, nc, d_cen, d_pre, d_shf, d_hist, d_kmin, d_kmax);
+        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;      // (always joined: it holds references to this frame)
+        if (rc || rc_in) return rc ? rc : rc_in;
+    }
+    if (out_on_host) {                                        // the histograms, and nothing else, cross the bus
+        MTS_HIP(hipMemcpyAsync(o_hist, d_hist, (size_t)hist_bytes, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(o_kmin, d_kmin, (size_t)k_bytes, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(o_kmax, d_kmax, (size_t)k_bytes, hipMemcpyDeviceToHost, st));
+    }
+    MTS_HIP(hipStreamSynchronize(st));
+    for (long t = 0; t < n_tiles; t++) if (ok[tiles[t].chunk]) count[tile_win[t]] += tiles[t].n_rows;
+    return MTS_OK;
+}
+
 // ---- decimation (mts_decimate, mts_dev_decimate) ---------------------------------------------------------------------------
 // The chunks of a call are cut into pieces of MTS_PIPE_BYTES of decoded bytes to decode (pipe_pieces; resident chunks weigh
 // nothing).  Piece p owns the outputs whose newest row (first_row + k * q) lies in its chunks; their support reaches L - 1 rows
@@ -2348,6 +2558,47 @@ int mts_dev_window_stats(int device, void *stream, const unsigned char *d_cdata,
     return window_stats_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
                             n_channels, itemsize, flags, row_begin, row_end, window_rows, n_cols, cols, d_min, d_max, d_sum, d_sumsq, false,
                             count, chunk_status);
+}
+
+int mts_rank_hist(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                  const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
+                  long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
+                  const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *out_hist, unsigned long long *out_kmin,
+                  unsigned long long *out_kmax, long *out_count, int *chunk_status)
+{
+    DevCache *c = nullptr;
+    if (cache_id) {
+        int cdev = 0;
+        c = find_cache(cache_id, &cdev);
+        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
+    }
+    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;      // (destroyed while this call waited for the engine)
+    MTS_HIP(hipSetDevice(E->dev));
+    return rank_hist_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize,
+                         flags, row_begin, row_end, window_rows, n_cols, cols, mode, center, sel_prefix, sel_shift, out_hist, out_kmin, out_kmax,
+                         true, out_count, chunk_status);
+}
+
+int mts_dev_rank_hist(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                      const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin,
+                      long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
+                      const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *d_hist, unsigned long long *d_kmin,
+                      unsigned long long *d_kmax, long *count, int *chunk_status)
+{
+    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    MTS_HIP(hipSetDevice(E->dev));
+    return rank_hist_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
+                         n_channels, itemsize, flags, row_begin, row_end, window_rows, n_cols, cols, mode, center, sel_prefix, sel_shift, d_hist,
+                         d_kmin, d_kmax, false, count, chunk_status);
 }
 
 int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,

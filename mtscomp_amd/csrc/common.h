@@ -159,6 +159,14 @@ int launch_stats_tiles(hipStream_t st, int itemsize, int flags, const StatTile *
 int launch_stats_combine(hipStream_t st, int itemsize, int flags, const u8 *d_slab, long n_tiles, const long *d_win_tiles, long n_windows,
                          int n_cols, void *d_min, void *d_max, void *d_sum, void *d_sumsq);
 
+// select.hip: one round of a radix select over decoded chunks (mts_rank_hist).  Tiles as above, of at most SEL_TILE_ROWS rows;
+// d_tile_win[t]: the window of tile t.  Selectors and outputs: (n_windows, MTS_RANK_SELECTORS, [256,] n_cols), see include/mtscomp_hip.h;
+// the outputs are accumulated with integer atomics (the caller sets hist = 0, kmin = all ones, kmax = 0 first)
+constexpr int SEL_TILE_ROWS = 4096;                                     // rows of a tile: one workgroup, one LDS histogram flush per 64 columns
+int launch_rank_hist(hipStream_t st, int itemsize, int flags, int mode, const StatTile *d_tiles, const long *d_tile_win, const int *d_ids,
+                     int n_launch, const int *d_ok, const int *d_cols, int n_cols, int n_channels, const double *d_center, const u64 *d_prefix,
+                     const int *d_shift, u32 *d_hist, u64 *d_kmin, u64 *d_kmax);
+
 // decimate.hip: FIR + keep every q-th row of decoded chunks (mts_decimate).  Outputs k in [k_begin, k_end) of the call:
 // out[(k - k_begin) * n_cols + c] = sum_j taps[j] * x[first_row + k * q - j, cols[c]] in the out_itemsize float type, j ascending,
 // x = 0 outside [valid_begin, valid_end) and outside the segments; segment s holds file rows [seg_row0[s], seg_row0[s + 1]) at

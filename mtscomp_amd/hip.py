@@ -113,6 +113,11 @@ def lib():
                            C.c_long, C.c_int, ip, vp, vp, ip]
     L.mts_dev_gram.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
                                C.c_long, C.c_int, ip, vp, vp, ip]
+    up = C.POINTER(C.c_ulonglong)
+    L.mts_rank_hist.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
+                                C.c_int, ip, C.c_int, dp, up, ip, C.POINTER(C.c_uint), up, up, lp, ip]
+    L.mts_dev_rank_hist.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
+                                    C.c_int, ip, C.c_int, dp, up, ip, vp, vp, vp, lp, ip]
     L.mts_release.restype = None
     _lib = L
     return L
@@ -126,7 +131,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
            'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_welch', 'mts_dev_welch',
-           'mts_gram', 'mts_dev_gram']
+           'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
 
 
 def _check(rc, what):
@@ -405,6 +410,153 @@ def dev_window_stats(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, r
         if a.nbytes:
             _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(int(o)), a.nbytes, 1), 'mts_dev_copy')
     return [int(x) for x in status[:rows.size]], dict(min=mn, max=mx, sum=sm, sumsq=sq, count=cnt[:nw]), out
+
+
+# ------------------------------------------------------------------------------------------------
+# order statistics: one round of a radix select (an extension: the reference has no such call)
+# ------------------------------------------------------------------------------------------------
+RANK_BITS = 8                # digit width (MTS_RANK_BITS)
+RANK_SELECTORS = 2           # selectors per (window, column) cell and call (MTS_RANK_SELECTORS)
+RANK_KEY_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)      # kmin of a selector without candidates (its kmax is 0)
+
+
+def rank_key_bits(dtype, mode=0):
+    """Significant bits of the order keys: the item's own width in mode 0, 64 in modes 1 and 2 (float64 keys)."""
+    return 64 if mode else 8 * np.dtype(dtype).itemsize
+
+
+def rank_key_nan(dtype, mode=0):
+    """The key every NaN maps to (all ones): kmax of a prefix-free selector equals it exactly when the cell holds a NaN."""
+    return np.uint64((1 << rank_key_bits(dtype, mode)) - 1)
+
+
+def _float_keys(x):
+    x = np.ascontiguousarray(x)
+    u = np.dtype('u%d' % x.dtype.itemsize).type
+    b = x.view(u)
+    sign = u(1 << (8 * x.dtype.itemsize - 1))
+    k = np.where(b & sign, ~b, b | sign)
+    k = np.where(x == 0, sign, k)                                 # -0 and +0: one key
+    k = np.where(np.isnan(x), u(sign | (sign - u(1))), k)         # every NaN, of either sign: all ones
+    return k.astype(np.uint64)
+
+
+def rank_keys(x, mode=0, center=None):
+    """The order keys of mts_rank_hist as uint64 (their unsigned order is np.sort's order of the items).  mode 0: the items in their
+    own type -- unsigned: the value; signed: the sign bit flipped; floats: NaN -> all ones, -0 and +0 -> one key, negative numbers'
+    bits inverted, the others' sign bit set.  mode 1: the float64 x.astype(float64) - center, mode 2: its absolute value (center
+    broadcasts against x; None is 0)."""
+    x = np.asarray(x)
+    if mode:
+        with np.errstate(invalid='ignore', over='ignore'):
+            d = x.astype(np.float64) - (0.0 if center is None else np.asarray(center, dtype=np.float64))
+        return _float_keys(np.abs(d) if mode == 2 else d)
+    if x.dtype.kind == 'f':
+        return _float_keys(x)
+    if x.dtype.kind == 'u':
+        return x.astype(np.uint64)
+    u = np.dtype('u%d' % x.dtype.itemsize)
+    return np.ascontiguousarray(x).view(u).astype(np.uint64) ^ np.uint64(1 << (8 * x.dtype.itemsize - 1))
+
+
+def rank_values(keys, dtype, mode=0):
+    """The inverse of rank_keys: the items (mode 0, in `dtype`) or the float64 differences (modes 1, 2) that the keys stand for; the
+    all-ones key gives NaN, the key of the zeros +0."""
+    dtype = np.dtype(np.float64 if mode else dtype)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    u = np.dtype('u%d' % dtype.itemsize)
+    k = keys.astype(u)
+    sign = u.type(1 << (8 * dtype.itemsize - 1))
+    if dtype.kind == 'u':
+        return k
+    if dtype.kind == 'i':
+        return (k ^ sign).view(dtype)
+    out = np.where(k & sign, k & ~sign, ~k).view(dtype).copy()
+    out[keys == rank_key_nan(dtype)] = np.nan
+    return out
+
+
+def rank_bit_length(x):
+    """int.bit_length of every entry of a uint64 array, as uint64: the keys of a round's candidates agree above bit
+    rank_bit_length(kmin ^ kmax)."""
+    x = np.asarray(x, dtype=np.uint64)
+    d = np.zeros(x.shape, np.uint64)
+    for b in (32, 16, 8, 4, 2, 1):
+        m = (x >> np.uint64(b)) != 0
+        d += np.where(m, np.uint64(b), np.uint64(0))
+        x = np.where(m, x >> np.uint64(b), x)
+    return d + (x != 0).astype(np.uint64)
+
+
+def _rank_args(n_windows, n_cols, mode, center, sel_prefix, sel_shift):
+    shape = (int(n_windows), RANK_SELECTORS, int(n_cols))
+    pre = np.ascontiguousarray(sel_prefix, dtype=np.uint64)
+    shf = np.ascontiguousarray(sel_shift, dtype=np.int32)
+    assert pre.shape == shape and shf.shape == shape, 'selectors must be (n_windows, %d, n_cols)' % RANK_SELECTORS
+    cen = None
+    if mode:
+        cen = np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if center is None else center, dtype=np.float64), (shape[0], shape[2])))
+    hist = np.zeros((shape[0], RANK_SELECTORS, 1 << RANK_BITS, shape[2]), np.uint32)
+    kmin, kmax = np.full(shape, RANK_KEY_NONE, np.uint64), np.zeros(shape, np.uint64)
+    return pre, shf, cen, hist, kmin, kmax, np.zeros(max(shape[0], 1), np.int64)
+
+
+def _ullp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+
+
+def rank_hist(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, mode, center,
+              sel_prefix, sel_shift, device=0):
+    """mts_rank_hist: one round of the radix select over the chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])) on the grid of
+    window_stats.  sel_prefix / sel_shift: (n_windows, RANK_SELECTORS, n_cols); shift < 0 marks an inactive selector; the candidates of
+    the others are the cell's items with rank_keys(x, mode, center) >> (shift + 8) == prefix.  cache_id 0: no cache, every chunk comes
+    with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, dict hist (n_windows, 2,
+    256, n_cols) uint32, kmin, kmax (n_windows, 2, n_cols) uint64, count) -- the partials of these chunks: integers, to be added
+    (hist, count) and combined with minimum / maximum (kmin, kmax) in any order."""
+    dtype = check_dtype(dtype)
+    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    n = int(rows.size)
+    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
+    assert not n or int((offs + lens).max()) <= cdata.size
+    nw = _n_windows(row_begin, row_end, window_rows)
+    pre, shf, cen, hist, kmin, kmax, cnt = _rank_args(nw, cols.size, mode, center, sel_prefix, sel_shift)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    _check(lib().mts_rank_hist(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows),
+                               int(n_channels), dtype.itemsize, stats_flags(flags, dtype), int(row_begin), int(row_end), int(window_rows),
+                               int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)), int(mode),
+                               cen.ctypes.data_as(C.POINTER(C.c_double)) if cen is not None else None, _ullp(pre),
+                               shf.ctypes.data_as(C.POINTER(C.c_int)), hist.ctypes.data_as(C.POINTER(C.c_uint)), _ullp(kmin), _ullp(kmax),
+                               _lp(cnt), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_rank_hist')
+    return [int(x) for x in status[:n]], dict(hist=hist, kmin=kmin, kmax=kmax, count=cnt[:nw])
+
+
+def dev_rank_hist(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, mode, center, sel_prefix,
+                  sel_shift, out=None, fetch=True):
+    """mts_dev_rank_hist on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the three result arrays (made
+    when None; returned so that a caller timing repeated calls can pass it again); fetch=False leaves them there.  Returns (status
+    list, dict as rank_hist, out)."""
+    dtype = check_dtype(dtype)
+    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    nw = _n_windows(row_begin, row_end, window_rows)
+    pre, shf, cen, hist, kmin, kmax, cnt = _rank_args(nw, cols.size, mode, center, sel_prefix, sel_shift)
+    parts = [a.nbytes for a in (hist, kmin, kmax)]
+    at = np.concatenate(([0], np.cumsum([(b + 255) // 256 * 256 for b in parts])))
+    if out is None or out.nbytes < int(at[-1]) + 256:
+        out = DevBuffer(int(at[-1]) + 256, device=cbuf.device)
+    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
+    _check(lib().mts_dev_rank_hist(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
+                                   dtype.itemsize, stats_flags(flags, dtype), int(row_begin), int(row_end), int(window_rows), int(cols.size),
+                                   cols.ctypes.data_as(C.POINTER(C.c_int)), int(mode),
+                                   cen.ctypes.data_as(C.POINTER(C.c_double)) if cen is not None else None, _ullp(pre),
+                                   shf.ctypes.data_as(C.POINTER(C.c_int)), out.at(int(at[0])), out.at(int(at[1])), out.at(int(at[2])),
+                                   _lp(cnt), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_rank_hist')
+    if fetch:
+        for a, o in zip((hist, kmin, kmax), at[:3]):
+            if a.nbytes:
+                _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(int(o)), a.nbytes, 1), 'mts_dev_copy')
+    return [int(x) for x in status[:rows.size]], dict(hist=hist, kmin=kmin, kmax=kmax, count=cnt[:nw]), out
 
 
 # ------------------------------------------------------------------------------------------------
