@@ -264,7 +264,14 @@ int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, c
  *                  a group's entry is its slabs' entries added in slab order from +0, in double.  G[i, j] and G[j, i] are the same
  *                  value (one triangle, mirrored).  Nothing depends on chunks, calls, pieces, lanes, cache residency or the other
  *                  columns.  For an error bound: a product of a row goes through at most h = min(rows, SLAB) + slabs - 1 roundings
- *                  inside its group (a 4-row step rounds a term at most 4 times), plus the groups of the window on the host.
+ *                  inside its group (a 4-row step rounds a term at most 4 times), plus the groups of the window on the host:
+ *                  |G - sum x_i x_j| <= gamma_{h+3} * sum |x_i x_j| + n * 2^-1074 for a window of n rows.  The second term is the
+ *                  underflow: float64 subnormals are kept, as operands and as results (the matrix cores do not flush them, and
+ *                  the kernels are built with hipcc's default float mode, which keeps them elsewhere), so a product that lands
+ *                  below 2^-1022 is rounded to a multiple of 2^-1074, an absolute error of at most 2^-1075 that no relative
+ *                  term covers; sums inside the subnormal range are exact; n products, each scaled by less than 2 by the later
+ *                  roundings.  Items k * 2^e whose products and sums are exactly representable, subnormal or not, give exact
+ *                  entries.
  *                  Column sums: per slab, the items added in row order from 0 (integers: int64 modulo 2^64; floats: double from +0),
  *                  slabs in slab order.
  *   out_gram       (group_end - group_begin, n_cols, n_cols): int64 for 1- and 2-byte integers (exact: a group's sum of products is

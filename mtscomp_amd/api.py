@@ -1875,7 +1875,9 @@ class Reader:
         wrap included) for 1- and 2-byte integers, else float64 with the items converted to float64 once (8-byte integers rounded);
         mean = sum / count; cov = (float64(gram) - np.outer(float64(sum), mean)) / (count - ddof), NaN where count - ddof <= 0; start,
         stop, window, channels.  The summation tree (include/mtscomp_hip.h, mts_gram) depends on the rows' offsets in their window
-        only: the same bits whatever the lanes, calls, cache residency, column set or order; G[i, j] and G[j, i] are equal.  The
+        only: the same bits whatever the lanes, calls, cache residency, column set or order; G[i, j] and G[j, i] are equal.
+        float64 subnormals are kept, as items and as results: nothing is flushed to zero, and a product below 2^-1022 is rounded to
+        a multiple of 2^-1074 like any IEEE product (the error bound in the header has an absolute term n * 2^-1074 for it).  The
         raw-moment formula loses relative accuracy on float data whose mean is large compared with its spread (no centred two-pass
         form).  Chunks resident in the device cache are read where they lie; the others are decoded in a transient workspace and NOT
         kept.  A damaged chunk raises the IOError of Reader[...]."""

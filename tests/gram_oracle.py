@@ -1,8 +1,21 @@
 """Test-only restatements of mts_gram in numpy: the groups of Reader.cov's grid (exact types: int64 Gram entries from float64 BLAS over
 blocks of at most 2^20 rows; float types: float64 per group, groups added in order), a lane codec built on it so that the CPU suite
 drives Reader.cov (argument handling, calls, lanes, cache use, errors), a reference in np.longdouble, and the error bounds the GPU
-results are held to: gram_bound for the Gram entries (the height of the tree include/mtscomp_hip.h documents) and cov_bound for the
-covariance formula."""
+results are held to: gram_bound for the Gram entries (the height of the tree include/mtscomp_hip.h documents, plus the absolute
+underflow term derived below) and cov_bound for the covariance formula.
+
+Underflow.  With gradual underflow the standard model of a float64 operation gains an absolute term for products only:
+fl(a * b) = a * b * (1 + d) + e and fl(a * b + c) = (a * b + c) * (1 + d) + e with |d| <= u, |e| <= 2^-1075 (half the smallest subnormal;
+e != 0 only when the result is subnormal, and then d = 0), while fl(a + b) needs no e at all: a sum of two doubles that lands in the
+subnormal range is a multiple of 2^-1074 below 2^-1022 and therefore exact.  A Gram entry of a window of n rows holds n products, each
+rounded once where it is formed (alone or fused with the running sum), so at most n such e enter it; the h later roundings of the tree
+scale each by at most 1 + gamma_h < 2.  The sum of |x_ti x_tj| the relative term is taken from is itself computed in float64 and may fall
+short of the true one by n * 2^-1075, which moves the relative term by less than gamma_{h+3} * n * 2^-1075.  Together: an absolute
+allowance of n * 2^-1075 * (1 + gamma_h + gamma_{h+3}) <= n * 2^-1074 = underflow_term(n).  The new bound is the old one plus that
+term and nothing else; wherever the sum of |x_ti x_tj| reaches n * 2^-1021 (1e-303 for a window of 2^20 rows) the term is below u times
+that sum, one of the h + 3 units of the relative part.  The longdouble reference has a 15-bit exponent and does not underflow on
+float64 items.  (A kernel that flushed subnormal operands or results to zero would need n * 2^-1022 per flushed product instead; the
+exact scaled-integer cases of tests/cov_quantile_cases.py show by bytes that k_gram does not.)"""
 from fractions import Fraction
 
 import numpy as np
@@ -128,9 +141,18 @@ def tree_height(n_rows_window):
     return inner + max(len(groups) - 1, 0)
 
 
-def gram_bound(h, absgram):
-    """|G - sum_t x_ti x_tj| <= gamma_{h+3} * sum_t |x_ti x_tj| for a tree of height h (absgram: computed in float64 from |x|)."""
-    return gamma(h + 3) * absgram
+TINY = 2.0 ** -1074                            # the smallest float64 subnormal
+
+
+def underflow_term(n_rows):
+    """n * 2^-1074: what n products rounded in the subnormal range can add to a Gram entry (the module's docstring derives it)."""
+    return np.asarray(n_rows, np.float64) * TINY
+
+
+def gram_bound(h, absgram, n_rows=0):
+    """|G - sum_t x_ti x_tj| <= gamma_{h+3} * sum_t |x_ti x_tj| + n_rows * 2^-1074 for a tree of height h over n_rows rows (absgram:
+    computed in float64 from |x|).  n_rows = 0 is the purely relative bound, which holds only where no product is subnormal."""
+    return gamma(h + 3) * absgram + underflow_term(n_rows)
 
 
 def reference(x):
@@ -147,7 +169,7 @@ def reference(x):
 def gram_allowance(x, h):
     """The allowance of a float Gram against `reference`: gram_bound(h) + the reference's own error.  -> (ref, allowance)."""
     ref, ref_err, absgram = reference(x)
-    return ref, gram_bound(h, absgram) + ref_err
+    return ref, gram_bound(h, absgram, np.asarray(x).shape[0]) + ref_err
 
 
 def assert_gram_within(got, x, h):
@@ -155,11 +177,42 @@ def assert_gram_within(got, x, h):
     single row of x would move some entry of the exact Gram by more than the allowance."""
     ref, allow = gram_allowance(x, h)
     err = np.abs(got.astype(np.longdouble) - ref)
-    assert (err <= allow).all(), 'max err / allowance %.3g' % float((err / np.maximum(allow, 1e-300)).max())
+    assert (err <= allow).all(), 'max err / allowance %.3g' % float((err / np.maximum(allow, TINY)).max())
     xf = widen(x)
     outer_diag = xf * xf                                     # row t's contribution to the diagonal entries
     assert (outer_diag > np.diag(allow)[None, :]).any(axis=1).all(), 'a row whose removal the bound would not catch'
-    return float((err / np.maximum(allow, 1e-300)).max())
+    return float((err / np.maximum(allow, TINY)).max())
+
+
+def assert_order_free(x, start, stop, window):
+    """Whether an entry of the Gram of x (float items, the columns chosen) is finite, +-inf or NaN must depend neither on the order of
+    its sum nor on whether a product is rounded before it is added (a fused multiply-add sees the finite product 1e400 where the
+    separate multiplication sees +inf: -inf + 1e400 is -inf fused and NaN unfused), or no reference could say what the kernel owes.
+    Per window and entry, with the products formed in np.longdouble (which holds them all):
+      * a NaN product (a NaN item, inf * 0) makes the entry NaN whatever the arithmetic;
+      * a product is `huge` when it is infinite or at least 2 * max in magnitude (infinite even when fused with a finite addend of
+        the other sign); the huge products of an entry must all have one sign (the entry is that infinity), unless infinite items
+        alone give both signs (NaN, fused or not);
+      * all other products are finite, and the sum of their magnitudes must stay below max / 2: no partial sum overflows.
+    A case that fails here needs other inputs, not a skipped check.  (Only entries with a column that holds a non-finite item or one
+    beyond 2^500 are walked: among the others a window of fewer than 2^20 rows sums to less than 2^1020.)"""
+    fmax = np.longdouble(np.finfo(np.float64).max)
+    w = window or max(stop - start, 1)
+    assert w < 1 << 20
+    with np.errstate(invalid='ignore'):
+        hot = np.flatnonzero(~(np.abs(widen(x[start:stop])) <= 2.0 ** 500).all(axis=0))
+    for a in range(start, stop, w):
+        xl = widen(x[a:min(a + w, stop)]).astype(np.longdouble)
+        for i in hot:
+            with np.errstate(invalid='ignore', over='ignore'):
+                p = xl[:, i:i + 1] * xl
+            nan = np.isnan(p)
+            huge = ~nan & (np.abs(p) >= 2 * fmax)
+            both = (huge & (p > 0)).any(axis=0) & (huge & (p < 0)).any(axis=0)
+            both_inf = (np.isposinf(p)).any(axis=0) & (np.isneginf(p)).any(axis=0)
+            rest = np.where(nan | huge, 0, np.abs(p)).sum(axis=0)
+            ok = nan.any(axis=0) | both_inf | (~both & (rest < fmax / 2))
+            assert ok.all(), 'window at row %d, entries (%d, %s): the order of the sum decides' % (a, i, np.flatnonzero(~ok)[:5].tolist())
 
 
 def cov_exact(G, s, n, ddof):
@@ -236,7 +289,7 @@ def check_cov_result(got, x, start, stop, window, ddof=1, teeth=True):
             ref64 = np.swapaxes(Xf, 1, 2) @ Xf
         h = np.array([tree_height(c) for c in counts], np.float64)
         gam = (h + 3) * U / (1 - (h + 3) * U)
-        allow = gam[:, None, None] * absgram + (counts + 2)[:, None, None] * UL * absgram
+        allow = gam[:, None, None] * absgram + (counts + 2)[:, None, None] * UL * absgram + underflow_term(counts)[:, None, None]
         fin = np.isfinite(absgram)
         g = got.gram
         assert np.array_equal(np.isnan(g), np.isnan(ref64))
@@ -247,7 +300,7 @@ def check_cov_result(got, x, start, stop, window, ddof=1, teeth=True):
             w, i, j = np.argwhere(~ok)[0]
             raise AssertionError('gram[%d, %d, %d] = %r, reference %r, allowance %r' % (w, i, j, g[w, i, j], float(ref[w, i, j]), allow[w, i, j]))
         if fin.any():
-            worst = float(np.max(np.where(fin, err / np.maximum(allow, 1e-300), 0)))
+            worst = float(np.max(np.where(fin, err / np.maximum(allow, TINY), 0)))
         # teeth: in a window of finite items, every row with a nonzero item would, if dropped, move a diagonal entry by more than its
         # allowance (windows that hold NaN or +-inf are checked for where those land, and the finite entries for the bound)
         d = np.einsum('wii->wi', allow)
