@@ -1243,7 +1243,7 @@ class Reader:
                 g = owners[j]
                 keys = [k for k in run if k % lanes == g]
                 cache = self._cache_for(g) if use_cache else 0
-                st, res = self._lane_window_stats(cache, keys, rb, re, window, cols, g)
+                st, res = self._lane_call(self.codec.window_stats, cache, keys, g, rb, re, window, cols)
                 parts[j] = (keys, st, res)
             self.codec.run_lanes(one, len(owners))
             for keys, st, res in parts:                             # lanes in order: the float sums are the same every time
@@ -1267,10 +1267,10 @@ class Reader:
                 out[key] = out[key][:, 0]
         return out
 
-    def _lane_window_stats(self, cache, keys, row_begin, row_end, window, cols, lane):
-        """One codec.window_stats call for the chunks `keys` of one lane: chunks resident in its cache go without bytes, the
-        others' compressed bytes come from a mapping of the file (or one read); sent whole once more if an entry was dropped
-        between the query and the call.  -> (status list, partials)."""
+    def _lane_call(self, fn, cache, keys, lane, *args):
+        """One call of a codec's reduction `fn` (window_stats, rank_hist, decimate, welch or gram) for the chunks `keys` of one lane:
+        chunks resident in its cache go without bytes, the others' compressed bytes come from a mapping of the file (or one read); sent
+        whole once more if an entry was dropped between the query and the call.  -> what `fn` returns."""
         row0 = [self.chunk_bounds[k] for k in keys]
         rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
         present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
@@ -1284,8 +1284,7 @@ class Reader:
             if buf is None:
                 buf = self._pread(nbytes, base)
             try:
-                return self.codec.window_stats(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(),
-                                               row_begin, row_end, window, cols, lane=lane)
+                return fn(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), *args, lane=lane)
             except hip.HipError as e:
                 if e.code != hip.E_MISS or attempt:
                     raise
@@ -1458,7 +1457,7 @@ class Reader:
                 g = owners[j]
                 keys = [k for k in run if k % lanes == g]
                 cache = self._cache_for(g) if use_cache else 0
-                st, res = self._lane_rank_hist(cache, keys, cb, ce, window, cols, mode, cen, pre, shf, g)
+                st, res = self._lane_call(self.codec.rank_hist, cache, keys, g, cb, ce, window, cols, mode, cen, pre, shf)
                 parts[j] = (keys, st, res)
             self.codec.run_lanes(one, len(owners))
             for keys, st, res in parts:
@@ -1468,30 +1467,6 @@ class Reader:
                 kmax[sl] = np.maximum(kmax[sl], res['kmax'])
         self._raise_for(status)
         return hist, kmin, kmax
-
-    def _lane_rank_hist(self, cache, keys, row_begin, row_end, window, cols, mode, center, pref, sel_shift, lane):
-        """One codec.rank_hist call for the chunks `keys` of one lane: chunks resident in its cache go without bytes, the others'
-        compressed bytes come from a mapping of the file (or one read); sent whole once more if an entry was dropped between the
-        query and the call.  -> (status list, partials)."""
-        row0 = [self.chunk_bounds[k] for k in keys]
-        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
-        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
-        for attempt in range(2):
-            need = [k for k, p in zip(keys, present) if not p]
-            base = self.chunk_offsets[need[0]] if need else 0
-            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
-            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
-            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
-            buf = self._map_range(nbytes, base) if need else b''
-            if buf is None:
-                buf = self._pread(nbytes, base)
-            try:
-                return self.codec.rank_hist(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), row_begin,
-                                            row_end, window, cols, mode, center, pref, sel_shift, lane=lane)
-            except hip.HipError as e:
-                if e.code != hip.E_MISS or attempt:
-                    raise
-                present = [False] * len(keys)                       # dropped since the query: send everything
 
     def quantile(self, q, start=0, stop=None, channels=slice(None), window=None, method='linear', center=None, absolute=False):
         """Exact per-window, per-channel quantiles of rows [start, stop), selected on the device: only digit histograms cross the
@@ -1689,7 +1664,7 @@ class Reader:
                     c1 = bisect.bisect_right(self.chunk_bounds, phi - 1) - 1
                     keys = list(range(c0, c1 + 1))
                     cache = self._cache_for(g) if use_cache else 0
-                    st, y = self._lane_decimate(cache, keys, vb, ve, fr, b - a, q, taps, out_dtype, cols, g)
+                    st, y = self._lane_call(self.codec.decimate, cache, keys, g, vb, ve, fr, b - a, q, taps, out_dtype, cols)
                     res[g] = (keys, st, y)
                 self.codec.run_lanes(one, nl)
                 for g in range(nl):
@@ -1702,29 +1677,6 @@ class Reader:
                     out[parts[g]:parts[g + 1]] = y
             self._raise_for(status)
         return out[:, 0] if squeeze else out
-
-    def _lane_decimate(self, cache, keys, vb, ve, first_row, n_out, q, taps, out_dtype, cols, lane):
-        """One codec.decimate call on one lane: chunks resident in its cache go without bytes, the others' compressed bytes come
-        from a mapping of the file (or one read); sent whole once more if an entry was dropped between the query and the call."""
-        row0 = [self.chunk_bounds[k] for k in keys]
-        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
-        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
-        for attempt in range(2):
-            need = [k for k, p in zip(keys, present) if not p]
-            base = self.chunk_offsets[need[0]] if need else 0
-            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
-            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
-            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
-            buf = self._map_range(nbytes, base) if need else b''
-            if buf is None:
-                buf = self._pread(nbytes, base)
-            try:
-                return self.codec.decimate(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), vb, ve,
-                                           first_row, n_out, q, taps, out_dtype, cols, lane=lane)
-            except hip.HipError as e:
-                if e.code != hip.E_MISS or attempt:
-                    raise
-                present = [False] * len(keys)                       # dropped since the query: send everything
 
     # -- power spectral density on the device (an extension: the reference's users run scipy.signal.welch on Reader[...])
     def welch(self, nperseg=256, start=0, stop=None, channels=slice(None), noverlap=None, window='hann', detrend='constant',
@@ -1821,7 +1773,7 @@ class Reader:
                     c0, c1 = chunk_span(a, b)
                     keys = list(range(c0, c1 + 1))
                     cache = self._cache_for(g) if use_cache else 0
-                    st, part = self._lane_welch(cache, keys, i0, a * G, min(b * G, n_seg), nperseg, step, taper, dt, cdt, cols, g)
+                    st, part = self._lane_call(self.codec.welch, cache, keys, g, i0, a * G, min(b * G, n_seg), nperseg, step, taper, dt, cdt, cols)
                     res[g] = (keys, st, part)
                 self.codec.run_lanes(one, nl)
                 for g in range(nl):
@@ -1840,29 +1792,6 @@ class Reader:
         psd[1:-1] *= 2.0
         psd /= n_seg
         return f, (psd[:, 0] if squeeze else psd)
-
-    def _lane_welch(self, cache, keys, row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, compute_dtype, cols, lane):
-        """One codec.welch call on one lane: chunks resident in its cache go without bytes, the others' compressed bytes come from a
-        mapping of the file (or one read); sent whole once more if an entry was dropped between the query and the call."""
-        row0 = [self.chunk_bounds[k] for k in keys]
-        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
-        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
-        for attempt in range(2):
-            need = [k for k, p in zip(keys, present) if not p]
-            base = self.chunk_offsets[need[0]] if need else 0
-            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
-            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
-            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
-            buf = self._map_range(nbytes, base) if need else b''
-            if buf is None:
-                buf = self._pread(nbytes, base)
-            try:
-                return self.codec.welch(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), row_seg0,
-                                        seg_begin, seg_end, nperseg, step, taper, detrend, compute_dtype, cols, lane=lane)
-            except hip.HipError as e:
-                if e.code != hip.E_MISS or attempt:
-                    raise
-                present = [False] * len(keys)                       # dropped since the query: send everything
 
     # -- channel covariance on the device (an extension: the reference's users form x.T @ x of Reader[...] on the host)
     def cov(self, start=0, stop=None, channels=slice(None), window=None, ddof=1):
@@ -1934,7 +1863,7 @@ class Reader:
                         return
                     keys = list(range(int(gc0[a]), int(gc1[b - 1]) + 1))
                     cache = self._cache_for(j) if use_cache else 0
-                    res[j] = (keys,) + tuple(self._lane_gram(cache, keys, i0, i1, window, a, b, cols, j))
+                    res[j] = (keys,) + tuple(self._lane_call(self.codec.gram, cache, keys, j, i0, i1, window, a, b, cols))
                 self.codec.run_lanes(one, nl)
                 for j in range(nl):                                 # groups in order: the float sums are the same every time
                     if res[j] is None:
@@ -1959,29 +1888,6 @@ class Reader:
             cov = (gram.astype(np.float64) - sf[:, :, None] * mean[:, None, :]) / denom[:, None, None]
         cov[denom <= 0] = np.nan
         return Bunch(count=cnt, sum=sm, gram=gram, mean=mean, cov=cov, start=i0, stop=i1, window=window, channels=cols)
-
-    def _lane_gram(self, cache, keys, range_begin, range_end, window, group_begin, group_end, cols, lane):
-        """One codec.gram call on one lane: chunks resident in its cache go without bytes, the others' compressed bytes come from a
-        mapping of the file (or one read); sent whole once more if an entry was dropped between the query and the call."""
-        row0 = [self.chunk_bounds[k] for k in keys]
-        rows = [self.chunk_bounds[k + 1] - self.chunk_bounds[k] for k in keys]
-        present = [int(p) >= self.n_channels for p in self.codec.cache_query(cache, keys)] if cache else [False] * len(keys)
-        for attempt in range(2):
-            need = [k for k, p in zip(keys, present) if not p]
-            base = self.chunk_offsets[need[0]] if need else 0
-            nbytes = self.chunk_offsets[need[-1] + 1] - base if need else 0
-            offs = [self.chunk_offsets[k] - base if not p else 0 for k, p in zip(keys, present)]
-            lens = [self.chunk_offsets[k + 1] - self.chunk_offsets[k] if not p else 0 for k, p in zip(keys, present)]
-            buf = self._map_range(nbytes, base) if need else b''
-            if buf is None:
-                buf = self._pread(nbytes, base)
-            try:
-                return self.codec.gram(cache, keys, row0, buf, offs, lens, rows, self.n_channels, self.dtype, self._flags(), range_begin,
-                                       range_end, window, group_begin, group_end, cols, lane=lane)
-            except hip.HipError as e:
-                if e.code != hip.E_MISS or attempt:
-                    raise
-                present = [False] * len(keys)                       # dropped since the query: send everything
 
     def _read_range(self, b0, b1):
         """The compressed bytes of chunks b0 .. b1-1 in one read."""

@@ -1631,104 +1631,360 @@ int mts_debug_inflate(int device, const unsigned char *zbytes, long zlen, unsign
     return MTS_OK;
 }
 
+}  // extern "C"
+
+// ================================================================================================
+// How a reduction is fed (window_stats_run, rank_hist_run, decimate_run, welch_run, gram_run)
+// ================================================================================================
+// A reduction reads the rows of some chunks and never keeps them.  A chunk that is whole in the call's device cache (resident) is read
+// where it lies; every other chunk (missing) comes with its compressed bytes and is decoded into the piece workspace E.h_out.  The
+// missing chunks are cut into pieces of MTS_PIPE_BYTES of decoded bytes (pipe_pieces; resident chunks weigh nothing, device input is
+// one piece: nothing to copy beside the kernels, and smaller batches inflate slower): while piece p is decoded and reduced, the
+// compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
+//   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
+//        and each piece decodes exactly its own missing chunks (TilePlan);
+//   halo (decimate, welch, gram): a unit of output (outputs, blocks, groups -- the op maps them to pieces itself) reads rows of
+//        several adjacent chunks, so a piece reads chunks [c0, c1] through a table of segment bases and first rows, and decodes the
+//        missing ones among them -- a boundary chunk in both pieces (plan_pieces, segment_tables).
+// What every caller keeps to, and feed_pieces and ChunkFeed hold up:
+//   - An allocation that fails empties this device's caches before it tries again (DBuf::ensure -> drop_device_caches: hipFree,
+//     which waits for the kernels already launched -- earlier reads are done).  So every allocation of the call (the op's own DBuf,
+//     then ChunkFeed::ensure) comes BEFORE the first use of a resident entry's address, and ensure looks every resident entry up
+//     again: a call whose entries went ends with MTS_E_MISS (the Reader sends every chunk's bytes once more).
+//   - A decode allocates again (decompress_batch).  The tile family therefore reduces the resident tiles and waits for the stream
+//     before the first decode (only when there are resident tiles); the halo family checks after each piece's decode and before its
+//     launch that every resident chunk the piece reads is still in the cache at the address its table holds (still_placed).
+//   - The helper thread's copy of piece p + 1 starts before piece p's decode and is always joined before feed_pieces returns, on
+//     error paths too: it holds references to the caller's frame.
+//   - The first dev_decompress of a call starts the stage times (add_times false), every later one adds to them.
+//   - The compressed bytes of the missing chunks lie in E.h_in in chunk order, at mcoff[]: chunks back to back in the caller's buffer
+//     keep their distances (a run of them with adjacent chunk indices is one staged copy), a gap starts at the next multiple of 16.
+namespace {
+
+int check_items(int sz, int flags)
+{
+    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
+    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    return MTS_OK;
+}
+
+int check_columns(const int *cols, int n_cols, int nc)
+{
+    for (int j = 0; j < n_cols; j++)
+        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
+    return MTS_OK;
+}
+
+// adjacent: every chunk begins where the one before it ends (the halo family); else the chunks are in order, do not overlap and each
+// holds a row of [row_begin, row_end) (the tile family)
+int check_chunk_table(bool adjacent, bool have_cache, const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz,
+                      long row_begin = 0, long row_end = 0)
+{
+    for (int i = 0; i < n_chunks; i++) {
+        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
+        if (adjacent) {
+            if (i && row0[i] != row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: chunks must be adjacent", i); return MTS_E_ARG; }
+        } else {
+            if (i && row0[i] < row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: rows out of order or overlapping", i); return MTS_E_ARG; }
+            if (row0[i] >= row_end || row0[i] + n_rows[i] <= row_begin) { set_error("chunk %d holds no row of [%ld, %ld)", i, row_begin, row_end); return MTS_E_ARG; }
+        }
+        if (!have_cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
+        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
+    }
+    return MTS_OK;
+}
+
+// the chunk holding `row` (clamped to the chunks)
+int chunk_of(const long *row0, int n_chunks, long row)
+{
+    int lo = 0, hi = n_chunks - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row0[mid] <= row) lo = mid; else hi = mid - 1; }
+    return lo;
+}
+
+// one piece: the missing chunks `miss` (ascending) are decoded to E.h_out + ooff[]; a halo piece covers the op's units [u0, u1) and
+// reads chunks [c0, c1] (c1 < c0: nothing to read)
+struct FeedPiece {
+    long u0 = 0, u1 = 0;
+    int c0 = 0, c1 = -1;
+    std::vector<int> miss;
+    std::vector<long> ooff;
+    u64 ws = 0;
+    void add(int chunk, u64 bytes) { miss.push_back(chunk); ooff.push_back((long)ws); ws += align_up(bytes, 256); }
+};
+
+// which chunks of a call are resident, where the bytes of the others lie, and their way into E.h_out
+struct ChunkFeed {
+    DevCache *cache;
+    const long *keys;
+    const u8 *cdata;
+    bool on_device;
+    const long *c_off, *c_len, *n_rows;
+    int n_chunks, nc, sz;
+    u64 row_bytes;
+    std::vector<char> resident, copied;
+    std::vector<const u8 *> res_ptr;                          // the address of each resident entry the tables hold (halo family)
+    std::vector<long> mcoff;                                  // per missing chunk: its compressed bytes in src()
+    u64 ctot = 0;
+    bool any_miss = false, first_decode = true;
+
+    ChunkFeed(DevCache *cache_, const long *keys_, const u8 *cdata_, bool on_device_, const long *c_off_, const long *c_len_,
+              const long *n_rows_, int n_chunks_, int nc_, int sz_)
+        : cache(cache_), keys(keys_), cdata(cdata_), on_device(on_device_), c_off(c_off_), c_len(c_len_), n_rows(n_rows_), n_chunks(n_chunks_),
+          nc(nc_), sz(sz_), row_bytes((u64)nc_ * sz_), resident(n_chunks_, 0), copied(n_chunks_, 0), res_ptr(n_chunks_, nullptr),
+          mcoff(n_chunks_, 0) {}
+
+    const CacheEntry *entry_of(int i) const                   // chunk i whole in the cache, or nullptr
+    {
+        if (!cache) return nullptr;
+        auto it = cache->map.find(keys[i]);
+        if (it == cache->map.end()) return nullptr;
+        const CacheEntry &e = it->second;
+        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
+    }
+    long key_of(int i) const { return keys ? keys[i] : (long)i; }
+    const u8 *src(Engine &E) const { return on_device ? cdata : E.h_in.as<u8>(); }
+
+    // resident or missing (a missing chunk without bytes: MTS_E_MISS), and the layout of the missing chunks' bytes in E.h_in
+    int classify()
+    {
+        int prev = -1;
+        for (int i = 0; i < n_chunks; i++) {
+            if (entry_of(i)) { resident[i] = 1; continue; }
+            if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", key_of(i)); return MTS_E_MISS; }
+            any_miss = true;
+            if (on_device) { mcoff[i] = c_off[i]; continue; }
+            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
+            if (!joins) ctot = align_up(ctot + (prev >= 0 ? 16 : 0), 16);
+            mcoff[i] = (long)ctot; ctot += (u64)c_len[i];
+            prev = i;
+        }
+        ctot += 16;
+        return MTS_OK;
+    }
+
+    // chunks [pb[p], pb[p + 1]) are decoded in piece p
+    std::vector<int> piece_bounds() const
+    {
+        if (on_device) return {0, n_chunks};
+        std::vector<long> weight(n_chunks, 0);
+        for (int i = 0; i < n_chunks; i++) if (!resident[i]) weight[i] = n_rows[i];
+        return pipe_pieces(weight.data(), false, n_chunks, row_bytes);
+    }
+
+    // the last allocations of the call (after the op's own), then the resident entries once more
+    int ensure(Engine &E, u64 piece_cap)
+    {
+        int rc;
+        if (any_miss && !on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
+        if (piece_cap && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
+        for (int i = 0; i < n_chunks; i++)
+            if (resident[i] && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", key_of(i)); return MTS_E_MISS; }
+        return MTS_OK;
+    }
+
+    // the compressed bytes of `chunks` (ascending, missing) into E.h_in, each chunk once in a call; runs on the helper thread
+    int copy_in(Engine &E, const std::vector<int> &chunks)
+    {
+        if (on_device) return MTS_OK;
+        MTS_HIP(hipSetDevice(E.dev));
+        for (size_t a = 0; a < chunks.size();) {
+            if (copied[chunks[a]]) { a++; continue; }
+            size_t e = a + 1;                                     // a run of chunks back to back here and in the caller's buffer
+            while (e < chunks.size() && !copied[chunks[e]] && chunks[e] == chunks[e - 1] + 1 &&
+                   c_off[chunks[e]] == c_off[chunks[e - 1]] + c_len[chunks[e - 1]] && mcoff[chunks[e]] == mcoff[chunks[e - 1]] + c_len[chunks[e - 1]]) e++;
+            u64 len = 0;
+            for (size_t z = a; z < e; z++) { len += (u64)c_len[chunks[z]]; copied[chunks[z]] = 1; }
+            if (len) { const int rc = staged_h2d(E, E.h_in.as<u8>() + mcoff[chunks[a]], cdata + c_off[chunks[a]], (size_t)len); if (rc) return rc; }
+            a = e;
+        }
+        return MTS_OK;
+    }
+
+    // a piece's missing chunks into E.h_out; status[] of each of them
+    int decode(Engine &E, hipStream_t st, const FeedPiece &P, int dflags, int *status)
+    {
+        const int nm = (int)P.miss.size();
+        if (!nm) return MTS_OK;
+        std::vector<long> co(nm), cl(nm), nr(nm);
+        std::vector<int> mst(nm, MTS_CHUNK_CORRUPT);
+        for (int z = 0; z < nm; z++) { co[z] = mcoff[P.miss[z]]; cl[z] = c_len[P.miss[z]]; nr[z] = n_rows[P.miss[z]]; }
+        const int rc = dev_decompress(E, st, src(E), co.data(), cl.data(), nr.data(), nm, nc, sz, dflags, E.h_out.as<u8>(), P.ooff.data(), mst.data(),
+                                      0, !first_decode);
+        first_decode = false;
+        if (!rc) for (int z = 0; z < nm; z++) status[P.miss[z]] = mst[z];
+        return rc;
+    }
+
+    // after a piece's decode: every resident chunk its table points at is still in the cache at that address
+    int still_placed(const FeedPiece &P) const
+    {
+        for (int i = P.c0; i <= P.c1; i++) {
+            if (!resident[i]) continue;
+            const CacheEntry *e = entry_of(i);
+            if (!e || e->d != res_ptr[i]) { set_error("chunk key %ld was dropped from the cache during the call", key_of(i)); return MTS_E_MISS; }
+        }
+        return MTS_OK;
+    }
+};
+
+// piece after piece: the next piece's bytes are copied beside this piece's decode and launch(p)
+template <class Launch>
+int feed_pieces(ChunkFeed &F, Engine &E, hipStream_t st, const std::vector<FeedPiece> &pieces, int dflags, int *status, Launch &&launch)
+{
+    auto copy_in = [&](int p) -> int { return F.copy_in(E, pieces[p].miss); };
+    const int np = (int)pieces.size();
+    int rc;
+    if (np > 0 && (rc = copy_in(0))) return rc;
+    for (int p = 0; p < np; p++) {
+        std::future<int> f_in;
+        if (p + 1 < np) f_in = copy_beside(copy_in, p + 1);
+        rc = F.decode(E, st, pieces[p], dflags, status);
+        if (!rc) rc = launch(p);
+        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;      // (always joined: it holds references to this frame)
+        if (rc || rc_in) return rc ? rc : rc_in;
+    }
+    return MTS_OK;
+}
+
+// ---- halo family: the chunks [c0, c1] of every piece are set by the op
+// fills miss / ooff / ws of every piece; -> where each piece's segment table begins ((c1 - c0 + 1) bases, then (c1 - c0 + 2) first rows)
+std::vector<long> plan_pieces(const ChunkFeed &F, std::vector<FeedPiece> &pieces, u64 *piece_cap)
+{
+    std::vector<long> seg_at(pieces.size() + 1, 0);
+    *piece_cap = 0;
+    for (size_t p = 0; p < pieces.size(); p++) {
+        FeedPiece &P = pieces[p];
+        for (int i = P.c0; i <= P.c1; i++) if (!F.resident[i]) P.add(i, (u64)F.n_rows[i] * F.row_bytes);
+        *piece_cap = std::max(*piece_cap, P.ws);
+        seg_at[p + 1] = seg_at[p] + 2l * (P.c1 - P.c0 + 1) + 1;
+    }
+    return seg_at;
+}
+
+// the segment tables, one after the other (after ChunkFeed::ensure: they hold the resident entries' addresses, kept in F.res_ptr)
+std::vector<long> segment_tables(ChunkFeed &F, Engine &E, const std::vector<FeedPiece> &pieces, const std::vector<long> &seg_at, const long *row0)
+{
+    std::vector<long> seg(seg_at.back() + 1, 0);
+    for (int i = 0; i < F.n_chunks; i++) if (F.resident[i]) F.res_ptr[i] = F.entry_of(i)->d;
+    for (size_t p = 0; p < pieces.size(); p++) {
+        const FeedPiece &P = pieces[p];
+        long *b = seg.data() + seg_at[p], *r = b + (P.c1 - P.c0 + 1);
+        size_t m = 0;
+        for (int i = P.c0; i <= P.c1; i++) {
+            const u8 *base = F.resident[i] ? F.res_ptr[i] : E.h_out.as<u8>() + P.ooff[m++];
+            b[i - P.c0] = (long)(uintptr_t)base;
+            r[i - P.c0] = row0[i];
+        }
+        r[P.c1 - P.c0 + 1] = P.c1 >= P.c0 ? row0[P.c1] + F.n_rows[P.c1] : 0;
+    }
+    return seg;
+}
+
+// ---- tile family: the rows of every (chunk ∩ window) segment cut into tiles of tile_rows rows, in row order
+struct TilePlan {
+    std::vector<StatTile> tiles;
+    std::vector<long> tile_win, chunk_tile0;
+    std::vector<FeedPiece> pieces;
+    u64 piece_cap = 0;
+    std::vector<int> ids;                                     // the tiles in launch order: the resident chunks', then piece after piece
+    std::vector<long> launch0;                                // ids [launch0[0], launch0[1]): resident, [launch0[1 + p], launch0[2 + p]): piece p
+
+    TilePlan(const ChunkFeed &F, const long *row0, long row_begin, long row_end, long window_rows, long tile_rows) : chunk_tile0(F.n_chunks + 1)
+    {
+        for (int i = 0; i < F.n_chunks; i++) {
+            chunk_tile0[i] = (long)tiles.size();
+            const long a = row0[i] > row_begin ? row0[i] : row_begin, b = row0[i] + F.n_rows[i] < row_end ? row0[i] + F.n_rows[i] : row_end;
+            for (long r = a; r < b;) {
+                const long w = (r - row_begin) / window_rows, wend = row_begin + (w + 1) * window_rows, e = b < wend ? b : wend;
+                for (long q = r; q < e; q += tile_rows) {
+                    StatTile t;
+                    t.base = nullptr; t.row_lo = q - row0[i]; t.n_rows = (e - q) < tile_rows ? (e - q) : tile_rows; t.chunk = i; t.pad = 0;
+                    tiles.push_back(t);
+                    tile_win.push_back(w);
+                }
+                r = e;
+            }
+        }
+        chunk_tile0[F.n_chunks] = (long)tiles.size();
+        const std::vector<int> pb = F.piece_bounds();
+        for (size_t p = 0; p + 1 < pb.size(); p++) {
+            FeedPiece P;
+            for (int i = pb[p]; i < pb[p + 1]; i++) if (!F.resident[i]) P.add(i, (u64)F.n_rows[i] * F.row_bytes);
+            if (P.miss.empty()) continue;
+            piece_cap = std::max(piece_cap, P.ws);
+            pieces.push_back(std::move(P));
+        }
+    }
+
+    // after ChunkFeed::ensure: the tiles' bases and the order of the launches; resident chunks are ok and their status is set
+    void place(const ChunkFeed &F, Engine &E, std::vector<int> &ok, int *status)
+    {
+        auto take = [&](int i, const u8 *base) { for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = base; ids.push_back((int)t); } };
+        launch0.push_back(0);
+        for (int i = 0; i < F.n_chunks; i++) {
+            if (!F.resident[i]) continue;
+            take(i, F.entry_of(i)->d);
+            ok[i] = 1;
+            status[i] = MTS_CHUNK_OK;
+        }
+        for (const FeedPiece &P : pieces) {
+            launch0.push_back((long)ids.size());
+            for (size_t z = 0; z < P.miss.size(); z++) take(P.miss[z], E.h_out.as<u8>() + P.ooff[z]);
+        }
+        launch0.push_back((long)ids.size());
+    }
+
+    // after piece p's decode: which of its chunks are good, for the kernel (tiles of the others are identities)
+    int mark_decoded(int p, const int *status, std::vector<int> &ok, int *d_ok, hipStream_t st) const
+    {
+        for (int i : pieces[p].miss) ok[i] = status[i] == MTS_CHUNK_OK;
+        hipError_t e = hipMemcpyAsync(d_ok, ok.data(), 4 * ok.size(), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); return MTS_E_HIP; }
+        return MTS_OK;
+    }
+
+    void add_counts(const std::vector<int> &ok, long *count) const
+    {
+        for (size_t t = 0; t < tiles.size(); t++) if (ok[tiles[t].chunk]) count[tile_win[t]] += tiles[t].n_rows;
+    }
+};
+
+}  // namespace
+
 // ---- per-window statistics (mts_window_stats, mts_dev_window_stats) ---------------------------------
-// The rows of every (chunk ∩ window) segment are cut into tiles of STAT_TILE_ROWS rows, in row order (stats.hip).  Resident chunks
-// are reduced first, where they lie; the others piece by piece (pipe_pieces): inflate into the piece workspace (E.h_out), reduce,
-// and the next piece's compressed bytes cross the bus on a helper thread meanwhile.  One combine launch at the end.
+// Tiles of STAT_TILE_ROWS rows (stats.hip), one partial per (tile, column); one combine launch at the end takes the tiles of
+// window w, [win_tiles[w], win_tiles[w + 1]), in row order.
 static int window_stats_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device,
                             const long *c_off, const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz,
                             int flags, long row_begin, long row_end, long window_rows, int n_cols, const int *cols, void *o_min,
                             void *o_max, void *o_sum, void *o_sq, bool out_on_host, long *count, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
-    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    int rc;
+    if ((rc = check_items(sz, flags))) return rc;
     if (nc <= 0 || n_chunks < 0 || n_cols < 1 || !cols) { set_error("window stats: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
     if (window_rows < 1) { set_error("window_rows %ld < 1", window_rows); return MTS_E_ARG; }
     if (row_begin < 0 || row_end < row_begin) { set_error("row range [%ld, %ld) invalid", row_begin, row_end); return MTS_E_ARG; }
-    for (int j = 0; j < n_cols; j++)
-        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
     const bool exact = !(flags & MTS_FLAG_FLOAT) && sz <= 2;
     const long span = row_end - row_begin;
     if (exact && (window_rows < span ? window_rows : span) > (1l << 31)) { set_error("windows of more than 2^31 rows on the exact path"); return MTS_E_ARG; }
-    for (int i = 0; i < n_chunks; i++) {
-        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
-        if (i && row0[i] < row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: rows out of order or overlapping", i); return MTS_E_ARG; }
-        if (row0[i] >= row_end || row0[i] + n_rows[i] <= row_begin) { set_error("chunk %d holds no row of [%ld, %ld)", i, row_begin, row_end); return MTS_E_ARG; }
-        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
-        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
-    }
+    if ((rc = check_chunk_table(false, cache != nullptr, c_len, row0, n_rows, n_chunks, nc, sz, row_begin, row_end))) return rc;
     const long n_win = (span + window_rows - 1) / window_rows;
     if (n_win && (!o_min || !o_max || !o_sum || !o_sq || !count)) return MTS_E_ARG;
     for (long w = 0; w < n_win; w++) count[w] = 0;
     if (n_win == 0) return MTS_OK;                           // (no chunk can hold a row of an empty range: n_chunks is 0)
 
-    // ---- tiles, in row order; the tiles of window w are [win_tiles[w], win_tiles[w + 1])
-    std::vector<StatTile> tiles;
-    std::vector<long> tile_win, chunk_tile0(n_chunks + 1);
-    for (int i = 0; i < n_chunks; i++) {
-        chunk_tile0[i] = (long)tiles.size();
-        const long a = row0[i] > row_begin ? row0[i] : row_begin, b = row0[i] + n_rows[i] < row_end ? row0[i] + n_rows[i] : row_end;
-        for (long r = a; r < b;) {
-            const long w = (r - row_begin) / window_rows, wend = row_begin + (w + 1) * window_rows, e = b < wend ? b : wend;
-            for (long q = r; q < e; q += STAT_TILE_ROWS) {
-                StatTile t;
-                t.base = nullptr; t.row_lo = q - row0[i]; t.n_rows = (e - q) < STAT_TILE_ROWS ? (e - q) : STAT_TILE_ROWS; t.chunk = i; t.pad = 0;
-                tiles.push_back(t);
-                tile_win.push_back(w);
-            }
-            r = e;
-        }
-    }
-    chunk_tile0[n_chunks] = (long)tiles.size();
-    const long n_tiles = (long)tiles.size();
+    ChunkFeed F(cache, keys, cdata, cdata_on_device, c_off, c_len, n_rows, n_chunks, nc, sz);
+    if ((rc = F.classify())) return rc;
+    TilePlan P(F, row0, row_begin, row_end, window_rows, STAT_TILE_ROWS);
+    const long n_tiles = (long)P.tiles.size();
     std::vector<long> win_tiles(n_win + 1, 0);
-    for (long t = 0; t < n_tiles; t++) win_tiles[tile_win[t] + 1]++;
+    for (long t = 0; t < n_tiles; t++) win_tiles[P.tile_win[t] + 1]++;
     for (long w = 0; w < n_win; w++) win_tiles[w + 1] += win_tiles[w];
 
-    // ---- which chunks are resident (whole rows), which are decoded here, in which pieces
-    auto entry_of = [&](int i) -> const CacheEntry * {
-        if (!cache) return nullptr;
-        auto it = cache->map.find(keys[i]);
-        if (it == cache->map.end()) return nullptr;
-        const CacheEntry &e = it->second;
-        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
-    };
-    std::vector<int> miss;
-    for (int i = 0; i < n_chunks; i++) {
-        if (entry_of(i)) continue;
-        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-        miss.push_back(i);
-    }
-    const int m = (int)miss.size();
-    const u64 row_bytes = (u64)nc * sz;
-    std::vector<long> mrows(m), mcoff(m), mclen(m), mooff(m);
-    for (int k = 0; k < m; k++) { mrows[k] = n_rows[miss[k]]; mclen[k] = c_len[miss[k]]; }
-    // (device input: nothing to copy beside the kernels -- one piece, one decode batch; smaller batches inflate slower)
-    const std::vector<int> pb = cdata_on_device ? std::vector<int>{0, m} : pipe_pieces(mrows.data(), false, m, row_bytes);
-    const int np = (int)pb.size() - 1;
-    u64 piece_cap = 0;
-    for (int k = 0; k < np; k++) {
-        u64 o = 0;
-        for (int q = pb[k]; q < pb[k + 1]; q++) { mooff[q] = (long)o; o += align_up((u64)mrows[q] * row_bytes, 256); }
-        if (o > piece_cap) piece_cap = o;
-    }
-    u64 ctot = 0;
-    if (!cdata_on_device) {
-        // (chunks that lie back to back in the caller's buffer keep their distances: one staged copy per run)
-        for (int k = 0; k < m; k++) {
-            const int i = miss[k];
-            const bool joins = k > 0 && c_off[i] == c_off[miss[k - 1]] + mclen[k - 1];
-            if (!joins) ctot = align_up(ctot + (k ? 16 : 0), 16);
-            mcoff[k] = (long)ctot; ctot += (u64)mclen[k];
-        }
-        ctot += 16;
-    } else {
-        for (int k = 0; k < m; k++) mcoff[k] = c_off[miss[k]];
-    }
-
-    // ---- workspace: every allocation of the call comes BEFORE the resident entries are looked at (a workspace allocation that
-    //      fails drops this device's decoded chunks, DBuf::ensure)
+    // ---- workspace
     const u64 plane = (u64)n_tiles * n_cols * 8;
     const size_t o_tiles = 0, o_ids = align_up(sizeof(StatTile) * (n_tiles + 1), 256), o_ok = o_ids + align_up(4 * (u64)(n_tiles + 1), 256),
                  o_cols = o_ok + align_up(4 * (u64)(n_chunks + 1), 256), o_wt = o_cols + align_up(4 * (u64)n_cols, 256),
@@ -1736,86 +1992,37 @@ static int window_stats_run(Engine &E, hipStream_t st, DevCache *cache, const lo
     const u64 n_items = (u64)n_win * n_cols;
     const size_t o_omin = o_out, o_omax = o_omin + align_up(n_items * sz, 256), o_osum = o_omax + align_up(n_items * sz, 256),
                  o_osq = o_osum + align_up(n_items * 8, 256), o_end = out_on_host ? o_osq + align_up(n_items * 8, 256) : o_out;
-    int rc;
     if ((rc = E.stats.ensure(o_end + 256))) return rc;
-    if (m && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
-    if (m && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
-    if (cache) {
-        for (int i = 0; i < n_chunks; i++)                   // (the allocations above may have emptied the cache)
-            if (c_len[i] == 0 && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-    }
+    if ((rc = F.ensure(E, P.piece_cap))) return rc;
     u8 *ws = E.stats.as<u8>();
     StatTile *d_tiles = (StatTile *)(ws + o_tiles);
     int *d_ids = (int *)(ws + o_ids), *d_ok = (int *)(ws + o_ok), *d_cols = (int *)(ws + o_cols);
     long *d_wt = (long *)(ws + o_wt);
     u8 *d_slab = ws + o_slab;
-    // tile pointers and the order of the launches: resident chunks first, then piece after piece
-    std::vector<int> ok(n_chunks + 1, 0), ids;
-    std::vector<long> launch0;                               // [0]: the resident tiles, [1 + k]: piece k's
-    std::vector<char> decoded(n_chunks, 0);
-    for (int k = 0; k < m; k++) decoded[miss[k]] = 1;
-    launch0.push_back(0);
-    for (int i = 0; i < n_chunks; i++) {
-        if (decoded[i]) continue;
-        const CacheEntry *e = entry_of(i);
-        for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = e->d; ids.push_back((int)t); }
-        ok[i] = 1;
-        status[i] = MTS_CHUNK_OK;
-    }
-    for (int k = 0; k < np; k++) {
-        launch0.push_back((long)ids.size());
-        for (int q = pb[k]; q < pb[k + 1]; q++) {
-            const int i = miss[q];
-            for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = E.h_out.as<u8>() + mooff[q]; ids.push_back((int)t); }
-        }
-    }
-    launch0.push_back((long)ids.size());
+    std::vector<int> ok(n_chunks + 1, 0);
+    P.place(F, E, ok, status);
     // (pageable sources: hipMemcpyAsync has staged them when it returns; the vectors live to the end of the call anyway)
-    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(StatTile) * n_tiles, hipMemcpyHostToDevice, st));
-    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_ids, ids.data(), 4 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tiles, P.tiles.data(), sizeof(StatTile) * n_tiles, hipMemcpyHostToDevice, st));
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_ids, P.ids.data(), 4 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(d_ok, ok.data(), 4 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(d_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(d_wt, win_tiles.data(), 8 * (size_t)(n_win + 1), hipMemcpyHostToDevice, st));
     const int dflags = flags & ~MTS_FLAG_UNSIGNED;           // (the decoder compares the transform flags as a whole)
-    // resident chunks: reduced and waited for before any decode (whose workspace allocations could drop cache entries)
-    if (launch0[1] > 0) {
-        if ((rc = launch_stats_tiles(st, sz, flags, d_tiles, d_ids, (int)launch0[1], d_ok, d_cols, n_cols, nc, d_slab, n_tiles))) return rc;
+    const std::vector<long> &l0 = P.launch0;
+    auto launch = [&](long first, long n) {
+        return launch_stats_tiles(st, sz, flags, d_tiles, d_ids + first, (int)n, d_ok, d_cols, n_cols, nc, d_slab, n_tiles);
+    };
+    // resident chunks: reduced and waited for before any decode
+    if (l0[1] > 0) {
+        if ((rc = launch(0, l0[1]))) return rc;
         MTS_HIP(hipStreamSynchronize(st));
     }
     // ---- the other chunks, piece by piece
-    const int dev = E.dev;
-    auto copy_in = [&](int k) -> int {
-        if (cdata_on_device) return MTS_OK;
-        MTS_HIP(hipSetDevice(dev));
-        for (int q = pb[k]; q < pb[k + 1];) {
-            int e = q + 1;
-            while (e < pb[k + 1] && c_off[miss[e]] == c_off[miss[e - 1]] + mclen[e - 1] && mcoff[e] == mcoff[e - 1] + mclen[e - 1]) e++;
-            u64 len = 0;
-            for (int z = q; z < e; z++) len += (u64)mclen[z];
-            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[q], cdata + c_off[miss[q]], (size_t)len); if (rc1) return rc1; }
-            q = e;
-        }
-        return MTS_OK;
-    };
-    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
-    std::vector<int> mst(m > 0 ? m : 1, MTS_CHUNK_CORRUPT);
-    if (np > 0 && m > 0 && (rc = copy_in(0))) return rc;
-    for (int k = 0; k < np && m > 0; k++) {
-        std::future<int> f_in;
-        if (k + 1 < np) f_in = copy_beside(copy_in, k + 1);
-        const int q0 = pb[k], nq = pb[k + 1] - pb[k];
-        rc = dev_decompress(E, st, d_src, mcoff.data() + q0, mclen.data() + q0, mrows.data() + q0, nq, nc, sz, dflags, E.h_out.as<u8>(),
-                            mooff.data() + q0, mst.data() + q0, 0, k > 0);
-        if (!rc) {
-            for (int q = q0; q < q0 + nq; q++) { status[miss[q]] = mst[q]; ok[miss[q]] = mst[q] == MTS_CHUNK_OK; }
-            hipError_t e = hipMemcpyAsync(d_ok, ok.data(), 4 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); rc = MTS_E_HIP; }
-        }
-        if (!rc) rc = launch_stats_tiles(st, sz, flags, d_tiles, d_ids + launch0[1 + k], (int)(launch0[2 + k] - launch0[1 + k]), d_ok, d_cols,
-                                         n_cols, nc, d_slab, n_tiles);
-        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;      // (always joined: it holds references to this frame)
-        if (rc || rc_in) return rc ? rc : rc_in;
-    }
+    rc = feed_pieces(F, E, st, P.pieces, dflags, status, [&](int p) {
+        const int r = P.mark_decoded(p, status, ok, d_ok, st);
+        return r ? r : launch(l0[1 + p], l0[2 + p] - l0[1 + p]);
+    });
+    if (rc) return rc;
     // ---- windows: the tiles in order
     void *c_min = out_on_host ? (void *)(ws + o_omin) : o_min, *c_max = out_on_host ? (void *)(ws + o_omax) : o_max;
     void *c_sum = out_on_host ? (void *)(ws + o_osum) : o_sum, *c_sq = out_on_host ? (void *)(ws + o_osq) : o_sq;
@@ -1827,14 +2034,13 @@ static int window_stats_run(Engine &E, hipStream_t st, DevCache *cache, const lo
         MTS_HIP(hipMemcpyAsync(o_sq, c_sq, n_items * 8, hipMemcpyDeviceToHost, st));
     }
     MTS_HIP(hipStreamSynchronize(st));
-    for (long t = 0; t < n_tiles; t++) if (ok[tiles[t].chunk]) count[tile_win[t]] += tiles[t].n_rows;
+    P.add_counts(ok, count);
     return MTS_OK;
 }
 
 // ---- one round of a radix select (mts_rank_hist, mts_dev_rank_hist) ---------------------------------
-// The tiles, the residency rules and the pieces of window_stats_run, with tiles of SEL_TILE_ROWS rows and no combine launch: every
-// tile adds its counts to the histograms of its window with integer atomics (select.hip), so the outputs are the same whatever the
-// order of the launches.
+// Tiles of SEL_TILE_ROWS rows and no combine launch: every tile adds its counts to the histograms of its window with integer
+// atomics (select.hip), so the outputs are the same whatever the order of the launches.
 static int rank_hist_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device,
                          const long *c_off, const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz, int flags,
                          long row_begin, long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
@@ -1842,23 +2048,16 @@ static int rank_hist_run(Engine &E, hipStream_t st, DevCache *cache, const long 
                          unsigned long long *o_kmax, bool out_on_host, long *count, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
-    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    int rc;
+    if ((rc = check_items(sz, flags))) return rc;
     if (nc <= 0 || n_chunks < 0 || n_cols < 1 || !cols) { set_error("rank hist: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
     if (window_rows < 1) { set_error("window_rows %ld < 1", window_rows); return MTS_E_ARG; }
     if (row_begin < 0 || row_end < row_begin) { set_error("row range [%ld, %ld) invalid", row_begin, row_end); return MTS_E_ARG; }
     if (mode < 0 || mode > 2) { set_error("rank hist: mode %d (0, 1 or 2)", mode); return MTS_E_ARG; }
-    for (int j = 0; j < n_cols; j++)
-        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
     const long span = row_end - row_begin;
     if ((window_rows < span ? window_rows : span) >= (1l << 32)) { set_error("windows of 2^32 rows or more"); return MTS_E_ARG; }
-    for (int i = 0; i < n_chunks; i++) {
-        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
-        if (i && row0[i] < row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: rows out of order or overlapping", i); return MTS_E_ARG; }
-        if (row0[i] >= row_end || row0[i] + n_rows[i] <= row_begin) { set_error("chunk %d holds no row of [%ld, %ld)", i, row_begin, row_end); return MTS_E_ARG; }
-        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
-        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
-    }
+    if ((rc = check_chunk_table(false, cache != nullptr, c_len, row0, n_rows, n_chunks, nc, sz, row_begin, row_end))) return rc;
     const long n_win = (span + window_rows - 1) / window_rows;
     if (n_win && (!o_hist || !o_kmin || !o_kmax || !count || !sel_prefix || !sel_shift || (mode && !center))) {
         set_error("rank hist: selectors, center or outputs missing"); return MTS_E_ARG;
@@ -1875,66 +2074,12 @@ static int rank_hist_run(Engine &E, hipStream_t st, DevCache *cache, const long 
     for (long w = 0; w < n_win; w++) count[w] = 0;
     if (n_win == 0) return MTS_OK;                           // (no chunk can hold a row of an empty range: n_chunks is 0)
 
-    // ---- tiles, in row order
-    std::vector<StatTile> tiles;
-    std::vector<long> tile_win, chunk_tile0(n_chunks + 1);
-    for (int i = 0; i < n_chunks; i++) {
-        chunk_tile0[i] = (long)tiles.size();
-        const long a = row0[i] > row_begin ? row0[i] : row_begin, b = row0[i] + n_rows[i] < row_end ? row0[i] + n_rows[i] : row_end;
-        for (long r = a; r < b;) {
-            const long w = (r - row_begin) / window_rows, wend = row_begin + (w + 1) * window_rows, e = b < wend ? b : wend;
-            for (long q = r; q < e; q += SEL_TILE_ROWS) {
-                StatTile t;
-                t.base = nullptr; t.row_lo = q - row0[i]; t.n_rows = (e - q) < SEL_TILE_ROWS ? (e - q) : SEL_TILE_ROWS; t.chunk = i; t.pad = 0;
-                tiles.push_back(t);
-                tile_win.push_back(w);
-            }
-            r = e;
-        }
-    }
-    chunk_tile0[n_chunks] = (long)tiles.size();
-    const long n_tiles = (long)tiles.size();
+    ChunkFeed F(cache, keys, cdata, cdata_on_device, c_off, c_len, n_rows, n_chunks, nc, sz);
+    if ((rc = F.classify())) return rc;
+    TilePlan P(F, row0, row_begin, row_end, window_rows, SEL_TILE_ROWS);
+    const long n_tiles = (long)P.tiles.size();
 
-    // ---- which chunks are resident (whole rows), which are decoded here, in which pieces
-    auto entry_of = [&](int i) -> const CacheEntry * {
-        if (!cache) return nullptr;
-        auto it = cache->map.find(keys[i]);
-        if (it == cache->map.end()) return nullptr;
-        const CacheEntry &e = it->second;
-        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
-    };
-    std::vector<int> miss;
-    for (int i = 0; i < n_chunks; i++) {
-        if (entry_of(i)) continue;
-        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-        miss.push_back(i);
-    }
-    const int m = (int)miss.size();
-    const u64 row_bytes = (u64)nc * sz;
-    std::vector<long> mrows(m), mcoff(m), mclen(m), mooff(m);
-    for (int k = 0; k < m; k++) { mrows[k] = n_rows[miss[k]]; mclen[k] = c_len[miss[k]]; }
-    const std::vector<int> pb = cdata_on_device ? std::vector<int>{0, m} : pipe_pieces(mrows.data(), false, m, row_bytes);
-    const int np = (int)pb.size() - 1;
-    u64 piece_cap = 0;
-    for (int k = 0; k < np; k++) {
-        u64 o = 0;
-        for (int q = pb[k]; q < pb[k + 1]; q++) { mooff[q] = (long)o; o += align_up((u64)mrows[q] * row_bytes, 256); }
-        if (o > piece_cap) piece_cap = o;
-    }
-    u64 ctot = 0;
-    if (!cdata_on_device) {
-        for (int k = 0; k < m; k++) {
-            const int i = miss[k];
-            const bool joins = k > 0 && c_off[i] == c_off[miss[k - 1]] + mclen[k - 1];
-            if (!joins) ctot = align_up(ctot + (k ? 16 : 0), 16);
-            mcoff[k] = (long)ctot; ctot += (u64)mclen[k];
-        }
-        ctot += 16;
-    } else {
-        for (int k = 0; k < m; k++) mcoff[k] = c_off[miss[k]];
-    }
-
-    // ---- workspace: every allocation of the call comes BEFORE the resident entries are looked at
+    // ---- workspace
     const u64 n_cells = (u64)n_win * n_cols, hist_bytes = n_sel * (4ull << MTS_RANK_BITS), k_bytes = n_sel * 8;
     const size_t o_tiles = 0, o_tw = align_up(sizeof(StatTile) * (n_tiles + 1), 256), o_ids = o_tw + align_up(8 * (u64)(n_tiles + 1), 256),
                  o_ok = o_ids + align_up(4 * (u64)(n_tiles + 1), 256), o_cols = o_ok + align_up(4 * (u64)(n_chunks + 1), 256),
@@ -1942,14 +2087,8 @@ static int rank_hist_run(Engine &E, hipStream_t st, DevCache *cache, const long 
                  o_shf = o_pre + align_up(k_bytes, 256), o_out = o_shf + align_up(n_sel * 4, 256);
     const size_t w_hist = o_out, w_kmin = w_hist + align_up(hist_bytes, 256), w_kmax = w_kmin + align_up(k_bytes, 256),
                  o_end = out_on_host ? w_kmax + align_up(k_bytes, 256) : o_out;
-    int rc;
     if ((rc = E.stats.ensure(o_end + 256))) return rc;
-    if (m && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
-    if (m && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
-    if (cache) {
-        for (int i = 0; i < n_chunks; i++)                   // (the allocations above may have emptied the cache)
-            if (c_len[i] == 0 && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-    }
+    if ((rc = F.ensure(E, P.piece_cap))) return rc;
     u8 *ws = E.stats.as<u8>();
     StatTile *d_tiles = (StatTile *)(ws + o_tiles);
     long *d_tw = (long *)(ws + o_tw);
@@ -1958,30 +2097,11 @@ static int rank_hist_run(Engine &E, hipStream_t st, DevCache *cache, const long 
     u64 *d_pre = (u64 *)(ws + o_pre);
     u32 *d_hist = out_on_host ? (u32 *)(ws + w_hist) : (u32 *)o_hist;
     u64 *d_kmin = out_on_host ? (u64 *)(ws + w_kmin) : (u64 *)o_kmin, *d_kmax = out_on_host ? (u64 *)(ws + w_kmax) : (u64 *)o_kmax;
-    // tile pointers and the order of the launches: resident chunks first, then piece after piece
-    std::vector<int> ok(n_chunks + 1, 0), ids;
-    std::vector<long> launch0;
-    std::vector<char> decoded(n_chunks, 0);
-    for (int k = 0; k < m; k++) decoded[miss[k]] = 1;
-    launch0.push_back(0);
-    for (int i = 0; i < n_chunks; i++) {
-        if (decoded[i]) continue;
-        const CacheEntry *e = entry_of(i);
-        for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = e->d; ids.push_back((int)t); }
-        ok[i] = 1;
-        status[i] = MTS_CHUNK_OK;
-    }
-    for (int k = 0; k < np; k++) {
-        launch0.push_back((long)ids.size());
-        for (int q = pb[k]; q < pb[k + 1]; q++) {
-            const int i = miss[q];
-            for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = E.h_out.as<u8>() + mooff[q]; ids.push_back((int)t); }
-        }
-    }
-    launch0.push_back((long)ids.size());
-    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tiles, tiles.data(), sizeof(StatTile) * n_tiles, hipMemcpyHostToDevice, st));
-    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tw, tile_win.data(), 8 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
-    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_ids, ids.data(), 4 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
+    std::vector<int> ok(n_chunks + 1, 0);
+    P.place(F, E, ok, status);
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tiles, P.tiles.data(), sizeof(StatTile) * n_tiles, hipMemcpyHostToDevice, st));
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_tw, P.tile_win.data(), 8 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
+    if (n_tiles) MTS_HIP(hipMemcpyAsync(d_ids, P.ids.data(), 4 * (size_t)n_tiles, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(d_ok, ok.data(), 4 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(d_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
     if (mode) MTS_HIP(hipMemcpyAsync(d_cen, center, 8 * (size_t)n_cells, hipMemcpyHostToDevice, st));
@@ -1991,70 +2111,44 @@ static int rank_hist_run(Engine &E, hipStream_t st, DevCache *cache, const long 
     MTS_HIP(hipMemsetAsync(d_kmin, 0xff, (size_t)k_bytes, st));
     MTS_HIP(hipMemsetAsync(d_kmax, 0, (size_t)k_bytes, st));
     const int dflags = flags & ~MTS_FLAG_UNSIGNED;           // (the decoder compares the transform flags as a whole)
-    // resident chunks: counted and waited for before any decode (whose workspace allocations could drop cache entries)
-    if (launch0[1] > 0) {
-        if ((rc = launch_rank_hist(st, sz, flags, mode, d_tiles, d_tw, d_ids, (int)launch0[1], d_ok, d_cols, n_cols, nc, d_cen, d_pre, d_shf,
-                                   d_hist, d_kmin, d_kmax))) return rc;
+    const std::vector<long> &l0 = P.launch0;
+    auto launch = [&](long first, long n) {
+        return launch_rank_hist(st, sz, flags, mode, d_tiles, d_tw, d_ids + first, (int)n, d_ok, d_cols, n_cols, nc, d_cen, d_pre, d_shf, d_hist,
+                                d_kmin, d_kmax);
+    };
+    // resident chunks: counted and waited for before any decode
+    if (l0[1] > 0) {
+        if ((rc = launch(0, l0[1]))) return rc;
         MTS_HIP(hipStreamSynchronize(st));
     }
     // ---- the other chunks, piece by piece
-    const int dev = E.dev;
-    auto copy_in = [&](int k) -> int {
-        if (cdata_on_device) return MTS_OK;
-        MTS_HIP(hipSetDevice(dev));
-        for (int q = pb[k]; q < pb[k + 1];) {
-            int e = q + 1;
-            while (e < pb[k + 1] && c_off[miss[e]] == c_off[miss[e - 1]] + mclen[e - 1] && mcoff[e] == mcoff[e - 1] + mclen[e - 1]) e++;
-            u64 len = 0;
-            for (int z = q; z < e; z++) len += (u64)mclen[z];
-            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[q], cdata + c_off[miss[q]], (size_t)len); if (rc1) return rc1; }
-            q = e;
-        }
-        return MTS_OK;
-    };
-    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
-    std::vector<int> mst(m > 0 ? m : 1, MTS_CHUNK_CORRUPT);
-    if (np > 0 && m > 0 && (rc = copy_in(0))) return rc;
-    for (int k = 0; k < np && m > 0; k++) {
-        std::future<int> f_in;
-        if (k + 1 < np) f_in = copy_beside(copy_in, k + 1);
-        const int q0 = pb[k], nq = pb[k + 1] - pb[k];
-        rc = dev_decompress(E, st, d_src, mcoff.data() + q0, mclen.data() + q0, mrows.data() + q0, nq, nc, sz, dflags, E.h_out.as<u8>(),
-                            mooff.data() + q0, mst.data() + q0, 0, k > 0);
-        if (!rc) {
-            for (int q = q0; q < q0 + nq; q++) { status[miss[q]] = mst[q]; ok[miss[q]] = mst[q] == MTS_CHUNK_OK; }
-            hipError_t e = hipMemcpyAsync(d_ok, ok.data(), 4 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice, st);
-            if (e != hipSuccess) { set_error("hipMemcpyAsync: %s", hipGetErrorString(e)); rc = MTS_E_HIP; }
-        }
-        if (!rc) rc = launch_rank_hist(st, sz, flags, mode, d_tiles, d_tw, d_ids + launch0[1 + k], (int)(launch0[2 + k] - launch0[1 + k]), d_ok,
-                                       d_cols, n_cols, nc, d_cen, d_pre, d_shf, d_hist, d_kmin, d_kmax);
-        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;      // (always joined: it holds references to this frame)
-        if (rc || rc_in) return rc ? rc : rc_in;
-    }
+    rc = feed_pieces(F, E, st, P.pieces, dflags, status, [&](int p) {
+        const int r = P.mark_decoded(p, status, ok, d_ok, st);
+        return r ? r : launch(l0[1 + p], l0[2 + p] - l0[1 + p]);
+    });
+    if (rc) return rc;
     if (out_on_host) {                                        // the histograms, and nothing else, cross the bus
         MTS_HIP(hipMemcpyAsync(o_hist, d_hist, (size_t)hist_bytes, hipMemcpyDeviceToHost, st));
         MTS_HIP(hipMemcpyAsync(o_kmin, d_kmin, (size_t)k_bytes, hipMemcpyDeviceToHost, st));
         MTS_HIP(hipMemcpyAsync(o_kmax, d_kmax, (size_t)k_bytes, hipMemcpyDeviceToHost, st));
     }
     MTS_HIP(hipStreamSynchronize(st));
-    for (long t = 0; t < n_tiles; t++) if (ok[tiles[t].chunk]) count[tile_win[t]] += tiles[t].n_rows;
+    P.add_counts(ok, count);
     return MTS_OK;
 }
 
 // ---- decimation (mts_decimate, mts_dev_decimate) ---------------------------------------------------------------------------
-// The chunks of a call are cut into pieces of MTS_PIPE_BYTES of decoded bytes to decode (pipe_pieces; resident chunks weigh
-// nothing).  Piece p owns the outputs whose newest row (first_row + k * q) lies in its chunks; their support reaches L - 1 rows
-// further down, so a group decodes its own missing chunks and those of the halo below (a boundary chunk is decoded in both
-// pieces).  Every output is computed once, from the same rows, in the same order: the result does not depend on the pieces.
-// While piece p is decoded and filtered, the compressed bytes of piece p + 1 cross the bus on a helper thread.
+// Piece p owns the outputs whose newest row (first_row + k * q) lies in its chunks; their support reaches L - 1 rows further down,
+// so a group reads its own chunks and those of the halo below.  Every output is computed once, from the same rows, in the same
+// order: the result does not depend on the pieces.
 static int decimate_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device, const long *c_off,
                         const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz, int flags, long vb, long ve,
                         long first_row, long n_out, int q, int n_taps, const double *taps, int osz, int n_cols, const int *cols, void *out,
                         bool out_on_host, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
-    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    int rc;
+    if ((rc = check_items(sz, flags))) return rc;
     if (nc <= 0 || n_chunks < 0 || n_cols < 1 || n_cols > 64 * 65535 || !cols) { set_error("decimate: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
     if (q < 1) { set_error("decimate: q %d < 1", q); return MTS_E_ARG; }
     if (n_taps < 1 || n_taps > MTS_DECIMATE_MAX_TAPS || !taps) { set_error("decimate: %d taps (1 .. %d)", n_taps, MTS_DECIMATE_MAX_TAPS); return MTS_E_ARG; }
@@ -2065,14 +2159,8 @@ static int decimate_run(Engine &E, hipStream_t st, DevCache *cache, const long *
         set_error("decimate: rows or outputs invalid"); return MTS_E_ARG;
     }
     if (n_out && !out) { set_error("decimate: no output buffer"); return MTS_E_ARG; }
-    for (int j = 0; j < n_cols; j++)
-        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
-    for (int i = 0; i < n_chunks; i++) {
-        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
-        if (i && row0[i] != row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: chunks must be adjacent", i); return MTS_E_ARG; }
-        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
-        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
-    }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, cache != nullptr, c_len, row0, n_rows, n_chunks, nc, sz))) return rc;
     // the rows the outputs read: support ∩ valid range; the chunks must cover them
     const long need_lo = n_out ? std::max(vb, first_row - (n_taps - 1)) : 0, need_hi = n_out ? std::min(ve, first_row + (n_out - 1) * q + 1) : 0;
     if (need_lo < need_hi) {
@@ -2083,24 +2171,10 @@ static int decimate_run(Engine &E, hipStream_t st, DevCache *cache, const long *
     for (int i = 0; i < n_chunks; i++) status[i] = MTS_CHUNK_OK;
     if (n_out == 0) return MTS_OK;
 
-    // ---- which chunks are resident (whole rows), which are decoded here
-    auto entry_of = [&](int i) -> const CacheEntry * {
-        if (!cache) return nullptr;
-        auto it = cache->map.find(keys[i]);
-        if (it == cache->map.end()) return nullptr;
-        const CacheEntry &e = it->second;
-        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
-    };
-    std::vector<char> resident(n_chunks, 0);
-    std::vector<long> weight(n_chunks, 0);
-    for (int i = 0; i < n_chunks; i++) {
-        if (entry_of(i)) { resident[i] = 1; continue; }
-        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-        weight[i] = n_rows[i];
-    }
-    const u64 row_bytes = (u64)nc * sz;
-    // ---- groups of outputs: [gk[g], gk[g + 1]) reads chunks [gc0[g], gc1[g]]
-    std::vector<int> pb = cdata_on_device ? std::vector<int>{0, n_chunks} : pipe_pieces(weight.data(), false, n_chunks, row_bytes);
+    ChunkFeed F(cache, keys, cdata, cdata_on_device, c_off, c_len, n_rows, n_chunks, nc, sz);
+    if ((rc = F.classify())) return rc;
+    // ---- groups of outputs: [u0, u1) reads chunks [c0, c1]
+    const std::vector<int> pb = F.piece_bounds();
     const int np = (int)pb.size() - 1;
     std::vector<long> gk;
     gk.push_back(0);
@@ -2111,161 +2185,56 @@ static int decimate_run(Engine &E, hipStream_t st, DevCache *cache, const long *
         gk.push_back(std::max(k, gk.back()));
     }
     gk.push_back(n_out);
-    auto chunk_of = [&](long row) -> int {                     // the chunk holding `row` (clamped to the chunks)
-        int lo = 0, hi = n_chunks - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row0[mid] <= row) lo = mid; else hi = mid - 1; }
-        return lo;
-    };
-    struct Group { long k0, k1; int c0, c1; std::vector<int> miss; std::vector<long> ooff; u64 ws = 0; };
-    std::vector<Group> groups;
-    u64 piece_cap = 0;
+    std::vector<FeedPiece> groups;
     for (int g = 0; g < np; g++) {
         if (gk[g + 1] <= gk[g]) continue;
-        Group G;
-        G.k0 = gk[g]; G.k1 = gk[g + 1];
-        const long lo = std::max(vb, first_row + G.k0 * q - (n_taps - 1)), hi = std::min(ve, first_row + (G.k1 - 1) * q + 1);
-        if (lo < hi && n_chunks) {
-            G.c0 = chunk_of(lo); G.c1 = chunk_of(hi - 1);
-            for (int i = G.c0; i <= G.c1; i++)
-                if (!resident[i]) { G.miss.push_back(i); G.ooff.push_back((long)G.ws); G.ws += align_up((u64)n_rows[i] * row_bytes, 256); }
-        } else {
-            G.c0 = 0; G.c1 = -1;                                 // (nothing valid to read: every row is 0)
-        }
-        piece_cap = std::max(piece_cap, G.ws);
+        FeedPiece G;
+        G.u0 = gk[g]; G.u1 = gk[g + 1];
+        const long lo = std::max(vb, first_row + G.u0 * q - (n_taps - 1)), hi = std::min(ve, first_row + (G.u1 - 1) * q + 1);
+        if (lo < hi && n_chunks) { G.c0 = chunk_of(row0, n_chunks, lo); G.c1 = chunk_of(row0, n_chunks, hi - 1); }
+        // (else nothing valid to read, c1 < c0: every row is 0)
         groups.push_back(std::move(G));
     }
-    // compressed bytes of every chunk decoded here, once (chunks back to back in the caller's buffer keep their distances)
-    std::vector<long> mcoff(n_chunks, 0);
-    u64 ctot = 0;
-    bool any_miss = false;
-    {
-        int prev = -1;
-        for (int i = 0; i < n_chunks; i++) {
-            if (resident[i]) continue;
-            any_miss = true;
-            if (cdata_on_device) { mcoff[i] = c_off[i]; continue; }
-            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
-            if (!joins) ctot = align_up(ctot + (prev >= 0 ? 16 : 0), 16);
-            mcoff[i] = (long)ctot; ctot += (u64)c_len[i];
-            prev = i;
-        }
-        ctot += 16;
-    }
-    // segment tables, one after the other: per group (c1 - c0 + 1) bases, then (c1 - c0 + 2) first rows
-    std::vector<long> seg_at(groups.size() + 1, 0);
-    for (size_t g = 0; g < groups.size(); g++) seg_at[g + 1] = seg_at[g] + 2l * (groups[g].c1 - groups[g].c0 + 1) + 1;
+    u64 piece_cap;
+    const std::vector<long> seg_at = plan_pieces(F, groups, &piece_cap);
     const u64 n_items = (u64)n_out * n_cols;
     const size_t o_taps = 0, o_cols = align_up(8 * (u64)n_taps, 256), o_seg = o_cols + align_up(4 * (u64)n_cols, 256),
                  o_out = o_seg + align_up(8 * (u64)(seg_at.back() + 1), 256), o_end = out_on_host ? o_out + align_up(n_items * osz, 256) : o_out;
-    // ---- workspace: these allocations come BEFORE the resident entries are looked at.  The decode of each group allocates
-    //      again (decompress_batch's DBuf::ensure), and an allocation that fails there drops this device's decoded chunks: the
-    //      resident entries of a group are therefore checked once more after its decode and before its launch (below)
-    int rc;
+    // ---- workspace
     if ((rc = E.dec.ensure(o_end + 256))) return rc;
-    if (any_miss && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
-    if (piece_cap && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
-    if (cache) {
-        for (int i = 0; i < n_chunks; i++)                       // (the allocations above may have emptied the cache)
-            if (resident[i] && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-    }
+    if ((rc = F.ensure(E, piece_cap))) return rc;
     u8 *ws = E.dec.as<u8>();
     std::vector<u8> h_taps(8 * (size_t)n_taps);
     for (int j = 0; j < n_taps; j++) {
         if (osz == 4) { const float f = (float)taps[j]; memcpy(h_taps.data() + 4 * j, &f, 4); }
         else memcpy(h_taps.data() + 8 * j, &taps[j], 8);
     }
-    std::vector<long> seg(seg_at.back() + 1, 0);
-    std::vector<const u8 *> res_ptr(n_chunks, nullptr);       // the address of each resident entry the tables hold
-    for (int i = 0; i < n_chunks; i++) if (resident[i]) res_ptr[i] = entry_of(i)->d;
-    for (size_t g = 0; g < groups.size(); g++) {
-        const Group &G = groups[g];
-        long *b = seg.data() + seg_at[g], *r = b + (G.c1 - G.c0 + 1);
-        size_t m = 0;
-        for (int i = G.c0; i <= G.c1; i++) {
-            const u8 *base;
-            if (resident[i]) base = res_ptr[i];
-            else base = E.h_out.as<u8>() + G.ooff[m++];
-            b[i - G.c0] = (long)(uintptr_t)base;
-            r[i - G.c0] = row0[i];
-        }
-        r[G.c1 - G.c0 + 1] = G.c1 >= G.c0 ? row0[G.c1] + n_rows[G.c1] : 0;
-    }
+    const std::vector<long> seg = segment_tables(F, E, groups, seg_at, row0);
     MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), (size_t)osz * n_taps, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_seg, seg.data(), 8 * seg.size(), hipMemcpyHostToDevice, st));
     void *d_out = out_on_host ? (void *)(ws + o_out) : out;
     const int dflags = flags & ~MTS_FLAG_UNSIGNED;           // (the decoder compares the transform flags as a whole)
-    const int dev = E.dev;
-    std::vector<char> copied(n_chunks, 0);
-    auto copy_in = [&](int g) -> int {
-        if (cdata_on_device) return MTS_OK;
-        MTS_HIP(hipSetDevice(dev));
-        const std::vector<int> &mi = groups[g].miss;
-        for (size_t a = 0; a < mi.size();) {
-            if (copied[mi[a]]) { a++; continue; }
-            size_t e = a + 1;                                     // a run of chunks back to back here and in the caller's buffer
-            while (e < mi.size() && !copied[mi[e]] && mi[e] == mi[e - 1] + 1 && c_off[mi[e]] == c_off[mi[e - 1]] + c_len[mi[e - 1]] &&
-                   mcoff[mi[e]] == mcoff[mi[e - 1]] + c_len[mi[e - 1]]) e++;
-            u64 len = 0;
-            for (size_t z = a; z < e; z++) { len += (u64)c_len[mi[z]]; copied[mi[z]] = 1; }
-            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[mi[a]], cdata + c_off[mi[a]], (size_t)len); if (rc1) return rc1; }
-            a = e;
-        }
-        return MTS_OK;
-    };
-    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
-    const int ng = (int)groups.size();
-    if (ng > 0 && (rc = copy_in(0))) return rc;
-    bool first_decode = true;
-    for (int g = 0; g < ng; g++) {
-        std::future<int> f_in;
-        if (g + 1 < ng) f_in = copy_beside(copy_in, g + 1);
-        const Group &G = groups[g];
-        const int nm = (int)G.miss.size();
-        if (nm) {
-            std::vector<long> co(nm), cl(nm), nr(nm);
-            std::vector<int> mst(nm, MTS_CHUNK_CORRUPT);
-            for (int z = 0; z < nm; z++) { co[z] = mcoff[G.miss[z]]; cl[z] = c_len[G.miss[z]]; nr[z] = n_rows[G.miss[z]]; }
-            rc = dev_decompress(E, st, d_src, co.data(), cl.data(), nr.data(), nm, nc, sz, dflags, E.h_out.as<u8>(), G.ooff.data(), mst.data(), 0,
-                                !first_decode);
-            first_decode = false;
-            if (!rc) for (int z = 0; z < nm; z++) if (mst[z] != MTS_CHUNK_OK) status[G.miss[z]] = mst[z];
-        }
-        if (!rc && cache) {
-            // a decode allocation that failed drops the decoded chunks (drop_device_caches: hipFree, which waits for the kernels
-            // already launched on the device -- the earlier groups' reads are done).  The tables of this group must not point at a
-            // freed entry: every resident chunk it reads is still in the cache at the same address, or the call ends with
-            // MTS_E_MISS (the Reader sends every chunk's bytes again), before this group's kernel is launched.
-            for (int i = G.c0; i <= G.c1 && !rc; i++) {
-                if (!resident[i]) continue;
-                const CacheEntry *e = entry_of(i);
-                if (!e || e->d != res_ptr[i]) {
-                    set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i);
-                    rc = MTS_E_MISS;
-                }
-            }
-        }
-        if (!rc) {
-            const long *sb = (const long *)(ws + o_seg) + seg_at[g];
-            const int ns = G.c1 - G.c0 + 1;
-            rc = launch_decimate(st, sz, flags, osz, (const u8 *const *)sb, sb + (ns > 0 ? ns : 0), ns > 0 ? ns : 0, nc, (const int *)(ws + o_cols), n_cols,
-                                 ws + o_taps, n_taps, q, first_row, G.k0, G.k1, ns > 0 ? vb : 0, ns > 0 ? ve : 0,
-                                 (u8 *)d_out + (u64)G.k0 * n_cols * osz);
-        }
-        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;      // (always joined: it holds references to this frame)
-        if (rc || rc_in) return rc ? rc : rc_in;
-    }
+    rc = feed_pieces(F, E, st, groups, dflags, status, [&](int g) {
+        const FeedPiece &G = groups[g];
+        const int r = F.still_placed(G);
+        if (r) return r;
+        const long *sb = (const long *)(ws + o_seg) + seg_at[g];
+        const int ns = G.c1 - G.c0 + 1;
+        return launch_decimate(st, sz, flags, osz, (const u8 *const *)sb, sb + (ns > 0 ? ns : 0), ns > 0 ? ns : 0, nc, (const int *)(ws + o_cols), n_cols,
+                               ws + o_taps, n_taps, q, first_row, G.u0, G.u1, ns > 0 ? vb : 0, ns > 0 ? ve : 0,
+                               (u8 *)d_out + (u64)G.u0 * n_cols * osz);
+    });
+    if (rc) return rc;
     if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, n_items * osz, hipMemcpyDeviceToHost, st));
     MTS_HIP(hipStreamSynchronize(st));
     return MTS_OK;
 }
 
 // ---- Welch PSD (mts_welch, mts_dev_welch) ------------------------------------------------------------------------------------
-// The call's segments are cut into blocks of B (WELCH_BLOCK_SEGMENTS) and groups of G; the chunks into pieces of MTS_PIPE_BYTES of
-// decoded bytes to decode (pipe_pieces; resident chunks weigh nothing).  Piece p owns the blocks whose first row lies in its chunks
-// and decodes the missing chunks those blocks read (a chunk read by blocks of two pieces is decoded in both).  A piece's blocks are
-// launched in runs that keep the partial slab <= WELCH_SLAB_BYTES, each followed by the combine that adds them to their groups'
-// sums in block order: every group sum is the same sequence of additions whatever the pieces and runs.
+// The call's segments are cut into blocks of B (WELCH_BLOCK_SEGMENTS) and groups of G.  Piece p owns the blocks whose first row lies
+// in its chunks.  A piece's blocks are launched in runs that keep the partial slab <= WELCH_SLAB_BYTES, each followed by the combine
+// that adds them to their groups' sums in block order: every group sum is the same sequence of additions whatever the pieces and runs.
 static const u64 WELCH_SLAB_BYTES = 256ull << 20;
 
 // exp(-2 pi i q / n) for q < n: the first octant in extended precision, the rest by exact symmetries (q = 0 gives exactly 1)
@@ -2294,8 +2263,8 @@ static int welch_run(Engine &E, hipStream_t st, DevCache *cache, const long *key
                      bool out_on_host, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
-    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    int rc;
+    if ((rc = check_items(sz, flags))) return rc;
     if (nc <= 0 || n_chunks < 0 || n_cols < 1 || n_cols > (1 << 24) || !cols) { set_error("welch: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
     if (nperseg < 16 || nperseg > MTS_WELCH_MAX_NPERSEG || (nperseg & (nperseg - 1))) {
         set_error("welch: nperseg %d is not a power of two in [16, %d]", nperseg, MTS_WELCH_MAX_NPERSEG); return MTS_E_ARG;
@@ -2311,14 +2280,8 @@ static int welch_run(Engine &E, hipStream_t st, DevCache *cache, const long *key
         set_error("welch: segments [%ld, %ld) invalid or not aligned to groups of %ld", seg_begin, seg_end, G); return MTS_E_ARG;
     }
     if (!out) { set_error("welch: no output buffer"); return MTS_E_ARG; }
-    for (int j = 0; j < n_cols; j++)
-        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
-    for (int i = 0; i < n_chunks; i++) {
-        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
-        if (i && row0[i] != row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: chunks must be adjacent", i); return MTS_E_ARG; }
-        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
-        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
-    }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, cache != nullptr, c_len, row0, n_rows, n_chunks, nc, sz))) return rc;
     // the rows the segments read; the chunks must cover them
     const long need_lo = row_seg0 + seg_begin * step, need_hi = row_seg0 + (seg_end - 1) * step + nperseg;
     if (n_chunks == 0 || row0[0] > need_lo || row0[n_chunks - 1] + n_rows[n_chunks - 1] < need_hi) {
@@ -2331,24 +2294,10 @@ static int welch_run(Engine &E, hipStream_t st, DevCache *cache, const long *key
     const long b_first = seg_begin / B;                              // the call's block 0 (absolute)
     const long n_elems = (long)(nperseg / 2 + 1) * n_cols;
 
-    // ---- which chunks are resident (whole rows), which are decoded here
-    auto entry_of = [&](int i) -> const CacheEntry * {
-        if (!cache) return nullptr;
-        auto it = cache->map.find(keys[i]);
-        if (it == cache->map.end()) return nullptr;
-        const CacheEntry &e = it->second;
-        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
-    };
-    std::vector<char> resident(n_chunks, 0);
-    std::vector<long> weight(n_chunks, 0);
-    for (int i = 0; i < n_chunks; i++) {
-        if (entry_of(i)) { resident[i] = 1; continue; }
-        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-        weight[i] = n_rows[i];
-    }
-    const u64 row_bytes = (u64)nc * sz;
-    // ---- pieces of blocks: [gb[p], gb[p + 1]) (call-local block indices) read chunks [c0, c1]
-    std::vector<int> pb = cdata_on_device ? std::vector<int>{0, n_chunks} : pipe_pieces(weight.data(), false, n_chunks, row_bytes);
+    ChunkFeed F(cache, keys, cdata, cdata_on_device, c_off, c_len, n_rows, n_chunks, nc, sz);
+    if ((rc = F.classify())) return rc;
+    // ---- pieces of blocks: [u0, u1) (call-local block indices) read chunks [c0, c1]
+    const std::vector<int> pb = F.piece_bounds();
     const int np = (int)pb.size() - 1;
     const long block_rows = step * B, row_b0 = row_seg0 + seg_begin * step; // first row of call block 0
     std::vector<long> gb;
@@ -2360,46 +2309,18 @@ static int welch_run(Engine &E, hipStream_t st, DevCache *cache, const long *key
         gb.push_back(std::max(k, gb.back()));
     }
     gb.push_back(n_blocks);
-    auto chunk_of = [&](long row) -> int {
-        int lo = 0, hi = n_chunks - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row0[mid] <= row) lo = mid; else hi = mid - 1; }
-        return lo;
-    };
-    struct Piece { long b0, b1; int c0, c1; std::vector<int> miss; std::vector<long> ooff; u64 ws = 0; };
-    std::vector<Piece> pieces;
-    u64 piece_cap = 0;
+    std::vector<FeedPiece> pieces;
     for (int p = 0; p < np; p++) {
         if (gb[p + 1] <= gb[p]) continue;
-        Piece Pc;
-        Pc.b0 = gb[p]; Pc.b1 = gb[p + 1];
-        const long s_lo = seg_begin + Pc.b0 * B, s_hi = std::min(seg_end, seg_begin + Pc.b1 * B);
-        Pc.c0 = chunk_of(row_seg0 + s_lo * step);
-        Pc.c1 = chunk_of(row_seg0 + (s_hi - 1) * step + nperseg - 1);
-        for (int i = Pc.c0; i <= Pc.c1; i++)
-            if (!resident[i]) { Pc.miss.push_back(i); Pc.ooff.push_back((long)Pc.ws); Pc.ws += align_up((u64)n_rows[i] * row_bytes, 256); }
-        piece_cap = std::max(piece_cap, Pc.ws);
+        FeedPiece Pc;
+        Pc.u0 = gb[p]; Pc.u1 = gb[p + 1];
+        const long s_lo = seg_begin + Pc.u0 * B, s_hi = std::min(seg_end, seg_begin + Pc.u1 * B);
+        Pc.c0 = chunk_of(row0, n_chunks, row_seg0 + s_lo * step);
+        Pc.c1 = chunk_of(row0, n_chunks, row_seg0 + (s_hi - 1) * step + nperseg - 1);
         pieces.push_back(std::move(Pc));
     }
-    // compressed bytes of every chunk decoded here, once
-    std::vector<long> mcoff(n_chunks, 0);
-    u64 ctot = 0;
-    bool any_miss = false;
-    {
-        int prev = -1;
-        for (int i = 0; i < n_chunks; i++) {
-            if (resident[i]) continue;
-            any_miss = true;
-            if (cdata_on_device) { mcoff[i] = c_off[i]; continue; }
-            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
-            if (!joins) ctot = align_up(ctot + (prev >= 0 ? 16 : 0), 16);
-            mcoff[i] = (long)ctot; ctot += (u64)c_len[i];
-            prev = i;
-        }
-        ctot += 16;
-    }
-    // segment tables, one per piece: (c1 - c0 + 1) bases, then (c1 - c0 + 2) first rows
-    std::vector<long> seg_at(pieces.size() + 1, 0);
-    for (size_t g = 0; g < pieces.size(); g++) seg_at[g + 1] = seg_at[g] + 2l * (pieces[g].c1 - pieces[g].c0 + 1) + 1;
+    u64 piece_cap;
+    const std::vector<long> seg_at = plan_pieces(F, pieces, &piece_cap);
     // blocks per launch: the slab of partials stays <= WELCH_SLAB_BYTES (at least one block)
     const u64 blk_bytes = 8 * (u64)n_elems;
     long run_blocks = (long)std::max<u64>(1, WELCH_SLAB_BYTES / blk_bytes);
@@ -2408,15 +2329,9 @@ static int welch_run(Engine &E, hipStream_t st, DevCache *cache, const long *key
                  o_seg = o_cols + align_up(4 * (u64)n_cols, 256), o_part = o_seg + align_up(8 * (u64)(seg_at.back() + 1), 256),
                  o_acc = o_part + align_up(blk_bytes * run_blocks, 256),
                  o_end = out_on_host ? o_acc + align_up(8 * (u64)n_groups * n_elems, 256) : o_acc;
-    // ---- workspace: allocated BEFORE the resident entries are looked at (see decimate_run)
-    int rc;
+    // ---- workspace
     if ((rc = E.welch.ensure(o_end + 256))) return rc;
-    if (any_miss && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
-    if (piece_cap && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
-    if (cache) {
-        for (int i = 0; i < n_chunks; i++)
-            if (resident[i] && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-    }
+    if ((rc = F.ensure(E, piece_cap))) return rc;
     u8 *ws = E.welch.as<u8>();
     // taper and twiddles, rounded once to the compute type
     std::vector<u8> h_tt((size_t)csize * 3 * nperseg);
@@ -2435,20 +2350,7 @@ static int welch_run(Engine &E, hipStream_t st, DevCache *cache, const long *key
             memcpy(h_tt.data() + 8 * nperseg + 16 * j + 8, &ti, 8);
         }
     }
-    std::vector<long> seg(seg_at.back() + 1, 0);
-    std::vector<const u8 *> res_ptr(n_chunks, nullptr);
-    for (int i = 0; i < n_chunks; i++) if (resident[i]) res_ptr[i] = entry_of(i)->d;
-    for (size_t g = 0; g < pieces.size(); g++) {
-        const Piece &Pc = pieces[g];
-        long *b = seg.data() + seg_at[g], *r = b + (Pc.c1 - Pc.c0 + 1);
-        size_t m = 0;
-        for (int i = Pc.c0; i <= Pc.c1; i++) {
-            const u8 *base = resident[i] ? res_ptr[i] : E.h_out.as<u8>() + Pc.ooff[m++];
-            b[i - Pc.c0] = (long)(uintptr_t)base;
-            r[i - Pc.c0] = row0[i];
-        }
-        r[Pc.c1 - Pc.c0 + 1] = row0[Pc.c1] + n_rows[Pc.c1];
-    }
+    const std::vector<long> seg = segment_tables(F, E, pieces, seg_at, row0);
     MTS_HIP(hipMemcpyAsync(ws + o_taper, h_tt.data(), (size_t)csize * nperseg, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_tw, h_tt.data() + (size_t)csize * nperseg, 2 * (size_t)csize * nperseg, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
@@ -2457,232 +2359,29 @@ static int welch_run(Engine &E, hipStream_t st, DevCache *cache, const long *key
     MTS_HIP(hipMemsetAsync(d_acc, 0, 8 * (size_t)n_groups * n_elems, st));
     double *d_part = (double *)(ws + o_part);
     const int dflags = flags & ~MTS_FLAG_UNSIGNED;
-    const int dev = E.dev;
-    std::vector<char> copied(n_chunks, 0);
-    auto copy_in = [&](int g) -> int {
-        if (cdata_on_device) return MTS_OK;
-        MTS_HIP(hipSetDevice(dev));
-        const std::vector<int> &mi = pieces[g].miss;
-        for (size_t a = 0; a < mi.size();) {
-            if (copied[mi[a]]) { a++; continue; }
-            size_t e = a + 1;
-            while (e < mi.size() && !copied[mi[e]] && mi[e] == mi[e - 1] + 1 && c_off[mi[e]] == c_off[mi[e - 1]] + c_len[mi[e - 1]] &&
-                   mcoff[mi[e]] == mcoff[mi[e - 1]] + c_len[mi[e - 1]]) e++;
-            u64 len = 0;
-            for (size_t z = a; z < e; z++) { len += (u64)c_len[mi[z]]; copied[mi[z]] = 1; }
-            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[mi[a]], cdata + c_off[mi[a]], (size_t)len); if (rc1) return rc1; }
-            a = e;
-        }
-        return MTS_OK;
-    };
-    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
-    const int ng = (int)pieces.size();
-    if (ng > 0 && (rc = copy_in(0))) return rc;
-    bool first_decode = true;
-    for (int g = 0; g < ng; g++) {
-        std::future<int> f_in;
-        if (g + 1 < ng) f_in = copy_beside(copy_in, g + 1);
-        const Piece &Pc = pieces[g];
-        const int nm = (int)Pc.miss.size();
-        if (nm) {
-            std::vector<long> co(nm), cl(nm), nr(nm);
-            std::vector<int> mst(nm, MTS_CHUNK_CORRUPT);
-            for (int z = 0; z < nm; z++) { co[z] = mcoff[Pc.miss[z]]; cl[z] = c_len[Pc.miss[z]]; nr[z] = n_rows[Pc.miss[z]]; }
-            rc = dev_decompress(E, st, d_src, co.data(), cl.data(), nr.data(), nm, nc, sz, dflags, E.h_out.as<u8>(), Pc.ooff.data(), mst.data(), 0,
-                                !first_decode);
-            first_decode = false;
-            if (!rc) for (int z = 0; z < nm; z++) if (mst[z] != MTS_CHUNK_OK) status[Pc.miss[z]] = mst[z];
-        }
-        if (!rc && cache) {
-            // (as in decimate_run: a decode allocation that failed drops the decoded chunks; this piece's tables must not point at a
-            // freed entry)
-            for (int i = Pc.c0; i <= Pc.c1 && !rc; i++) {
-                if (!resident[i]) continue;
-                const CacheEntry *e = entry_of(i);
-                if (!e || e->d != res_ptr[i]) {
-                    set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i);
-                    rc = MTS_E_MISS;
-                }
-            }
-        }
-        const long *sb = (const long *)(ws + o_seg) + seg_at[g];
+    rc = feed_pieces(F, E, st, pieces, dflags, status, [&](int p) {
+        const FeedPiece &Pc = pieces[p];
+        int r = F.still_placed(Pc);
+        const long *sb = (const long *)(ws + o_seg) + seg_at[p];
         const int ns = Pc.c1 - Pc.c0 + 1;
-        for (long lb = Pc.b0; !rc && lb < Pc.b1; lb += run_blocks) {
-            const long lb1 = std::min(Pc.b1, lb + run_blocks);
-            rc = launch_welch(st, sz, flags, csize, log2n, (const u8 *const *)sb, sb + ns, ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taper,
-                              ws + o_tw, row_seg0, step, seg_end, b_first + lb, lb1 - lb, detrend ? 1 : 0, d_part);
-            if (!rc) rc = launch_welch_combine(st, d_part, lb, lb1, GB, n_elems, d_acc);
+        for (long lb = Pc.u0; !r && lb < Pc.u1; lb += run_blocks) {
+            const long lb1 = std::min(Pc.u1, lb + run_blocks);
+            r = launch_welch(st, sz, flags, csize, log2n, (const u8 *const *)sb, sb + ns, ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taper,
+                             ws + o_tw, row_seg0, step, seg_end, b_first + lb, lb1 - lb, detrend ? 1 : 0, d_part);
+            if (!r) r = launch_welch_combine(st, d_part, lb, lb1, GB, n_elems, d_acc);
         }
-        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;
-        if (rc || rc_in) return rc ? rc : rc_in;
-    }
+        return r;
+    });
+    if (rc) return rc;
     if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_acc, 8 * (size_t)n_groups * n_elems, hipMemcpyDeviceToHost, st));
     MTS_HIP(hipStreamSynchronize(st));
     return MTS_OK;
 }
 
-int mts_window_stats(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
-                     const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
-                     long row_end, long window_rows, int n_cols, const int *cols, void *out_min, void *out_max, void *out_sum, void *out_sumsq,
-                     long *out_count, int *chunk_status)
-{
-    DevCache *c = nullptr;
-    if (cache_id) {
-        int cdev = 0;
-        c = find_cache(cache_id, &cdev);
-        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
-    }
-    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;      // (destroyed while this call waited for the engine)
-    MTS_HIP(hipSetDevice(E->dev));
-    return window_stats_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize,
-                            flags, row_begin, row_end, window_rows, n_cols, cols, out_min, out_max, out_sum, out_sumsq, true, out_count,
-                            chunk_status);
-}
-
-int mts_dev_window_stats(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
-                         const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin,
-                         long row_end, long window_rows, int n_cols, const int *cols, void *d_min, void *d_max, void *d_sum, void *d_sumsq,
-                         long *count, int *chunk_status)
-{
-    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    MTS_HIP(hipSetDevice(E->dev));
-    return window_stats_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
-                            n_channels, itemsize, flags, row_begin, row_end, window_rows, n_cols, cols, d_min, d_max, d_sum, d_sumsq, false,
-                            count, chunk_status);
-}
-
-int mts_rank_hist(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
-                  const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
-                  long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
-                  const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *out_hist, unsigned long long *out_kmin,
-                  unsigned long long *out_kmax, long *out_count, int *chunk_status)
-{
-    DevCache *c = nullptr;
-    if (cache_id) {
-        int cdev = 0;
-        c = find_cache(cache_id, &cdev);
-        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
-    }
-    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;      // (destroyed while this call waited for the engine)
-    MTS_HIP(hipSetDevice(E->dev));
-    return rank_hist_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize,
-                         flags, row_begin, row_end, window_rows, n_cols, cols, mode, center, sel_prefix, sel_shift, out_hist, out_kmin, out_kmax,
-                         true, out_count, chunk_status);
-}
-
-int mts_dev_rank_hist(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
-                      const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin,
-                      long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
-                      const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *d_hist, unsigned long long *d_kmin,
-                      unsigned long long *d_kmax, long *count, int *chunk_status)
-{
-    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    MTS_HIP(hipSetDevice(E->dev));
-    return rank_hist_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
-                         n_channels, itemsize, flags, row_begin, row_end, window_rows, n_cols, cols, mode, center, sel_prefix, sel_shift, d_hist,
-                         d_kmin, d_kmax, false, count, chunk_status);
-}
-
-int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
-                 const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
-                 long valid_end, long first_row, long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols,
-                 void *out, int *chunk_status)
-{
-    DevCache *c = nullptr;
-    if (cache_id) {
-        int cdev = 0;
-        c = find_cache(cache_id, &cdev);
-        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
-    }
-    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;      // (destroyed while this call waited for the engine)
-    MTS_HIP(hipSetDevice(E->dev));
-    return decimate_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
-                        valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols, out, true, chunk_status);
-}
-
-int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
-                     const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row,
-                     long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols, void *d_out,
-                     int *chunk_status)
-{
-    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    MTS_HIP(hipSetDevice(E->dev));
-    return decimate_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
-                        itemsize, flags, valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols, d_out, false,
-                        chunk_status);
-}
-
-int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
-              const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_seg0,
-              long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,
-              const int *cols, double *out, int *chunk_status)
-{
-    DevCache *c = nullptr;
-    if (cache_id) {
-        int cdev = 0;
-        c = find_cache(cache_id, &cdev);
-        if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
-    }
-    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;
-    MTS_HIP(hipSetDevice(E->dev));
-    return welch_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
-                     row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, csize, n_cols, cols, out, true, chunk_status);
-}
-
-int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
-                  const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0, long seg_begin, long seg_end,
-                  int nperseg, long step, const double *taper, int detrend, int csize, int n_cols, const int *cols, double *d_out,
-                  int *chunk_status)
-{
-    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    MTS_HIP(hipSetDevice(E->dev));
-    return welch_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
-                     itemsize, flags, row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, csize, n_cols, cols, d_out, false,
-                     chunk_status);
-}
-
 // ---- Gram matrices (mts_gram, mts_dev_gram) ----------------------------------------------------------------------------------
-// The call's groups are cut into slabs of GRAM_SLAB_ROWS rows; the chunks into pieces of MTS_PIPE_BYTES of decoded bytes to decode
-// (pipe_pieces; resident chunks weigh nothing).  Piece p owns the groups whose first row lies in its chunks and decodes the missing
-// chunks those groups read (a chunk read by groups of two pieces is decoded in both).  A piece's slabs are launched in runs that keep
-// the partial slab <= GRAM_SLAB_BYTES, each followed by the combine that adds them to their groups' accumulators in slab order: every
-// group sum is the same sequence of additions whatever the pieces and runs.
+// The call's groups are cut into slabs of GRAM_SLAB_ROWS rows.  Piece p owns the groups whose first row lies in its chunks.  A piece's
+// slabs are launched in runs that keep the partial slab <= GRAM_SLAB_BYTES, each followed by the combine that adds them to their
+// groups' accumulators in slab order: every group sum is the same sequence of additions whatever the pieces and runs.
 static const u64 GRAM_SLAB_BYTES = 256ull << 20;
 
 static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device, const long *c_off,
@@ -2691,8 +2390,8 @@ static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys
                     bool out_on_host, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
-    if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
+    int rc;
+    if ((rc = check_items(sz, flags))) return rc;
     if (nc <= 0 || n_chunks < 0 || n_cols < 1 || n_cols > MTS_GRAM_MAX_COLS || !cols) {
         set_error("gram: n_channels, n_chunks or columns invalid (1 <= n_cols <= %d)", MTS_GRAM_MAX_COLS); return MTS_E_ARG;
     }
@@ -2706,14 +2405,8 @@ static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys
         set_error("gram: groups [%ld, %ld) empty or outside the %ld groups of the range", group_begin, group_end, total_groups); return MTS_E_ARG;
     }
     if (!out_gram || !out_sum) { set_error("gram: no output buffer"); return MTS_E_ARG; }
-    for (int j = 0; j < n_cols; j++)
-        if (cols[j] < 0 || cols[j] >= nc) { set_error("column %d out of range (%d channels)", cols[j], nc); return MTS_E_ARG; }
-    for (int i = 0; i < n_chunks; i++) {
-        if (n_rows[i] <= 0 || row0[i] < 0 || c_len[i] < 0) { set_error("chunk %d: rows or bytes invalid", i); return MTS_E_ARG; }
-        if (i && row0[i] != row0[i - 1] + n_rows[i - 1]) { set_error("chunk %d: chunks must be adjacent", i); return MTS_E_ARG; }
-        if (!cache && c_len[i] == 0) { set_error("chunk %d: no compressed bytes and no cache", i); return MTS_E_ARG; }
-        if (c_len[i] && (u64)n_rows[i] * nc * sz >= (1ull << 31)) { set_error("chunk %d: chunks must be < 2 GiB", i); return MTS_E_ARG; }
-    }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, cache != nullptr, c_len, row0, n_rows, n_chunks, nc, sz))) return rc;
     // the groups' rows: group g -> [grow[g], grow_end(g))
     const long n_groups = group_end - group_begin;
     if (n_groups > (1l << 31)) { set_error("gram: too many groups in one call"); return MTS_E_ARG; }
@@ -2748,24 +2441,10 @@ static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys
         for (long s = gfirst[g], r = lo; s < gfirst[g + 1]; s++, r += SR) { slab_rows[2 * s] = r; slab_rows[2 * s + 1] = std::min(r + SR, hi); }
     }
 
-    // ---- which chunks are resident (whole rows), which are decoded here
-    auto entry_of = [&](int i) -> const CacheEntry * {
-        if (!cache) return nullptr;
-        auto it = cache->map.find(keys[i]);
-        if (it == cache->map.end()) return nullptr;
-        const CacheEntry &e = it->second;
-        return e.rows == n_rows[i] && e.cols == nc && e.size == (u64)n_rows[i] * nc * sz ? &e : nullptr;
-    };
-    std::vector<char> resident(n_chunks, 0);
-    std::vector<long> weight(n_chunks, 0);
-    for (int i = 0; i < n_chunks; i++) {
-        if (entry_of(i)) { resident[i] = 1; continue; }
-        if (c_len[i] == 0) { set_error("chunk key %ld is not resident and no compressed bytes were given", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-        weight[i] = n_rows[i];
-    }
-    const u64 row_bytes = (u64)nc * sz;
-    // ---- pieces of groups: [gp[p], gp[p + 1]) (call-local group indices) read chunks [c0, c1]
-    std::vector<int> pb = cdata_on_device ? std::vector<int>{0, n_chunks} : pipe_pieces(weight.data(), false, n_chunks, row_bytes);
+    ChunkFeed F(cache, keys, cdata, cdata_on_device, c_off, c_len, n_rows, n_chunks, nc, sz);
+    if ((rc = F.classify())) return rc;
+    // ---- pieces of groups: [u0, u1) (call-local group indices) read chunks [c0, c1]
+    const std::vector<int> pb = F.piece_bounds();
     const int np = (int)pb.size() - 1;
     std::vector<long> gp;
     gp.push_back(0);
@@ -2775,45 +2454,17 @@ static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys
         gp.push_back(std::max(k, gp.back()));
     }
     gp.push_back(n_groups);
-    auto chunk_of = [&](long row) -> int {
-        int lo = 0, hi = n_chunks - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row0[mid] <= row) lo = mid; else hi = mid - 1; }
-        return lo;
-    };
-    struct Piece { long g0, g1; int c0, c1; std::vector<int> miss; std::vector<long> ooff; u64 ws = 0; };
-    std::vector<Piece> pieces;
-    u64 piece_cap = 0;
+    std::vector<FeedPiece> pieces;
     for (int p = 0; p < np; p++) {
         if (gp[p + 1] <= gp[p]) continue;
-        Piece Pc;
-        Pc.g0 = gp[p]; Pc.g1 = gp[p + 1];
-        Pc.c0 = chunk_of(slab_rows[2 * gfirst[Pc.g0]]);
-        Pc.c1 = chunk_of(slab_rows[2 * gfirst[Pc.g1] - 1] - 1);
-        for (int i = Pc.c0; i <= Pc.c1; i++)
-            if (!resident[i]) { Pc.miss.push_back(i); Pc.ooff.push_back((long)Pc.ws); Pc.ws += align_up((u64)n_rows[i] * row_bytes, 256); }
-        piece_cap = std::max(piece_cap, Pc.ws);
+        FeedPiece Pc;
+        Pc.u0 = gp[p]; Pc.u1 = gp[p + 1];
+        Pc.c0 = chunk_of(row0, n_chunks, slab_rows[2 * gfirst[Pc.u0]]);
+        Pc.c1 = chunk_of(row0, n_chunks, slab_rows[2 * gfirst[Pc.u1] - 1] - 1);
         pieces.push_back(std::move(Pc));
     }
-    // compressed bytes of every chunk decoded here, once
-    std::vector<long> mcoff(n_chunks, 0);
-    u64 ctot = 0;
-    bool any_miss = false;
-    {
-        int prev = -1;
-        for (int i = 0; i < n_chunks; i++) {
-            if (resident[i]) continue;
-            any_miss = true;
-            if (cdata_on_device) { mcoff[i] = c_off[i]; continue; }
-            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
-            if (!joins) ctot = align_up(ctot + (prev >= 0 ? 16 : 0), 16);
-            mcoff[i] = (long)ctot; ctot += (u64)c_len[i];
-            prev = i;
-        }
-        ctot += 16;
-    }
-    // segment tables, one per piece: (c1 - c0 + 1) bases, then (c1 - c0 + 2) first rows
-    std::vector<long> seg_at(pieces.size() + 1, 0);
-    for (size_t g = 0; g < pieces.size(); g++) seg_at[g + 1] = seg_at[g] + 2l * (pieces[g].c1 - pieces[g].c0 + 1) + 1;
+    u64 piece_cap;
+    const std::vector<long> seg_at = plan_pieces(F, pieces, &piece_cap);
     // slabs per launch: the partials stay <= GRAM_SLAB_BYTES (at least one slab)
     const u64 slab_bytes = (u64)gram_slab_bytes(n_cols);
     long run_slabs = (long)std::max<u64>(1, GRAM_SLAB_BYTES / slab_bytes);
@@ -2825,30 +2476,11 @@ static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys
                  o_acc = o_psum + align_up((u64)run_slabs * 8 * n_cols, 256),
                  o_accs = o_acc + (out_on_host ? align_up(8 * (u64)n_groups * nn, 256) : 0),
                  o_end = o_accs + (out_on_host ? align_up(8 * (u64)n_groups * n_cols, 256) : 0);
-    // ---- workspace: allocated BEFORE the resident entries are looked at (see decimate_run)
-    int rc;
+    // ---- workspace
     if ((rc = E.gram.ensure(o_end + 256))) return rc;
-    if (any_miss && !cdata_on_device && (rc = E.h_in.ensure(ctot + 256))) return rc;
-    if (piece_cap && (rc = E.h_out.ensure(piece_cap + 256))) return rc;
-    if (cache) {
-        for (int i = 0; i < n_chunks; i++)
-            if (resident[i] && !entry_of(i)) { set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i); return MTS_E_MISS; }
-    }
+    if ((rc = F.ensure(E, piece_cap))) return rc;
     u8 *ws = E.gram.as<u8>();
-    std::vector<long> seg(seg_at.back() + 1, 0);
-    std::vector<const u8 *> res_ptr(n_chunks, nullptr);
-    for (int i = 0; i < n_chunks; i++) if (resident[i]) res_ptr[i] = entry_of(i)->d;
-    for (size_t g = 0; g < pieces.size(); g++) {
-        const Piece &Pc = pieces[g];
-        long *b = seg.data() + seg_at[g], *r = b + (Pc.c1 - Pc.c0 + 1);
-        size_t m = 0;
-        for (int i = Pc.c0; i <= Pc.c1; i++) {
-            const u8 *base = resident[i] ? res_ptr[i] : E.h_out.as<u8>() + Pc.ooff[m++];
-            b[i - Pc.c0] = (long)(uintptr_t)base;
-            r[i - Pc.c0] = row0[i];
-        }
-        r[Pc.c1 - Pc.c0 + 1] = row0[Pc.c1] + n_rows[Pc.c1];
-    }
+    const std::vector<long> seg = segment_tables(F, E, pieces, seg_at, row0);
     MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_slab, slab_rows.data(), 16 * (size_t)n_slabs, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_gf, gfirst.data(), 8 * (size_t)(n_groups + 1), hipMemcpyHostToDevice, st));
@@ -2863,69 +2495,24 @@ static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys
     const bool exact = !(flags & MTS_FLAG_FLOAT) && sz <= 2;
     const int float_sum = (flags & MTS_FLAG_FLOAT) ? 1 : 0;
     const int dflags = flags & ~MTS_FLAG_UNSIGNED;
-    const int dev = E.dev;
-    std::vector<char> copied(n_chunks, 0);
-    auto copy_in = [&](int g) -> int {
-        if (cdata_on_device) return MTS_OK;
-        MTS_HIP(hipSetDevice(dev));
-        const std::vector<int> &mi = pieces[g].miss;
-        for (size_t a = 0; a < mi.size();) {
-            if (copied[mi[a]]) { a++; continue; }
-            size_t e = a + 1;
-            while (e < mi.size() && !copied[mi[e]] && mi[e] == mi[e - 1] + 1 && c_off[mi[e]] == c_off[mi[e - 1]] + c_len[mi[e - 1]] &&
-                   mcoff[mi[e]] == mcoff[mi[e - 1]] + c_len[mi[e - 1]]) e++;
-            u64 len = 0;
-            for (size_t z = a; z < e; z++) { len += (u64)c_len[mi[z]]; copied[mi[z]] = 1; }
-            if (len) { const int rc1 = staged_h2d(E, E.h_in.as<u8>() + mcoff[mi[a]], cdata + c_off[mi[a]], (size_t)len); if (rc1) return rc1; }
-            a = e;
-        }
-        return MTS_OK;
-    };
-    const u8 *d_src = cdata_on_device ? cdata : E.h_in.as<u8>();
-    const int ng = (int)pieces.size();
-    if (ng > 0 && (rc = copy_in(0))) return rc;
-    bool first_decode = true;
-    for (int g = 0; g < ng; g++) {
-        std::future<int> f_in;
-        if (g + 1 < ng) f_in = copy_beside(copy_in, g + 1);
-        const Piece &Pc = pieces[g];
-        const int nm = (int)Pc.miss.size();
-        if (nm) {
-            std::vector<long> co(nm), cl(nm), nr(nm);
-            std::vector<int> mst(nm, MTS_CHUNK_CORRUPT);
-            for (int z = 0; z < nm; z++) { co[z] = mcoff[Pc.miss[z]]; cl[z] = c_len[Pc.miss[z]]; nr[z] = n_rows[Pc.miss[z]]; }
-            rc = dev_decompress(E, st, d_src, co.data(), cl.data(), nr.data(), nm, nc, sz, dflags, E.h_out.as<u8>(), Pc.ooff.data(), mst.data(), 0,
-                                !first_decode);
-            first_decode = false;
-            if (!rc) for (int z = 0; z < nm; z++) if (mst[z] != MTS_CHUNK_OK) status[Pc.miss[z]] = mst[z];
-        }
-        if (!rc && cache) {
-            // (as in decimate_run: a decode allocation that failed drops the decoded chunks; this piece's tables must not point at a
-            // freed entry)
-            for (int i = Pc.c0; i <= Pc.c1 && !rc; i++) {
-                if (!resident[i]) continue;
-                const CacheEntry *e = entry_of(i);
-                if (!e || e->d != res_ptr[i]) {
-                    set_error("chunk key %ld was dropped from the cache during the call", keys ? keys[i] : (long)i);
-                    rc = MTS_E_MISS;
-                }
-            }
-        }
-        const long *sb = (const long *)(ws + o_seg) + seg_at[g];
+    rc = feed_pieces(F, E, st, pieces, dflags, status, [&](int p) {
+        const FeedPiece &Pc = pieces[p];
+        int r = F.still_placed(Pc);
+        const long *sb = (const long *)(ws + o_seg) + seg_at[p];
         const int ns = Pc.c1 - Pc.c0 + 1;
-        const long p_s0 = gfirst[Pc.g0], p_s1 = gfirst[Pc.g1];
-        for (long s = p_s0; !rc && s < p_s1; s += run_slabs) {
+        const long p_s0 = gfirst[Pc.u0], p_s1 = gfirst[Pc.u1];
+        for (long s = p_s0; !r && s < p_s1; s += run_slabs) {
             const long s1 = std::min(p_s1, s + run_slabs);
-            rc = launch_gram(st, sz, flags, (const u8 *const *)sb, sb + ns, ns, nc, (const int *)(ws + o_cols), n_cols, d_slab, s, s1 - s, d_part, d_psum);
+            r = launch_gram(st, sz, flags, (const u8 *const *)sb, sb + ns, ns, nc, (const int *)(ws + o_cols), n_cols, d_slab, s, s1 - s, d_part, d_psum);
             // the groups the slabs [s, s1) belong to
             const long g0 = std::upper_bound(gfirst.begin(), gfirst.end(), s) - gfirst.begin() - 1;
             const long g1 = std::lower_bound(gfirst.begin(), gfirst.end(), s1) - gfirst.begin();
-            for (long ga = g0; !rc && ga < g1; ga += 65535)
-                rc = launch_gram_combine(st, d_part, d_psum, s, s1, ga, std::min(g1, ga + 65535), d_gf, n_cols, float_sum, d_gram, d_sum);
+            for (long ga = g0; !r && ga < g1; ga += 65535)
+                r = launch_gram_combine(st, d_part, d_psum, s, s1, ga, std::min(g1, ga + 65535), d_gf, n_cols, float_sum, d_gram, d_sum);
         }
-        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;
-        if (rc || rc_in) return rc ? rc : rc_in;
-    }
+        return r;
+    });
+    if (rc) return rc;
     if (exact && (rc = launch_gram_finish(st, d_gram, n_groups * (long)nn))) return rc;
     if (out_on_host) {
         MTS_HIP(hipMemcpyAsync(out_gram, d_gram, 8 * (size_t)n_groups * nn, hipMemcpyDeviceToHost, st));
@@ -2935,10 +2522,10 @@ static int gram_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys
     return MTS_OK;
 }
 
-int mts_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
-             const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long range_begin,
-             long range_end, long window_rows, long group_begin, long group_end, int n_cols, const int *cols, void *out_gram, void *out_sum,
-             int *chunk_status)
+// ---- the entries of the reductions: the cache (host entries), the engine and its lock, the device, then run(engine, cache).
+// bad_table: the wrapper's own null-pointer check, which answers after a cache that does not exist and before everything else
+template <class Run>
+static int host_entry(int device, long cache_id, bool bad_table, Run &&run)
 {
     DevCache *c = nullptr;
     if (cache_id) {
@@ -2946,30 +2533,156 @@ int mts_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, co
         c = find_cache(cache_id, &cdev);
         if (!c || cdev != device) { set_error("cache %ld does not exist on device %d", cache_id, device); return MTS_E_ARG; }
     }
-    if (n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys))) return MTS_E_ARG;
+    if (bad_table) return MTS_E_ARG;
     Engine *E;
     int rc = get_engine(device, &E);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(E->mu);
-    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;
+    if (c && !cache_alive(cache_id, c)) return MTS_E_ARG;      // (destroyed while this call waited for the engine)
     MTS_HIP(hipSetDevice(E->dev));
-    return gram_run(*E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
-                    range_begin, range_end, window_rows, group_begin, group_end, n_cols, cols, out_gram, out_sum, true, chunk_status);
+    return run(*E, c);
+}
+
+template <class Run>
+static int dev_entry(int device, bool bad_table, Run &&run)
+{
+    if (bad_table) return MTS_E_ARG;
+    Engine *E;
+    int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    MTS_HIP(hipSetDevice(E->dev));
+    return run(*E);
+}
+
+extern "C" {
+
+int mts_window_stats(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                     const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
+                     long row_end, long window_rows, int n_cols, const int *cols, void *out_min, void *out_max, void *out_sum, void *out_sumsq,
+                     long *out_count, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys));
+    return host_entry(device, cache_id, bad, [&](Engine &E, DevCache *c) {
+        return window_stats_run(E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize,
+                                flags, row_begin, row_end, window_rows, n_cols, cols, out_min, out_max, out_sum, out_sumsq, true, out_count,
+                                chunk_status);
+    });
+}
+
+int mts_dev_window_stats(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                         const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin,
+                         long row_end, long window_rows, int n_cols, const int *cols, void *d_min, void *d_max, void *d_sum, void *d_sumsq,
+                         long *count, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status);
+    return dev_entry(device, bad, [&](Engine &E) {
+        return window_stats_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
+                                n_channels, itemsize, flags, row_begin, row_end, window_rows, n_cols, cols, d_min, d_max, d_sum, d_sumsq, false,
+                                count, chunk_status);
+    });
+}
+
+int mts_rank_hist(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                  const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
+                  long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
+                  const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *out_hist, unsigned long long *out_kmin,
+                  unsigned long long *out_kmax, long *out_count, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys));
+    return host_entry(device, cache_id, bad, [&](Engine &E, DevCache *c) {
+        return rank_hist_run(E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize,
+                             flags, row_begin, row_end, window_rows, n_cols, cols, mode, center, sel_prefix, sel_shift, out_hist, out_kmin,
+                             out_kmax, true, out_count, chunk_status);
+    });
+}
+
+int mts_dev_rank_hist(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                      const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin,
+                      long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center,
+                      const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *d_hist, unsigned long long *d_kmin,
+                      unsigned long long *d_kmax, long *count, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status);
+    return dev_entry(device, bad, [&](Engine &E) {
+        return rank_hist_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
+                             n_channels, itemsize, flags, row_begin, row_end, window_rows, n_cols, cols, mode, center, sel_prefix, sel_shift,
+                             d_hist, d_kmin, d_kmax, false, count, chunk_status);
+    });
+}
+
+int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                 const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                 long valid_end, long first_row, long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols,
+                 void *out, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys));
+    return host_entry(device, cache_id, bad, [&](Engine &E, DevCache *c) {
+        return decimate_run(E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize,
+                            flags, valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols, out, true, chunk_status);
+    });
+}
+
+int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
+                     const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row,
+                     long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols, void *d_out,
+                     int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status);
+    return dev_entry(device, bad, [&](Engine &E) {
+        return decimate_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
+                            n_channels, itemsize, flags, valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols,
+                            d_out, false, chunk_status);
+    });
+}
+
+int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+              const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_seg0,
+              long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,
+              const int *cols, double *out, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys));
+    return host_entry(device, cache_id, bad, [&](Engine &E, DevCache *c) {
+        return welch_run(E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
+                         row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, csize, n_cols, cols, out, true, chunk_status);
+    });
+}
+
+int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
+                  const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0, long seg_begin, long seg_end,
+                  int nperseg, long step, const double *taper, int detrend, int csize, int n_cols, const int *cols, double *d_out,
+                  int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status);
+    return dev_entry(device, bad, [&](Engine &E) {
+        return welch_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
+                         itemsize, flags, row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, csize, n_cols, cols, d_out, false,
+                         chunk_status);
+    });
+}
+
+int mts_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+             const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long range_begin,
+             long range_end, long window_rows, long group_begin, long group_end, int n_cols, const int *cols, void *out_gram, void *out_sum,
+             int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys));
+    return host_entry(device, cache_id, bad, [&](Engine &E, DevCache *c) {
+        return gram_run(E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
+                        range_begin, range_end, window_rows, group_begin, group_end, n_cols, cols, out_gram, out_sum, true, chunk_status);
+    });
 }
 
 int mts_dev_gram(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
                  const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long range_begin, long range_end, long window_rows,
                  long group_begin, long group_end, int n_cols, const int *cols, void *d_gram, void *d_sum, int *chunk_status)
 {
-    if (n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status)) return MTS_E_ARG;
-    Engine *E;
-    int rc = get_engine(device, &E);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(E->mu);
-    MTS_HIP(hipSetDevice(E->dev));
-    return gram_run(*E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
-                    itemsize, flags, range_begin, range_end, window_rows, group_begin, group_end, n_cols, cols, d_gram, d_sum, false,
-                    chunk_status);
+    const bool bad = n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status);
+    return dev_entry(device, bad, [&](Engine &E) {
+        return gram_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
+                        itemsize, flags, range_begin, range_end, window_rows, group_begin, group_end, n_cols, cols, d_gram, d_sum, false,
+                        chunk_status);
+    });
 }
 
 // ---- debug taps ---------------------------------------------------------------------------------

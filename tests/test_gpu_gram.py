@@ -4,6 +4,10 @@ across column sets, lanes, calls and residency, column counts that exercise part
 configs[1] recording in HBM, the cache, damaged chunks and argument errors."""
 import ctypes as C
 import json
+import os
+import pathlib
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -17,6 +21,7 @@ from tests.test_gpu_window_stats import _hbm_recording, _oracle_decode
 pytestmark = pytest.mark.gpu
 
 E_ARG = -1
+ROOT = pathlib.Path(__file__).resolve().parent.parent
 GOLDEN = sorted(n for n, c in CASES.items() if golden_cbin(c) is not None)
 
 
@@ -273,6 +278,67 @@ def test_cache_untouched_by_a_scan_resident_equals_cold_and_e_miss(tmp_cfg):
         hip.gram(cache, keys, bounds[:-1], data, offs, lens_bad, np.diff(bounds), nc, np.int16, flags, 0, n, 3001, 0, ng, range(nc))
     assert e.value.code == hip.E_MISS
     r.close()
+
+
+_PIECES_SCRIPT = '''
+import sys, numpy as np
+sys.path.insert(0, sys.argv[1])
+import mtscomp_amd
+from mtscomp_amd import api, hip
+r = mtscomp_amd.decompress(sys.argv[2], sys.argv[3], codec=api.HipCodec(devices=[0]), check_after_decompress=False)
+n, b = r.n_samples, r.chunk_bounds
+keys = list(range(len(b) - 1))
+cache = r._cache_for(0)
+out = {}
+def run(tag):
+    for i, (w, lo, hi) in enumerate(((None, 0, n), (4321, 1234, n - 77))):
+        c = r.cov(lo, hi, window=w)
+        for k in ('count', 'sum', 'gram', 'mean', 'cov'):
+            out['%s_%s_%d' % (tag, k, i)] = c[k]
+assert not any(hip.cache_query(cache, keys).tolist())
+run('cold')
+assert not any(hip.cache_query(cache, keys).tolist())             # (a scan inserts nothing)
+r[b[3] + 5:b[4] + 7]               # chunks 3, 4 and 9: a resident run between missing chunks, missing runs after a resident chunk
+r[b[9] + 1:b[9] + 3]
+assert [k for k, p in zip(keys, hip.cache_query(cache, keys).tolist()) if p] == [3, 4, 9]
+run('part')
+np.savez(sys.argv[4], **out)
+'''
+
+
+@pytest.mark.parametrize('dtype', ['int16', 'float32'])
+def test_cov_pieces_and_residency_do_not_change_the_result(tmp_cfg, dtype):
+    """MTS_PIPE_BYTES unset (one piece) and two chunks a piece (>= 5 pieces), each cold and with chunks 3, 4 and 9 of 12 resident:
+    every output of Reader.cov is the same bytes, and right by the oracle."""
+    rows, nc = 12 * 3000, 40
+    x = (np.random.RandomState(8).randn(rows, nc) * 300).astype(dtype)
+    assert hip.gram_groups(1234, rows - 77, 4321) > 1 and 4321 < hip.GRAM_GROUP_ROWS        # the windowed call: several groups
+    raw = tmp_cfg / 'd.bin'
+    x.tofile(raw)
+    mtscomp_amd.compress(raw, tmp_cfg / 'd.cbin', tmp_cfg / 'd.ch', sample_rate=3000., n_channels=nc, dtype=dtype,
+                         do_time_diff=dtype != 'float32', check_after_compress=False)
+    script = tmp_cfg / 'pieces.py'
+    script.write_text(_PIECES_SCRIPT)
+    outs = []
+    for pipe in (None, str(2 * 3000 * nc * np.dtype(dtype).itemsize)):         # one piece; two chunks a piece: >= 5 pieces
+        env = dict(os.environ)
+        env.pop('MTS_PIPE_BYTES', None)
+        env['HOME'] = str(tmp_cfg)
+        env['MTSCOMP_READ_AHEAD'] = '0'                                        # (exactly the chunks touched become resident)
+        if pipe:
+            env['MTS_PIPE_BYTES'] = pipe
+        p = tmp_cfg / ('o%d.npz' % len(outs))
+        subprocess.run([sys.executable, str(script), str(ROOT), str(tmp_cfg / 'd.cbin'), str(tmp_cfg / 'd.ch'), str(p)], env=env,
+                       check=True, timeout=300)
+        outs.append(dict(np.load(p)))
+    assert sorted(outs[0]) == sorted(outs[1]) and len(outs[0]) == 20
+    for k in outs[0]:
+        assert outs[0][k].tobytes() == outs[1][k].tobytes(), k
+        if k.startswith('part_'):
+            assert outs[1][k].tobytes() == outs[1]['cold_' + k[5:]].tobytes(), k
+    for i, (w, lo, hi) in enumerate(((None, 0, rows), (4321, 1234, rows - 77))):
+        got = type('B', (), {k: outs[1]['part_%s_%d' % (k, i)] for k in ('count', 'sum', 'gram', 'mean', 'cov')})
+        check_cov_result(got, x, lo, hi, w)
 
 
 def test_damaged_chunk(tmp_cfg):
