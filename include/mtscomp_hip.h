@@ -45,7 +45,7 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_welch, mts_gram and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_detect, mts_welch, mts_gram and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
 #define MTS_WELCH_MAX_NPERSEG 16384
 #define MTS_WELCH_BLOCK_SEGMENTS 32   /* mts_welch: segments per block (B), summed in order on the device */
@@ -53,6 +53,9 @@ extern "C" {
 #define MTS_GRAM_GROUP_ROWS (1l << 20)  /* mts_gram: rows per group of a window (aligned to the window's start; the last may be short) */
 #define MTS_GRAM_SLAB_ROWS 4096         /* mts_gram: rows per slab of a group (aligned to the group's start; the last may be short) */
 #define MTS_GRAM_MAX_COLS 16384
+#define MTS_DETECT_MAX_EXCLUDE 255      /* mts_detect: rows either side in which a larger sample suppresses an event */
+#define MTS_DETECT_MAX_SPREAD 32        /* ... and column positions either side */
+#define MTS_DETECT_MAX_REF_COLS 1024    /* columns of a median reference: a row's order keys are sorted in 4 KiB of LDS by one wave */
 
 int mts_version(void);
 int mts_device_count(void);                 /* number of gfx950 devices visible; 0 if none */
@@ -219,6 +222,46 @@ int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys
                  int *chunk_status);
 
 /*
+ * Threshold-crossing peak detection on filtered rows (an extension: the reference has no such call; its users filter Reader[...],
+ * subtract a per-sample median and look for peaks on the host).  Only the events cross the bus.  Everything is float32 and a
+ * definition, not a tolerance:
+ *   filter         y[t, j] = sum_{k=0..n_taps-1} taps[k] * x[t + half - k, cols[j]], half = (n_taps - 1) / 2, x = 0 outside
+ *                  [valid_begin, valid_end): the arithmetic of mts_decimate with q = 1 and out_itemsize 4, bit for bit
+ *   reference      0: z = y.  1: z = y - m[t] (one rounding), m[t] the median of y[t, 0 .. n_cols) with repeated columns counted:
+ *                  the values in np.sort's order, NaN last; the middle one for an odd n_cols, 0.5f * (a + b) of the two middle ones
+ *                  (the sum rounded to float) for an even one; NaN when the row holds a NaN
+ *   sign           0: v = -z, 1: v = z, 2: v = |z|
+ *   event          (t, j) with row_begin <= t < row_end, v[t, j] > threshold[j] and no neighbour that beats it.  Neighbours:
+ *                  (t', j') != (t, j) with |t' - t| <= exclude_rows, |j' - j| <= exclude_cols (positions in cols), valid_begin <= t'
+ *                  < valid_end, 0 <= j' < n_cols -- inside or outside [row_begin, row_end).  It beats (t, j) when v' > v, or v' == v
+ *                  and (t', j') precedes (t, j) in (t, j) order.  A NaN beats nothing and is no event; a plateau gives one event, at
+ *                  its first row and lowest position.  Calls on [a, b) and [b, c) together give the events of [a, c).
+ *   threshold      n_cols finite floats > 0 on the host
+ *   outputs        the events in ascending (t, j) order: out_row[i] = t (file row), out_pos[i] = j, out_amp[i] = z[t, j].
+ *                  *n_events: the events found, which may exceed max_events; then the first max_events of them are written and the
+ *                  call still answers MTS_OK (call again with room for *n_events).  max_events 0: a count, the outputs may be null.
+ *                  The same bytes whatever the call, its pieces, its slabs, the cache or the device.
+ *   limits         1 <= n_taps <= MTS_DECIMATE_MAX_TAPS finite doubles; exclude_rows <= MTS_DETECT_MAX_EXCLUDE; exclude_cols <=
+ *                  MTS_DETECT_MAX_SPREAD (a true peak visits (2 exclude_rows + 1) * (2 exclude_cols + 1) samples: the limits keep that
+ *                  near 33000 loads); with a reference n_cols <= MTS_DETECT_MAX_REF_COLS
+ *   chunks         as mts_decimate: adjacent, ascending, covering [row_begin - exclude_rows + half - n_taps + 1, row_end + exclude_rows +
+ *                  half) within [valid_begin, valid_end); valid_begin <= row_begin <= row_end <= valid_end
+ *   chunk_status   MTS_CHUNK_* per chunk; the events near a failed chunk are undefined
+ * mts_detect: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated piece by piece (MTS_PIPE_BYTES) in a
+ * transient workspace and NOT inserted; a piece owns the rows of its chunks and a chunk in the halo of two pieces is inflated in
+ * both.  Within a piece the rows go through the float workspace in slabs of at most 256 MiB.  The outputs are host memory.
+ * mts_dev_detect: device d_cdata and d_* outputs on `device`; threshold, n_events and chunk_status on the host; no cache.
+ * MTS_E_ARG before anything is launched: any argument outside the ranges above, a threshold that is not a finite positive number,
+ * a tap that is not finite, max_events < 0 or no output buffer for it, chunks not adjacent or not covering the rows read.
+ */
+int mts_detect(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+               const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+               long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols,
+               const float *threshold, int sign, int reference, int exclude_rows, int exclude_cols, long max_events, long *out_row,
+               int *out_pos, float *out_amp, long *n_events, int *chunk_status);
+
+/*
  * Per-channel power spectral density, Welch's method (an extension: the reference has no such call; its users run
  * scipy.signal.welch on Reader[...] on the host).  Only one float64 partial per (group, bin, column) crosses the bus.
  *   segments       segment s covers file rows [row_seg0 + s * step, row_seg0 + s * step + nperseg); the call computes segments
@@ -360,6 +403,11 @@ int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, con
                      int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row,
                      long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols,
                      const int *cols, void *d_out, int *chunk_status /* host */);
+int mts_dev_detect(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                   const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                   long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols,
+                   const float *threshold /* host */, int sign, int reference, int exclude_rows, int exclude_cols, long max_events,
+                   long *d_row, int *d_pos, float *d_amp, long *n_events /* host */, int *chunk_status /* host */);
 int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                   const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0,
                   long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,

@@ -64,6 +64,9 @@ MAP_CDATA = os.environ.get('MTSCOMP_MAP_CDATA', '1') not in ('', '0')      # sli
 PREAD_THREADS = int(os.environ.get('MTSCOMP_PREAD_THREADS', 8))      # threads that read the compressed bytes of a slice's missing chunks (a few MB and more)
 WINDOW_STATS_CALL_BYTES = 1 << 30      # Reader.window_stats: compressed bytes per device call (a longer range is split on chunk boundaries)
 WINDOW_STATS_SLAB_BYTES = 1 << 30      # ... and partial results per call on the device (one per column and tile of <= 512 rows of a window)
+DETECT_CALL_BYTES = 1 << 30            # Reader.detect: compressed bytes per device call (a longer range is split at chunk boundaries)
+DETECT_GUESS_MIN = 4096                # Reader.detect: events a call's first buffer holds at least, and one more per this many samples:
+DETECT_GUESS_SAMPLES = 256             # a call that finds more says how many and is made once more
 DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per device call (a longer range is split at output-row boundaries)
 WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
 GRAM_CALL_BYTES = 1 << 30              # Reader.cov: compressed bytes per device call (a longer range is split at group boundaries)
@@ -191,6 +194,25 @@ def decimate_taps(q):
     return h / h.sum()
 
 
+def highpass_taps(cutoff_hz, sample_rate, n_taps=101):
+    """scipy.signal.firwin(n_taps, cutoff_hz, pass_zero=False, fs=sample_rate) restated in numpy: a Hamming-windowed high-pass of odd
+    length, scaled to unit gain at Nyquist.  The spike band of Reader.detect is highpass_taps(300, sample_rate)."""
+    if not isinstance(n_taps, (int, np.integer)) or isinstance(n_taps, bool) or n_taps < 3 or n_taps % 2 == 0:
+        raise ValueError("highpass_taps needs an odd int n_taps >= 3, got %r" % (n_taps,))
+    try:
+        cutoff, rate = float(cutoff_hz), float(sample_rate)
+    except (TypeError, ValueError):
+        raise ValueError("cutoff_hz and sample_rate must be numbers") from None
+    if not (np.isfinite(rate) and rate > 0 and 0 < cutoff < rate / 2):
+        raise ValueError("highpass_taps needs 0 < cutoff_hz < sample_rate / 2, got %r and %r" % (cutoff_hz, sample_rate))
+    n = int(n_taps)
+    m = np.arange(n) - (n - 1) / 2.0
+    f = 2.0 * cutoff / rate
+    h = np.sinc(m) - f * np.sinc(f * m)
+    h *= 0.54 - 0.46 * np.cos(2.0 * np.pi * np.arange(n) / (n - 1))
+    return h / (h * np.cos(np.pi * m)).sum()
+
+
 def welch_window(window, nperseg):
     """The taper of Reader.welch: 'hann', 'hamming' or 'boxcar' as the periodic windows of scipy.signal.get_window(window, nperseg)
     (restated in numpy), or a 1-D array of nperseg finite numbers, as float64."""
@@ -312,6 +334,15 @@ class HipCodec:
         device = self.devices[(lane or 0) % len(self.devices)]
         return hip.decimate(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row,
                             n_out, q, taps, out_dtype, cols, device=device)
+
+    def detect(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end,
+               taps, cols, threshold, sign, reference, exclude_rows, exclude_cols, max_events, lane=None):
+        """The events of rows [row_begin, row_end) from the adjacent chunks `keys` on one device (`lane` modulo the devices, default
+        the first): mts_detect.  cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0 are read there.  -> (status
+        list, n_events, row int64, pos int32, amp float32): the first min(n_events, max_events) events in (row, pos) order."""
+        device = self.devices[(lane or 0) % len(self.devices)]
+        return hip.detect(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin,
+                          row_end, taps, cols, threshold, sign, reference, exclude_rows, exclude_cols, max_events, device=device)
 
     def welch(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg, step,
               taper, detrend, compute_dtype, cols, lane=None):
@@ -1268,7 +1299,7 @@ class Reader:
         return out
 
     def _lane_call(self, fn, cache, keys, lane, *args):
-        """One call of a codec's reduction `fn` (window_stats, rank_hist, decimate, welch or gram) for the chunks `keys` of one lane:
+        """One call of a codec's reduction `fn` (window_stats, rank_hist, decimate, detect, welch or gram) for the chunks `keys` of one lane:
         chunks resident in its cache go without bytes, the others' compressed bytes come from a mapping of the file (or one read); sent
         whole once more if an entry was dropped between the query and the call.  -> what `fn` returns."""
         row0 = [self.chunk_bounds[k] for k in keys]
@@ -1677,6 +1708,101 @@ class Reader:
                     out[parts[g]:parts[g + 1]] = y
             self._raise_for(status)
         return out[:, 0] if squeeze else out
+
+    # -- peak detection on the device (an extension: the reference's users filter Reader[...] and look for peaks on the host)
+    def detect(self, threshold, start=0, stop=None, channels=slice(None), taps=None, sign='neg', reference=None, exclude=0, spread=0):
+        """Threshold crossings of the filtered rows [start, stop), on the device: only the events cross the bus.  All in float32:
+        y[t, j] = sum_{k < L} taps[k] * x[t + half - k, cols[j]], half = (L - 1) // 2, x = 0 outside the recording -- the bytes of
+        decimate(1, taps=taps, edge='recording', dtype=float32); taps=None is [1.0], highpass_taps(300, sample_rate) the spike band.
+        reference='median': z = y - the median over the selected columns of row t (np.sort's order; 0.5 * (a + b) for an even
+        number; NaN if the row holds one), else z = y.  v = -z (sign='neg'), z ('pos') or |z| ('both').  (t, j) is an event when
+        v > threshold[j] and no neighbour within `exclude` rows and `spread` column positions (positions in `channels`, inside the
+        recording, inside or outside [start, stop)) beats it: v' > v, or v' == v at an earlier (t, j).  So a plateau gives one event,
+        NaN none, and detect(a, b) followed by detect(b, c) is detect(a, c).  threshold: a positive finite number or one per column
+        (5 * mad(...).mad / 0.6745 is the usual choice).  Returns a Bunch: sample (int64 file rows), channel (int64, the entries of
+        `channels`), amplitude (float32 z, signed), in ascending (sample, position) order; threshold (the float32 array used), start,
+        stop, channels.  start / stop follow Reader[...]; channels: an int, a slice with step >= 1, or a sequence of ints (repeats
+        allowed).  exclude <= 255, spread <= 32, a median over at most 1024 columns.  The same bytes whatever the lanes, calls,
+        pieces or cache residency.  Chunks resident in the device cache are read where they lie; the others are decoded in a
+        transient workspace and NOT kept.  A damaged chunk in the support raises the IOError of Reader[...]."""
+        if not callable(getattr(self.codec, 'detect', None)):
+            raise NotImplementedError("detect needs a codec that detects on the device (HipCodec); %r has none"
+                                      % getattr(self.codec, 'name', self.codec))
+        if sign not in hip.DETECT_SIGNS:
+            raise ValueError("sign must be 'neg', 'pos' or 'both', got %r" % (sign,))
+        if reference not in (None, 'median'):
+            raise ValueError("reference must be None or 'median', got %r" % (reference,))
+        for name, v, top in (('exclude', exclude, hip.DETECT_MAX_EXCLUDE), ('spread', spread, hip.DETECT_MAX_SPREAD)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= v <= top:
+                raise ValueError("%s must be an int in [0, %d], got %r" % (name, top, v))
+        taps = np.asarray([1.0] if taps is None else taps, dtype=np.float64)
+        if taps.ndim != 1 or not 1 <= taps.size <= hip.DECIMATE_MAX_TAPS or not np.isfinite(taps).all():
+            raise ValueError("taps must be a 1-D sequence of 1 to %d finite numbers" % hip.DECIMATE_MAX_TAPS)
+        i0 = self._validate_index(start, 0)
+        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        cols, _ = self._stats_channels(channels)
+        thr = np.asarray(threshold)
+        if thr.dtype.kind not in 'fiu' or thr.shape not in ((), (cols.size,)):
+            raise ValueError("threshold must be a number or one per column (%d)" % cols.size)
+        with np.errstate(over='ignore'):
+            thr = np.ascontiguousarray(np.broadcast_to(thr.astype(np.float32), (cols.size,)))
+        if not (np.isfinite(thr) & (thr > 0)).all():
+            raise ValueError("threshold must be positive and finite in float32")
+        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
+            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
+        R, S, n_taps, N = int(exclude), int(spread), int(taps.size), self.n_samples
+        half = (n_taps - 1) // 2
+        sign_code, ref_code = hip.DETECT_SIGNS[sign], 1 if reference else 0
+        found = []                                                  # (row, pos, amp) of every part, in order
+        if i1 > i0 and cols.size:
+            # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they lie in pass DETECT_CALL_BYTES
+            first = bisect.bisect_right(self.chunk_bounds, i0) - 1
+            last = bisect.bisect_right(self.chunk_bounds, i1 - 1) - 1
+            cuts, acc = [i0], 0
+            for k in range(first, last + 1):
+                b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
+                if acc and acc + b > DETECT_CALL_BYTES and self.chunk_bounds[k] > cuts[-1]:
+                    cuts.append(self.chunk_bounds[k])
+                    acc = 0
+                acc += b
+            cuts.append(i1)
+            lanes = self._n_lanes()
+            use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
+            status = {}
+            for ra, rb in zip(cuts[:-1], cuts[1:]):
+                # lanes: contiguous parts of the call's rows (a part's halo is decoded by that part alone)
+                nl = max(1, min(lanes, rb - ra))
+                parts = [ra + (rb - ra) * g // nl for g in range(nl + 1)]
+                res = [None] * nl
+
+                def one(g, parts=parts, res=res):
+                    a, b = parts[g], parts[g + 1]
+                    if b <= a:
+                        return
+                    lo, hi = max(0, a - R + half - (n_taps - 1)), min(N, b + R + half)
+                    c0 = bisect.bisect_right(self.chunk_bounds, lo) - 1
+                    c1 = bisect.bisect_right(self.chunk_bounds, hi - 1) - 1
+                    keys = list(range(c0, c1 + 1))
+                    cache = self._cache_for(g) if use_cache else 0
+                    cap = max(DETECT_GUESS_MIN, (b - a) * cols.size // DETECT_GUESS_SAMPLES)
+                    out = self._lane_call(self.codec.detect, cache, keys, g, 0, N, a, b, taps, cols, thr, sign_code, ref_code, R, S, cap)
+                    if out[1] > cap and all(v == hip.CHUNK_OK for v in out[0]):      # the buffer was short: once more, with room for all
+                        out = self._lane_call(self.codec.detect, cache, keys, g, 0, N, a, b, taps, cols, thr, sign_code, ref_code, R, S, out[1])
+                    res[g] = (keys,) + tuple(out)
+                self.codec.run_lanes(one, nl)
+                for g in range(nl):
+                    if res[g] is None:
+                        continue
+                    keys, st, n_ev, row, pos, amp = res[g]
+                    for k, v in zip(keys, st):
+                        if v != hip.CHUNK_OK or k not in status:
+                            status[k] = v
+                    found.append((row, pos, amp))
+            self._raise_for(status)
+        row = np.concatenate([f[0] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
+        pos = np.concatenate([f[1] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
+        amp = np.concatenate([f[2] for f in found]).astype(np.float32) if found else np.zeros(0, np.float32)
+        return Bunch(sample=row, channel=cols.astype(np.int64)[pos], amplitude=amp, threshold=thr, start=i0, stop=i1, channels=cols)
 
     # -- power spectral density on the device (an extension: the reference's users run scipy.signal.welch on Reader[...])
     def welch(self, nperseg=256, start=0, stop=None, channels=slice(None), noverlap=None, window='hann', detrend='constant',

@@ -148,6 +148,9 @@ struct Engine {
     DBuf stats;
     // decimation: taps, columns, segment tables, the output of the host entry point
     DBuf dec;
+    // peak detection: taps, columns, thresholds, segment tables, the filtered slab, its event bitmap, block counts and offsets,
+    // the outputs of the host entry point
+    DBuf det;
     // Welch PSD: taper, twiddles, columns, segment tables, block partials, group sums
     DBuf welch;
     // Gram matrices: columns, slab and group tables, slab partials, the accumulators of the host entry point
@@ -201,7 +204,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &welch, &gram};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &welch, &gram};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();
@@ -2231,6 +2234,143 @@ static int decimate_run(Engine &E, hipStream_t st, DevCache *cache, const long *
     return MTS_OK;
 }
 
+// ---- peak detection (mts_detect, mts_dev_detect) -------------------------------------------------------------------------------
+// The unit is a row.  Piece p owns the rows of [row_begin, row_end) in its chunks; their events need the detection value R rows either
+// side, and that the filter's support: piece p reads the chunks from the one holding u0 - R + half - (L - 1) to the one holding
+// u1 - 1 + R + half, within the valid range.  A piece's rows go through the float32 workspace in slabs that keep it <= the slab bound
+// (filter -> median -> mask -> count / scan / emit on the stream); the write position is carried on the device from slab to slab and
+// piece to piece.  Every value is computed from the same rows in the same order whatever the pieces and slabs.
+static const u64 DETECT_SLAB_BYTES = 256ull << 20;
+static const long DETECT_SLAB_MAX_ROWS = 1l << 22;                  // (bounds the bitmap of narrow selections: <= 32 MiB up to 64 columns)
+
+static u64 detect_slab_bytes()
+{
+    const char *e = getenv("MTS_DETECT_SLAB_BYTES");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (u64)v : DETECT_SLAB_BYTES;
+}
+
+static int detect_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device, const long *c_off,
+                      const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz, int flags, long vb, long ve,
+                      long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, const float *threshold, int sign,
+                      int reference, int R, int S, long max_events, long *out_row, int *out_pos, float *out_amp, bool out_on_host,
+                      long *n_events, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    int rc;
+    if ((rc = check_items(sz, flags))) return rc;
+    if (nc <= 0 || n_chunks < 0 || n_cols < 1 || n_cols > 64 * 65535 || !cols) { set_error("detect: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
+    if (n_taps < 1 || n_taps > MTS_DECIMATE_MAX_TAPS || !taps) { set_error("detect: %d taps (1 .. %d)", n_taps, MTS_DECIMATE_MAX_TAPS); return MTS_E_ARG; }
+    for (int j = 0; j < n_taps; j++)
+        if (!std::isfinite(taps[j])) { set_error("detect: tap %d is not finite", j); return MTS_E_ARG; }
+    if (!threshold) { set_error("detect: no thresholds"); return MTS_E_ARG; }
+    for (int j = 0; j < n_cols; j++)
+        if (!std::isfinite(threshold[j]) || !(threshold[j] > 0)) { set_error("detect: threshold %d is not a finite positive number", j); return MTS_E_ARG; }
+    if (sign < 0 || sign > 2) { set_error("detect: sign %d (0 neg, 1 pos, 2 both)", sign); return MTS_E_ARG; }
+    if (reference < 0 || reference > 1) { set_error("detect: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
+    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("detect: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
+    if (R < 0 || R > MTS_DETECT_MAX_EXCLUDE || S < 0 || S > MTS_DETECT_MAX_SPREAD) {
+        set_error("detect: exclude_rows %d (0 .. %d) or exclude_cols %d (0 .. %d)", R, MTS_DETECT_MAX_EXCLUDE, S, MTS_DETECT_MAX_SPREAD); return MTS_E_ARG;
+    }
+    if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve) { set_error("detect: rows invalid"); return MTS_E_ARG; }
+    if (max_events < 0 || max_events > (1l << 40) || !n_events) { set_error("detect: max_events invalid or no n_events"); return MTS_E_ARG; }
+    if (max_events && (!out_row || !out_pos || !out_amp)) { set_error("detect: no output buffers"); return MTS_E_ARG; }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, cache != nullptr, c_len, row0, n_rows, n_chunks, nc, sz))) return rc;
+    const long half = (n_taps - 1) / 2;
+    const bool any = row_end > row_begin;
+    // the rows the events read: (rows + R either side)'s support ∩ valid range; the chunks must cover them
+    const long need_lo = any ? std::max(vb, row_begin - R + half - (n_taps - 1)) : 0, need_hi = any ? std::min(ve, row_end + R + half) : 0;
+    if (need_lo < need_hi) {
+        if (n_chunks == 0 || row0[0] > need_lo || row0[n_chunks - 1] + n_rows[n_chunks - 1] < need_hi) {
+            set_error("detect: the chunks do not cover rows [%ld, %ld)", need_lo, need_hi); return MTS_E_ARG;
+        }
+    }
+    for (int i = 0; i < n_chunks; i++) status[i] = MTS_CHUNK_OK;
+    *n_events = 0;
+    if (!any) return MTS_OK;
+
+    ChunkFeed F(cache, keys, cdata, cdata_on_device, c_off, c_len, n_rows, n_chunks, nc, sz);
+    if ((rc = F.classify())) return rc;
+    // ---- pieces of rows: [u0, u1) reads chunks [c0, c1]
+    const std::vector<int> pb = F.piece_bounds();
+    const int np = (int)pb.size() - 1;
+    std::vector<long> gr;
+    gr.push_back(row_begin);
+    for (int p = 1; p < np; p++) gr.push_back(std::max(gr.back(), std::min(row_end, row0[pb[p]])));
+    gr.push_back(row_end);
+    std::vector<FeedPiece> pieces;
+    for (int p = 0; p < np; p++) {
+        if (gr[p + 1] <= gr[p]) continue;
+        FeedPiece Pc;
+        Pc.u0 = gr[p]; Pc.u1 = gr[p + 1];
+        const long lo = std::max(vb, Pc.u0 - R + half - (n_taps - 1)), hi = std::min(ve, Pc.u1 + R + half);
+        if (lo < hi && n_chunks) { Pc.c0 = chunk_of(row0, n_chunks, lo); Pc.c1 = chunk_of(row0, n_chunks, hi - 1); }
+        pieces.push_back(std::move(Pc));
+    }
+    u64 piece_cap;
+    const std::vector<long> seg_at = plan_pieces(F, pieces, &piece_cap);
+    // rows a slab owns: the workspace holds them and R rows either side
+    const long cap_rows = (long)std::min<u64>(detect_slab_bytes() / (4 * (u64)n_cols), (u64)DETECT_SLAB_MAX_ROWS);
+    const long own = std::min(row_end - row_begin, std::max(1l, cap_rows - 2l * R));
+    const long max_words = detect_bitmap_words(own, n_cols), max_blocks = detect_blocks(max_words);
+    const size_t o_taps = 0, o_cols = align_up(4 * (u64)n_taps, 256), o_thr = o_cols + align_up(4 * (u64)n_cols, 256),
+                 o_seg = o_thr + align_up(4 * (u64)n_cols, 256), o_total = o_seg + align_up(8 * (u64)(seg_at.back() + 1), 256),
+                 o_y = o_total + 256, o_bits = o_y + align_up(4 * (u64)(own + 2l * R) * n_cols, 256), o_cnt = o_bits + align_up(8 * (u64)max_words, 256),
+                 o_offs = o_cnt + align_up(4 * (u64)max_blocks, 256), o_row = o_offs + align_up(8 * (u64)max_blocks, 256),
+                 o_pos = out_on_host ? o_row + align_up(8 * (u64)max_events, 256) : o_row,
+                 o_amp = out_on_host ? o_pos + align_up(4 * (u64)max_events, 256) : o_row,
+                 o_end = out_on_host ? o_amp + align_up(4 * (u64)max_events, 256) : o_row;
+    // ---- workspace
+    if ((rc = E.det.ensure(o_end + 256))) return rc;
+    if ((rc = F.ensure(E, piece_cap))) return rc;
+    u8 *ws = E.det.as<u8>();
+    std::vector<float> h_taps(n_taps);
+    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
+    const std::vector<long> seg = segment_tables(F, E, pieces, seg_at, row0);
+    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_thr, threshold, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_seg, seg.data(), 8 * seg.size(), hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemsetAsync(ws + o_total, 0, 8, st));
+    long *d_row = out_on_host ? (long *)(ws + o_row) : out_row;
+    int *d_pos = out_on_host ? (int *)(ws + o_pos) : out_pos;
+    float *d_amp = out_on_host ? (float *)(ws + o_amp) : out_amp;
+    float *d_y = (float *)(ws + o_y);
+    u64 *d_bits = (u64 *)(ws + o_bits), *d_total = (u64 *)(ws + o_total);
+    const int dflags = flags & ~MTS_FLAG_UNSIGNED;           // (the decoder compares the transform flags as a whole)
+    rc = feed_pieces(F, E, st, pieces, dflags, status, [&](int p) {
+        const FeedPiece &Pc = pieces[p];
+        int r = F.still_placed(Pc);
+        const long *sb = (const long *)(ws + o_seg) + seg_at[p];
+        const int ns = Pc.c1 - Pc.c0 + 1 > 0 ? Pc.c1 - Pc.c0 + 1 : 0;
+        for (long s0 = Pc.u0; !r && s0 < Pc.u1; s0 += own) {
+            const long s1 = std::min(Pc.u1, s0 + own), a = std::max(vb, s0 - R), b = std::min(ve, s1 + R);
+            // y[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k
+            r = launch_decimate(st, sz, flags, 4, (const u8 *const *)sb, sb + ns, ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1,
+                                half, a, b, ns ? vb : 0, ns ? ve : 0, d_y);
+            if (!r && reference) r = launch_row_median(st, d_y, b - a, n_cols);
+            if (!r) r = launch_detect_mask(st, d_y, a, b - a, n_cols, (const float *)(ws + o_thr), sign, R, S, s0, s1, d_bits);
+            if (!r) r = launch_detect_emit(st, d_bits, detect_bitmap_words(s1 - s0, n_cols), (u32 *)(ws + o_cnt), (u64 *)(ws + o_offs), d_total, d_y,
+                                           a, n_cols, s0, max_events, d_row, d_pos, d_amp);
+        }
+        return r;
+    });
+    if (rc) return rc;
+    u64 total = 0;
+    MTS_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    MTS_HIP(hipStreamSynchronize(st));
+    *n_events = (long)total;
+    const size_t n_w = (size_t)std::min<u64>(total, (u64)max_events);
+    if (out_on_host && n_w) {
+        MTS_HIP(hipMemcpyAsync(out_row, d_row, 8 * n_w, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_pos, d_pos, 4 * n_w, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_amp, d_amp, 4 * n_w, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipStreamSynchronize(st));
+    }
+    return MTS_OK;
+}
+
 // ---- Welch PSD (mts_welch, mts_dev_welch) ------------------------------------------------------------------------------------
 // The call's segments are cut into blocks of B (WELCH_BLOCK_SEGMENTS) and groups of G.  Piece p owns the blocks whose first row lies
 // in its chunks.  A piece's blocks are launched in runs that keep the partial slab <= WELCH_SLAB_BYTES, each followed by the combine
@@ -2633,6 +2773,34 @@ int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, con
         return decimate_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
                             n_channels, itemsize, flags, valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols,
                             d_out, false, chunk_status);
+    });
+}
+
+int mts_detect(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+               const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+               long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols,
+               const float *threshold, int sign, int reference, int exclude_rows, int exclude_cols, long max_events, long *out_row,
+               int *out_pos, float *out_amp, long *n_events, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys));
+    return host_entry(device, cache_id, bad, [&](Engine &E, DevCache *c) {
+        return detect_run(E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags,
+                          valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, threshold, sign, reference, exclude_rows,
+                          exclude_cols, max_events, out_row, out_pos, out_amp, true, n_events, chunk_status);
+    });
+}
+
+int mts_dev_detect(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                   const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                   long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols,
+                   const float *threshold, int sign, int reference, int exclude_rows, int exclude_cols, long max_events, long *d_row,
+                   int *d_pos, float *d_amp, long *n_events, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status);
+    return dev_entry(device, bad, [&](Engine &E) {
+        return detect_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels,
+                          itemsize, flags, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, threshold, sign, reference,
+                          exclude_rows, exclude_cols, max_events, d_row, d_pos, d_amp, false, n_events, chunk_status);
     });
 }
 

@@ -175,6 +175,20 @@ int launch_decimate(hipStream_t st, int itemsize, int flags, int out_itemsize, c
                     int n_channels, const int *d_cols, int n_cols, const void *d_taps, int n_taps, int q, long first_row, long k_begin,
                     long k_end, long valid_begin, long valid_end, void *d_out);
 
+// detect.hip: peak detection on a float32 workspace z of file rows [ws_row0, ws_row0 + ws_rows) x n_cols that launch_decimate (q = 1)
+// filled (mts_detect).  launch_row_median subtracts every row's median in place.  launch_detect_mask: one bit per (row of [s0, s1),
+// column position), row-major in words of 64 positions ((n_cols + 63) / 64 words per row): 1 = an event; neighbours outside the
+// workspace do not exist.  launch_detect_emit: the events of the bitmap in (row, position) order to d_row / d_pos / d_amp from position
+// *d_total on, those at positions >= max_events counted only; *d_total += the events of the bitmap.  d_counts / d_offsets: one entry
+// per detect_blocks(n_words)
+int launch_row_median(hipStream_t st, float *d_y, long n_rows, int n_cols);
+long detect_bitmap_words(long n_rows, int n_cols);
+long detect_blocks(long n_words);
+int launch_detect_mask(hipStream_t st, const float *d_z, long ws_row0, long ws_rows, int n_cols, const float *d_thr, int sign, int exclude_rows,
+                       int exclude_cols, long s0, long s1, u64 *d_bitmap);
+int launch_detect_emit(hipStream_t st, const u64 *d_bitmap, long n_words, u32 *d_counts, u64 *d_offsets, u64 *d_total, const float *d_z,
+                       long ws_row0, int n_cols, long s0, long max_events, long *d_row, int *d_pos, float *d_amp);
+
 // welch.hip: Welch PSD partials (mts_welch).  Segments s of blocks [block0, block0 + n_blocks) (block b: segments [b * B, (b + 1) * B)
 // ∩ [.., seg_end)) start at file row row_seg0 + s * step; d_part[(b - block0), k, c] = sum over the block's segments, in order, of
 // |X_k|^2 of column cols[c] (float64; X in the csize float type).  d_taper: 2^log2n values, d_tw: 2^log2n complex values

@@ -105,6 +105,11 @@ def lib():
                                C.c_long, C.c_int, C.c_int, dp, C.c_int, C.c_int, ip, vp, ip]
     L.mts_dev_decimate.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
                                    C.c_int, C.c_int, dp, C.c_int, C.c_int, ip, vp, ip]
+    fp = C.POINTER(C.c_float)
+    L.mts_detect.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
+                             C.c_int, dp, C.c_int, ip, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, vp, vp, vp, lp, ip]
+    L.mts_dev_detect.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
+                                 C.c_int, dp, C.c_int, ip, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, vp, vp, vp, lp, ip]
     L.mts_welch.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int,
                             C.c_long, dp, C.c_int, C.c_int, C.c_int, ip, vp, ip]
     L.mts_dev_welch.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int,
@@ -130,7 +135,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_last_stage_times', 'mts_debug_match_tables', 'mts_debug_tokens', 'mts_debug_deflate',
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
-           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_welch', 'mts_dev_welch',
+           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
 
 
@@ -613,6 +618,79 @@ def dev_decimate(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid
         if res.nbytes:
             _check(lib().mts_dev_copy(out.device, None, _ptr(res), out.at(), res.nbytes, 1), 'mts_dev_copy')
     return [int(x) for x in status[:rows.size]], res, out
+
+
+# ------------------------------------------------------------------------------------------------
+# Threshold-crossing peak detection (an extension: the reference has no such call)
+# ------------------------------------------------------------------------------------------------
+DETECT_MAX_EXCLUDE = 255
+DETECT_MAX_SPREAD = 32
+DETECT_MAX_REF_COLS = 1024
+DETECT_SIGNS = {'neg': 0, 'pos': 1, 'both': 2}
+
+
+def _det_args(taps, cols, threshold):
+    taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).ravel())
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float32), (cols.size,)))
+    return taps, cols, thr
+
+
+def detect(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols,
+           threshold, sign, reference, exclude_rows, exclude_cols, max_events, device=0):
+    """mts_detect: the events of rows [row_begin, row_end) (include/mtscomp_hip.h) from the adjacent chunks `keys`.  sign 0 / 1 / 2,
+    reference 0 / 1.  cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError
+    E_MISS).  Returns (status list, n_events, row int64, pos int32, amp float32): the first min(n_events, max_events) events."""
+    dtype = check_dtype(dtype)
+    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
+    taps, cols, thr = _det_args(taps, cols, threshold)
+    n = int(rows.size)
+    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
+    assert not n or int((offs + lens).max()) <= cdata.size
+    cap = max(int(max_events), 0)
+    o_row, o_pos, o_amp = np.empty(cap, np.int64), np.empty(cap, np.int32), np.empty(cap, np.float32)
+    n_ev = np.zeros(1, np.int64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    _check(lib().mts_detect(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
+                            dtype.itemsize, stats_flags(flags, dtype), int(valid_begin), int(valid_end), int(row_begin), int(row_end),
+                            int(taps.size), taps.ctypes.data_as(C.POINTER(C.c_double)), int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)),
+                            thr.ctypes.data_as(C.POINTER(C.c_float)), int(sign), int(reference), int(exclude_rows), int(exclude_cols),
+                            int(max_events), _ptr(o_row) if cap else None, _ptr(o_pos) if cap else None, _ptr(o_amp) if cap else None,
+                            _lp(n_ev), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_detect')
+    k = min(int(n_ev[0]), cap)
+    return [int(x) for x in status[:n]], int(n_ev[0]), o_row[:k], o_pos[:k], o_amp[:k]
+
+
+def dev_detect(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign,
+               reference, exclude_rows, exclude_cols, max_events, out=None, download=True):
+    """mts_dev_detect on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the three event arrays (made when
+    None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, n_events, (row, pos, amp) or None,
+    out)."""
+    dtype = check_dtype(dtype)
+    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
+    taps, cols, thr = _det_args(taps, cols, threshold)
+    cap = max(int(max_events), 0)
+    at = [0, (8 * cap + 255) // 256 * 256]
+    at.append(at[1] + (4 * cap + 255) // 256 * 256)
+    at.append(at[2] + (4 * cap + 255) // 256 * 256)
+    if out is None or out.nbytes < at[3] + 256:
+        out = DevBuffer(at[3] + 256, device=cbuf.device)
+    n_ev = np.zeros(1, np.int64)
+    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
+    _check(lib().mts_dev_detect(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
+                                dtype.itemsize, stats_flags(flags, dtype), int(valid_begin), int(valid_end), int(row_begin), int(row_end),
+                                int(taps.size), taps.ctypes.data_as(C.POINTER(C.c_double)), int(cols.size),
+                                cols.ctypes.data_as(C.POINTER(C.c_int)), thr.ctypes.data_as(C.POINTER(C.c_float)), int(sign), int(reference),
+                                int(exclude_rows), int(exclude_cols), int(max_events), out.at(at[0]), out.at(at[1]), out.at(at[2]), _lp(n_ev),
+                                status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_detect')
+    res = None
+    if download:
+        k = min(int(n_ev[0]), cap)
+        res = (np.empty(k, np.int64), np.empty(k, np.int32), np.empty(k, np.float32))
+        for a, o in zip(res, at[:3]):
+            if a.nbytes:
+                _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(o), a.nbytes, 1), 'mts_dev_copy')
+    return [int(x) for x in status[:rows.size]], int(n_ev[0]), res, out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,0 +1,105 @@
+"""The two restatements of mts_detect in tests/detect_oracle.py against each other: the vectorised one every other test leans on and
+the brute-force one (plain loops over every sample and neighbour), on ties, plateaus, special values, edges and every option."""
+import numpy as np
+import pytest
+
+from mtscomp_amd import api
+from mtscomp_amd.synth import synth_int16
+from tests.detect_oracle import detect_events, detect_events_brute, row_median, tied_events
+
+
+def _same(a, b):
+    assert [v.dtype for v in a] == [v.dtype for v in b] == [np.int64, np.int64, np.float32]
+    assert all(u.tobytes() == v.tobytes() for u, v in zip(a, b)), (a[0][:10], b[0][:10])
+
+
+@pytest.mark.parametrize('sign', [0, 1, 2])
+@pytest.mark.parametrize('reference', [0, 1])
+def test_filtered_noise(sign, reference):
+    x = synth_int16(0, 420, 9, 2)
+    taps = api.highpass_taps(300, 5000, 33)
+    n_ev = 0
+    for R, S in [(0, 0), (1, 0), (0, 2), (5, 1), (40, 8)]:
+        for i0, i1 in [(0, 420), (17, 333), (200, 201)]:
+            args = (x, 0, 0, 420, i0, i1, taps, 9.0, sign, reference, R, S)
+            got = detect_events(*args)
+            _same(got, detect_events_brute(*args))
+            n_ev += got[0].size
+    assert n_ev > 200
+
+
+def test_ties_and_plateaus():
+    x = (synth_int16(0, 300, 11, 9) // 8).astype(np.int16)
+    for R, S in [(3, 0), (3, 2), (0, 1), (12, 10)]:
+        args = (x, 0, 0, 300, 5, 290, [1.0], 2.5, 2, 0, R, S)
+        got = detect_events(*args)
+        _same(got, detect_events_brute(*args))
+        assert tied_events(x, 0, 0, 300, 5, 290, [1.0], 2, 0, R, S, got[0], got[1]) > 0
+    flat = np.full((60, 7), 5, np.int16)                        # one event per chain of neighbourhoods: the first sample
+    r = detect_events(flat, 0, 0, 60, 0, 60, [1.0], 1.0, 1, 0, 4, 7)
+    _same(r, detect_events_brute(flat, 0, 0, 60, 0, 60, [1.0], 1.0, 1, 0, 4, 7))
+    assert (r[0].tolist(), r[1].tolist()) == ([0], [0])
+    r = detect_events(flat, 0, 0, 60, 0, 60, [1.0], 1.0, 1, 0, 4, 0)        # spread 0: every column is a chain of its own
+    assert (r[0].tolist(), r[1].tolist()) == ([0] * 7, list(range(7)))
+    r = detect_events(flat, 0, 0, 60, 0, 60, [1.0], 1.0, 1, 0, 0, 0)        # no neighbours: every sample
+    assert r[0].size == 420
+    ramp = np.arange(1, 61, dtype=np.int16)[:, None] * np.ones((1, 3), np.int16)
+    r = detect_events(ramp, 0, 0, 60, 0, 60, [1.0], 0.5, 1, 0, 2, 1)
+    assert (r[0].tolist(), r[1].tolist()) == ([59], [0])
+
+
+def test_special_values_and_the_median():
+    rs = np.random.RandomState(5)
+    x = (rs.randn(200, 8) * 10).astype(np.float32)
+    x[20, 3] = np.nan
+    x[50, 1] = np.inf
+    x[90, 2] = -np.inf
+    x[120, 4] = -0.0
+    x[121] = 0.0
+    x[150, [0, 7]] = [np.inf, -np.inf]                       # an even row whose middle is fine, one whose ends cancel
+    taps = [0.25, 0.5, 0.25]
+    for reference in (0, 1):
+        for sign in (0, 1, 2):
+            args = (x, 0, 0, 200, 0, 200, taps, 6.0, sign, reference, 3, 2)
+            got = detect_events(*args)
+            _same(got, detect_events_brute(*args))
+            assert got[0].size > 10
+            assert not np.isin(got[0], [19, 20, 21])[got[1] == 3].any()      # NaN in the support: no event there
+            if reference:
+                assert not np.isin(got[0], [19, 20, 21]).any()               # ... and in no column of those rows
+    y = np.array([[3, 1, 2], [np.nan, 1, 2], [np.inf, -np.inf, 0], [-0.0, 0.0, 5]], np.float32)
+    m = row_median(y)
+    assert m[0] == 2 and np.isnan(m[1]) and m[2] == 0 and m[3] == 0
+    y = np.array([[4, 1, 2, 3], [np.inf, -np.inf, 1, 2], [np.inf, np.inf, -1, 7]], np.float32)
+    m = row_median(y)
+    assert m[0] == 2.5 and m[1] == 1.5 and m[2] == np.inf
+    a = rs.randn(50, 12).astype(np.float32)
+    assert np.array_equal(row_median(a), np.median(a, axis=1))
+    assert np.array_equal(row_median(a[:, :7]), np.median(a[:, :7], axis=1))
+
+
+@pytest.mark.parametrize('dtype', ['int8', 'uint8', 'uint16', 'int32', 'uint32', 'int64', 'uint64', 'float64'])
+def test_item_types_and_offsets(dtype):
+    rs = np.random.RandomState(11)
+    dt = np.dtype(dtype)
+    if dt.kind == 'f':
+        x = (rs.randn(260, 6) * 100).astype(dt)
+    else:
+        info = np.iinfo(dt)
+        x = rs.randint(max(info.min, -2 ** 62), min(info.max, 2 ** 62), size=(260, 6), dtype=np.int64).astype(dt)
+    scale = float(np.abs(x.astype(np.float64)).max())
+    taps = rs.randn(6)                                        # even length
+    # the rows given start at file row 40 of a recording of 300: rows [40, 300), zeros outside [0, 300) are never read
+    args = (x, 40, 0, 300, 60, 280, taps, 0.3 * scale, 2, 1, 2, 1)
+    got = detect_events(*args)
+    _same(got, detect_events_brute(*args))
+    assert got[0].size > 20 and got[0].min() >= 60 and got[0].max() < 280
+
+
+def test_stitching_is_exact():
+    x = synth_int16(0, 900, 12, 3)
+    taps = api.highpass_taps(300, 5000, 21)
+    whole = detect_events(x, 0, 0, 900, 100, 800, taps, 10.0, 0, 1, 9, 2)
+    parts = [detect_events(x, 0, 0, 900, a, b, taps, 10.0, 0, 1, 9, 2) for a, b in [(100, 400), (400, 403), (403, 800)]]
+    _same(whole, tuple(np.concatenate([p[k] for p in parts]) for k in range(3)))
+    assert whole[0].size > 50
