@@ -231,6 +231,45 @@ def welch_window(window, nperseg):
     return w
 
 
+def _float_dtype(dtype):
+    """The compute type of Reader.decimate / welch: float32 or float64 as a numpy dtype."""
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
+    return dt
+
+
+def _fir_taps(taps):
+    """The taps of Reader.decimate / detect as a float64 array: 1 to hip.DECIMATE_MAX_TAPS finite numbers."""
+    taps = np.asarray(taps, dtype=np.float64)
+    if taps.ndim != 1 or not 1 <= taps.size <= hip.DECIMATE_MAX_TAPS or not np.isfinite(taps).all():
+        raise ValueError("taps must be a 1-D sequence of 1 to %d finite numbers" % hip.DECIMATE_MAX_TAPS)
+    return taps
+
+
+def _window_rows(window, i0, i1):
+    """The window of Reader.window_stats / quantile / cov over rows [i0, i1) as an int: None is one window over the range."""
+    if window is None:
+        window = max(i1 - i0, 1)
+    if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1:
+        raise ValueError("window must be an int >= 1 or None, got %r" % (window,))
+    return int(window)
+
+
+def _lane_reduction(name):
+    """HipCodec.<name>(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, <the op's own arguments>, lane=None):
+    hip.<name> (looked up when called) on the device of `lane` (modulo the devices, default the first) -> what it returns."""
+    def call(self, cache_id, *args, lane=None):
+        return getattr(hip, name)(cache_id or 0, *args, device=self.devices[(lane or 0) % len(self.devices)])
+    call.__name__, call.__qualname__ = name, 'HipCodec.' + name
+    call.__doc__ = ("mts_%s for the chunks `keys` on one device; cache_id: the lane's decoded-chunk cache (0: none), chunks with "
+                    "lens[i] == 0 are read there (hip.%s)." % (name, name))
+    return call
+
+
 class HipCodec:
     """Per-chunk codec on MI355X.  ``devices``: list of device indices (default: all visible)."""
 
@@ -316,60 +355,9 @@ class HipCodec:
     host_buffer_take = staticmethod(hip.pinned_pool.take)
     host_buffer_give = staticmethod(hip.pinned_pool.give)
 
-    def window_stats(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols,
-                     lane=None):
-        """Per-window statistics of the chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])) on one device (`lane` modulo the
-        devices, default the first): mts_window_stats.  cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0
-        are read there.  -> (status list, dict min/max/sum/sumsq/count): the partials of these chunks, identities for windows they
-        do not touch (Reader.window_stats combines the lanes)."""
-        device = self.devices[(lane or 0) % len(self.devices)]
-        return hip.window_stats(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end,
-                                window_rows, cols, device=device)
-
-    def decimate(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row, n_out, q,
-                 taps, out_dtype, cols, lane=None):
-        """FIR + decimation of the adjacent chunks `keys` on one device (`lane` modulo the devices, default the first): mts_decimate.
-        cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0 are read there.  -> (status list, (n_out, n_cols)
-        out_dtype)."""
-        device = self.devices[(lane or 0) % len(self.devices)]
-        return hip.decimate(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row,
-                            n_out, q, taps, out_dtype, cols, device=device)
-
-    def detect(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end,
-               taps, cols, threshold, sign, reference, exclude_rows, exclude_cols, max_events, lane=None):
-        """The events of rows [row_begin, row_end) from the adjacent chunks `keys` on one device (`lane` modulo the devices, default
-        the first): mts_detect.  cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0 are read there.  -> (status
-        list, n_events, row int64, pos int32, amp float32): the first min(n_events, max_events) events in (row, pos) order."""
-        device = self.devices[(lane or 0) % len(self.devices)]
-        return hip.detect(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin,
-                          row_end, taps, cols, threshold, sign, reference, exclude_rows, exclude_cols, max_events, device=device)
-
-    def welch(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg, step,
-              taper, detrend, compute_dtype, cols, lane=None):
-        """Welch group sums of the adjacent chunks `keys` on one device (`lane` modulo the devices, default the first): mts_welch.
-        cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0 are read there.  -> (status list, (n_groups,
-        nperseg // 2 + 1, n_cols) float64)."""
-        device = self.devices[(lane or 0) % len(self.devices)]
-        return hip.welch(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg,
-                         step, taper, detrend, compute_dtype, cols, device=device)
-
-    def gram(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows, group_begin,
-             group_end, cols, lane=None):
-        """Gram entries and column sums of groups [group_begin, group_end) of the grid (range, window_rows) from the adjacent chunks
-        `keys` on one device (`lane` modulo the devices, default the first): mts_gram.  cache_id: the lane's decoded-chunk cache (0:
-        none); chunks with lens[i] == 0 are read there.  -> (status list, gram (n_groups, n_cols, n_cols), sum (n_groups, n_cols))."""
-        device = self.devices[(lane or 0) % len(self.devices)]
-        return hip.gram(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows,
-                        group_begin, group_end, cols, device=device)
-
-    def rank_hist(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, mode,
-                  center, sel_prefix, sel_shift, lane=None):
-        """One round of the radix select over the chunks `keys` on one device (`lane` modulo the devices, default the first):
-        mts_rank_hist.  cache_id: the lane's decoded-chunk cache (0: none); chunks with lens[i] == 0 are read there.  -> (status list,
-        dict hist/kmin/kmax/count): the partials of these chunks, all integers (Reader.quantile combines the lanes in any order)."""
-        device = self.devices[(lane or 0) % len(self.devices)]
-        return hip.rank_hist(cache_id or 0, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows,
-                             cols, mode, center, sel_prefix, sel_shift, device=device)
+    # the device reductions of the Reader, one call for the chunks of one lane
+    window_stats, rank_hist, decimate, detect, welch, gram = map(
+        _lane_reduction, ('window_stats', 'rank_hist', 'decimate', 'detect', 'welch', 'gram'))
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1225,16 +1213,9 @@ class Reader:
         for 1/2-byte integers); mean = sum / count and rms = sqrt(sumsq / count) in float64; start, stop, window, channels.
         Chunks resident in the device cache are read where they lie; the others are decoded in a transient workspace and NOT
         kept.  A damaged chunk raises the IOError of Reader[...]."""
-        if not callable(getattr(self.codec, 'window_stats', None)):
-            raise NotImplementedError("window_stats needs a codec that reduces on the device (HipCodec); %r has none"
-                                      % getattr(self.codec, 'name', self.codec))
-        i0 = self._validate_index(start, 0)
-        i1 = max(i0, self._validate_index(stop, self.n_samples))
-        if window is None:
-            window = max(i1 - i0, 1)
-        if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1:
-            raise ValueError("window must be an int >= 1 or None, got %r" % (window,))
-        window = int(window)
+        self._need_codec('window_stats', 'window_stats', 'reduces')
+        i0, i1 = self._row_range(start, stop)
+        window = _window_rows(window, i0, i1)
         cols, squeeze = self._stats_channels(channels)
         n_win = -(-(i1 - i0) // window)
         t_dt, s_dt, q_dt = hip.stats_dtypes(self.dtype)
@@ -1243,43 +1224,17 @@ class Reader:
         mn = np.full(shape, np.inf if self.dtype.kind == 'f' else fi(self.dtype).max, dtype=t_dt)
         mx = np.full(shape, -np.inf if self.dtype.kind == 'f' else fi(self.dtype).min, dtype=t_dt)
         sm, sq, cnt = np.zeros(shape, s_dt), np.zeros(shape, q_dt), np.zeros(n_win, np.int64)
-        first = bisect.bisect_right(self.chunk_bounds, i0) - 1
-        last = bisect.bisect_left(self.chunk_bounds, i1) - 1
-        chunks = [k for k in range(max(first, 0), min(last, self.n_chunks - 1) + 1)
-                  if self.chunk_bounds[k + 1] > max(i0, self.chunk_bounds[k]) and self.chunk_bounds[k] < i1] if n_win and cols.size else []
-        # calls: runs of chunks whose compressed bytes and partial results fit one device call
-        calls, run, nbytes, slab = [], [], 0, 0
+        # calls: runs of chunks whose compressed bytes and partial results (32 bytes per column and tile) fit one device call
         tile_rows = min(window, 512)
-        for k in chunks:
-            b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
-            t = (-(-(self.chunk_bounds[k + 1] - self.chunk_bounds[k]) // tile_rows) + 1) * cols.size * 32
-            if run and (nbytes + b > WINDOW_STATS_CALL_BYTES or slab + t > WINDOW_STATS_SLAB_BYTES):
-                calls.append(run)
-                run, nbytes, slab = [], 0, 0
-            run.append(k)
-            nbytes, slab = nbytes + b, slab + t
-        if run:
-            calls.append(run)
-        lanes = self._n_lanes()
-        use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
+        calls = self._chunk_runs(self._chunks_in(i0, i1) if n_win and cols.size else [], WINDOW_STATS_CALL_BYTES, WINDOW_STATS_SLAB_BYTES,
+                                 lambda k: (-(-(self.chunk_bounds[k + 1] - self.chunk_bounds[k]) // tile_rows) + 1) * cols.size * 32)
         status = {}
         for run in calls:
             lo, hi = max(i0, self.chunk_bounds[run[0]]), min(i1, self.chunk_bounds[run[-1] + 1])
             w0, w1 = (lo - i0) // window, -(-(hi - i0) // window)
             rb, re = i0 + w0 * window, min(i1, i0 + w1 * window)
-            owners = sorted({k % lanes for k in run})
-            parts = [None] * len(owners)
-
-            def one(j, run=run, rb=rb, re=re, owners=owners, parts=parts):
-                g = owners[j]
-                keys = [k for k in run if k % lanes == g]
-                cache = self._cache_for(g) if use_cache else 0
-                st, res = self._lane_call(self.codec.window_stats, cache, keys, g, rb, re, window, cols)
-                parts[j] = (keys, st, res)
-            self.codec.run_lanes(one, len(owners))
-            for keys, st, res in parts:                             # lanes in order: the float sums are the same every time
-                status.update(zip(keys, st))
-                sl = slice(w0, w1)
+            sl = slice(w0, w1)
+            for res in self._on_owner_lanes(self.codec.window_stats, run, status, rb, re, window, cols):      # lanes in order: the float sums are the same every time
                 mn[sl] = np.minimum(mn[sl], res['min'])
                 mx[sl] = np.maximum(mx[sl], res['max'])
                 sm[sl] += res['sum']
@@ -1297,6 +1252,120 @@ class Reader:
             for key in ('min', 'max', 'sum', 'sumsq', 'mean', 'rms'):
                 out[key] = out[key][:, 0]
         return out
+
+    # -- what the device reductions share: argument checks, the cut of a range into device calls, the lanes of a call
+    def _need_codec(self, what, method, does):
+        if not callable(getattr(self.codec, method, None)):
+            raise NotImplementedError("%s needs a codec that %s on the device (HipCodec); %r has none"
+                                      % (what, does, getattr(self.codec, 'name', self.codec)))
+
+    def _row_range(self, start, stop):
+        """Rows [i0, i1) for start / stop as Reader[...] takes them (None, negative, clipped)."""
+        i0 = self._validate_index(start, 0)
+        return i0, max(i0, self._validate_index(stop, self.n_samples))
+
+    def _lane_cache(self, lane):
+        """The cache a reduction on `lane` reads resident chunks from, 0 when the Reader keeps none."""
+        return self._cache_for(lane) if getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0 else 0
+
+    def _chunks_in(self, lo, hi):
+        """The chunks that hold rows of [lo, hi), in order."""
+        first = bisect.bisect_right(self.chunk_bounds, lo) - 1
+        last = bisect.bisect_left(self.chunk_bounds, hi) - 1
+        return [k for k in range(max(first, 0), min(last, self.n_chunks - 1) + 1)
+                if self.chunk_bounds[k + 1] > max(lo, self.chunk_bounds[k]) and self.chunk_bounds[k] < hi]
+
+    def _chunk_runs(self, chunks, max_bytes, max_weight=None, weight=None):
+        """The tile family's calls (window_stats, rank_hist): `chunks` cut into runs of at most max_bytes compressed bytes and, given
+        weight(k), at most max_weight in all; a run holds one chunk at least."""
+        runs, run, nbytes, total = [], [], 0, 0
+        for k in chunks:
+            b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
+            t = weight(k) if weight else 0
+            if run and (nbytes + b > max_bytes or (weight and total + t > max_weight)):
+                runs.append(run)
+                run, nbytes, total = [], 0, 0
+            run.append(k)
+            nbytes, total = nbytes + b, total + t
+        if run:
+            runs.append(run)
+        return runs
+
+    def _on_owner_lanes(self, fn, run, status, *args):
+        """One call of the tile family: the chunks of `run` on their owner lanes (chunk k on lane k mod lanes: where the cache holds it),
+        all lanes at once.  Every chunk is in one lane's call: its status goes into `status`.  -> the lanes' results, in lane order."""
+        lanes = self._n_lanes()
+        owners = sorted({k % lanes for k in run})
+        parts = [None] * len(owners)
+
+        def one(j):
+            g = owners[j]
+            keys = [k for k in run if k % lanes == g]
+            st, res = self._lane_call(fn, self._lane_cache(g), keys, g, *args)
+            parts[j] = (keys, st, res)
+        self.codec.run_lanes(one, len(owners))
+        for keys, st, _ in parts:
+            status.update(zip(keys, st))
+        return [res for _, _, res in parts]
+
+    def _halo_cuts(self, lo, hi, max_bytes, u0, u1, unit_at):
+        """The calls of decimate and detect: units [u0, u1) (outputs, rows) cut where the compressed bytes of the chunks of rows [lo, hi)
+        pass max_bytes; unit_at(row): the first unit that starts at or after a chunk boundary.  -> the cut list, u0 first, u1 last."""
+        first = bisect.bisect_right(self.chunk_bounds, lo) - 1
+        last = bisect.bisect_right(self.chunk_bounds, hi - 1) - 1
+        cuts, acc = [u0], 0
+        for k in range(first, last + 1):
+            b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
+            if acc and acc + b > max_bytes:
+                u = unit_at(self.chunk_bounds[k])
+                if u > cuts[-1]:
+                    cuts.append(u)
+                    acc = 0
+            acc += b
+        cuts.append(u1)
+        return cuts
+
+    def _chunk_span(self, lo, hi):
+        """The adjacent chunks that hold rows [lo, hi), lo < hi, as a list of keys."""
+        return list(range(bisect.bisect_right(self.chunk_bounds, lo) - 1, bisect.bisect_right(self.chunk_bounds, hi - 1)))
+
+    def _halo_parts(self, fn, cuts, part, again=None):
+        """The halo family's calls (decimate, detect, welch, gram): every [cuts[i], cuts[i + 1]) of the op's unit axis (outputs, rows,
+        groups) is one round of calls, split into contiguous parts [a, b), one per lane (a part's halo is decoded by that part alone).
+        part(a, b) -> (keys, args): the adjacent chunks the part reads and the op's own arguments, or None when it reads nothing.
+        again(result, args) -> the arguments of a second call of the part, or None.  A chunk may be in several parts' calls: a
+        status that is not CHUNK_OK wins.  Yields (a, b, result without the status) in order; the error of a chunk that did not
+        decode is raised after the last."""
+        lanes = self._n_lanes()
+        status = {}
+        for ca, cb in zip(cuts[:-1], cuts[1:]):
+            if cb <= ca:
+                continue
+            nl = max(1, min(lanes, cb - ca))
+            at = [ca + (cb - ca) * g // nl for g in range(nl + 1)]
+            res = [None] * nl
+
+            def one(g, at=at, res=res):
+                what = part(at[g], at[g + 1])
+                if what is None:
+                    return
+                keys, args = what
+                cache = self._lane_cache(g)
+                got = self._lane_call(fn, cache, keys, g, *args)
+                more = again(got, args) if again else None
+                if more is not None:
+                    got = self._lane_call(fn, cache, keys, g, *more)
+                res[g] = (keys, got)
+            self.codec.run_lanes(one, nl)
+            for g in range(nl):
+                if res[g] is None:
+                    continue
+                keys, got = res[g]
+                for k, v in zip(keys, got[0]):
+                    if v != hip.CHUNK_OK or k not in status:
+                        status[k] = v
+                yield at[g], at[g + 1], got[1:]
+        self._raise_for(status)
 
     def _lane_call(self, fn, cache, keys, lane, *args):
         """One call of a codec's reduction `fn` (window_stats, rank_hist, decimate, detect, welch or gram) for the chunks `keys` of one lane:
@@ -1323,16 +1392,9 @@ class Reader:
 
     # -- exact order statistics on the device (an extension: the reference's users sort Reader[...] on the host)
     def _rank_setup(self, what, start, stop, window, channels):
-        if not callable(getattr(self.codec, 'rank_hist', None)):
-            raise NotImplementedError("%s needs a codec that selects on the device (HipCodec); %r has none"
-                                      % (what, getattr(self.codec, 'name', self.codec)))
-        i0 = self._validate_index(start, 0)
-        i1 = max(i0, self._validate_index(stop, self.n_samples))
-        if window is None:
-            window = max(i1 - i0, 1)
-        if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1:
-            raise ValueError("window must be an int >= 1 or None, got %r" % (window,))
-        window = int(window)
+        self._need_codec(what, 'rank_hist', 'selects')
+        i0, i1 = self._row_range(start, stop)
+        window = _window_rows(window, i0, i1)
         if min(window, i1 - i0) >= 1 << 32:
             raise ValueError("windows of 2^32 rows or more are not supported")
         cols, squeeze = self._stats_channels(channels)
@@ -1370,20 +1432,7 @@ class Reader:
         for ws in range(0, n_win, run_wins):
             we = min(n_win, ws + run_wins)
             rb, re = i0 + ws * window, min(i1, i0 + we * window)
-            first = bisect.bisect_right(self.chunk_bounds, rb) - 1
-            last = bisect.bisect_left(self.chunk_bounds, re) - 1
-            chunks = [k for k in range(max(first, 0), min(last, self.n_chunks - 1) + 1)
-                      if self.chunk_bounds[k + 1] > max(rb, self.chunk_bounds[k]) and self.chunk_bounds[k] < re]
-            calls, run, nbytes = [], [], 0
-            for k in chunks:
-                b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
-                if run and nbytes + b > QUANTILE_CALL_BYTES:
-                    calls.append(run)
-                    run, nbytes = [], 0
-                run.append(k)
-                nbytes += b
-            if run:
-                calls.append(run)
+            calls = self._chunk_runs(self._chunks_in(rb, re), QUANTILE_CALL_BYTES)
             cen = center[ws:we] if mode else None
             for r0 in range(0, R, S):
                 rk = ranks[ws:we, r0:r0 + S]
@@ -1472,27 +1521,14 @@ class Reader:
         hist = np.zeros((nw, S, nb, C), np.uint32)
         kmin = np.full((nw, S, C), hip.RANK_KEY_NONE, np.uint64)
         kmax = np.zeros((nw, S, C), np.uint64)
-        lanes = self._n_lanes()
-        use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
         for run in calls:
             lo, hi = max(rb, self.chunk_bounds[run[0]]), min(re, self.chunk_bounds[run[-1] + 1])
             w0, w1 = (lo - rb) // window, -(-(hi - rb) // window)
             cb, ce = rb + w0 * window, min(re, rb + w1 * window)
-            owners = sorted({k % lanes for k in run})
-            parts = [None] * len(owners)
             sl = slice(w0, w1)
             cen = None if center is None else np.ascontiguousarray(center[sl])
             pre, shf = np.ascontiguousarray(pref[sl]), np.ascontiguousarray(sel_shift[sl])
-
-            def one(j, run=run, owners=owners, parts=parts, cb=cb, ce=ce, cen=cen, pre=pre, shf=shf):
-                g = owners[j]
-                keys = [k for k in run if k % lanes == g]
-                cache = self._cache_for(g) if use_cache else 0
-                st, res = self._lane_call(self.codec.rank_hist, cache, keys, g, cb, ce, window, cols, mode, cen, pre, shf)
-                parts[j] = (keys, st, res)
-            self.codec.run_lanes(one, len(owners))
-            for keys, st, res in parts:
-                status.update(zip(keys, st))
+            for res in self._on_owner_lanes(self.codec.rank_hist, run, status, cb, ce, window, cols, mode, cen, pre, shf):
                 hist[sl] += res['hist']
                 kmin[sl] = np.minimum(kmin[sl], res['kmin'])
                 kmax[sl] = np.maximum(kmax[sl], res['kmax'])
@@ -1626,9 +1662,7 @@ class Reader:
         >= 1, or a sequence of ints.  No IIR filters, no rational resampling, no other edge modes.  Chunks resident in the device
         cache are read where they lie; the others are decoded in a transient workspace and NOT kept.  A damaged chunk in the
         support raises the IOError of Reader[...]."""
-        if not callable(getattr(self.codec, 'decimate', None)):
-            raise NotImplementedError("decimate needs a codec that filters on the device (HipCodec); %r has none"
-                                      % getattr(self.codec, 'name', self.codec))
+        self._need_codec('decimate', 'decimate', 'filters')
         if not isinstance(q, (int, np.integer)) or isinstance(q, bool) or q < 1:
             raise ValueError("q must be an int >= 1, got %r" % (q,))
         q = int(q)
@@ -1636,19 +1670,11 @@ class Reader:
             if q == 1:
                 raise ValueError("decimate(1) needs explicit taps")
             taps = decimate_taps(q)
-        taps = np.asarray(taps, dtype=np.float64)
-        if taps.ndim != 1 or not 1 <= taps.size <= hip.DECIMATE_MAX_TAPS or not np.isfinite(taps).all():
-            raise ValueError("taps must be a 1-D sequence of 1 to %d finite numbers" % hip.DECIMATE_MAX_TAPS)
-        try:
-            out_dtype = np.dtype(dtype)
-        except TypeError:
-            raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
-        if out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
+        taps = _fir_taps(taps)
+        out_dtype = _float_dtype(dtype)
         if edge not in ('zeros', 'recording'):
             raise ValueError("edge must be 'zeros' or 'recording', got %r" % (edge,))
-        i0 = self._validate_index(start, 0)
-        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        i0, i1 = self._row_range(start, stop)
         cols, squeeze = self._stats_channels(channels)
         n_taps = int(taps.size)
         n_out = -(-(i1 - i0) // q)
@@ -1658,55 +1684,15 @@ class Reader:
         lo, hi = max(vb, first_row - (n_taps - 1)), min(ve, first_row + (n_out - 1) * q + 1)
         if n_out and cols.size and lo < hi:
             # calls: cut the outputs where the compressed bytes of the chunks their newest rows lie in pass DECIMATE_CALL_BYTES
-            first = bisect.bisect_right(self.chunk_bounds, lo) - 1
-            last = bisect.bisect_right(self.chunk_bounds, hi - 1) - 1
-            cuts, acc = [0], 0
-            for k in range(first, last + 1):
-                b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
-                if acc and acc + b > DECIMATE_CALL_BYTES:
-                    r = self.chunk_bounds[k] - first_row
-                    kc = min(n_out, max(0, -(-r // q)))
-                    if kc > cuts[-1]:
-                        cuts.append(kc)
-                        acc = 0
-                acc += b
-            cuts.append(n_out)
-            lanes = self._n_lanes()
-            use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
-            status = {}
-            for ka, kb in zip(cuts[:-1], cuts[1:]):
-                if kb <= ka:
-                    continue
-                # lanes: contiguous parts of the call's outputs (a part's halo is decoded by that part alone)
-                nl = max(1, min(lanes, kb - ka))
-                parts = [ka + (kb - ka) * g // nl for g in range(nl + 1)]
-                res = [None] * nl
+            cuts = self._halo_cuts(lo, hi, DECIMATE_CALL_BYTES, 0, n_out, lambda row: min(n_out, max(0, -(-(row - first_row) // q))))
 
-                def one(g, parts=parts, res=res):
-                    a, b = parts[g], parts[g + 1]
-                    if b <= a:
-                        return
-                    fr = first_row + a * q
-                    plo, phi = max(vb, fr - (n_taps - 1)), min(ve, fr + (b - a - 1) * q + 1)
-                    if plo >= phi:
-                        res[g] = ([], [], np.zeros((b - a, cols.size), out_dtype))
-                        return
-                    c0 = bisect.bisect_right(self.chunk_bounds, plo) - 1
-                    c1 = bisect.bisect_right(self.chunk_bounds, phi - 1) - 1
-                    keys = list(range(c0, c1 + 1))
-                    cache = self._cache_for(g) if use_cache else 0
-                    st, y = self._lane_call(self.codec.decimate, cache, keys, g, vb, ve, fr, b - a, q, taps, out_dtype, cols)
-                    res[g] = (keys, st, y)
-                self.codec.run_lanes(one, nl)
-                for g in range(nl):
-                    if res[g] is None:
-                        continue
-                    keys, st, y = res[g]
-                    for k, v in zip(keys, st):
-                        if v != hip.CHUNK_OK or k not in status:
-                            status[k] = v
-                    out[parts[g]:parts[g + 1]] = y
-            self._raise_for(status)
+            def part(a, b):
+                fr = first_row + a * q
+                plo, phi = max(vb, fr - (n_taps - 1)), min(ve, fr + (b - a - 1) * q + 1)
+                if plo < phi:                                       # (outputs that read no valid row stay 0)
+                    return self._chunk_span(plo, phi), (vb, ve, fr, b - a, q, taps, out_dtype, cols)
+            for a, b, (y,) in self._halo_parts(self.codec.decimate, cuts, part):
+                out[a:b] = y
         return out[:, 0] if squeeze else out
 
     # -- peak detection on the device (an extension: the reference's users filter Reader[...] and look for peaks on the host)
@@ -1725,9 +1711,7 @@ class Reader:
         allowed).  exclude <= 255, spread <= 32, a median over at most 1024 columns.  The same bytes whatever the lanes, calls,
         pieces or cache residency.  Chunks resident in the device cache are read where they lie; the others are decoded in a
         transient workspace and NOT kept.  A damaged chunk in the support raises the IOError of Reader[...]."""
-        if not callable(getattr(self.codec, 'detect', None)):
-            raise NotImplementedError("detect needs a codec that detects on the device (HipCodec); %r has none"
-                                      % getattr(self.codec, 'name', self.codec))
+        self._need_codec('detect', 'detect', 'detects')
         if sign not in hip.DETECT_SIGNS:
             raise ValueError("sign must be 'neg', 'pos' or 'both', got %r" % (sign,))
         if reference not in (None, 'median'):
@@ -1735,11 +1719,8 @@ class Reader:
         for name, v, top in (('exclude', exclude, hip.DETECT_MAX_EXCLUDE), ('spread', spread, hip.DETECT_MAX_SPREAD)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= v <= top:
                 raise ValueError("%s must be an int in [0, %d], got %r" % (name, top, v))
-        taps = np.asarray([1.0] if taps is None else taps, dtype=np.float64)
-        if taps.ndim != 1 or not 1 <= taps.size <= hip.DECIMATE_MAX_TAPS or not np.isfinite(taps).all():
-            raise ValueError("taps must be a 1-D sequence of 1 to %d finite numbers" % hip.DECIMATE_MAX_TAPS)
-        i0 = self._validate_index(start, 0)
-        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        taps = _fir_taps([1.0] if taps is None else taps)
+        i0, i1 = self._row_range(start, stop)
         cols, _ = self._stats_channels(channels)
         thr = np.asarray(threshold)
         if thr.dtype.kind not in 'fiu' or thr.shape not in ((), (cols.size,)):
@@ -1756,49 +1737,17 @@ class Reader:
         found = []                                                  # (row, pos, amp) of every part, in order
         if i1 > i0 and cols.size:
             # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they lie in pass DETECT_CALL_BYTES
-            first = bisect.bisect_right(self.chunk_bounds, i0) - 1
-            last = bisect.bisect_right(self.chunk_bounds, i1 - 1) - 1
-            cuts, acc = [i0], 0
-            for k in range(first, last + 1):
-                b = self.chunk_offsets[k + 1] - self.chunk_offsets[k]
-                if acc and acc + b > DETECT_CALL_BYTES and self.chunk_bounds[k] > cuts[-1]:
-                    cuts.append(self.chunk_bounds[k])
-                    acc = 0
-                acc += b
-            cuts.append(i1)
-            lanes = self._n_lanes()
-            use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
-            status = {}
-            for ra, rb in zip(cuts[:-1], cuts[1:]):
-                # lanes: contiguous parts of the call's rows (a part's halo is decoded by that part alone)
-                nl = max(1, min(lanes, rb - ra))
-                parts = [ra + (rb - ra) * g // nl for g in range(nl + 1)]
-                res = [None] * nl
+            cuts = self._halo_cuts(i0, i1, DETECT_CALL_BYTES, i0, i1, lambda row: row)
 
-                def one(g, parts=parts, res=res):
-                    a, b = parts[g], parts[g + 1]
-                    if b <= a:
-                        return
-                    lo, hi = max(0, a - R + half - (n_taps - 1)), min(N, b + R + half)
-                    c0 = bisect.bisect_right(self.chunk_bounds, lo) - 1
-                    c1 = bisect.bisect_right(self.chunk_bounds, hi - 1) - 1
-                    keys = list(range(c0, c1 + 1))
-                    cache = self._cache_for(g) if use_cache else 0
-                    cap = max(DETECT_GUESS_MIN, (b - a) * cols.size // DETECT_GUESS_SAMPLES)
-                    out = self._lane_call(self.codec.detect, cache, keys, g, 0, N, a, b, taps, cols, thr, sign_code, ref_code, R, S, cap)
-                    if out[1] > cap and all(v == hip.CHUNK_OK for v in out[0]):      # the buffer was short: once more, with room for all
-                        out = self._lane_call(self.codec.detect, cache, keys, g, 0, N, a, b, taps, cols, thr, sign_code, ref_code, R, S, out[1])
-                    res[g] = (keys,) + tuple(out)
-                self.codec.run_lanes(one, nl)
-                for g in range(nl):
-                    if res[g] is None:
-                        continue
-                    keys, st, n_ev, row, pos, amp = res[g]
-                    for k, v in zip(keys, st):
-                        if v != hip.CHUNK_OK or k not in status:
-                            status[k] = v
-                    found.append((row, pos, amp))
-            self._raise_for(status)
+            def part(a, b):
+                keys = self._chunk_span(max(0, a - R + half - (n_taps - 1)), min(N, b + R + half))
+                cap = max(DETECT_GUESS_MIN, (b - a) * cols.size // DETECT_GUESS_SAMPLES)
+                return keys, (0, N, a, b, taps, cols, thr, sign_code, ref_code, R, S, cap)
+
+            def again(out, args):                                   # the buffer was short: once more, with room for all
+                if out[1] > args[-1] and all(v == hip.CHUNK_OK for v in out[0]):
+                    return args[:-1] + (out[1],)
+            found = [ev[1:] for _, _, ev in self._halo_parts(self.codec.detect, cuts, part, again)]
         row = np.concatenate([f[0] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
         pos = np.concatenate([f[1] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
         amp = np.concatenate([f[2] for f in found]).astype(np.float32) if found else np.zeros(0, np.float32)
@@ -1821,9 +1770,7 @@ class Reader:
         column does not depend on the lanes, calls, pieces, cache residency or the other columns (the summation tree depends on
         (nperseg, step, dtype) only).  Chunks resident in the device cache are read where they lie; the others are decoded in a
         transient workspace and NOT kept.  A damaged chunk among the rows read raises the IOError of Reader[...]."""
-        if not callable(getattr(self.codec, 'welch', None)):
-            raise NotImplementedError("welch needs a codec that computes spectra on the device (HipCodec); %r has none"
-                                      % getattr(self.codec, 'name', self.codec))
+        self._need_codec('welch', 'welch', 'computes spectra')
         if (not isinstance(nperseg, (int, np.integer)) or isinstance(nperseg, bool) or not 16 <= nperseg <= hip.WELCH_MAX_NPERSEG
                 or nperseg & (nperseg - 1)):
             raise ValueError("nperseg must be a power of two in [16, %d], got %r" % (hip.WELCH_MAX_NPERSEG, nperseg))
@@ -1846,14 +1793,8 @@ class Reader:
             scale = 1.0 / float(taper.sum()) ** 2
         else:
             raise ValueError("scaling must be 'density' or 'spectrum', got %r" % (scaling,))
-        try:
-            cdt = np.dtype(dtype)
-        except TypeError:
-            raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
-        if cdt not in (np.dtype(np.float32), np.dtype(np.float64)):
-            raise ValueError("dtype must be float32 or float64, got %r" % (dtype,))
-        i0 = self._validate_index(start, 0)
-        i1 = max(i0, self._validate_index(stop, self.n_samples))
+        cdt = _float_dtype(dtype)
+        i0, i1 = self._row_range(start, stop)
         if i1 - i0 < nperseg:
             raise ValueError("welch: rows [%d, %d) hold fewer than nperseg = %d rows" % (i0, i1, nperseg))
         cols, squeeze = self._stats_channels(channels)
@@ -1865,55 +1806,25 @@ class Reader:
             G = hip.welch_group_segments(step)
             n_groups = -(-n_seg // G)
 
-            def group_rows(g0, g1):                                  # rows read by groups [g0, g1)
-                return i0 + g0 * G * step, i0 + (min(g1 * G, n_seg) - 1) * step + nperseg
-
-            def chunk_span(g0, g1):
-                lo, hi = group_rows(g0, g1)
-                return bisect.bisect_right(self.chunk_bounds, lo) - 1, bisect.bisect_right(self.chunk_bounds, hi - 1) - 1
+            def group_keys(g0, g1):                                  # the chunks of the rows read by groups [g0, g1)
+                return self._chunk_span(i0 + g0 * G * step, i0 + (min(g1 * G, n_seg) - 1) * step + nperseg)
 
             # calls: whole groups, cut where the compressed bytes of their chunks pass WELCH_CALL_BYTES
             cuts, acc = [0], 0
             for g in range(n_groups):
-                c0, c1 = chunk_span(g, g + 1)
-                b = self.chunk_offsets[c1 + 1] - self.chunk_offsets[c0]
+                keys = group_keys(g, g + 1)
+                b = self.chunk_offsets[keys[-1] + 1] - self.chunk_offsets[keys[0]]
                 if acc and acc + b > WELCH_CALL_BYTES:
                     cuts.append(g)
                     acc = 0
                 acc += b
             cuts.append(n_groups)
-            lanes = self._n_lanes()
-            use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
-            status = {}
-            parts_by_group = [None] * n_groups
-            for ga, gb in zip(cuts[:-1], cuts[1:]):
-                # lanes: contiguous runs of the call's groups
-                nl = max(1, min(lanes, gb - ga))
-                runs = [ga + (gb - ga) * g // nl for g in range(nl + 1)]
-                res = [None] * nl
 
-                def one(g, runs=runs, res=res):
-                    a, b = runs[g], runs[g + 1]
-                    if b <= a:
-                        return
-                    c0, c1 = chunk_span(a, b)
-                    keys = list(range(c0, c1 + 1))
-                    cache = self._cache_for(g) if use_cache else 0
-                    st, part = self._lane_call(self.codec.welch, cache, keys, g, i0, a * G, min(b * G, n_seg), nperseg, step, taper, dt, cdt, cols)
-                    res[g] = (keys, st, part)
-                self.codec.run_lanes(one, nl)
-                for g in range(nl):
-                    if res[g] is None:
-                        continue
-                    keys, st, part = res[g]
-                    for k, v in zip(keys, st):
-                        if v != hip.CHUNK_OK or k not in status:
-                            status[k] = v
-                    for j in range(runs[g + 1] - runs[g]):
-                        parts_by_group[runs[g] + j] = part[j]
-            self._raise_for(status)
-            for part in parts_by_group:                              # the range: groups in order, float64, from +0
-                total = total + part
+            def part(a, b):
+                return group_keys(a, b), (i0, a * G, min(b * G, n_seg), nperseg, step, taper, dt, cdt, cols)
+            for _, _, (sums,) in self._halo_parts(self.codec.welch, cuts, part):
+                for group in sums:                                   # the range: groups in order, float64, from +0
+                    total = total + group
         psd = total * scale
         psd[1:-1] *= 2.0
         psd /= n_seg
@@ -1936,16 +1847,9 @@ class Reader:
         raw-moment formula loses relative accuracy on float data whose mean is large compared with its spread (no centred two-pass
         form).  Chunks resident in the device cache are read where they lie; the others are decoded in a transient workspace and NOT
         kept.  A damaged chunk raises the IOError of Reader[...]."""
-        if not callable(getattr(self.codec, 'gram', None)):
-            raise NotImplementedError("cov needs a codec that forms Gram matrices on the device (HipCodec); %r has none"
-                                      % getattr(self.codec, 'name', self.codec))
-        i0 = self._validate_index(start, 0)
-        i1 = max(i0, self._validate_index(stop, self.n_samples))
-        if window is None:
-            window = max(i1 - i0, 1)
-        if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1:
-            raise ValueError("window must be an int >= 1 or None, got %r" % (window,))
-        window = int(window)
+        self._need_codec('cov', 'gram', 'forms Gram matrices')
+        i0, i1 = self._row_range(start, stop)
+        window = _window_rows(window, i0, i1)
         if not isinstance(ddof, (int, np.integer)) or isinstance(ddof, bool) or ddof < 0:
             raise ValueError("ddof must be an int >= 0, got %r" % (ddof,))
         ddof = int(ddof)
@@ -1974,39 +1878,17 @@ class Reader:
                 a = cuts[-1]
                 b = int(np.searchsorted(cum, cum[a] + GRAM_CALL_BYTES, 'right')) - 1
                 cuts.append(min(n_groups, a + per_call, max(b, a + 1)))
-            lanes = self._n_lanes()
-            use_cache = getattr(self.codec, 'device_cache', False) and self._dev_cache_bytes > 0
-            status = {}
-            for ga, gb in zip(cuts[:-1], cuts[1:]):
-                # lanes: contiguous runs of the call's groups
-                nl = max(1, min(lanes, gb - ga))
-                runs = [ga + (gb - ga) * j // nl for j in range(nl + 1)]
-                res = [None] * nl
 
-                def one(j, runs=runs, res=res):
-                    a, b = runs[j], runs[j + 1]
-                    if b <= a:
-                        return
-                    keys = list(range(int(gc0[a]), int(gc1[b - 1]) + 1))
-                    cache = self._cache_for(j) if use_cache else 0
-                    res[j] = (keys,) + tuple(self._lane_call(self.codec.gram, cache, keys, j, i0, i1, window, a, b, cols))
-                self.codec.run_lanes(one, nl)
-                for j in range(nl):                                 # groups in order: the float sums are the same every time
-                    if res[j] is None:
-                        continue
-                    keys, st, gp, sp = res[j]
-                    for k, v in zip(keys, st):
-                        if v != hip.CHUNK_OK or k not in status:
-                            status[k] = v
-                    a, b = runs[j], runs[j + 1]
-                    if K == 1:
-                        gram[a:b] += gp
-                        sm[a:b] += sp
-                    else:
-                        for z in range(b - a):
-                            gram[(a + z) // K] += gp[z]
-                            sm[(a + z) // K] += sp[z]
-            self._raise_for(status)
+            def part(a, b):
+                return list(range(int(gc0[a]), int(gc1[b - 1]) + 1)), (i0, i1, window, a, b, cols)
+            for a, b, (gp, sp) in self._halo_parts(self.codec.gram, cuts, part):      # groups in order: the float sums are the same every time
+                if K == 1:
+                    gram[a:b] += gp
+                    sm[a:b] += sp
+                else:
+                    for z in range(b - a):
+                        gram[(a + z) // K] += gp[z]
+                        sm[(a + z) // K] += sp[z]
         with np.errstate(invalid='ignore', divide='ignore'):
             sf = sm.astype(np.float64)
             mean = sf / cnt[:, None]

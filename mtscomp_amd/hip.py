@@ -96,33 +96,21 @@ def lib():
                                         C.c_long, ip]
     L.mts_cache_read_slices_leading.argtypes = [C.c_long, C.c_int, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, lp, vp, lp,
                                                 C.c_long, ip]
-    L.mts_window_stats.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long,
-                                   C.c_long, C.c_int, ip, vp, vp, vp, vp, lp, ip]
-    L.mts_dev_window_stats.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
-                                       C.c_int, ip, vp, vp, vp, vp, lp, ip]
-    dp = C.POINTER(C.c_double)
-    L.mts_decimate.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
-                               C.c_long, C.c_int, C.c_int, dp, C.c_int, C.c_int, ip, vp, ip]
-    L.mts_dev_decimate.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
-                                   C.c_int, C.c_int, dp, C.c_int, C.c_int, ip, vp, ip]
-    fp = C.POINTER(C.c_float)
-    L.mts_detect.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
-                             C.c_int, dp, C.c_int, ip, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, vp, vp, vp, lp, ip]
-    L.mts_dev_detect.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
-                                 C.c_int, dp, C.c_int, ip, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, vp, vp, vp, lp, ip]
-    L.mts_welch.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int,
-                            C.c_long, dp, C.c_int, C.c_int, C.c_int, ip, vp, ip]
-    L.mts_dev_welch.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int,
-                                C.c_long, dp, C.c_int, C.c_int, C.c_int, ip, vp, ip]
-    L.mts_gram.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
-                           C.c_long, C.c_int, ip, vp, vp, ip]
-    L.mts_dev_gram.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long,
-                               C.c_long, C.c_int, ip, vp, vp, ip]
-    up = C.POINTER(C.c_ulonglong)
-    L.mts_rank_hist.argtypes = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
-                                C.c_int, ip, C.c_int, dp, up, ip, C.POINTER(C.c_uint), up, up, lp, ip]
-    L.mts_dev_rank_hist.argtypes = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
-                                    C.c_int, ip, C.c_int, dp, up, ip, vp, vp, vp, lp, ip]
+    # the device reductions: the chunk table (host entry: device, cache, n, keys, row0, cdata, offs, lens, rows, n_channels, itemsize,
+    # flags; device entry: device, stream, cbuf, offs, lens, row0, rows, n, n_channels, itemsize, flags), the op's own arguments, the
+    # results and the status
+    host = [C.c_int, C.c_long, C.c_int, lp, lp, vp, lp, lp, lp, C.c_int, C.c_int, C.c_int]
+    dev = [C.c_int, vp, vp, lp, lp, lp, lp, C.c_int, C.c_int, C.c_int, C.c_int]
+    ci, cl, dp, fp, up = C.c_int, C.c_long, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong)
+    for name, mid, tail, dev_tail in (
+            ('window_stats', [cl, cl, cl, ci, ip], [vp, vp, vp, vp, lp, ip], None),
+            ('decimate', [cl, cl, cl, cl, ci, ci, dp, ci, ci, ip], [vp, ip], None),
+            ('detect', [cl, cl, cl, cl, ci, dp, ci, ip, fp, ci, ci, ci, ci, cl], [vp, vp, vp, lp, ip], None),
+            ('welch', [cl, cl, cl, ci, cl, dp, ci, ci, ci, ip], [vp, ip], None),
+            ('gram', [cl, cl, cl, cl, cl, ci, ip], [vp, vp, ip], None),
+            ('rank_hist', [cl, cl, cl, ci, ip, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip], [vp, vp, vp, lp, ip])):
+        getattr(L, 'mts_' + name).argtypes = host + mid + tail
+        getattr(L, 'mts_dev_' + name).argtypes = dev + mid + (dev_tail or tail)
     L.mts_release.restype = None
     _lib = L
     return L
@@ -344,13 +332,81 @@ def cache_read_slices(cache_id, keys, cdata, offs, lens, n_rows, n_channels, dty
 
 
 # ------------------------------------------------------------------------------------------------
-# per-window statistics (an extension: the reference has no such call)
+# the device reductions (extensions: the reference has no such calls).  Every op has a host entry mts_<op> (compressed bytes in host
+# memory, resident chunks in a decoded-chunk cache) and a device entry mts_dev_<op> (a DevBuffer of compressed chunks).  Both take the
+# chunk table, then the op's own arguments, then the results and the chunks' status: each of the three is marshalled in one place.
 # ------------------------------------------------------------------------------------------------
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ullp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+
+
+def _cols32(cols):
+    return np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+
+
 def stats_flags(flags, dtype):
-    """flags as mts_window_stats wants them: the float bit and the unsigned bit come from the dtype."""
+    """flags as the reductions want them: the float bit and the unsigned bit come from the dtype."""
     return _dflags(flags, dtype) | (FLAG_UNSIGNED if np.dtype(dtype).kind == 'u' else 0)
 
 
+def _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags):
+    """The chunk table of a host entry: chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])), their bytes at offs / lens of cdata.
+    cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).
+    -> (the leading arguments of mts_<op>, n, the status array to pass last)."""
+    dtype = check_dtype(dtype)
+    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
+    n = int(rows.size)
+    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
+    assert not n or int((offs + lens).max()) <= cdata.size        # (only the chunks' own bytes are copied: no padding needed here)
+    head = (int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
+            dtype.itemsize, stats_flags(flags, dtype))
+    return head, n, np.zeros(max(n, 1), dtype=np.int32)
+
+
+def _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags):
+    """The chunk table of a device entry: compressed chunks at offs / lens of the DevBuffer cbuf.  -> as _host_chunks, for
+    mts_dev_<op>."""
+    dtype = check_dtype(dtype)
+    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
+    n = int(rows.size)
+    head = (cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), n, int(n_channels), dtype.itemsize,
+            stats_flags(flags, dtype))
+    return head, n, np.zeros(max(n, 1), dtype=np.int32)
+
+
+def _status(status, n):
+    return [int(x) for x in status[:n]]
+
+
+def _dev_results(out, device, sizes):
+    """Room for result arrays of `sizes` bytes in the DevBuffer `out`, each at a 256-byte aligned offset, 256 spare bytes behind
+    the last: `out` is made when None or too small.  -> (out, the pointers to hand to the library, the offsets)."""
+    at = [0]
+    for b in sizes[:-1]:
+        at.append(at[-1] + (int(b) + 255) // 256 * 256)
+    need = at[-1] + int(sizes[-1]) + 256
+    if out is None or out.nbytes < need:
+        out = DevBuffer(need, device=device)
+    return out, [out.at(o) for o in at], at
+
+
+def _dev_fetch(out, at, arrays):
+    """The result arrays copied out of the DevBuffer `out`, where _dev_results put them."""
+    for a, o in zip(arrays, at):
+        if a.nbytes:
+            _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(o), a.nbytes, 1), 'mts_dev_copy')
+    return arrays
+
+
+# -- per-window statistics
 def stats_exact(dtype):
     """1- and 2-byte integers: the sum of squares is the exact uint64 sum (converted to float64 once, by the caller)."""
     dtype = np.dtype(dtype)
@@ -363,63 +419,43 @@ def stats_dtypes(dtype):
     return dtype, np.dtype(np.float64 if dtype.kind == 'f' else np.int64), np.dtype(np.uint64 if stats_exact(dtype) else np.float64)
 
 
-def _stats_outputs(n_windows, n_cols, dtype):
-    t, s, q = stats_dtypes(dtype)
-    shape = (int(n_windows), int(n_cols))
-    return np.empty(shape, t), np.empty(shape, t), np.empty(shape, s), np.empty(shape, q), np.zeros(max(int(n_windows), 1), np.int64)
-
-
 def _n_windows(row_begin, row_end, window_rows):
     return max(0, -(-(int(row_end) - int(row_begin)) // int(window_rows))) if int(window_rows) >= 1 else 0
+
+
+def _stats_args(dtype, row_begin, row_end, window_rows, cols):
+    """-> (the op's own arguments of mts_window_stats, the arrays min, max, sum, sumsq, the count array, n_windows)."""
+    cols = _cols32(cols)
+    nw = _n_windows(row_begin, row_end, window_rows)
+    t, s, q = stats_dtypes(dtype)
+    shape = (nw, int(cols.size))
+    res = (np.empty(shape, t), np.empty(shape, t), np.empty(shape, s), np.empty(shape, q))
+    return (int(row_begin), int(row_end), int(window_rows), int(cols.size), _ip(cols)), res, np.zeros(max(nw, 1), np.int64), nw
 
 
 def window_stats(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, device=0):
     """mts_window_stats: per-window statistics of the chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])).  cache_id 0: no cache,
     every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list,
     Bunch-like dict min, max, sum, sumsq, count) -- the partials of these chunks: sumsq is uint64 for 1/2-byte integers."""
-    dtype = check_dtype(dtype)
-    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
-    n = int(rows.size)
-    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
-    assert not n or int((offs + lens).max()) <= cdata.size        # (only the chunks' own bytes are copied: no padding needed here)
-    nw = _n_windows(row_begin, row_end, window_rows)
-    mn, mx, sm, sq, cnt = _stats_outputs(nw, cols.size, dtype)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-    _check(lib().mts_window_stats(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows),
-                                  int(n_channels), dtype.itemsize, stats_flags(flags, dtype), int(row_begin), int(row_end), int(window_rows),
-                                  int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)), _ptr(mn), _ptr(mx), _ptr(sm), _ptr(sq), _lp(cnt),
-                                  status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_window_stats')
-    return [int(x) for x in status[:n]], dict(min=mn, max=mx, sum=sm, sumsq=sq, count=cnt[:nw])
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, res, cnt, nw = _stats_args(dtype, row_begin, row_end, window_rows, cols)
+    _check(lib().mts_window_stats(*head, *mid, *map(_ptr, res), _lp(cnt), _ip(status)), 'mts_window_stats')
+    return _status(status, n), dict(zip(('min', 'max', 'sum', 'sumsq'), res), count=cnt[:nw])
 
 
 def dev_window_stats(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, out=None):
     """mts_dev_window_stats on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the four result arrays
     (made when None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, dict of numpy
     arrays as window_stats, out)."""
-    dtype = check_dtype(dtype)
-    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
-    nw = _n_windows(row_begin, row_end, window_rows)
-    mn, mx, sm, sq, cnt = _stats_outputs(nw, cols.size, dtype)
-    parts = [a.nbytes for a in (mn, mx, sm, sq)]
-    at = np.concatenate(([0], np.cumsum([(b + 255) // 256 * 256 for b in parts])))
-    if out is None or out.nbytes < int(at[-1]) + 256:
-        out = DevBuffer(int(at[-1]) + 256, device=cbuf.device)
-    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
-    _check(lib().mts_dev_window_stats(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
-                                      dtype.itemsize, stats_flags(flags, dtype), int(row_begin), int(row_end), int(window_rows), int(cols.size),
-                                      cols.ctypes.data_as(C.POINTER(C.c_int)), out.at(int(at[0])), out.at(int(at[1])), out.at(int(at[2])),
-                                      out.at(int(at[3])), _lp(cnt), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_window_stats')
-    for a, o in zip((mn, mx, sm, sq), at[:4]):
-        if a.nbytes:
-            _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(int(o)), a.nbytes, 1), 'mts_dev_copy')
-    return [int(x) for x in status[:rows.size]], dict(min=mn, max=mx, sum=sm, sumsq=sq, count=cnt[:nw]), out
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, res, cnt, nw = _stats_args(dtype, row_begin, row_end, window_rows, cols)
+    out, ptrs, at = _dev_results(out, cbuf.device, [a.nbytes for a in res])
+    _check(lib().mts_dev_window_stats(*head, *mid, *ptrs, _lp(cnt), _ip(status)), 'mts_dev_window_stats')
+    _dev_fetch(out, at, res)
+    return _status(status, n), dict(zip(('min', 'max', 'sum', 'sumsq'), res), count=cnt[:nw]), out
 
 
-# ------------------------------------------------------------------------------------------------
-# order statistics: one round of a radix select (an extension: the reference has no such call)
-# ------------------------------------------------------------------------------------------------
+# -- order statistics: one round of a radix select
 RANK_BITS = 8                # digit width (MTS_RANK_BITS)
 RANK_SELECTORS = 2           # selectors per (window, column) cell and call (MTS_RANK_SELECTORS)
 RANK_KEY_NONE = np.uint64(0xFFFFFFFFFFFFFFFF)      # kmin of a selector without candidates (its kmax is 0)
@@ -493,21 +529,21 @@ def rank_bit_length(x):
     return d + (x != 0).astype(np.uint64)
 
 
-def _rank_args(n_windows, n_cols, mode, center, sel_prefix, sel_shift):
-    shape = (int(n_windows), RANK_SELECTORS, int(n_cols))
+def _rank_args(row_begin, row_end, window_rows, cols, mode, center, sel_prefix, sel_shift):
+    """-> (the op's own arguments of mts_rank_hist, the arrays hist, kmin, kmax, the count array, n_windows)."""
+    cols = _cols32(cols)
+    nw = _n_windows(row_begin, row_end, window_rows)
+    shape = (nw, RANK_SELECTORS, int(cols.size))
     pre = np.ascontiguousarray(sel_prefix, dtype=np.uint64)
     shf = np.ascontiguousarray(sel_shift, dtype=np.int32)
     assert pre.shape == shape and shf.shape == shape, 'selectors must be (n_windows, %d, n_cols)' % RANK_SELECTORS
     cen = None
     if mode:
-        cen = np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if center is None else center, dtype=np.float64), (shape[0], shape[2])))
-    hist = np.zeros((shape[0], RANK_SELECTORS, 1 << RANK_BITS, shape[2]), np.uint32)
-    kmin, kmax = np.full(shape, RANK_KEY_NONE, np.uint64), np.zeros(shape, np.uint64)
-    return pre, shf, cen, hist, kmin, kmax, np.zeros(max(shape[0], 1), np.int64)
-
-
-def _ullp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_ulonglong))
+        cen = _dp(np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if center is None else center, dtype=np.float64), (shape[0], shape[2]))))
+    res = (np.zeros((shape[0], RANK_SELECTORS, 1 << RANK_BITS, shape[2]), np.uint32), np.full(shape, RANK_KEY_NONE, np.uint64),
+           np.zeros(shape, np.uint64))
+    mid = (int(row_begin), int(row_end), int(window_rows), int(cols.size), _ip(cols), int(mode), cen, _ullp(pre), _ip(shf))
+    return mid, res, np.zeros(max(nw, 1), np.int64), nw
 
 
 def rank_hist(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, mode, center,
@@ -518,22 +554,11 @@ def rank_hist(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype
     with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, dict hist (n_windows, 2,
     256, n_cols) uint32, kmin, kmax (n_windows, 2, n_cols) uint64, count) -- the partials of these chunks: integers, to be added
     (hist, count) and combined with minimum / maximum (kmin, kmax) in any order."""
-    dtype = check_dtype(dtype)
-    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
-    n = int(rows.size)
-    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
-    assert not n or int((offs + lens).max()) <= cdata.size
-    nw = _n_windows(row_begin, row_end, window_rows)
-    pre, shf, cen, hist, kmin, kmax, cnt = _rank_args(nw, cols.size, mode, center, sel_prefix, sel_shift)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-    _check(lib().mts_rank_hist(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows),
-                               int(n_channels), dtype.itemsize, stats_flags(flags, dtype), int(row_begin), int(row_end), int(window_rows),
-                               int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)), int(mode),
-                               cen.ctypes.data_as(C.POINTER(C.c_double)) if cen is not None else None, _ullp(pre),
-                               shf.ctypes.data_as(C.POINTER(C.c_int)), hist.ctypes.data_as(C.POINTER(C.c_uint)), _ullp(kmin), _ullp(kmax),
-                               _lp(cnt), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_rank_hist')
-    return [int(x) for x in status[:n]], dict(hist=hist, kmin=kmin, kmax=kmax, count=cnt[:nw])
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, (hist, kmin, kmax), cnt, nw = _rank_args(row_begin, row_end, window_rows, cols, mode, center, sel_prefix, sel_shift)
+    _check(lib().mts_rank_hist(*head, *mid, hist.ctypes.data_as(C.POINTER(C.c_uint)), _ullp(kmin), _ullp(kmax), _lp(cnt), _ip(status)),
+           'mts_rank_hist')
+    return _status(status, n), dict(hist=hist, kmin=kmin, kmax=kmax, count=cnt[:nw])
 
 
 def dev_rank_hist(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_begin, row_end, window_rows, cols, mode, center, sel_prefix,
@@ -541,40 +566,27 @@ def dev_rank_hist(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_
     """mts_dev_rank_hist on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the three result arrays (made
     when None; returned so that a caller timing repeated calls can pass it again); fetch=False leaves them there.  Returns (status
     list, dict as rank_hist, out)."""
-    dtype = check_dtype(dtype)
-    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
-    nw = _n_windows(row_begin, row_end, window_rows)
-    pre, shf, cen, hist, kmin, kmax, cnt = _rank_args(nw, cols.size, mode, center, sel_prefix, sel_shift)
-    parts = [a.nbytes for a in (hist, kmin, kmax)]
-    at = np.concatenate(([0], np.cumsum([(b + 255) // 256 * 256 for b in parts])))
-    if out is None or out.nbytes < int(at[-1]) + 256:
-        out = DevBuffer(int(at[-1]) + 256, device=cbuf.device)
-    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
-    _check(lib().mts_dev_rank_hist(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
-                                   dtype.itemsize, stats_flags(flags, dtype), int(row_begin), int(row_end), int(window_rows), int(cols.size),
-                                   cols.ctypes.data_as(C.POINTER(C.c_int)), int(mode),
-                                   cen.ctypes.data_as(C.POINTER(C.c_double)) if cen is not None else None, _ullp(pre),
-                                   shf.ctypes.data_as(C.POINTER(C.c_int)), out.at(int(at[0])), out.at(int(at[1])), out.at(int(at[2])),
-                                   _lp(cnt), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_rank_hist')
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, res, cnt, nw = _rank_args(row_begin, row_end, window_rows, cols, mode, center, sel_prefix, sel_shift)
+    out, ptrs, at = _dev_results(out, cbuf.device, [a.nbytes for a in res])
+    _check(lib().mts_dev_rank_hist(*head, *mid, *ptrs, _lp(cnt), _ip(status)), 'mts_dev_rank_hist')
     if fetch:
-        for a, o in zip((hist, kmin, kmax), at[:3]):
-            if a.nbytes:
-                _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(int(o)), a.nbytes, 1), 'mts_dev_copy')
-    return [int(x) for x in status[:rows.size]], dict(hist=hist, kmin=kmin, kmax=kmax, count=cnt[:nw]), out
+        _dev_fetch(out, at, res)
+    return _status(status, n), dict(zip(('hist', 'kmin', 'kmax'), res), count=cnt[:nw]), out
 
 
-# ------------------------------------------------------------------------------------------------
-# FIR low-pass + decimation (an extension: the reference has no such call)
-# ------------------------------------------------------------------------------------------------
+# -- FIR low-pass + decimation
 DECIMATE_MAX_TAPS = 8192
 
 
-def _dec_args(taps, out_dtype, cols):
+def _dec_args(valid_begin, valid_end, first_row, n_out, q, taps, out_dtype, cols):
+    """-> (the op's own arguments of mts_decimate, the shape of the result, its dtype)."""
     taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).ravel())
     out_dtype = np.dtype(out_dtype)
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
-    return taps, out_dtype, cols
+    cols = _cols32(cols)
+    mid = (int(valid_begin), int(valid_end), int(first_row), int(n_out), int(q), int(taps.size), _dp(taps), out_dtype.itemsize,
+           int(cols.size), _ip(cols))
+    return mid, (max(int(n_out), 0), int(cols.size)), out_dtype
 
 
 def decimate(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row, n_out, q, taps,
@@ -582,58 +594,41 @@ def decimate(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype,
     """mts_decimate: y[k, c] = sum_j taps[j] * x[first_row + k * q - j, cols[c]] (x = 0 outside [valid_begin, valid_end)) for k < n_out,
     from the adjacent chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])).  cache_id 0: no cache, every chunk comes with its
     bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, (n_out, n_cols) out_dtype)."""
-    dtype = check_dtype(dtype)
-    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
-    taps, out_dtype, cols = _dec_args(taps, out_dtype, cols)
-    n = int(rows.size)
-    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
-    assert not n or int((offs + lens).max()) <= cdata.size
-    out = np.empty((max(int(n_out), 0), cols.size), out_dtype)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-    _check(lib().mts_decimate(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
-                              dtype.itemsize, stats_flags(flags, dtype), int(valid_begin), int(valid_end), int(first_row), int(n_out), int(q),
-                              int(taps.size), taps.ctypes.data_as(C.POINTER(C.c_double)), out_dtype.itemsize, int(cols.size),
-                              cols.ctypes.data_as(C.POINTER(C.c_int)), _ptr(out), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_decimate')
-    return [int(x) for x in status[:n]], out
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, shape, out_dtype = _dec_args(valid_begin, valid_end, first_row, n_out, q, taps, out_dtype, cols)
+    out = np.empty(shape, out_dtype)
+    _check(lib().mts_decimate(*head, *mid, _ptr(out), _ip(status)), 'mts_decimate')
+    return _status(status, n), out
 
 
 def dev_decimate(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row, n_out, q, taps, out_dtype, cols,
                  out=None, download=True):
     """mts_dev_decimate on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the result (made when None;
     returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
-    dtype = check_dtype(dtype)
-    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
-    taps, out_dtype, cols = _dec_args(taps, out_dtype, cols)
-    nbytes = max(int(n_out), 0) * cols.size * out_dtype.itemsize
-    if out is None or out.nbytes < nbytes + 256:
-        out = DevBuffer(nbytes + 256, device=cbuf.device)
-    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
-    _check(lib().mts_dev_decimate(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
-                                  dtype.itemsize, stats_flags(flags, dtype), int(valid_begin), int(valid_end), int(first_row), int(n_out), int(q),
-                                  int(taps.size), taps.ctypes.data_as(C.POINTER(C.c_double)), out_dtype.itemsize, int(cols.size),
-                                  cols.ctypes.data_as(C.POINTER(C.c_int)), out.at(), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_decimate')
-    res = None
-    if download:
-        res = np.empty((max(int(n_out), 0), cols.size), out_dtype)
-        if res.nbytes:
-            _check(lib().mts_dev_copy(out.device, None, _ptr(res), out.at(), res.nbytes, 1), 'mts_dev_copy')
-    return [int(x) for x in status[:rows.size]], res, out
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, shape, out_dtype = _dec_args(valid_begin, valid_end, first_row, n_out, q, taps, out_dtype, cols)
+    out, ptrs, at = _dev_results(out, cbuf.device, [shape[0] * shape[1] * out_dtype.itemsize])
+    _check(lib().mts_dev_decimate(*head, *mid, *ptrs, _ip(status)), 'mts_dev_decimate')
+    res = _dev_fetch(out, at, [np.empty(shape, out_dtype)])[0] if download else None
+    return _status(status, n), res, out
 
 
-# ------------------------------------------------------------------------------------------------
-# Threshold-crossing peak detection (an extension: the reference has no such call)
-# ------------------------------------------------------------------------------------------------
+# -- threshold-crossing peak detection
 DETECT_MAX_EXCLUDE = 255
 DETECT_MAX_SPREAD = 32
 DETECT_MAX_REF_COLS = 1024
 DETECT_SIGNS = {'neg': 0, 'pos': 1, 'both': 2}
+_DETECT_DTYPES = (np.int64, np.int32, np.float32)       # row, pos, amp of an event
 
 
-def _det_args(taps, cols, threshold):
+def _det_args(valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign, reference, exclude_rows, exclude_cols, max_events):
+    """-> (the op's own arguments of mts_detect, the events the buffers hold, the array for n_events)."""
     taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).ravel())
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
+    cols = _cols32(cols)
     thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float32), (cols.size,)))
-    return taps, cols, thr
+    mid = (int(valid_begin), int(valid_end), int(row_begin), int(row_end), int(taps.size), _dp(taps), int(cols.size), _ip(cols),
+           thr.ctypes.data_as(C.POINTER(C.c_float)), int(sign), int(reference), int(exclude_rows), int(exclude_cols), int(max_events))
+    return mid, max(int(max_events), 0), np.zeros(1, np.int64)
 
 
 def detect(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols,
@@ -641,24 +636,13 @@ def detect(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, f
     """mts_detect: the events of rows [row_begin, row_end) (include/mtscomp_hip.h) from the adjacent chunks `keys`.  sign 0 / 1 / 2,
     reference 0 / 1.  cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError
     E_MISS).  Returns (status list, n_events, row int64, pos int32, amp float32): the first min(n_events, max_events) events."""
-    dtype = check_dtype(dtype)
-    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
-    taps, cols, thr = _det_args(taps, cols, threshold)
-    n = int(rows.size)
-    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
-    assert not n or int((offs + lens).max()) <= cdata.size
-    cap = max(int(max_events), 0)
-    o_row, o_pos, o_amp = np.empty(cap, np.int64), np.empty(cap, np.int32), np.empty(cap, np.float32)
-    n_ev = np.zeros(1, np.int64)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-    _check(lib().mts_detect(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
-                            dtype.itemsize, stats_flags(flags, dtype), int(valid_begin), int(valid_end), int(row_begin), int(row_end),
-                            int(taps.size), taps.ctypes.data_as(C.POINTER(C.c_double)), int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)),
-                            thr.ctypes.data_as(C.POINTER(C.c_float)), int(sign), int(reference), int(exclude_rows), int(exclude_cols),
-                            int(max_events), _ptr(o_row) if cap else None, _ptr(o_pos) if cap else None, _ptr(o_amp) if cap else None,
-                            _lp(n_ev), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_detect')
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, cap, n_ev = _det_args(valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign, reference, exclude_rows, exclude_cols,
+                               max_events)
+    res = [np.empty(cap, t) for t in _DETECT_DTYPES]
+    _check(lib().mts_detect(*head, *mid, *(_ptr(a) if cap else None for a in res), _lp(n_ev), _ip(status)), 'mts_detect')
     k = min(int(n_ev[0]), cap)
-    return [int(x) for x in status[:n]], int(n_ev[0]), o_row[:k], o_pos[:k], o_amp[:k]
+    return (_status(status, n), int(n_ev[0])) + tuple(a[:k] for a in res)
 
 
 def dev_detect(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign,
@@ -666,36 +650,18 @@ def dev_detect(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_b
     """mts_dev_detect on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the three event arrays (made when
     None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, n_events, (row, pos, amp) or None,
     out)."""
-    dtype = check_dtype(dtype)
-    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
-    taps, cols, thr = _det_args(taps, cols, threshold)
-    cap = max(int(max_events), 0)
-    at = [0, (8 * cap + 255) // 256 * 256]
-    at.append(at[1] + (4 * cap + 255) // 256 * 256)
-    at.append(at[2] + (4 * cap + 255) // 256 * 256)
-    if out is None or out.nbytes < at[3] + 256:
-        out = DevBuffer(at[3] + 256, device=cbuf.device)
-    n_ev = np.zeros(1, np.int64)
-    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
-    _check(lib().mts_dev_detect(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
-                                dtype.itemsize, stats_flags(flags, dtype), int(valid_begin), int(valid_end), int(row_begin), int(row_end),
-                                int(taps.size), taps.ctypes.data_as(C.POINTER(C.c_double)), int(cols.size),
-                                cols.ctypes.data_as(C.POINTER(C.c_int)), thr.ctypes.data_as(C.POINTER(C.c_float)), int(sign), int(reference),
-                                int(exclude_rows), int(exclude_cols), int(max_events), out.at(at[0]), out.at(at[1]), out.at(at[2]), _lp(n_ev),
-                                status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_detect')
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, cap, n_ev = _det_args(valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign, reference, exclude_rows, exclude_cols,
+                               max_events)
+    out, ptrs, at = _dev_results(out, cbuf.device, [cap * np.dtype(t).itemsize for t in _DETECT_DTYPES])
+    _check(lib().mts_dev_detect(*head, *mid, *ptrs, _lp(n_ev), _ip(status)), 'mts_dev_detect')
     res = None
     if download:
-        k = min(int(n_ev[0]), cap)
-        res = (np.empty(k, np.int64), np.empty(k, np.int32), np.empty(k, np.float32))
-        for a, o in zip(res, at[:3]):
-            if a.nbytes:
-                _check(lib().mts_dev_copy(out.device, None, _ptr(a), out.at(o), a.nbytes, 1), 'mts_dev_copy')
-    return [int(x) for x in status[:rows.size]], int(n_ev[0]), res, out
+        res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _DETECT_DTYPES]))
+    return _status(status, n), int(n_ev[0]), res, out
 
 
-# ------------------------------------------------------------------------------------------------
-# Welch power spectral density (an extension: the reference has no such call)
-# ------------------------------------------------------------------------------------------------
+# -- Welch power spectral density
 WELCH_MAX_NPERSEG = 16384
 WELCH_BLOCK_SEGMENTS = 32              # B: segments summed in order on the device (MTS_WELCH_BLOCK_SEGMENTS)
 WELCH_GROUP_ROWS = 1 << 20             # G: the smallest multiple of B segments with G * step >= this (MTS_WELCH_GROUP_ROWS)
@@ -707,15 +673,14 @@ def welch_group_segments(step):
     return b * -(-WELCH_GROUP_ROWS // (int(step) * b))
 
 
-def _welch_args(taper, compute_dtype, cols):
+def _welch_args(row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, compute_dtype, cols):
+    """-> (the op's own arguments of mts_welch, the shape of the float64 group sums)."""
     taper = np.ascontiguousarray(np.asarray(taper, dtype=np.float64).ravel())
-    csize = np.dtype(compute_dtype).itemsize
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
-    return taper, csize, cols
-
-
-def _welch_groups(seg_begin, seg_end, step):
-    return -(-(int(seg_end) - int(seg_begin)) // welch_group_segments(step))
+    cols = _cols32(cols)
+    mid = (int(row_seg0), int(seg_begin), int(seg_end), int(nperseg), int(step), _dp(taper), int(bool(detrend)),
+           np.dtype(compute_dtype).itemsize, int(cols.size), _ip(cols))
+    n_groups = -(-(int(seg_end) - int(seg_begin)) // welch_group_segments(step))
+    return mid, (max(n_groups, 0), int(nperseg) // 2 + 1, int(cols.size))
 
 
 def welch(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg, step, taper,
@@ -724,48 +689,26 @@ def welch(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, fl
     covering file rows [row_seg0 + s * step, + nperseg), from the adjacent chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])).
     cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).
     Returns (status list, partials)."""
-    dtype = check_dtype(dtype)
-    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
-    taper, csize, cols = _welch_args(taper, compute_dtype, cols)
-    n = int(rows.size)
-    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
-    assert not n or int((offs + lens).max()) <= cdata.size
-    out = np.empty((max(_welch_groups(seg_begin, seg_end, step), 0), int(nperseg) // 2 + 1, cols.size), np.float64)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-    _check(lib().mts_welch(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
-                           dtype.itemsize, stats_flags(flags, dtype), int(row_seg0), int(seg_begin), int(seg_end), int(nperseg), int(step),
-                           taper.ctypes.data_as(C.POINTER(C.c_double)), int(bool(detrend)), csize, int(cols.size),
-                           cols.ctypes.data_as(C.POINTER(C.c_int)), _ptr(out), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_welch')
-    return [int(x) for x in status[:n]], out
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, shape = _welch_args(row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, compute_dtype, cols)
+    out = np.empty(shape, np.float64)
+    _check(lib().mts_welch(*head, *mid, _ptr(out), _ip(status)), 'mts_welch')
+    return _status(status, n), out
 
 
 def dev_welch(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend,
               compute_dtype, cols, out=None, download=True):
     """mts_dev_welch on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the partials (made when None;
     returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
-    dtype = check_dtype(dtype)
-    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
-    taper, csize, cols = _welch_args(taper, compute_dtype, cols)
-    shape = (max(_welch_groups(seg_begin, seg_end, step), 0), int(nperseg) // 2 + 1, cols.size)
-    nbytes = 8 * shape[0] * shape[1] * shape[2]
-    if out is None or out.nbytes < nbytes + 256:
-        out = DevBuffer(nbytes + 256, device=cbuf.device)
-    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
-    _check(lib().mts_dev_welch(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
-                               dtype.itemsize, stats_flags(flags, dtype), int(row_seg0), int(seg_begin), int(seg_end), int(nperseg), int(step),
-                               taper.ctypes.data_as(C.POINTER(C.c_double)), int(bool(detrend)), csize, int(cols.size),
-                               cols.ctypes.data_as(C.POINTER(C.c_int)), out.at(), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_welch')
-    res = None
-    if download:
-        res = np.empty(shape, np.float64)
-        if res.nbytes:
-            _check(lib().mts_dev_copy(out.device, None, _ptr(res), out.at(), res.nbytes, 1), 'mts_dev_copy')
-    return [int(x) for x in status[:rows.size]], res, out
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, shape = _welch_args(row_seg0, seg_begin, seg_end, nperseg, step, taper, detrend, compute_dtype, cols)
+    out, ptrs, at = _dev_results(out, cbuf.device, [8 * shape[0] * shape[1] * shape[2]])
+    _check(lib().mts_dev_welch(*head, *mid, *ptrs, _ip(status)), 'mts_dev_welch')
+    res = _dev_fetch(out, at, [np.empty(shape, np.float64)])[0] if download else None
+    return _status(status, n), res, out
 
 
-# ------------------------------------------------------------------------------------------------
-# channel x channel Gram matrices (an extension: the reference has no such call)
-# ------------------------------------------------------------------------------------------------
+# -- channel x channel Gram matrices
 GRAM_GROUP_ROWS = 1 << 20              # rows per group of a window, aligned to its start (MTS_GRAM_GROUP_ROWS)
 GRAM_SLAB_ROWS = 4096                  # rows per slab of a group, aligned to its start (MTS_GRAM_SLAB_ROWS)
 GRAM_MAX_COLS = 16384                  # MTS_GRAM_MAX_COLS
@@ -801,9 +744,13 @@ def gram_group_rows(range_begin, range_end, window_rows, g):
     return lo, min(lo + GRAM_GROUP_ROWS, w0 + w, int(range_end))
 
 
-def _gram_out(n_groups, n_cols, dtype, alloc=np.empty):
+def _gram_args(dtype, range_begin, range_end, window_rows, group_begin, group_end, cols):
+    """-> (the op's own arguments of mts_gram, the shapes and dtypes of the Gram entries and the sums)."""
+    cols = _cols32(cols)
+    ng, nc = max(int(group_end) - int(group_begin), 0), int(cols.size)
     g_dt, s_dt = gram_dtypes(dtype)
-    return alloc((max(int(n_groups), 0), int(n_cols), int(n_cols)), g_dt), alloc((max(int(n_groups), 0), int(n_cols)), s_dt)
+    mid = (int(range_begin), int(range_end), int(window_rows), int(group_begin), int(group_end), nc, _ip(cols))
+    return mid, (((ng, nc, nc), g_dt), ((ng, nc), s_dt))
 
 
 def gram(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows, group_begin, group_end,
@@ -812,19 +759,11 @@ def gram(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, fla
     adjacent chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])).  cache_id 0: no cache, every chunk comes with its bytes; else
     chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, gram (n_groups, n_cols, n_cols), sum (n_groups,
     n_cols)) in the gram_dtypes of the recording's dtype."""
-    dtype = check_dtype(dtype)
-    keys, row0, offs, lens, rows = _longs(keys), _longs(row0), _longs(offs), _longs(lens), _longs(n_rows)
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
-    n = int(rows.size)
-    cdata = np.frombuffer(cdata, dtype=np.uint8) if len(cdata) else np.zeros(16, dtype=np.uint8)
-    assert not n or int((offs + lens).max()) <= cdata.size
-    g, s = _gram_out(int(group_end) - int(group_begin), cols.size, dtype)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-    _check(lib().mts_gram(int(device), int(cache_id), n, _lp(keys), _lp(row0), _ptr(cdata), _lp(offs), _lp(lens), _lp(rows), int(n_channels),
-                          dtype.itemsize, stats_flags(flags, dtype), int(range_begin), int(range_end), int(window_rows), int(group_begin),
-                          int(group_end), int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)), _ptr(g), _ptr(s),
-                          status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_gram')
-    return [int(x) for x in status[:n]], g, s
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, outs = _gram_args(dtype, range_begin, range_end, window_rows, group_begin, group_end, cols)
+    g, s = (np.empty(*o) for o in outs)
+    _check(lib().mts_gram(*head, *mid, _ptr(g), _ptr(s), _ip(status)), 'mts_gram')
+    return _status(status, n), g, s
 
 
 def dev_gram(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, range_begin, range_end, window_rows, group_begin, group_end, cols,
@@ -832,28 +771,12 @@ def dev_gram(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, range_beg
     """mts_dev_gram on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for both results (Gram entries, then
     the sums at a 256-byte aligned offset; made when None, returned so that a caller timing repeated calls can pass it again).
     Returns (status list, gram or None, sum or None, out)."""
-    dtype = check_dtype(dtype)
-    offs, lens, row0, rows = _longs(offs), _longs(lens), _longs(row0), _longs(n_rows)
-    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int32))
-    ng = max(int(group_end) - int(group_begin), 0)
-    g_dt, s_dt = gram_dtypes(dtype)
-    g_bytes, s_bytes = 8 * ng * cols.size * cols.size, 8 * ng * cols.size
-    s_off = -(-g_bytes // 256) * 256
-    if out is None or out.nbytes < s_off + s_bytes + 256:
-        out = DevBuffer(s_off + s_bytes + 256, device=cbuf.device)
-    status = np.zeros(max(int(rows.size), 1), dtype=np.int32)
-    _check(lib().mts_dev_gram(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(row0), _lp(rows), int(rows.size), int(n_channels),
-                              dtype.itemsize, stats_flags(flags, dtype), int(range_begin), int(range_end), int(window_rows), int(group_begin),
-                              int(group_end), int(cols.size), cols.ctypes.data_as(C.POINTER(C.c_int)), out.at(), out.at(s_off),
-                              status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_gram')
-    g = s = None
-    if download:
-        g, s = _gram_out(ng, cols.size, dtype)
-        if g.nbytes:
-            _check(lib().mts_dev_copy(out.device, None, _ptr(g), out.at(), g.nbytes, 1), 'mts_dev_copy')
-        if s.nbytes:
-            _check(lib().mts_dev_copy(out.device, None, _ptr(s), out.at(s_off), s.nbytes, 1), 'mts_dev_copy')
-    return [int(x) for x in status[:rows.size]], g, s, out
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, outs = _gram_args(dtype, range_begin, range_end, window_rows, group_begin, group_end, cols)
+    out, ptrs, at = _dev_results(out, cbuf.device, [8 * int(np.prod(shape)) for shape, _ in outs])
+    _check(lib().mts_dev_gram(*head, *mid, *ptrs, _ip(status)), 'mts_dev_gram')
+    g, s = _dev_fetch(out, at, [np.empty(*o) for o in outs]) if download else (None, None)
+    return _status(status, n), g, s, out
 
 
 # ------------------------------------------------------------------------------------------------

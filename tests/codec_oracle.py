@@ -231,6 +231,31 @@ class LaneOracleCodec(LeadingOracleCodec):
         if errors:
             raise errors[0]
 
+    def _call_chunks(self, op, cache_id, keys, cdata, offs, lens, n_rows, n_channels, dtype, flags, fill=False):
+        """The chunks of one call of the reduction `op` as mts_<op> gets them: a chunk without bytes is read from the lane's cache dict
+        (E_MISS when it is not there), the others are decoded and NOT inserted.  self.miss_next_<op> = True makes the next call with
+        such a chunk miss, once (an entry dropped between the query and the call).  -> (status, arrays); a chunk that did not decode
+        is None, or zeros with `fill`."""
+        from mtscomp_amd import hip
+        if getattr(self, 'miss_next_' + op, False):
+            setattr(self, 'miss_next_' + op, False)
+            if not all(lens):
+                raise hip.HipError(hip.E_MISS, 'mts_' + op, 'a chunk was dropped from the cache during the call')
+        cache = self.caches.get(cache_id, {}) if cache_id else {}
+        status, arrays = [], []
+        for k, o, n, nr in zip(keys, offs, lens, n_rows):
+            if not n:
+                if k not in cache:
+                    raise hip.HipError(hip.E_MISS, 'mts_' + op, 'chunk key %d is not resident' % k)
+                status.append(0)
+                arrays.append(cache[k])
+                continue
+            st, arrs = super().decompress([bytes(memoryview(cdata)[o:o + n])], [nr], n_channels, dtype, flags)
+            self.calls.pop()                         # (the inner decompress call is not a codec call of its own)
+            status.append(st[0])
+            arrays.append(arrs[0] if st[0] == 0 or not fill else np.zeros((nr, n_channels), dtype))
+        return status, arrays
+
     def _note(self, cid, keys):
         self.lane_keys.setdefault(self.cache_lane[cid], set()).update(int(k) for k in keys)
 

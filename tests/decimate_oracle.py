@@ -66,25 +66,12 @@ class DecimateOracleCodec(LaneOracleCodec):
 
     def decimate(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, first_row, n_out, q,
                  taps, out_dtype, cols, lane=None):
-        from mtscomp_amd import hip
         dtype = np.dtype(dtype)
         self.decimate_calls.append((lane, [int(k) for k in keys], [int(n) for n in lens]))
-        cache = self.caches.get(cache_id, {}) if cache_id else {}
         cols = np.asarray(cols, dtype=np.int64)
         assert q >= 1 and cols.size and (cols >= 0).all() and (cols < n_channels).all()
         assert all(int(row0[i]) == int(row0[i - 1]) + int(n_rows[i - 1]) for i in range(1, len(keys))), 'chunks not adjacent'
-        status, arrays = [], []
-        for k, o, n, nr in zip(keys, offs, lens, n_rows):
-            if not n:
-                if k not in cache:
-                    raise hip.HipError(hip.E_MISS, 'mts_decimate', 'chunk key %d is not resident' % k)
-                status.append(0)
-                arrays.append(cache[k])
-                continue
-            st, arrs = super(LaneOracleCodec, self).decompress([bytes(memoryview(cdata)[o:o + n])], [nr], n_channels, dtype, flags)
-            self.calls.pop()
-            status.append(st[0])
-            arrays.append(arrs[0] if st[0] == 0 else np.zeros((nr, n_channels), dtype))
+        status, arrays = self._call_chunks('decimate', cache_id, keys, cdata, offs, lens, n_rows, n_channels, dtype, flags, fill=True)
         x = np.concatenate(arrays, axis=0)[:, cols] if arrays else np.zeros((0, cols.size), dtype)
         y = fir_decimate(x, int(row0[0]) if len(keys) else 0, valid_begin, valid_end, first_row, n_out, q, taps, out_dtype)
         return status, y

@@ -148,31 +148,14 @@ class DetectOracleCodec(LaneOracleCodec):
 
     def detect(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end,
                taps, cols, threshold, sign, reference, exclude_rows, exclude_cols, max_events, lane=None):
-        from mtscomp_amd import hip
         dtype = np.dtype(dtype)
         self.detect_calls.append((lane, [int(k) for k in keys], [int(n) for n in lens], int(max_events)))
-        if self.miss_next_detect:
-            self.miss_next_detect = False
-            if not all(lens):
-                raise hip.HipError(hip.E_MISS, 'mts_detect', 'a chunk was dropped from the cache during the call')
-        cache = self.caches.get(cache_id, {}) if cache_id else {}
         cols = np.asarray(cols, dtype=np.int64)
         assert cols.size and (cols >= 0).all() and (cols < n_channels).all()
         assert sign in (0, 1, 2) and reference in (0, 1) and max_events >= 0
         assert valid_begin <= row_begin <= row_end <= valid_end
         assert all(int(row0[i]) == int(row0[i - 1]) + int(n_rows[i - 1]) for i in range(1, len(keys))), 'chunks not adjacent'
-        status, arrays = [], []
-        for k, o, n, nr in zip(keys, offs, lens, n_rows):
-            if not n:
-                if k not in cache:
-                    raise hip.HipError(hip.E_MISS, 'mts_detect', 'chunk key %d is not resident' % k)
-                status.append(0)
-                arrays.append(cache[k])
-                continue
-            st, arrs = super(LaneOracleCodec, self).decompress([bytes(memoryview(cdata)[o:o + n])], [nr], n_channels, dtype, flags)
-            self.calls.pop()
-            status.append(st[0])
-            arrays.append(arrs[0] if st[0] == 0 else np.zeros((nr, n_channels), dtype))
+        status, arrays = self._call_chunks('detect', cache_id, keys, cdata, offs, lens, n_rows, n_channels, dtype, flags, fill=True)
         x = np.concatenate(arrays, axis=0)[:, cols]
         row, pos, amp = detect_events(x, int(row0[0]), valid_begin, valid_end, row_begin, row_end, taps, threshold, sign, reference,
                                       exclude_rows, exclude_cols)

@@ -108,23 +108,11 @@ class GramOracleCodec(LaneOracleCodec):
              group_end, cols, lane=None):
         dtype = np.dtype(dtype)
         self.gram_calls.append((lane, [int(k) for k in keys], [int(n) for n in lens], int(group_begin), int(group_end)))
-        cache = self.caches.get(cache_id, {}) if cache_id else {}
         cols = np.asarray(cols, dtype=np.int64)
         assert cols.size and (cols >= 0).all() and (cols < n_channels).all()
         assert 0 <= group_begin < group_end <= hip.gram_groups(range_begin, range_end, window_rows)
         assert all(int(row0[i]) == int(row0[i - 1]) + int(n_rows[i - 1]) for i in range(1, len(keys))), 'chunks not adjacent'
-        status, arrays = [], []
-        for k, o, n, nr in zip(keys, offs, lens, n_rows):
-            if not n:
-                if k not in cache:
-                    raise hip.HipError(hip.E_MISS, 'mts_gram', 'chunk key %d is not resident' % k)
-                status.append(0)
-                arrays.append(cache[k])
-                continue
-            st, arrs = super(LaneOracleCodec, self).decompress([bytes(memoryview(cdata)[o:o + n])], [nr], n_channels, dtype, flags)
-            self.calls.pop()
-            status.append(st[0])
-            arrays.append(arrs[0] if st[0] == 0 else np.zeros((nr, n_channels), dtype))
+        status, arrays = self._call_chunks('gram', cache_id, keys, cdata, offs, lens, n_rows, n_channels, dtype, flags, fill=True)
         x = np.concatenate(arrays, axis=0)[:, cols]
         G, S = gram_partials(x, int(row0[0]), range_begin, range_end, window_rows, group_begin, group_end)
         return status, G, S

@@ -101,7 +101,6 @@ class SelectOracleCodec(LaneOracleCodec):
                   center, sel_prefix, sel_shift, lane=None):
         dtype = np.dtype(dtype)
         self.rank_calls.append((lane, [int(k) for k in keys], [int(n) for n in lens], int(row_begin), int(row_end), int(mode)))
-        cache = self.caches.get(cache_id, {}) if cache_id else {}
         cols = np.asarray(cols, dtype=np.int64)
         assert cols.size and (cols >= 0).all() and (cols < n_channels).all()
         nw = -(-(row_end - row_begin) // window_rows)
@@ -113,21 +112,10 @@ class SelectOracleCodec(LaneOracleCodec):
         assert mode in (0, 1, 2) and (not mode or np.asarray(center).shape == (nw, cols.size))
         out = empty_outputs(nw, cols.size)
         count = np.zeros(nw, np.int64)
-        status = []
-        for k, r0, o, n, nr in zip(keys, row0, offs, lens, n_rows):
-            if not n:
-                if k not in cache:
-                    raise hip.HipError(hip.E_MISS, 'mts_rank_hist', 'chunk key %d is not resident' % k)
-                status.append(0)
-                a = cache[k]
-            else:
-                st, arrs = super(LaneOracleCodec, self).decompress([bytes(memoryview(cdata)[o:o + n])], [nr], n_channels, dtype, flags)
-                self.calls.pop()
-                status.append(st[0])
-                if st[0] != 0:
-                    continue
-                a = arrs[0]
-            count += round_add(out, a[:, cols], int(r0), row_begin, row_end, window_rows, mode, center, pref, shift)
+        status, arrays = self._call_chunks('rank_hist', cache_id, keys, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+        for r0, st, a in zip(row0, status, arrays):
+            if st == 0:
+                count += round_add(out, a[:, cols], int(r0), row_begin, row_end, window_rows, mode, center, pref, shift)
         return status, dict(hist=out[0], kmin=out[1], kmax=out[2], count=count)
 
 

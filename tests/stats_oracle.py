@@ -94,24 +94,11 @@ class StatsOracleCodec(LaneOracleCodec):
 
     def window_stats(self, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end,
                      window_rows, cols, lane=None):
-        from mtscomp_amd import hip
         dtype = np.dtype(dtype)
         self.stats_calls.append((lane, [int(k) for k in keys], [int(n) for n in lens]))
-        cache = self.caches.get(cache_id, {}) if cache_id else {}
         cols = np.asarray(cols, dtype=np.int64)
         assert window_rows >= 1 and cols.size and (cols >= 0).all() and (cols < n_channels).all()
-        status, arrays = [], []
-        for k, o, n, nr in zip(keys, offs, lens, n_rows):
-            if not n:
-                if k not in cache:
-                    raise hip.HipError(hip.E_MISS, 'mts_window_stats', 'chunk key %d is not resident' % k)
-                status.append(0)
-                arrays.append(cache[k])
-                continue
-            st, arrs = super(LaneOracleCodec, self).decompress([bytes(memoryview(cdata)[o:o + n])], [nr], n_channels, dtype, flags)
-            self.calls.pop()
-            status.append(st[0])
-            arrays.append(arrs[0])
+        status, arrays = self._call_chunks('window_stats', cache_id, keys, cdata, offs, lens, n_rows, n_channels, dtype, flags)
         nw = -(-(row_end - row_begin) // window_rows) if row_end > row_begin else 0
         mn, mx, s, q = _identity(nw, cols.size, dtype)
         cnt = np.zeros(nw, np.int64)
