@@ -103,3 +103,104 @@ def test_stitching_is_exact():
     parts = [detect_events(x, 0, 0, 900, a, b, taps, 10.0, 0, 1, 9, 2) for a, b in [(100, 400), (400, 403), (403, 800)]]
     _same(whole, tuple(np.concatenate([p[k] for p in parts]) for k in range(3)))
     assert whole[0].size > 50
+
+
+# ---- the cases of tests/test_gpu_detect_edges.py on the stand-in, with the brute-force restatement beside it where it is cheap ------------
+from tests import detect_cases as K  # noqa: E402
+from tests.detect_oracle import DetectOracleCodec  # noqa: E402
+
+
+@pytest.fixture
+def tmp_cfg(tmp_path, monkeypatch):
+    monkeypatch.setattr(api, 'CONFIG_PATH', tmp_path / '.mtscomp')
+    api.set_codec(None)
+    K.plain_env(monkeypatch)
+    return tmp_path
+
+
+def _make(tmp):
+    return lambda x, chunk_rows: K.recording(tmp, x, chunk_rows, codec=DetectOracleCodec(n_lanes=1, capacity_chunks=8))
+
+
+@pytest.mark.parametrize('dtype', ['float32', 'int16'])
+def test_median_widths_on_the_stand_in(tmp_cfg, dtype):
+    """The recording of the GPU test, every list length; the brute-force median and comparisons up to 3 columns."""
+    r, dec = _make(tmp_cfg)(K.median_recording(dtype), 64)
+    seen = K.run_median(r, dec, brute_upto=3)
+    assert set(seen) == set(K.MEDIAN_NS) and {K.network_size(n) for n in seen} == {2, 4, 64, 128, 256, 512, 1024}
+    for n, (share, n_dump, n_ordinary, n_sub) in seen.items():
+        assert share >= 0.99 or (n % 2 and n < 255), (n, share)
+        assert (n_sub >= 1) == (dtype == 'float32' and n >= 2)
+    r.close()
+
+
+def test_median_brute_force_on_wider_rows():
+    """The vectorised median against the sorted() one on a few rows of every family, at widths either side of a power of two."""
+    x = K.median_recording('float32')
+    rows = np.r_[0:2, K.MEDIAN_RANDOM_ROWS:x.shape[0]:9]
+    for n in (4, 63, 64, 65, 128):
+        args = (x[rows][:, :n], 0, 0, len(rows), 0, len(rows), [1.0], K.SUBNORMAL, 2, 1, 0, 0)
+        _same(detect_events(*args), detect_events_brute(*args))
+
+
+def test_scan_shapes_pass_262144_words():
+    from tests.test_gpu_detect_edges import SCAN_CASES
+    pers = []
+    for rows, nc, chunk, blocks, per, own in SCAN_CASES:
+        for slab in ([rows] if own is None else [own, rows - own]):
+            words, b, p = K.scan_shape(slab, nc)
+            assert (b, p) == (blocks, per) and (words > 262144) == (per > 1) and chunk < rows
+            pers.append(p)
+        x = K.spiky_int8(rows, nc, 4000, rows % 1000 + nc)              # the dump of these inputs emits >= 0.99 of the samples
+        assert np.count_nonzero(x) >= 0.99 * x.size
+    assert sorted(set(pers)) == [1, 2, 3]
+    assert K.scan_shape(262144, 1) == (262144, 256, 1) and K.scan_shape(262145, 1)[1:] == (257, 2)
+
+
+def test_scan_case_and_capacities_on_the_stand_in(tmp_cfg, monkeypatch):
+    x = K.spiky_int8(9000, 3, 300, 4)
+    r, dec = _make(tmp_cfg)(x, 2000)
+    n_sparse, total = K.run_scan(r, dec, monkeypatch, caps=K.SCAN_CAPS[:1] + K.SCAN_CAPS[3:], brute=True)
+    assert 150 <= n_sparse <= 300 and total >= 0.99 * x.size
+    r.close()
+
+
+@pytest.mark.parametrize('kind', [0, 1])
+def test_dense_events_and_second_call_on_the_stand_in(tmp_cfg, monkeypatch, kind):
+    mask = K.dense_masks(3000, 70)[kind]
+    r, dec = _make(tmp_cfg)(np.where(mask, 7, 0).astype(np.int16), 700)
+    K.run_dense(r, mask, monkeypatch, r.n_chunks)
+    small = dec[:40]
+    _same(detect_events(small, 0, 0, 40, 0, 40, [1.0], 1.0, 1, 0, 0, 0), detect_events_brute(small, 0, 0, 40, 0, 40, [1.0], 1.0, 1, 0, 0, 0))
+    r.close()
+
+
+@pytest.mark.parametrize('R', [1, 7])
+def test_slab_seam_recording_on_the_stand_in(tmp_cfg, monkeypatch, R):
+    assert K.run_seams(_make(tmp_cfg), R, monkeypatch, brute=True) >= 12
+
+
+def test_slab_seam_recording_at_255_is_what_it_says():
+    """The long recording's literal expectations, by the oracle alone (the stand-in has no slabs to cut it with)."""
+    R = 255
+    x, marks, tail = K.seam_recording(R)
+    for reference in (0, 1):
+        row, pos, amp = detect_events(x, 0, 0, len(x), 0, len(x), [1.0], K.SEAM_THR, 1, reference, R, 0)
+        K.seam_literals(K.api.Bunch(sample=row, channel=pos), R, marks)
+        assert row.size >= R + 4
+    assert len(x) - tail < 3000 and marks['pair_R'][1] > len(x) - 3000
+
+
+def test_word_seams_on_the_stand_in(tmp_cfg):
+    x, marks = K.word_recording()
+    r, dec = _make(tmp_cfg)(x, 100)
+    K.run_words(r, dec, marks, ns=(65, 129))
+    K.run_words(r, dec[:, :66], marks, ns=(64, 65), brute=True)
+    r.close()
+
+
+def test_threshold_is_strict_on_the_stand_in(tmp_cfg):
+    x, vals = K.threshold_recording()
+    r, dec = _make(tmp_cfg)(x, 16)
+    K.run_threshold(r, dec, vals, brute=True)
+    r.close()

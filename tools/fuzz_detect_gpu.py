@@ -1,8 +1,10 @@
 """Randomised parity of Reader.detect on a GPU box: random recordings (all ten item types, channel counts, chunk durations; float
 data with NaN, infinities and zeros of both signs sprinkled in; coarse integers for heavy ties) compressed with mtscomp_amd.compress
-and read back with random taps, exclude, spread, sign, reference, thresholds (a scalar or one per column), ranges, column lists (any
-order, repeats) and cache states (a random prefix read so that some chunks are resident).  Each case also draws the decode pieces
-(MTS_PIPE_BYTES), the slab bound (MTS_DETECT_SLAB_BYTES), one lane or two on device 0, DETECT_CALL_BYTES and the first buffer's size.
+and read back with random taps, exclude, spread, sign, reference, thresholds (a scalar or one per column; now and then so low that
+most samples are events), ranges, column lists (any order, repeats; up to 1024 columns under a median, so that its sorting network
+takes every size up to 1024) and cache states (a random prefix read so that some chunks are resident).  Each case also draws the
+decode pieces (MTS_PIPE_BYTES), the slab bound (MTS_DETECT_SLAB_BYTES), one lane or two on device 0, DETECT_CALL_BYTES and the first
+buffer's size.
 Every comparison is exact: sample, channel and amplitude byte for byte against tests/detect_oracle.py over the oracle's decode.
 
     python tools/fuzz_detect_gpu.py [seed] [seconds]
@@ -22,6 +24,7 @@ from mtscomp_amd import api  # noqa: E402
 from tests.codec_oracle import OracleCodec  # noqa: E402
 from tests.detect_oracle import SIGNS, detect_events, filtered  # noqa: E402
 
+MAX_SAMPLES = 12000 * 130
 DTYPES = ['int8', 'uint8', 'int16', 'uint16', 'int32', 'uint32', 'int64', 'uint64', 'float32', 'float64']
 
 
@@ -34,8 +37,8 @@ def _env(name, value):
 
 def one_case(rs, tmp):
     dt = np.dtype(DTYPES[rs.randint(len(DTYPES))])
-    nc = int(rs.choice([1, 2, 3, 17, 64, 65, 70, 130]))
-    rows = int(rs.randint(1, 12000))
+    nc = int(rs.choice([1, 2, 3, 17, 64, 65, 70, 130, 257, 600, 1024]))
+    rows = int(rs.randint(1, min(12000, MAX_SAMPLES // nc + 1)))                # (the wide ones are short: a case costs what a 130-column one does)
     _env('MTS_PIPE_BYTES', [None, 64 << 10, 300 << 10, 8 << 20][rs.randint(4)])
     _env('MTS_DETECT_SLAB_BYTES', [None, 1, 40 << 10, 1 << 20][rs.randint(4)])
     api.DETECT_CALL_BYTES = [1, 1 << 16, 1 << 30][rs.randint(3)]
@@ -76,13 +79,18 @@ def one_case(rs, tmp):
         S = int(rs.choice([0, 1, 3, 32]))
         sign = ['neg', 'pos', 'both'][rs.randint(3)]
         reference = [None, 'median'][rs.randint(2)]
+        if reference:
+            cols = cols[:1024]
+        dense = rs.randint(8) == 0                                 # most samples above the threshold: the compaction at full density
+        if dense:
+            R, S = min(R, 2), min(S, 1)                            # (the oracle pays per candidate and neighbour)
         xs = dec[:, cols]
         t = np.array([1.0]) if taps is None else taps
         y = filtered(xs, 0, 0, rows, 0, rows, t).astype(np.float64)
         fin = y[np.isfinite(y)]
         scale = float(fin.std()) if fin.size and fin.std() > 0 else 1.0
         scale = min(max(scale, 1e-30), 1e30)
-        thr = scale * float(rs.choice([0.2, 1.0, 2.0]))
+        thr = scale * (1e-3 if dense else float(rs.choice([0.2, 1.0, 2.0])))
         if rs.randint(2):
             thr = thr * rs.uniform(0.5, 2.0, size=len(cols))
         got = r.detect(thr, start, stop, channels=cols, taps=taps, sign=sign, reference=reference, exclude=R, spread=S)
