@@ -389,6 +389,10 @@ int mts_dev_compress_chunks(int device, void *stream, const void *d_raw, int n_c
                             const long *chunk_bounds, int n_chunks, int flags, int level,
                             unsigned char *d_out, const long *out_slot_offsets /* 16-B aligned */,
                             long *out_sizes /* host; valid when the call returns */);
+/* Chunk i is written at d_out + out_offsets[i].  That address must be a multiple of `itemsize`; any such offset is allowed (chunks
+ * back to back, no other alignment: the kernel stores 16 bytes, dwords or single items as the address permits, and never a byte
+ * outside the chunk's n_rows[i] * n_channels * itemsize bytes).  An address that is not returns MTS_E_ARG, with a message naming
+ * the chunk, before anything is launched.  A chunk whose status is not MTS_CHUNK_OK leaves its bytes of d_out untouched. */
 int mts_dev_decompress_chunks(int device, void *stream, const unsigned char *d_cdata,
                               const long *c_offsets, const long *c_lengths, const long *n_rows,
                               int n_chunks, int n_channels, int itemsize, int flags, void *d_out,

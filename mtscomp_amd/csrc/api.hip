@@ -892,6 +892,11 @@ static int dev_decompress(Engine &E, hipStream_t st, const u8 *d_cdata, const lo
     if (sz != 1 && sz != 2 && sz != 4 && sz != 8) { set_error("itemsize %d unsupported", sz); return MTS_E_ARG; }
     if ((flags & MTS_FLAG_FLOAT) && sz != 4 && sz != 8) { set_error("float items of %d bytes unsupported", sz); return MTS_E_ARG; }
     if (nc <= 0 || n_chunks < 0) return MTS_E_ARG;
+    for (int i = 0; i < n_chunks; i++)              // (K2 stores whole items; any multiple of the item size is allowed)
+        if (((uintptr_t)d_out + (u64)out_off[i]) % (unsigned)sz) {
+            set_error("chunk %d: output address (d_out + offset %ld) is not a multiple of the item size %d", i, out_off[i], sz);
+            return MTS_E_ARG;
+        }
     MTS_HIP(hipSetDevice(E.dev));
     const size_t budget = batch_budget_bytes() * 4;          // inflate needs ~5 bytes of workspace per byte
     const u64 row_bytes = (u64)(nc_full > nc ? nc_full : nc) * sz;

@@ -133,12 +133,16 @@ __host__ __device__ inline int rows_pitch(int nc, int itemsize)
     if (!(dw & 1)) dw++;
     return dw * per;
 }
-// largest tile height whose LDS image ((TT + 1) rows) stays within 64 KiB
+// largest tile height whose LDS image ((TT + 1) rows), with the static LDS k_delta_rows has beside it, stays within the 64 KiB
+// the launchers ask ensure_dynamic_lds for; 0: the generic kernels.  (tests/transform_cases.py restates this, rows_pitch and the
+// kernels' path predicates, and its transition table is asserted: a change here is made there too)
+constexpr int ROWS_LDS_LIMIT = 64 * 1024;
+constexpr int ROWS_STATIC_LDS = 8 * (int)sizeof(u64);          // k_delta_rows: red[8]
 static int rows_tile(int nc, int itemsize)
 {
     const long pitch_b = (long)rows_pitch(nc, itemsize) * itemsize;
     for (int tt = 64; tt >= 16; tt >>= 1)
-        if ((tt + 1) * pitch_b <= 64 * 1024) return tt;
+        if ((tt + 1) * pitch_b + ROWS_STATIC_LDS <= ROWS_LDS_LIMIT) return tt;
     return 0;
 }
 
@@ -163,7 +167,7 @@ __global__ __launch_bounds__(256) void k_delta_rows(const u8 *__restrict__ raw, 
 {
     extern __shared__ __attribute__((aligned(16))) u8 smem_rows[];
     T *tile = (T *)smem_rows;                                   // [tt_rows + 1][pitch]; row 0 = t0 - 1
-    __shared__ u64 red[8];
+    __shared__ u64 red[ROWS_STATIC_LDS / sizeof(u64)];
     int tile_x, chunk_y;
     if (!xcd_row_tile(ntile_max, tile_x, chunk_y)) return;
     const ChunkDesc ch = chunks[chunk_y];
@@ -282,15 +286,17 @@ __global__ __launch_bounds__(256) void k_delta_rows(const u8 *__restrict__ raw, 
 }
 
 template <typename T>
-static void run_delta_rows(hipStream_t st, const u8 *raw, u8 *stream, const ChunkDesc *d_chunks, int n_chunks, u32 max_rows,
+static int run_delta_rows(hipStream_t st, const u8 *raw, u8 *stream, const ChunkDesc *d_chunks, int n_chunks, u32 max_rows,
                            int nc, u64 *d_adler_acc)
 {
     const int tt = rows_tile(nc, (int)sizeof(T)), pitch = rows_pitch(nc, (int)sizeof(T));
     const size_t lds = (size_t)(tt + 1) * pitch * sizeof(T);
-    (void)ensure_dynamic_lds((const void *)k_delta_rows<T>, 64 * 1024);
+    const int rc = ensure_dynamic_lds((const void *)k_delta_rows<T>, ROWS_LDS_LIMIT);
+    if (rc) return rc;
     const int ntile = (int)((max_rows + tt - 1) / tt);
     hipLaunchKernelGGL(k_delta_rows<T>, dim3(xcd_row_grid(ntile, n_chunks)), dim3(256), lds, st, raw, stream, d_chunks, nc, tt, pitch, 0xffffffffu / (u32)nc + 1,
                        d_adler_acc, ntile);
+    return MTS_OK;
 }
 
 int launch_delta_transpose(hipStream_t st, const void *d_raw, void *d_stream, const ChunkDesc *d_chunks,
@@ -303,11 +309,13 @@ int launch_delta_transpose(hipStream_t st, const void *d_raw, void *d_stream, co
     const u8 *raw = (const u8 *)d_raw;
     u8 *stream = (u8 *)d_stream;
     if (flags == (MTS_FLAG_TIME_DIFF | MTS_FLAG_ORDER_F) && itemsize <= 4 && n_channels >= 2 && rows_tile(n_channels, itemsize) && !getenv("MTS_K12_GENERIC")) {
+        int rc;
         switch (itemsize) {
-        case 1: run_delta_rows<u8>(st, raw, stream, d_chunks, n_chunks, max_rows, n_channels, d_adler_acc); break;
-        case 2: run_delta_rows<u16>(st, raw, stream, d_chunks, n_chunks, max_rows, n_channels, d_adler_acc); break;
-        default: run_delta_rows<u32>(st, raw, stream, d_chunks, n_chunks, max_rows, n_channels, d_adler_acc); break;
+        case 1: rc = run_delta_rows<u8>(st, raw, stream, d_chunks, n_chunks, max_rows, n_channels, d_adler_acc); break;
+        case 2: rc = run_delta_rows<u16>(st, raw, stream, d_chunks, n_chunks, max_rows, n_channels, d_adler_acc); break;
+        default: rc = run_delta_rows<u32>(st, raw, stream, d_chunks, n_chunks, max_rows, n_channels, d_adler_acc); break;
         }
+        if (rc) return rc;
         MTS_HIP(hipGetLastError());
         return MTS_OK;
     }
@@ -777,18 +785,20 @@ __global__ __launch_bounds__(256) void k_cumsum_rows(const u8 *__restrict__ stre
 }
 
 template <typename T>
-static void run_cumsum_rows(hipStream_t st, const u8 *stream, u8 *out, const u64 *d_stream_off, const u64 *d_out_off,
+static int run_cumsum_rows(hipStream_t st, const u8 *stream, u8 *out, const u64 *d_stream_off, const u64 *d_out_off,
                             const u32 *d_rows, const int *d_status, int n_chunks, u32 max_rows, int nc, u32 *sums)
 {
     const int tt = rows_tile(nc, (int)sizeof(T)), pitch = rows_pitch(nc, (int)sizeof(T));
     const size_t lds = (size_t)tt * pitch * sizeof(T);
-    (void)ensure_dynamic_lds((const void *)k_cumsum_rows<T>, 64 * 1024);
+    const int rc = ensure_dynamic_lds((const void *)k_cumsum_rows<T>, ROWS_LDS_LIMIT);
+    if (rc) return rc;
     const int ntile = (max_rows + tt - 1) / tt;
     dim3 grid(xcd_row_grid(ntile, n_chunks));
     hipLaunchKernelGGL(k_rows_sums<T>, grid, dim3(256), 0, st, stream, d_stream_off, d_rows, d_status, nc, tt, ntile, sums);
     hipLaunchKernelGGL(k_rows_scan, dim3((nc + 63) / 64, n_chunks), dim3(64 * ROWS_SCAN_PARTS), 0, st, d_rows, d_status, nc, tt, ntile, sums);
     hipLaunchKernelGGL(k_cumsum_rows<T>, grid, dim3(256), lds, st, stream, out, d_stream_off, d_out_off, d_rows, d_status, nc, tt, pitch,
                        0xffffffffu / (u32)nc + 1, ntile, sums);
+    return MTS_OK;
 }
 
 static int segr_for(int itemsize) { return itemsize <= 2 ? 256 : itemsize == 4 ? 128 : 64; }
@@ -817,11 +827,13 @@ int launch_cumsum_transpose(hipStream_t st, const void *d_stream, void *d_out, c
         return MTS_E_ARG;
     }
     if (flags == (MTS_FLAG_TIME_DIFF | MTS_FLAG_ORDER_F) && itemsize <= 4 && n_channels >= 2 && rows_tile(n_channels, itemsize) && !getenv("MTS_K12_GENERIC")) {
+        int rc;
         switch (itemsize) {
-        case 1: run_cumsum_rows<u8>(st, s, o, d_stream_off, d_out_off, d_rows, d_status, n_chunks, max_rows, n_channels, (u32 *)ss); break;
-        case 2: run_cumsum_rows<u16>(st, s, o, d_stream_off, d_out_off, d_rows, d_status, n_chunks, max_rows, n_channels, (u32 *)ss); break;
-        default: run_cumsum_rows<u32>(st, s, o, d_stream_off, d_out_off, d_rows, d_status, n_chunks, max_rows, n_channels, (u32 *)ss); break;
+        case 1: rc = run_cumsum_rows<u8>(st, s, o, d_stream_off, d_out_off, d_rows, d_status, n_chunks, max_rows, n_channels, (u32 *)ss); break;
+        case 2: rc = run_cumsum_rows<u16>(st, s, o, d_stream_off, d_out_off, d_rows, d_status, n_chunks, max_rows, n_channels, (u32 *)ss); break;
+        default: rc = run_cumsum_rows<u32>(st, s, o, d_stream_off, d_out_off, d_rows, d_status, n_chunks, max_rows, n_channels, (u32 *)ss); break;
         }
+        if (rc) return rc;
         MTS_HIP(hipGetLastError());
         return MTS_OK;
     }

@@ -924,6 +924,8 @@ def dev_compress_chunks(raw, n_channels, itemsize, bounds, flags, level, out, sl
 
 
 def dev_decompress_chunks(cbuf, offs, lens, rows, n_channels, itemsize, flags, out, out_offs, status):
+    """mts_dev_decompress_chunks on DevBuffers: chunk i is written at out_offs[i] of `out`, any multiple of the item size (HipError
+    MTS_E_ARG otherwise); `status` (int32 array) is filled, a chunk that did not decode leaves its bytes of `out` as they were."""
     _check(lib().mts_dev_decompress_chunks(cbuf.device, None, cbuf.at(), _lp(offs), _lp(lens), _lp(rows), len(rows), n_channels, itemsize, int(flags),
                                            out.at(), _lp(out_offs), status.ctypes.data_as(C.POINTER(C.c_int))), 'mts_dev_decompress_chunks')
 
