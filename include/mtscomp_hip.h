@@ -45,8 +45,10 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_detect, mts_welch, mts_gram and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_welch, mts_gram and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
+#define MTS_PROJECT_MAX_COLS 1024
+#define MTS_PROJECT_MAX_OUT  1024
 #define MTS_WELCH_MAX_NPERSEG 16384
 #define MTS_WELCH_BLOCK_SEGMENTS 32   /* mts_welch: segments per block (B), summed in order on the device */
 #define MTS_WELCH_GROUP_ROWS (1l << 20) /* a group is the smallest multiple G of B segments with G * step >= this many rows */
@@ -220,6 +222,45 @@ int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys
                  int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row, long n_out,
                  int q, int n_taps, const double *taps, int out_itemsize, int n_cols, const int *cols, void *out,
                  int *chunk_status);
+
+/*
+ * Channel-mixing matrix products of decoded chunks (an extension: the reference has no such call; its users form Reader[...] @ W on
+ * the host).  Whitening, projection onto principal components, re-referencing, selecting and scaling channels are all this one
+ * row-by-row product.  Only the outputs cross the bus.
+ *   outputs        y[t, k] = sum_{j < n_cols} (x[t, cols[j]] - offset[j]) * weights[j, k] for row_begin <= t < row_end, k < n_out, in
+ *                  absolute file rows.  (row_end - row_begin, n_out) C order, F = float (out_itemsize 4) or double (8).
+ *   the chain      Items, offsets and weights are each rounded once to F (items as mts_decimate converts them, unsigned by
+ *                  MTS_FLAG_UNSIGNED); d[t, j] = F(x[t, cols[j]]) - F(offset[j]) is one IEEE subtraction in F; offset NULL means zeros.
+ *                  With n4 = n_cols rounded up to a multiple of 4, positions j >= n_cols enter as d = 0, w = 0.  y[t, k] is the chain
+ *                  of 4-column matrix steps over j = 0, 4, 8, .. < n4, in that order, from +0; each step is one
+ *                  v_mfma_f32_16x16x4_f32 (v_mfma_f64_16x16x4_f64) with d[t, j .. j + 3] as A and w[j .. j + 3, k] as B.  Zero
+ *                  weights are not skipped (inf * 0 is NaN).  y[t, k] depends on row t, cols, offset and column k of weights alone:
+ *                  not on the tile it lands in, the other output columns, the chunks, pieces, calls, lanes, cache residency or device.
+ *   float          a float32 step is bit for bit the k-ordered chain acc = fmaf(d_j, w_jk, acc), so y[t, k] is that chain over
+ *                  j = 0 .. n4 - 1 from +0: a definition, not a tolerance.  float32 subnormals are kept, as operands and as results
+ *                  (the kernels are built with hipcc's default float mode).
+ *   double         held to a bound, as mts_gram is: with u = 2^-53, |y - sum_j (x_j - o_j) w_jk| <= gamma_{n4+4} * sum_j (|x_j| + |o_j|)
+ *                  |w_jk| + n4 * 2^-1074 (item / offset conversion, subtraction, weight, and at most n4 roundings of the chain; the
+ *                  absolute term is the gradual underflow).  The same bound with u = 2^-24 and 2^-149 holds for float.
+ *   limits         1 <= n_cols <= MTS_PROJECT_MAX_COLS channel indices, any order, repeats allowed; 1 <= n_out <= MTS_PROJECT_MAX_OUT;
+ *                  weights (n_cols, n_out) C order and offset (n_cols or NULL) finite doubles on the host
+ *   chunks         as mts_decimate: adjacent, ascending, covering [row_begin, row_end).  row_begin == row_end is MTS_OK with nothing
+ *                  written.
+ *   chunk_status   MTS_CHUNK_* per chunk as in mts_decompress_chunks; the outputs of a failed chunk's rows are undefined
+ * mts_project: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated (whole chunks, adler32 checked) piece
+ * by piece (MTS_PIPE_BYTES) in a transient workspace, the compressed bytes of the next piece crossing the bus beside the kernels; a
+ * piece owns the rows of its chunks, so no chunk is inflated twice.  They are NOT inserted into the cache.  `out` is host memory.
+ * mts_dev_project: device d_cdata and d_out on `device`, chunk_status on the host; no cache.
+ * MTS_E_ARG with a message before anything is allocated or launched: n_cols or n_out outside their limits, a weight or an offset
+ * that is not finite, out_itemsize not 4 or 8, a column outside [0, n_channels), row_begin < 0 or row_end < row_begin, no output
+ * buffer, chunks not adjacent or not covering the rows, an empty chunk.
+ */
+int mts_project(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
+                long row_end, int n_cols, const int *cols, const double *offset /* n_cols or NULL */, int n_out,
+                const double *weights /* (n_cols, n_out) C order */, int out_itemsize, void *out /* (row_end - row_begin, n_out) C order */,
+                int *chunk_status);
 
 /*
  * Threshold-crossing peak detection on filtered rows (an extension: the reference has no such call; its users filter Reader[...],
@@ -407,6 +448,10 @@ int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, con
                      int n_channels, int itemsize, int flags, long valid_begin, long valid_end, long first_row,
                      long n_out, int q, int n_taps, const double *taps, int out_itemsize, int n_cols,
                      const int *cols, void *d_out, int *chunk_status /* host */);
+int mts_dev_project(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                    const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin,
+                    long row_end, int n_cols, const int *cols, const double *offset /* host */, int n_out, const double *weights /* host */,
+                    int out_itemsize, void *d_out, int *chunk_status /* host */);
 int mts_dev_detect(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                    const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
                    long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols,

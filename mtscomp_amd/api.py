@@ -68,6 +68,8 @@ DETECT_CALL_BYTES = 1 << 30            # Reader.detect: compressed bytes per dev
 DETECT_GUESS_MIN = 4096                # Reader.detect: events a call's first buffer holds at least, and one more per this many samples:
 DETECT_GUESS_SAMPLES = 256             # a call that finds more says how many and is made once more
 DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per device call (a longer range is split at output-row boundaries)
+PROJECT_CALL_BYTES = 1 << 30           # Reader.project: compressed bytes per device call (a longer range is split at chunk boundaries) ...
+PROJECT_OUT_BYTES = 1 << 30            # ... and the bytes of a call's result
 WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
 GRAM_CALL_BYTES = 1 << 30              # Reader.cov: compressed bytes per device call (a longer range is split at group boundaries)
 GRAM_SLAB_BYTES = 1 << 30              # ... and partial results per call (one Gram matrix and one row of sums per group)
@@ -250,6 +252,25 @@ def _fir_taps(taps):
     return taps
 
 
+def whitening_weights(cov, eps=0.0):
+    """The symmetric float64 ZCA whitening matrix E diag(1 / sqrt(max(lambda, 0) + eps)) E^T of a covariance matrix, from
+    np.linalg.eigh(cov).  With c = r.cov(), r.project(whitening_weights(c.cov[0], eps), offset=c.mean[0]) is the whitened recording.
+    ValueError for a matrix that is not square or not finite, a negative or non-finite eps, or a singular matrix with eps == 0."""
+    c = np.asarray(cov, dtype=np.float64)
+    if c.ndim != 2 or c.shape[0] != c.shape[1] or not c.shape[0]:
+        raise ValueError("cov must be a square matrix, got shape %r" % (c.shape,))
+    if not np.isfinite(c).all():
+        raise ValueError("cov must be finite")
+    if not isinstance(eps, (int, float, np.integer, np.floating)) or isinstance(eps, bool) or not np.isfinite(eps) or eps < 0:
+        raise ValueError("eps must be a finite number >= 0, got %r" % (eps,))
+    lam, vec = np.linalg.eigh(0.5 * (c + c.T))
+    d = np.maximum(lam, 0.0) + float(eps)
+    if d.min() <= 0 or (eps == 0 and d.min() <= d.max() * np.finfo(np.float64).eps * c.shape[0]):
+        raise ValueError("cov is singular (smallest eigenvalue %g): pass eps > 0" % lam.min())
+    w = (vec / np.sqrt(d)) @ vec.T
+    return 0.5 * (w + w.T)
+
+
 def _window_rows(window, i0, i1):
     """The window of Reader.window_stats / quantile / cov over rows [i0, i1) as an int: None is one window over the range."""
     if window is None:
@@ -358,6 +379,7 @@ class HipCodec:
     # the device reductions of the Reader, one call for the chunks of one lane
     window_stats, rank_hist, decimate, detect, welch, gram = map(
         _lane_reduction, ('window_stats', 'rank_hist', 'decimate', 'detect', 'welch', 'gram'))
+    project = _lane_reduction('project')
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1693,6 +1715,63 @@ class Reader:
                     return self._chunk_span(plo, phi), (vb, ve, fr, b - a, q, taps, out_dtype, cols)
             for a, b, (y,) in self._halo_parts(self.codec.decimate, cuts, part):
                 out[a:b] = y
+        return out[:, 0] if squeeze else out
+
+    # -- channel-mixing matrix products on the device (an extension: the reference's users form Reader[...] @ W on the host)
+    def project(self, weights, start=0, stop=None, channels=slice(None), offset=None, dtype=np.float32):
+        """Rows [start, stop) times a channel-mixing matrix, on the device: only the result crosses the bus.
+        y[t, k] = sum_j (x[t, cols[j]] - offset[j]) * weights[j, k], computed in `dtype` (float32 or float64) on the matrix cores:
+        items, offsets and weights are each rounded once to it, the subtraction is one operation, and the sum is the chain of
+        4-column matrix steps in column order from +0 -- for float32 bit for bit acc = fmaf(d_j, w_jk, acc) over j, for float64
+        within the bound include/mtscomp_hip.h states (gamma_{n+4} * sum_j (|x_j| + |o_j|) |w_jk| plus the underflow term, n the
+        columns rounded up to 4).  The same bits whatever the lanes, calls, pieces or cache residency; zero weights are not skipped
+        (inf * 0 is NaN).  weights: (n_cols, n_out) finite numbers, n_cols the
+        number of selected channels and both at most 1024; 1-D weights mean one output and a 1-D result.  offset: None, a finite
+        number or one per column.  Whitening (whitening_weights), projection onto principal components, re-referencing
+        (np.eye(n) - 1 / n) and selecting or scaling channels are all this call.  start / stop follow Reader[...]; channels: an
+        int (weights then have one row), a slice with step >= 1, or a sequence of ints (repeats allowed).  Returns a (stop -
+        start, n_out) array of `dtype`.  Chunks resident in the device cache are read where they lie; the others are decoded in
+        a transient workspace and NOT kept.  A damaged chunk raises the IOError of Reader[...]."""
+        self._need_codec('project', 'project', 'multiplies')
+        out_dtype = _float_dtype(dtype)
+        i0, i1 = self._row_range(start, stop)
+        cols, _ = self._stats_channels(channels)
+        w = np.asarray(weights)
+        if w.dtype.kind not in 'fiu' or w.ndim not in (1, 2):
+            raise ValueError("weights must be a 1-D or 2-D array of numbers")
+        squeeze = w.ndim == 1
+        w = np.ascontiguousarray((w[:, None] if squeeze else w).astype(np.float64))
+        if w.shape[0] != cols.size:
+            raise ValueError("weights have %d rows for %d columns" % (w.shape[0], cols.size))
+        if cols.size > hip.PROJECT_MAX_COLS:
+            raise ValueError("project takes at most %d columns, got %d" % (hip.PROJECT_MAX_COLS, cols.size))
+        if not 1 <= w.shape[1] <= hip.PROJECT_MAX_OUT:
+            raise ValueError("project gives 1 to %d outputs, got %d" % (hip.PROJECT_MAX_OUT, w.shape[1]))
+        if not np.isfinite(w).all():
+            raise ValueError("weights must be finite")
+        off = None
+        if offset is not None:
+            off = np.asarray(offset)
+            if off.dtype.kind not in 'fiu' or off.shape not in ((), (cols.size,)):
+                raise ValueError("offset must be None, a number or one per column (%d)" % cols.size)
+            off = np.ascontiguousarray(np.broadcast_to(off.astype(np.float64), (cols.size,)))
+            if not np.isfinite(off).all():
+                raise ValueError("offset must be finite")
+        n_out = w.shape[1]
+        if not (i1 > i0 and cols.size):                            # (nothing to read: no device call)
+            out = np.zeros((i1 - i0, n_out), out_dtype)
+        else:
+            out = np.empty((i1 - i0, n_out), out_dtype)             # (every row is written by a call)
+            # calls: cut the rows at the chunk boundaries where the compressed bytes pass PROJECT_CALL_BYTES, and so that a call's
+            # result stays within PROJECT_OUT_BYTES
+            rows = max(1, PROJECT_OUT_BYTES // (n_out * out_dtype.itemsize))
+            base = self._halo_cuts(i0, i1, PROJECT_CALL_BYTES, i0, i1, lambda row: row)
+            cuts = [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, rows)] + [i1]
+
+            def part(a, b):
+                return self._chunk_span(a, b), (a, b, cols, off, w, out_dtype)
+            for a, b, (y,) in self._halo_parts(self.codec.project, cuts, part):
+                out[a - i0:b - i0] = y
         return out[:, 0] if squeeze else out
 
     # -- peak detection on the device (an extension: the reference's users filter Reader[...] and look for peaks on the host)

@@ -155,6 +155,8 @@ struct Engine {
     DBuf welch;
     // Gram matrices: columns, slab and group tables, slab partials, the accumulators of the host entry point
     DBuf gram;
+    // channel-mixing products: weights, offsets, columns, segment tables, the output of the host entry point
+    DBuf proj;
     // geometry of the last compress batch whose per-segment / per-block / per-tile descriptors are on the device (a recording is
     // compressed batch after batch of the same shape: the 10 MB of index arrays need not be rebuilt and copied every call)
     // (valid while the three buffers are the allocations the arrays were copied into: DBuf::gen, not the address -- a buffer
@@ -204,7 +206,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &welch, &gram};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &welch, &gram, &proj};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();
@@ -2239,6 +2241,95 @@ static int decimate_run(Engine &E, hipStream_t st, DevCache *cache, const long *
     return MTS_OK;
 }
 
+// ---- channel-mixing products (mts_project, mts_dev_project) --------------------------------------------------------------------
+// The unit is a row and the halo is empty: piece p owns the rows of [row_begin, row_end) in its chunks and reads those chunks alone,
+// so no chunk is decoded twice.  A row's outputs depend on that row only: the result does not depend on the pieces.
+static int project_run(Engine &E, hipStream_t st, DevCache *cache, const long *keys, const u8 *cdata, bool cdata_on_device, const long *c_off,
+                       const long *c_len, const long *row0, const long *n_rows, int n_chunks, int nc, int sz, int flags, long row_begin,
+                       long row_end, int n_cols, const int *cols, const double *offset, int n_out, const double *weights, int osz, void *out,
+                       bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    int rc;
+    if ((rc = check_items(sz, flags))) return rc;
+    if (nc <= 0 || n_chunks < 0) { set_error("project: n_channels or n_chunks invalid"); return MTS_E_ARG; }
+    if (n_cols < 1 || n_cols > MTS_PROJECT_MAX_COLS || !cols) { set_error("project: %d columns (1 .. %d)", n_cols, MTS_PROJECT_MAX_COLS); return MTS_E_ARG; }
+    if (n_out < 1 || n_out > MTS_PROJECT_MAX_OUT || !weights) { set_error("project: %d outputs (1 .. %d)", n_out, MTS_PROJECT_MAX_OUT); return MTS_E_ARG; }
+    if (osz != 4 && osz != 8) { set_error("project: output itemsize %d (4 or 8)", osz); return MTS_E_ARG; }
+    for (long e = 0; e < (long)n_cols * n_out; e++)
+        if (!std::isfinite(weights[e])) { set_error("project: weight (%ld, %ld) is not finite", e / n_out, e % n_out); return MTS_E_ARG; }
+    for (int j = 0; offset && j < n_cols; j++)
+        if (!std::isfinite(offset[j])) { set_error("project: offset %d is not finite", j); return MTS_E_ARG; }
+    if (row_begin < 0 || row_end < row_begin || row_end - row_begin > (1l << 40)) { set_error("project: rows [%ld, %ld) invalid", row_begin, row_end); return MTS_E_ARG; }
+    if (row_end > row_begin && !out) { set_error("project: no output buffer"); return MTS_E_ARG; }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, cache != nullptr, c_len, row0, n_rows, n_chunks, nc, sz))) return rc;
+    if (row_begin < row_end && (n_chunks == 0 || row0[0] > row_begin || row0[n_chunks - 1] + n_rows[n_chunks - 1] < row_end)) {
+        set_error("project: the chunks do not cover rows [%ld, %ld)", row_begin, row_end); return MTS_E_ARG;
+    }
+    for (int i = 0; i < n_chunks; i++) status[i] = MTS_CHUNK_OK;
+    if (row_begin == row_end) return MTS_OK;
+
+    ChunkFeed F(cache, keys, cdata, cdata_on_device, c_off, c_len, n_rows, n_chunks, nc, sz);
+    if ((rc = F.classify())) return rc;
+    // ---- pieces: rows [u0, u1) of the range in chunks [c0, c1]
+    const std::vector<int> pb = F.piece_bounds();
+    std::vector<FeedPiece> pieces;
+    for (size_t p = 0; p + 1 < pb.size(); p++) {
+        if (pb[p + 1] <= pb[p]) continue;
+        FeedPiece P;
+        P.u0 = std::max(row_begin, row0[pb[p]]);
+        P.u1 = std::min(row_end, row0[pb[p + 1] - 1] + n_rows[pb[p + 1] - 1]);
+        if (P.u1 <= P.u0) continue;                               // (chunks outside the range are not read)
+        P.c0 = chunk_of(row0, n_chunks, P.u0); P.c1 = chunk_of(row0, n_chunks, P.u1 - 1);
+        pieces.push_back(std::move(P));
+    }
+    u64 piece_cap;
+    const std::vector<long> seg_at = plan_pieces(F, pieces, &piece_cap);
+    // ---- workspace: weights (padded with zeros to multiples of PROJECT_PAD rows and columns), offsets, columns, segment tables, output
+    const int kp = (int)align_up((u64)n_cols, PROJECT_PAD), wp = (int)align_up((u64)n_out, PROJECT_PAD);
+    const u64 n_items = (u64)(row_end - row_begin) * n_out;
+    const size_t o_w = 0, o_off = align_up((u64)osz * kp * wp, 256), o_cols = o_off + align_up((u64)osz * n_cols, 256),
+                 o_seg = o_cols + align_up(4 * (u64)n_cols, 256), o_out = o_seg + align_up(8 * (u64)(seg_at.back() + 1), 256),
+                 o_end = out_on_host ? o_out + align_up(n_items * osz, 256) : o_out;
+    if ((rc = E.proj.ensure(o_end + 256))) return rc;
+    if ((rc = F.ensure(E, piece_cap))) return rc;
+    u8 *ws = E.proj.as<u8>();
+    // weights and offsets rounded once to the compute type
+    std::vector<u8> h_w((size_t)osz * kp * wp + (size_t)osz * n_cols, 0);
+    u8 *h_off = h_w.data() + (size_t)osz * kp * wp;
+    for (int j = 0; j < n_cols; j++) {
+        if (osz == 4) {
+            float *d = (float *)h_w.data() + (size_t)j * wp;
+            for (int k = 0; k < n_out; k++) d[k] = (float)weights[(size_t)j * n_out + k];
+            ((float *)h_off)[j] = offset ? (float)offset[j] : 0.0f;
+        } else {
+            memcpy(h_w.data() + 8 * (size_t)j * wp, weights + (size_t)j * n_out, 8 * (size_t)n_out);
+            ((double *)h_off)[j] = offset ? offset[j] : 0.0;
+        }
+    }
+    const std::vector<long> seg = segment_tables(F, E, pieces, seg_at, row0);
+    MTS_HIP(hipMemcpyAsync(ws + o_w, h_w.data(), (size_t)osz * kp * wp, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_off, h_off, (size_t)osz * n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_seg, seg.data(), 8 * seg.size(), hipMemcpyHostToDevice, st));
+    void *d_out = out_on_host ? (void *)(ws + o_out) : out;
+    const int dflags = flags & ~MTS_FLAG_UNSIGNED;           // (the decoder compares the transform flags as a whole)
+    rc = feed_pieces(F, E, st, pieces, dflags, status, [&](int p) {
+        const FeedPiece &P = pieces[p];
+        const int r = F.still_placed(P);
+        if (r) return r;
+        const long *sb = (const long *)(ws + o_seg) + seg_at[p];
+        const int ns = P.c1 - P.c0 + 1;
+        return launch_project(st, sz, flags, osz, (const u8 *const *)sb, sb + ns, ns, nc, (const int *)(ws + o_cols), ws + o_off, n_cols, ws + o_w, wp,
+                              n_out, P.u0, P.u1, (u8 *)d_out + (u64)(P.u0 - row_begin) * n_out * osz);
+    });
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_w has been read before it goes)
+    if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, n_items * osz, hipMemcpyDeviceToHost, st));
+    MTS_HIP(hipStreamSynchronize(st));
+    return MTS_OK;
+}
+
 // ---- peak detection (mts_detect, mts_dev_detect) -------------------------------------------------------------------------------
 // The unit is a row.  Piece p owns the rows of [row_begin, row_end) in its chunks; their events need the detection value R rows either
 // side, and that the filter's support: piece p reads the chunks from the one holding u0 - R + half - (L - 1) to the one holding
@@ -2778,6 +2869,30 @@ int mts_dev_decimate(int device, void *stream, const unsigned char *d_cdata, con
         return decimate_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
                             n_channels, itemsize, flags, valid_begin, valid_end, first_row, n_out, q, n_taps, taps, out_itemsize, n_cols, cols,
                             d_out, false, chunk_status);
+    });
+}
+
+int mts_project(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long row_begin,
+                long row_end, int n_cols, const int *cols, const double *offset, int n_out, const double *weights, int out_itemsize, void *out,
+                int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status || (cache_id && !chunk_keys));
+    return host_entry(device, cache_id, bad, [&](Engine &E, DevCache *c) {
+        return project_run(E, nullptr, c, chunk_keys, cdata, false, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize,
+                           flags, row_begin, row_end, n_cols, cols, offset, n_out, weights, out_itemsize, out, true, chunk_status);
+    });
+}
+
+int mts_dev_project(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths, const long *chunk_row0,
+                    const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_begin, long row_end, int n_cols,
+                    const int *cols, const double *offset, int n_out, const double *weights, int out_itemsize, void *d_out, int *chunk_status)
+{
+    const bool bad = n_chunks > 0 && (!d_cdata || !chunk_row0 || !c_offsets || !c_lengths || !n_rows || !chunk_status);
+    return dev_entry(device, bad, [&](Engine &E) {
+        return project_run(E, (hipStream_t)stream, nullptr, nullptr, d_cdata, true, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks,
+                           n_channels, itemsize, flags, row_begin, row_end, n_cols, cols, offset, n_out, weights, out_itemsize, d_out, false,
+                           chunk_status);
     });
 }
 

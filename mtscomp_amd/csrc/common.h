@@ -220,6 +220,15 @@ int launch_gram_combine(hipStream_t st, const double *d_part, const u64 *d_psum,
                         int float_sum, double *d_gram, u64 *d_sum);
 int launch_gram_finish(hipStream_t st, double *d_gram, long n);
 
+// project.hip: channel-mixing products (mts_project).  out[(t - r_begin) * n_out + k] = the chain of 4-column MFMA steps over
+// (x[t, cols[j]] - offs[j]) * w[j, k], j ascending, for file rows t of [r_begin, r_end) in the out_itemsize float type.  d_offs: n_cols
+// values and d_w: (n_cols rounded up to PROJECT_PAD, w_pitch) values of that type, zeros past n_cols and n_out; w_pitch: n_out rounded
+// up to PROJECT_PAD
+constexpr int PROJECT_PAD = 64;
+int launch_project(hipStream_t st, int itemsize, int flags, int out_itemsize, const u8 *const *d_seg_base, const long *d_seg_row0, int n_segs,
+                   int n_channels, const int *d_cols, const void *d_offs, int n_cols, const void *d_w, int w_pitch, int n_out, long r_begin,
+                   long r_end, void *d_out);
+
 // deflate.hip
 size_t hash_sort_ws_bytes(int n_tiles);                            // the one-pass sort's per-tile records
 int launch_hash_sort(hipStream_t st, const u8 *d_stream, const TileDesc *d_tiles, int n_tiles, u32 *d_tmp, u32 *d_sorted,

@@ -105,6 +105,7 @@ def lib():
     for name, mid, tail, dev_tail in (
             ('window_stats', [cl, cl, cl, ci, ip], [vp, vp, vp, vp, lp, ip], None),
             ('decimate', [cl, cl, cl, cl, ci, ci, dp, ci, ci, ip], [vp, ip], None),
+            ('project', [cl, cl, ci, ip, dp, ci, dp, ci], [vp, ip], None),
             ('detect', [cl, cl, cl, cl, ci, dp, ci, ip, fp, ci, ci, ci, ci, cl], [vp, vp, vp, lp, ip], None),
             ('welch', [cl, cl, cl, ci, cl, dp, ci, ci, ci, ip], [vp, ip], None),
             ('gram', [cl, cl, cl, cl, cl, ci, ip], [vp, vp, ip], None),
@@ -123,7 +124,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_last_stage_times', 'mts_debug_match_tables', 'mts_debug_tokens', 'mts_debug_deflate',
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
-           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
+           'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_project', 'mts_dev_project', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
 
 
@@ -609,6 +610,48 @@ def dev_decimate(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid
     mid, shape, out_dtype = _dec_args(valid_begin, valid_end, first_row, n_out, q, taps, out_dtype, cols)
     out, ptrs, at = _dev_results(out, cbuf.device, [shape[0] * shape[1] * out_dtype.itemsize])
     _check(lib().mts_dev_decimate(*head, *mid, *ptrs, _ip(status)), 'mts_dev_decimate')
+    res = _dev_fetch(out, at, [np.empty(shape, out_dtype)])[0] if download else None
+    return _status(status, n), res, out
+
+
+# -- channel-mixing matrix products
+PROJECT_MAX_COLS = 1024                # MTS_PROJECT_MAX_COLS
+PROJECT_MAX_OUT = 1024                 # MTS_PROJECT_MAX_OUT
+
+
+def _proj_args(row_begin, row_end, cols, offset, weights, out_dtype):
+    """-> (the op's own arguments of mts_project, the shape of the result, its dtype)."""
+    cols = _cols32(cols)
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+    assert w.ndim == 2 and w.shape[0] == cols.size, 'weights must be (n_cols, n_out)'
+    off = None if offset is None else np.ascontiguousarray(np.broadcast_to(np.asarray(offset, dtype=np.float64), (cols.size,)))
+    out_dtype = np.dtype(out_dtype)
+    mid = (int(row_begin), int(row_end), int(cols.size), _ip(cols), None if off is None else _dp(off), int(w.shape[1]), _dp(w),
+           out_dtype.itemsize)
+    return mid, (max(int(row_end) - int(row_begin), 0), int(w.shape[1])), out_dtype, (cols, off, w)
+
+
+def project(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, row_begin, row_end, cols, offset, weights, out_dtype,
+            device=0):
+    """mts_project: y[t, k] = sum_j (x[t, cols[j]] - offset[j]) * weights[j, k] for file rows [row_begin, row_end), from the adjacent
+    chunks `keys` (file rows [row0[i], row0[i] + n_rows[i])); weights (n_cols, n_out), offset None, a scalar or (n_cols,).  cache_id 0:
+    no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status
+    list, (row_end - row_begin, n_out) out_dtype)."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, shape, out_dtype, _keep = _proj_args(row_begin, row_end, cols, offset, weights, out_dtype)
+    out = np.empty(shape, out_dtype)
+    _check(lib().mts_project(*head, *mid, _ptr(out), _ip(status)), 'mts_project')
+    return _status(status, n), out
+
+
+def dev_project(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_begin, row_end, cols, offset, weights, out_dtype, out=None,
+                download=True):
+    """mts_dev_project on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the result (made when None;
+    returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, shape, out_dtype, _keep = _proj_args(row_begin, row_end, cols, offset, weights, out_dtype)
+    out, ptrs, at = _dev_results(out, cbuf.device, [shape[0] * shape[1] * out_dtype.itemsize])
+    _check(lib().mts_dev_project(*head, *mid, *ptrs, _ip(status)), 'mts_dev_project')
     res = _dev_fetch(out, at, [np.empty(shape, out_dtype)])[0] if download else None
     return _status(status, n), res, out
 
