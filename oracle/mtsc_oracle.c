@@ -273,6 +273,7 @@ typedef struct {
     int heap[HEAP_SIZE]; int heap_len, heap_max;
     uint8_t depth[HEAP_SIZE];
     uint16_t bl_count[16];
+    int ovf[3];                 /* gen_bitlen's overflow before the repair loop, per tree kind (report only) */
 } blk_t;
 
 #define SMALLER(t, n, m) ((t)->freq[n] < (t)->freq[m] || ((t)->freq[n] == (t)->freq[m] && b->depth[n] <= b->depth[m]))
@@ -339,6 +340,7 @@ static void build_tree(blk_t *b, tree_t *t, int kind)
         if (kind == 0) b->static_len += f * (static_llen[n] + xbits);
         else if (kind == 1) b->static_len += f * (5 + xbits);
     }
+    b->ovf[kind] = overflow;
     if (overflow > 0) {
         do {
             bits = max_length - 1;
@@ -440,6 +442,8 @@ typedef struct {
     long opt_len, static_len;   /* in bits, as trees.c computes them (before the +3) */
     int btype, last;            /* 0 stored, 1 fixed, 2 dynamic */
     long bit_start, bit_end;    /* bit offsets in the zlib stream (incl. the 2-byte header) */
+    int ovf_l, ovf_d, ovf_bl;   /* gen_bitlen's overflow before the repair loop: literal/length, distance, bit-length tree */
+    long hdr_bits;              /* dynamic blocks: HLIT .. the last tree code, i.e. without the 3 block-type bits; else 0 */
 } orc_block_info;
 
 /* _tr_flush_block */
@@ -476,7 +480,7 @@ static void flush_block(bitw *w, const uint8_t *in, long in_start, long in_len, 
     b->opt_len += 3 * (max_blindex + 1) + 5 + 5 + 4;
     long opt_lenb = (b->opt_len + 3 + 7) >> 3, static_lenb = (b->static_len + 3 + 7) >> 3;
     if (static_lenb <= opt_lenb) opt_lenb = static_lenb;
-    long bit_start = w->pos * 8 + w->nbits;
+    long bit_start = w->pos * 8 + w->nbits, hdr_bits = 0;
     int btype;
     if (in_len + 4 <= opt_lenb && buf_ok) {
         btype = 0;
@@ -497,6 +501,7 @@ static void flush_block(bitw *w, const uint8_t *in, long in_start, long in_len, 
         for (int rank = 0; rank < max_blindex + 1; rank++) bw_put(w, b->bl.len[bl_order[rank]], 3);
         send_tree(b, w, &b->lt, b->lt.max_code);
         send_tree(b, w, &b->dt, b->dt.max_code);
+        hdr_bits = w->pos * 8 + w->nbits - bit_start - 3;
         compress_block(w, tk, ntok, b->lt.code, b->lt.len, b->dt.code, b->dt.len);
     }
     if (last) bw_align(w);
@@ -505,6 +510,7 @@ static void flush_block(bitw *w, const uint8_t *in, long in_start, long in_len, 
         info->opt_len = b->opt_len; info->static_len = b->static_len;
         info->btype = btype; info->last = last;
         info->bit_start = bit_start; info->bit_end = w->pos * 8 + w->nbits;
+        info->ovf_l = b->ovf[0]; info->ovf_d = b->ovf[1]; info->ovf_bl = b->ovf[2]; info->hdr_bits = hdr_bits;
     }
     free(b);
 }

@@ -40,7 +40,8 @@ class BlockInfo(C.Structure):
     _fields_ = [('tok_start', C.c_long), ('ntok', C.c_long), ('in_start', C.c_long),
                 ('in_len', C.c_long), ('opt_len', C.c_long), ('static_len', C.c_long),
                 ('btype', C.c_int), ('last', C.c_int), ('bit_start', C.c_long),
-                ('bit_end', C.c_long)]
+                ('bit_end', C.c_long),
+                ('ovf_l', C.c_int), ('ovf_d', C.c_int), ('ovf_bl', C.c_int), ('hdr_bits', C.c_long)]
 
 
 _lib = None
