@@ -1,0 +1,215 @@
+// How a reduction is fed: the part that decides and touches no device.  Which chunks go into which piece, where the compressed
+// bytes of the missing chunks lie in the staging buffer, where each of them is decoded to, which chunks a piece of the halo family
+// reads and what its segment table holds, how the tile family cuts and orders its tiles.  Addresses are plain integers here: the
+// header includes the C++ standard library only, so tests/plan_check.cpp sweeps these plans on the CPU.  reduce.hip puts the
+// device side around them (ChunkFeed, feed_pieces, HaloFeed, TileFeed) and says there what every caller keeps to.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+namespace mts {
+
+// chunks [pb[p], pb[p + 1]) make piece p: a piece ends before the chunk that would take it past `piece` bytes (0: one piece)
+inline std::vector<int> cut_pieces(const long *n_rows_or_bounds, bool is_bounds, int n_chunks, uint64_t row_bytes, size_t piece)
+{
+    std::vector<int> pb = {0};
+    if (piece) {
+        uint64_t acc = 0;
+        for (int i = 0; i < n_chunks; i++) {
+            const uint64_t n = (uint64_t)(is_bounds ? n_rows_or_bounds[i + 1] - n_rows_or_bounds[i] : n_rows_or_bounds[i]) * row_bytes;
+            if (acc && acc + n > piece) { pb.push_back(i); acc = 0; }
+            acc += n;
+        }
+    }
+    pb.push_back(n_chunks);
+    return pb;
+}
+
+// one piece: the missing chunks `miss` (ascending) are decoded to the piece workspace + ooff[]; a halo piece covers the op's units
+// [u0, u1) and reads chunks [c0, c1] (c1 < c0: nothing to read)
+struct FeedPiece {
+    long u0 = 0, u1 = 0;
+    int c0 = 0, c1 = -1;
+    std::vector<int> miss;
+    std::vector<long> ooff;
+    uint64_t ws = 0;
+    void add(int chunk, uint64_t bytes) { miss.push_back(chunk); ooff.push_back((long)ws); ws += (bytes + 255) / 256 * 256; }
+};
+
+// what the plans know of a call's chunks: the table, which chunks are resident (set by the owner before layout()), and the
+// layout of the missing chunks' compressed bytes in the staging buffer
+struct FeedPlan {
+    const long *c_off, *c_len, *row0, *n_rows;
+    int n_chunks;
+    uint64_t row_bytes;
+    bool on_device;
+    std::vector<char> resident;
+    std::vector<long> mcoff;                                  // per missing chunk: its compressed bytes in the staging buffer
+    uint64_t ctot = 0;
+    bool any_miss = false;
+
+    FeedPlan(const long *c_off_, const long *c_len_, const long *row0_, const long *n_rows_, int n_chunks_, uint64_t row_bytes_, bool on_device_)
+        : c_off(c_off_), c_len(c_len_), row0(row0_), n_rows(n_rows_), n_chunks(n_chunks_), row_bytes(row_bytes_), on_device(on_device_),
+          resident(n_chunks_, 0), mcoff(n_chunks_, 0) {}
+
+    uint64_t chunk_bytes(int i) const { return (uint64_t)n_rows[i] * row_bytes; }
+
+    // The compressed bytes of the missing chunks lie in the staging buffer in chunk order, at mcoff[]: chunks back to back in the
+    // caller's buffer keep their distances (a run of them with adjacent chunk indices is one staged copy), a gap starts at the next
+    // multiple of 16; ctot leaves 16 bytes behind the last.  Device input stays where it is.
+    // -> the first missing chunk without compressed bytes, or -1
+    int layout()
+    {
+        int prev = -1;
+        for (int i = 0; i < n_chunks; i++) {
+            if (resident[i]) continue;
+            if (c_len[i] == 0) return i;
+            any_miss = true;
+            if (on_device) { mcoff[i] = c_off[i]; continue; }
+            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
+            if (!joins) ctot = (ctot + (prev >= 0 ? 16 : 0) + 15) / 16 * 16;
+            mcoff[i] = (long)ctot; ctot += (uint64_t)c_len[i];
+            prev = i;
+        }
+        ctot += 16;
+        return -1;
+    }
+
+    // chunks [pb[p], pb[p + 1]) are decoded in piece p: pieces of `piece` decoded bytes, resident chunks weigh nothing; device
+    // input is one piece (nothing to copy beside the kernels, and smaller batches inflate slower)
+    std::vector<int> piece_bounds(size_t piece) const
+    {
+        if (on_device) return {0, n_chunks};
+        std::vector<long> weight(n_chunks, 0);
+        for (int i = 0; i < n_chunks; i++) if (!resident[i]) weight[i] = n_rows[i];
+        return cut_pieces(weight.data(), false, n_chunks, row_bytes, piece);
+    }
+
+    // the chunk holding `row` (clamped to the chunks)
+    int chunk_of(long row) const
+    {
+        int lo = 0, hi = n_chunks - 1;
+        while (lo < hi) { const int mid = (lo + hi + 1) / 2; if (row0[mid] <= row) lo = mid; else hi = mid - 1; }
+        return lo;
+    }
+};
+
+// ---- halo family: a unit of output (outputs, rows, blocks, groups) reads rows of several adjacent chunks.  The op says which:
+//   first(r)               the first unit owned by a piece that starts at file row r (any value: it is clamped to [0, n_units]);
+//   rows(u0, u1, &lo, &hi) the file rows [lo, hi) that the units [u0, u1) read; lo >= hi: none (c1 < c0, every row is 0).
+// Piece p owns the units from first(first row of its chunks) up to the next piece's; the pieces partition the units in order and a
+// piece without units is left out.  A piece reads chunks [c0, c1] through a table of segment bases and first rows ((c1 - c0 + 1)
+// bases, then (c1 - c0 + 2) first rows) and decodes the missing ones among them to ooff[] of the piece workspace: a boundary chunk
+// that two pieces read is decoded in both, chunks that no unit reads are not decoded at all.
+struct HaloPlan {
+    std::vector<FeedPiece> pieces;
+    std::vector<long> seg_at = {0};                           // piece p's table: seg[seg_at[p] ..)
+    uint64_t piece_cap = 0;
+
+    template <class First, class Rows>
+    HaloPlan(const FeedPlan &F, size_t piece, long n_units, First &&first, Rows &&rows)
+    {
+        const std::vector<int> pb = F.piece_bounds(piece);
+        const int np = (int)pb.size() - 1;
+        std::vector<long> cut = {0};
+        for (int p = 1; p < np; p++) cut.push_back(std::max(cut.back(), std::min(n_units, std::max(0l, (long)first(F.row0[pb[p]])))));
+        cut.push_back(n_units);
+        for (int p = 0; p < np; p++) {
+            if (cut[p + 1] <= cut[p]) continue;
+            FeedPiece P;
+            P.u0 = cut[p]; P.u1 = cut[p + 1];
+            long lo = 0, hi = 0;
+            rows(P.u0, P.u1, &lo, &hi);
+            if (lo < hi && F.n_chunks) { P.c0 = F.chunk_of(lo); P.c1 = F.chunk_of(hi - 1); }
+            for (int i = P.c0; i <= P.c1; i++) if (!F.resident[i]) P.add(i, F.chunk_bytes(i));
+            piece_cap = std::max(piece_cap, P.ws);
+            seg_at.push_back(seg_at.back() + 2l * (P.c1 - P.c0 + 1) + 1);
+            pieces.push_back(std::move(P));
+        }
+    }
+
+    // the segment tables, one after the other: res_base[i] is the address of resident chunk i, out_base that of the piece workspace
+    std::vector<long> tables(const FeedPlan &F, const uintptr_t *res_base, uintptr_t out_base) const
+    {
+        std::vector<long> seg(seg_at.back() + 1, 0);
+        for (size_t p = 0; p < pieces.size(); p++) {
+            const FeedPiece &P = pieces[p];
+            long *b = seg.data() + seg_at[p], *r = b + (P.c1 - P.c0 + 1);
+            size_t m = 0;
+            for (int i = P.c0; i <= P.c1; i++) {
+                b[i - P.c0] = (long)(F.resident[i] ? res_base[i] : out_base + (uintptr_t)P.ooff[m++]);
+                r[i - P.c0] = F.row0[i];
+            }
+            r[P.c1 - P.c0 + 1] = P.c1 >= P.c0 ? F.row0[P.c1] + F.n_rows[P.c1] : 0;
+        }
+        return seg;
+    }
+};
+
+// ---- tile family: the rows of every (chunk ∩ window) segment cut into tiles of tile_rows rows, in row order; a chunk's rows are
+// reduced on their own, so each piece decodes exactly its own missing chunks.  Tile is the kernels' descriptor
+// { base, row_lo, n_rows, chunk, pad }.
+template <class Tile>
+struct TilePlan {
+    std::vector<Tile> tiles;
+    std::vector<long> tile_win, chunk_tile0;
+    std::vector<FeedPiece> pieces;
+    uint64_t piece_cap = 0;
+    std::vector<int> ids;                                     // the tiles in launch order: the resident chunks', then piece after piece
+    std::vector<long> launch0;                                // ids [launch0[0], launch0[1]): resident, [launch0[1 + p], launch0[2 + p]): piece p
+
+    TilePlan(const FeedPlan &F, size_t piece, long row_begin, long row_end, long window_rows, long tile_rows) : chunk_tile0(F.n_chunks + 1)
+    {
+        for (int i = 0; i < F.n_chunks; i++) {
+            chunk_tile0[i] = (long)tiles.size();
+            const long a = std::max(F.row0[i], row_begin), b = std::min(F.row0[i] + F.n_rows[i], row_end);
+            for (long r = a; r < b;) {
+                const long w = (r - row_begin) / window_rows, wend = row_begin + (w + 1) * window_rows, e = b < wend ? b : wend;
+                for (long q = r; q < e; q += tile_rows) {
+                    Tile t;
+                    t.base = nullptr; t.row_lo = q - F.row0[i]; t.n_rows = (e - q) < tile_rows ? (e - q) : tile_rows; t.chunk = i; t.pad = 0;
+                    tiles.push_back(t);
+                    tile_win.push_back(w);
+                }
+                r = e;
+            }
+        }
+        chunk_tile0[F.n_chunks] = (long)tiles.size();
+        const std::vector<int> pb = F.piece_bounds(piece);
+        for (size_t p = 0; p + 1 < pb.size(); p++) {
+            FeedPiece P;
+            for (int i = pb[p]; i < pb[p + 1]; i++) if (!F.resident[i]) P.add(i, F.chunk_bytes(i));
+            if (P.miss.empty()) continue;
+            piece_cap = std::max(piece_cap, P.ws);
+            pieces.push_back(std::move(P));
+        }
+    }
+
+    // the tiles' bases and the order of the launches (res_base, out_base as in HaloPlan::tables)
+    void place(const FeedPlan &F, const uintptr_t *res_base, uintptr_t out_base)
+    {
+        auto take = [&](int i, uintptr_t base) {
+            for (long t = chunk_tile0[i]; t < chunk_tile0[i + 1]; t++) { tiles[t].base = (decltype(tiles[t].base))base; ids.push_back((int)t); }
+        };
+        launch0.push_back(0);
+        for (int i = 0; i < F.n_chunks; i++) if (F.resident[i]) take(i, res_base[i]);
+        for (const FeedPiece &P : pieces) {
+            launch0.push_back((long)ids.size());
+            for (size_t z = 0; z < P.miss.size(); z++) take(P.miss[z], out_base + (uintptr_t)P.ooff[z]);
+        }
+        launch0.push_back((long)ids.size());
+    }
+
+    // ok[chunk]: its rows count
+    void add_counts(const std::vector<int> &ok, long *count) const
+    {
+        for (size_t t = 0; t < tiles.size(); t++) if (ok[tiles[t].chunk]) count[tile_win[t]] += tiles[t].n_rows;
+    }
+};
+
+}  // namespace mts

@@ -121,13 +121,13 @@ class StatsOracleCodec(LaneOracleCodec):
 
 
 # ---- exact references: what the kernels' sums must come within a stated bound of -----------------------------------------------
-STAT_TILE_ROWS = 512                     # api.hip: rows per tile of one (chunk ∩ window) segment
+STAT_TILE_ROWS = 512                     # reduce.hip: rows per tile of one (chunk ∩ window) segment
 STAT_WAVES = 4                           # stats.hip: waves per tile, each taking every 4th row
 U = 2.0 ** -53                           # unit roundoff of float64
 
 
 def stat_tiles_per_window(chunk_bounds, start, stop, window):
-    """(tiles of each window, rows of its largest tile): the tiling of api.hip's window_stats_run -- every (chunk ∩ window)
+    """(tiles of each window, rows of its largest tile): the tiling of reduce_plan.h's TilePlan for window_stats_run -- every (chunk ∩ window)
     segment of [start, stop) cut into STAT_TILE_ROWS-row tiles."""
     n = stop - start
     nw = -(-n // window) if n > 0 else 0
