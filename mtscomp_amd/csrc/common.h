@@ -5,13 +5,9 @@
 #include <stddef.h>
 
 #include "../../include/mtscomp_hip.h"
+#include "codec_plan.h"      // the descriptors and constants the host plans share with the kernels: TileDesc, ChunkDesc, InfChunk, TILE, HALO, SEG, ...
 
 namespace mts {
-
-typedef uint8_t u8;
-typedef uint16_t u16;
-typedef uint32_t u32;
-typedef uint64_t u64;
 
 // ---- DEFLATE constants (zlib 1.2.11, windowBits 15, memLevel 8) --------------------------------
 constexpr int MIN_MATCH = 3;
@@ -19,68 +15,13 @@ constexpr int MAX_MATCH = 258;
 constexpr int WSIZE = 32768;
 constexpr int MAX_DIST = WSIZE - 262;      // 32506
 constexpr int TOO_FAR = 4096;
-constexpr int BLOCK_TOKENS = 16383;        // lit_bufsize - 1
 constexpr int L_CODES = 286;
 constexpr int D_CODES = 30;
 constexpr int BL_CODES = 19;
 
-// ---- stream layout ------------------------------------------------------------------------------
-// Every chunk's transformed byte stream lives in one device buffer at a 256-B aligned offset and is
-// followed by >= STREAM_PAD zero bytes, so kernels may over-read past a stream's end.
-constexpr int STREAM_PAD = 512;
-constexpr int STREAM_ALIGN = 256;
-
-// ---- match stage tiling ---------------------------------------------------------------------------
-// A tile's history (HALO) is sorted and staged again by the next tile, so bigger tiles mean less work.  While every
-// workgroup read its own window through L2, big tiles lost to locality (round 1: 64..96 Ki 41-42 ms, 160 Ki 53, 224 Ki 60);
-// with the workgroups of an XCD sharing a tile the window is L2 resident whatever its size and the biggest tile the 18-bit
-// window-relative positions allow wins (match 31 -> 28.5 ms, sort 12.9 -> 11.4 from 96 Ki to 224 Ki).
-// The 32-bit sort keys hold the window-relative position (REL_BITS allow windows up to 2^18) and the 7 hash bits
-// the second radix pass still needs; the first pass takes its 8 bits straight from the bytes.
-#ifndef MTS_REL_BITS
-#define MTS_REL_BITS 18
-#endif
-constexpr int REL_BITS = MTS_REL_BITS;     // 18 or 19 (a match entry word holds rel : 9 bits : the low bits of byte 7)
-constexpr int HALO = 32768;                // history a tile additionally needs (>= MAX_DIST)
-constexpr int WIN = 1 << REL_BITS;         // hashed window of a tile
-#ifndef MTS_TILE
-#define MTS_TILE (WIN - HALO)
-#endif
-constexpr int TILE = MTS_TILE;             // positions a match-stage workgroup owns (229376 / 491520; anything up to WIN - HALO)
-static_assert(TILE > 0 && TILE + HALO <= WIN && TILE % 64 == 0, "a tile and its history fit the window");
 constexpr u32 REL_MASK = (1u << REL_BITS) - 1;
 
-constexpr int SEG = 1024;                  // parse segment (positions per speculative walker); measured 512: 9.0, 1024: 8.5, 2048: 8.9, 4096: 9.3 ms (fixpoint + emit)
-
 struct LevelCfg { int good, lazy, nice, chain; };
-
-// one match-stage tile
-struct TileDesc {
-    u64 stream_off;      // byte offset of the chunk's stream in the stream buffer
-    u64 sorted_off;      // entry offset of this tile's sorted window in the sort buffers
-    u32 n;               // stream length (bytes) of the chunk
-    u32 a;               // first owned position
-    u32 w;               // window start (= max(0, a - HALO))
-    u32 wlen;            // hashed positions in the window: positions [w, w + wlen), all <= n - 3
-    u32 own_end;         // owned positions are [a, own_end)
-    u32 chunk;
-};
-
-// per-chunk descriptor of a compress batch
-struct ChunkDesc {
-    u64 stream_off;      // into the stream buffer
-    u64 tok_off;         // into the token buffer (capacity n + 1 tokens)
-    u64 out_off;         // byte offset of the chunk's slot in the output buffer (16-B aligned)
-    u64 raw_off;         // byte offset of the chunk's first row in the raw input
-    u32 n;               // stream bytes
-    u32 n_rows;
-    u32 seg0;            // first parse segment (global index)
-    u32 nseg;
-    u32 blk0;            // first block slot (global index); capacity n / 16383 + 2
-    u32 blk_cap;
-    u32 tile0;           // first match-stage tile of the chunk (global index)
-    u32 pad;
-};
 
 // per-block record produced by the tree stage
 struct BlockRec {
@@ -99,8 +40,6 @@ struct ChunkOut {
     u32 adler;
     u32 trailing;            // last token is the post-loop literal
 };
-
-inline __host__ __device__ u64 align_up(u64 x, u64 a) { return (x + a - 1) / a * a; }
 
 // wave-wide predicates straight from the condition's lane mask (HIP's __ballot / __any take an int: the mask is first turned into a
 // value per lane -- v_cndmask -- and compared again -- v_cmp: two vector instructions per use in kernels that are bound by them)
@@ -282,16 +221,6 @@ constexpr int BLK_CODE_WORDS = 320;     // per block: 286 lit/len + 30 dist (cod
 constexpr int BLK_HDR_WORDS = 96;       // per block: packed dynamic-tree header bits (<= 3072 bits)
 
 // inflate.hip
-struct InfChunk {
-    u64 c_off;           // compressed bytes offset in d_cdata
-    u64 c_len;
-    u64 stream_off;      // where the inflated stream goes (stream buffer)
-    u64 tok_off;         // token buffer offset (capacity n + 2)
-    u32 n_expect;        // expected inflated size (the whole chunk)
-    u32 n_need;          // 0, or: only the first n_need bytes of the stream are wanted (the leading channels of a channel-major
-                         // chunk, for Reader[rows, columns]): the block chain stops once it has them, c_len may be a prefix of
-                         // the chunk's bytes, no adler32 check; MTS_CHUNK_NEEDMORE when the bytes given do not get that far
-};
 constexpr int MTS_CHUNK_NEEDMORE = 1;      // internal per-chunk status (never leaves the library: the cache answers MTS_E_MISS)
 struct InfResult {
     int status;          // MTS_CHUNK_*
@@ -304,7 +233,7 @@ int launch_inflate(hipStream_t st, const u8 *d_cdata, const InfChunk *d_chunks, 
                    u8 *d_stream, u32 *d_tokens, InfResult *d_res, u64 *d_adler_acc, u32 max_n, int *d_status_out,
                    void *d_scratch, void *engine);
 size_t inflate_scratch_bytes(int n_chunks, const u64 *c_lens, const u32 *n_expect);
-void inflate_mark(void *engine, hipStream_t st, const char *name);   // stage timing hook (api.hip)
-u8 *inflate_host_stage(void *engine, size_t bytes);                    // zeroed host bytes the engine keeps until the next batch (api.hip)
+void inflate_mark(void *engine, hipStream_t st, const char *name);   // stage timing hook (codec.hip)
+u8 *inflate_host_stage(void *engine, size_t bytes);                    // zeroed host bytes the engine keeps until the next batch (codec.hip)
 
 }  // namespace mts

@@ -1,11 +1,14 @@
-// What the codec (api.hip) and the reductions (reduce.hip) share: the per-device engine and its workspaces, the decoded-chunk
-// cache, the staged copies and the decoder's entry.  The functions declared here are defined in api.hip.
+// What the codec (codec.hip), the decoded-chunk cache (cache.hip) and the reductions (reduce.hip) share: the per-device engine and
+// its workspaces, the entry guard, the cache's state, the staged copies, the piece loop and the decoder's entry.  Of the functions
+// declared here the engine registry, the arena and the staged copies are defined in api.hip, the cache registry in cache.hip, the
+// sub-batch drivers in codec.hip.
 #pragma once
 
 #include <string.h>
 
 #include <future>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -155,6 +158,22 @@ struct Engine {
 
 int get_engine(int device, Engine **out);
 
+// What an entry point begins with: open() finds the engine (MTS_E_NODEV, MTS_E_ARG), enter() takes its lock and makes its device
+// current.  The entry's own argument checks stand wherever they stood, between or behind the two.
+struct MTS_LOCAL EngineLock {
+    Engine *E = nullptr;
+    std::unique_lock<std::mutex> lk;
+    int open(int device) { return get_engine(device, &E); }
+    int enter()
+    {
+        lk = std::unique_lock<std::mutex>(E->mu);
+        MTS_HIP(hipSetDevice(E->dev));
+        return MTS_OK;
+    }
+    Engine *operator->() const { return E; }
+    Engine &operator*() const { return *E; }
+};
+
 // ---- decoded-chunk cache on the device (Reader random access) ------------------------------------
 struct CacheEntry { u8 *d = nullptr; u64 cap = 0, size = 0, stamp = 0; long rows = 0; int cols = 0; };      // (rows, cols) C order; cols < n_channels: the leading channels only
 struct DevCache {
@@ -206,9 +225,27 @@ DevCache *find_cache(long id, int *device = nullptr);
 // mts_cache_destroy unregisters a cache first and frees it under its engine's lock; an entry point that looked the cache
 // up before it took that lock asks again once it holds it, and never touches a cache that has gone in between
 bool cache_alive(long id, const DevCache *c);
+struct MTS_LOCAL CacheLock : EngineLock {
+    DevCache *c = nullptr;
+    int dev = 0;
+    bool find(long id) { c = find_cache(id, &dev); return c != nullptr; }
+    int open() { return EngineLock::open(dev); }
+    int enter(long id)
+    {
+        lk = std::unique_lock<std::mutex>(E->mu);
+        if (!cache_alive(id, c)) return MTS_E_ARG;             // (destroyed while this call waited for the engine)
+        MTS_HIP(hipSetDevice(E->dev));
+        return MTS_OK;
+    }
+};
+
+void clear_caches_of(int device) MTS_LOCAL;      // empties the caches of a device (the caller holds its engine's lock)
 
 // user memory -> device through the pinned pieces; complete on return
 int staged_h2d(Engine &E, void *d_dst, const void *src, size_t n);
+// device -> user memory, any number of pieces; the device data must be complete
+struct CopyItem { void *dst; const void *src; size_t n; };
+int staged_d2h_multi(Engine &E, const std::vector<CopyItem> &segs) MTS_LOCAL;
 
 // a piece's copy on a helper thread; when no thread can be started (std::system_error) the copy is made at once, on this one
 template <class F>
@@ -224,6 +261,30 @@ std::future<int> copy_beside(F &&f, int k)
         return p.get_future();
     }
 }
+
+// Piece after piece: while work(k) runs here, copy_in(k + 1) and copy_out(k - 1) (when there is one) run on helper threads.  Piece
+// 0's copy in and the last piece's copy out are made on this thread.  Every helper is joined before the return, on error paths too:
+// the copies hold references to the caller's frame.  Of several errors work's comes first, then copy_in's, then copy_out's.
+template <class In, class Work, class Out>
+int run_pieces(int np, In &&copy_in, Work &&work, Out &&copy_out)
+{
+    constexpr bool has_out = !std::is_same<typename std::decay<Out>::type, std::nullptr_t>::value;
+    int rc;
+    if (np > 0 && (rc = copy_in(0))) return rc;
+    for (int k = 0; k < np; k++) {
+        std::future<int> f_in, f_out;
+        if (k + 1 < np) f_in = copy_beside(copy_in, k + 1);
+        if constexpr (has_out) { if (k >= 1) f_out = copy_beside(copy_out, k - 1); }
+        rc = work(k);
+        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK, rc_out = f_out.valid() ? f_out.get() : MTS_OK;
+        if (rc || rc_in || rc_out) return rc ? rc : rc_in ? rc_in : rc_out;
+    }
+    if constexpr (has_out) { if (np > 0) return copy_out(np - 1); }
+    return MTS_OK;
+}
+template <class In, class Work>
+int run_pieces(int np, In &&copy_in, Work &&work) { return run_pieces(np, copy_in, work, nullptr); }
+
 size_t pipe_piece_bytes();      // MTS_PIPE_BYTES, read per call
 std::vector<int> pipe_pieces(const long *n_rows_or_bounds, bool is_bounds, int n_chunks, u64 row_bytes);
 

@@ -40,9 +40,10 @@ using namespace mts;
 //     launch that every resident chunk the piece reads is still in the cache at the address its table holds (HaloFeed::run, the
 //     only way to a piece's table).
 //   - The helper thread's copy of piece p + 1 starts before piece p's decode and is always joined before feed_pieces returns, on
-//     error paths too: it holds references to the caller's frame.
+//     error paths too: it holds references to the caller's frame (run_pieces, engine.h).
 //   - The first dev_decompress of a call starts the stage times (add_times false), every later one adds to them.
-//   - The compressed bytes of the missing chunks lie in E.h_in in chunk order, at mcoff[] (FeedPlan::layout).
+//   - The compressed bytes of the missing chunks lie in E.h_in in chunk order, at mcoff[] (FeedPlan::layout: the run-joined rule of
+//     codec_plan.h, which the decoded-chunk cache stages by as well).
 namespace {
 
 // the chunks of a call as every entry point receives them.  bad: a pointer the table needs is null -- the entry's own check,
@@ -146,16 +147,6 @@ void status_ok(const ChunkTable &T, int *status)
     for (int i = 0; i < T.n_chunks; i++) status[i] = MTS_CHUNK_OK;
 }
 
-// ---- an op's workspace: regions of 256-aligned sizes one behind the other, the outputs last.  An output lies in the workspace
-// only when the caller's buffer is host memory (out_on_host: it is copied there at the end); a device buffer is written directly.
-struct WsLayout {
-    bool out_on_host;
-    size_t end = 0;
-    size_t take(u64 bytes) { const size_t o = end; end += align_up(bytes, 256); return o; }
-    size_t take_out(u64 bytes) { return out_on_host ? take(bytes) : end; }
-    template <class T> T *out(u8 *ws, size_t off, T *caller) const { return out_on_host ? (T *)(ws + off) : caller; }
-};
-
 // which chunks of a call are resident, where the bytes of the others lie (FeedPlan), and their way into E.h_out
 struct ChunkFeed : FeedPlan {
     DevCache *cache;
@@ -212,16 +203,8 @@ struct ChunkFeed : FeedPlan {
     {
         if (on_device) return MTS_OK;
         MTS_HIP(hipSetDevice(E.dev));
-        for (size_t a = 0; a < chunks.size();) {
-            if (copied[chunks[a]]) { a++; continue; }
-            size_t e = a + 1;                                     // a run of chunks back to back here and in the caller's buffer
-            while (e < chunks.size() && !copied[chunks[e]] && chunks[e] == chunks[e - 1] + 1 &&
-                   c_off[chunks[e]] == c_off[chunks[e - 1]] + c_len[chunks[e - 1]] && mcoff[chunks[e]] == mcoff[chunks[e - 1]] + c_len[chunks[e - 1]]) e++;
-            u64 len = 0;
-            for (size_t z = a; z < e; z++) { len += (u64)c_len[chunks[z]]; copied[chunks[z]] = 1; }
-            if (len) { const int rc = staged_h2d(E, E.h_in.as<u8>() + mcoff[chunks[a]], cdata + c_off[chunks[a]], (size_t)len); if (rc) return rc; }
-            a = e;
-        }
+        for (const StageCopy &c : run_copies(c_off, c_len, mcoff.data(), chunks.data(), (int)chunks.size(), copied.data()))
+            if (const int rc = staged_h2d(E, E.h_in.as<u8>() + c.dst, cdata + c.src, (size_t)c.len)) return rc;
         return MTS_OK;
     }
 
@@ -256,19 +239,8 @@ struct ChunkFeed : FeedPlan {
 template <class Launch>
 int feed_pieces(ChunkFeed &F, Engine &E, hipStream_t st, const std::vector<FeedPiece> &pieces, int *status, Launch &&launch)
 {
-    auto copy_in = [&](int p) -> int { return F.copy_in(E, pieces[p].miss); };
-    const int np = (int)pieces.size();
-    int rc;
-    if (np > 0 && (rc = copy_in(0))) return rc;
-    for (int p = 0; p < np; p++) {
-        std::future<int> f_in;
-        if (p + 1 < np) f_in = copy_beside(copy_in, p + 1);
-        rc = F.decode(E, st, pieces[p], status);
-        if (!rc) rc = launch(p);
-        const int rc_in = f_in.valid() ? f_in.get() : MTS_OK;      // (always joined: it holds references to this frame)
-        if (rc || rc_in) return rc ? rc : rc_in;
-    }
-    return MTS_OK;
+    return run_pieces((int)pieces.size(), [&](int p) -> int { return F.copy_in(E, pieces[p].miss); },
+                      [&](int p) -> int { const int rc = F.decode(E, st, pieces[p], status); return rc ? rc : launch(p); });
 }
 
 // ---- halo family: the device side of a HaloPlan, in three steps with the op's own regions, uploads and kernel between them:

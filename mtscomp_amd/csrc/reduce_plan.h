@@ -12,6 +12,8 @@
 #include <utility>
 #include <vector>
 
+#include "codec_plan.h"
+
 namespace mts {
 
 // chunks [pb[p], pb[p + 1]) make piece p: a piece ends before the chunk that would take it past `piece` bytes (0: one piece)
@@ -59,24 +61,20 @@ struct FeedPlan {
 
     uint64_t chunk_bytes(int i) const { return (uint64_t)n_rows[i] * row_bytes; }
 
-    // The compressed bytes of the missing chunks lie in the staging buffer in chunk order, at mcoff[]: chunks back to back in the
-    // caller's buffer keep their distances (a run of them with adjacent chunk indices is one staged copy), a gap starts at the next
-    // multiple of 16; ctot leaves 16 bytes behind the last.  Device input stays where it is.
+    // The compressed bytes of the missing chunks lie in the staging buffer in chunk order, at mcoff[], by the run-joined rule
+    // (stage_runs, codec_plan.h).  Device input stays where it is.
     // -> the first missing chunk without compressed bytes, or -1
-    int layout()
+    MTS_LOCAL int layout()
     {
-        int prev = -1;
+        std::vector<int> miss;
         for (int i = 0; i < n_chunks; i++) {
             if (resident[i]) continue;
             if (c_len[i] == 0) return i;
-            any_miss = true;
-            if (on_device) { mcoff[i] = c_off[i]; continue; }
-            const bool joins = prev >= 0 && c_off[i] == c_off[prev] + c_len[prev];
-            if (!joins) ctot = (ctot + (prev >= 0 ? 16 : 0) + 15) / 16 * 16;
-            mcoff[i] = (long)ctot; ctot += (uint64_t)c_len[i];
-            prev = i;
+            miss.push_back(i);
+            if (on_device) mcoff[i] = c_off[i];
         }
-        ctot += 16;
+        any_miss = !miss.empty();
+        if (!on_device) ctot = stage_runs(c_off, c_len, miss.data(), (int)miss.size(), mcoff.data());
         return -1;
     }
 

@@ -1,9 +1,13 @@
-// A seeded sweep over the plans of the device reductions (mtscomp_amd/csrc/reduce_plan.h: no HIP in it), built with the address and
-// undefined-behaviour sanitizers by `make -C mtscomp_amd/csrc plan_check` and run by tests/test_feed_plan.py.  Small chunk tables, every
-// residency mask, compressed bytes with and without gaps, five piece sizes; the staging layout, the tile family's plan and, through a
-// stand-in for each op's map from units to rows, the halo family's.  Exits 1 with the case printed at the first property that fails.
+// A seeded sweep over the plans of the device reductions and of the codec (mtscomp_amd/csrc/reduce_plan.h, codec_plan.h: no HIP in
+// them), built with the address and undefined-behaviour sanitizers by `make -C mtscomp_amd/csrc plan_check` and run by
+// tests/test_feed_plan.py.  Reductions: small chunk tables, every residency mask, compressed bytes with and without gaps, five piece
+// sizes; the staging layout, the tile family's plan and, through a stand-in for each op's map from units to rows, the halo family's.
+// Codec: the compress and inflate batch geometry at every size where the arithmetic turns (0 .. 3 bytes, a segment, the history, a
+// tile, 2^31), the sub-batch cut, the phase width of levels 1..3 and both staging rules, each property stated from what the kernels and
+// the copies need, not from the code.  Exits 1 with the case printed at the first property that fails.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <functional>
 #include <random>
@@ -234,6 +238,349 @@ static void check_halo_ops(const Table &T, const FeedPlan &F, size_t piece, long
     g_case = base;
 }
 
+// ================================================================================================
+// the codec's plans (codec_plan.h)
+// ================================================================================================
+typedef unsigned long long ull;
+static size_t dim_sort_ws(int n_tiles) { return (size_t)(n_tiles + 1) * 48; }
+static size_t dim_marks(size_t n_segs) { return (n_segs + 64) / 64 * 64 * 4; }
+static const CompressDims DIMS = {dim_sort_ws, dim_marks, 14, 40, 24, 320, 96, 65536};
+static const ull TWO31 = 1ull << 31;
+
+// ---- a compress batch: chunk i is n[i] bytes (raw_is_stream: bounds in bytes; else rows of row_bytes)
+static void check_compress(const std::vector<ull> &rows, ull row_bytes, bool raw_is_stream, int level)
+{
+    const int nc = (int)rows.size();
+    std::vector<long> bounds(nc + 1, 5), slots(nc);
+    std::vector<ull> n(nc);
+    for (int i = 0; i < nc; i++) { bounds[i + 1] = bounds[i] + (long)rows[i]; n[i] = raw_is_stream ? rows[i] : rows[i] * row_bytes; slots[i] = 16l * i * 1000; }
+    const CompressPlan P(bounds.data(), nc, row_bytes, raw_is_stream, slots.data(), level, DIMS);
+    bool too_big = false;
+    for (int i = 0; i < nc; i++) too_big = too_big || n[i] >= TWO31;
+    CHECK((P.error[0] != 0) == too_big);                                             // 2^31 - 1 accepted, 2^31 refused
+    if (too_big) { CHECK(strstr(P.error, "2 GiB")); return; }
+    CHECK((int)P.cd.size() == nc);
+    ull seg = 0, blk = 0, tile = 0, max_n = 0, max_rows = 0, max_nseg = 0;
+    for (int i = 0; i < nc; i++) {
+        const ChunkDesc &c = P.cd[i];
+        CHECK(c.n == n[i] && c.n_rows == rows[i] && c.out_off == (ull)slots[i]);     // (no 32-bit field wraps)
+        CHECK(c.raw_off == (ull)(bounds[i] - bounds[0]) * (raw_is_stream ? 1 : row_bytes));
+        // streams: aligned, disjoint, STREAM_PAD bytes behind each; tokens: disjoint, room for n + 1
+        const ull s_end = i + 1 < nc ? P.cd[i + 1].stream_off : P.stream_bytes, t_end = i + 1 < nc ? P.cd[i + 1].tok_off : P.tok_words;
+        CHECK(c.stream_off % STREAM_ALIGN == 0 && c.stream_off + n[i] + STREAM_PAD <= s_end);
+        CHECK(c.tok_off + n[i] + 1 <= t_end);
+        // segments and block slots partition their ranges
+        CHECK(c.seg0 == seg && c.nseg == (n[i] + SEG - 1) / SEG && c.blk0 == blk && c.blk_cap == n[i] / BLOCK_TOKENS + 2);
+        seg += c.nseg; blk += c.blk_cap;
+        // tiles: a partition of [0, n) in order
+        CHECK(c.tile0 == tile);
+        ull at = 0;
+        while (at < n[i]) {
+            CHECK(tile < P.tiles.size());
+            const TileDesc &t = P.tiles[tile];
+            CHECK(t.chunk == (u32)i && t.n == n[i] && t.stream_off == c.stream_off);
+            CHECK(t.a == at && t.own_end > t.a && t.own_end - t.a <= (ull)TILE && t.own_end <= n[i]);
+            CHECK(t.own_end == n[i] || t.own_end - t.a == (ull)TILE);
+            CHECK(t.w == (t.a > (ull)HALO ? t.a - HALO : 0));
+            // the hashed window: every position has three bytes, and it reaches the last owned position that has
+            if (n[i] < 3) CHECK(t.wlen == 0);
+            else {
+                CHECK(t.wlen > 0 && (ull)t.w + t.wlen - 1 <= n[i] - 3);
+                CHECK((ull)t.w + t.wlen == std::min<ull>(t.own_end, n[i] - 2));
+                CHECK(t.wlen <= (ull)WIN);
+            }
+            // sorted regions: 64-aligned, disjoint, inside both sort buffers
+            const ull so_end = tile + 1 < P.tiles.size() ? P.tiles[tile + 1].sorted_off : P.sort_n;
+            CHECK(t.sorted_off % 64 == 0 && t.sorted_off + t.wlen <= so_end);
+            at = t.own_end; tile++;
+        }
+        CHECK(at == n[i]);
+        max_n = std::max(max_n, n[i]); max_rows = std::max(max_rows, rows[i]); max_nseg = std::max<ull>(max_nseg, c.nseg);
+    }
+    CHECK(tile == P.tiles.size() && seg == P.nseg && blk == P.nblk);
+    CHECK(P.max_n == max_n && P.max_rows == max_rows && P.max_nseg == max_nseg);
+    // the workspaces hold what is laid out in them
+    CHECK(P.sort_a >= P.sort_n * 4 && P.sort_a >= dim_marks(seg + 64) * 4 && P.sort_b >= P.sort_n * 4 && P.sort_ws >= dim_sort_ws((int)tile));
+    CHECK(P.tables >= (P.stream_bytes + 64) * 4 * (level < 4 ? 1 : 2) && P.table_words >= P.stream_bytes && P.table_words % 64 == 0);
+    CHECK(P.tokens >= (P.tok_words + 64) * 4 && P.segbuf >= (seg + 64) * 4 * (7 + 14) && P.blk >= (blk + 1) * (40 + 8));
+    CHECK(P.blkcodes >= (blk + 1) * 320 * 4 && P.blkhdr >= (blk + 1) * 96 * 4 && P.adler >= 16ull * nc + 8 + 65536 && P.misc >= 12ull * nc);
+    CHECK(P.o_chunks % 256 == 0 && P.o_tiles % 256 == 0 && P.o_cout % 256 == 0);
+    CHECK(P.o_chunks + sizeof(ChunkDesc) * nc <= P.o_tiles && P.o_tiles + sizeof(TileDesc) * (tile + 1) <= P.o_cout && P.o_cout + 24ull * nc <= P.desc);
+    // the index arrays agree with cd
+    std::vector<u32> h_seg, h_blk;
+    P.index_arrays(h_seg, h_blk);
+    CHECK(h_seg.size() == 2 * seg && h_blk.size() >= blk);
+    for (int i = 0; i < nc; i++) {
+        const ChunkDesc &c = P.cd[i];
+        for (u32 k = 0; k < c.nseg; k++) CHECK(h_seg[c.seg0 + k] == (u32)i && h_seg[seg + c.seg0 + k] == k * (u32)SEG && (ull)k * SEG < n[i]);
+        for (u32 k = 0; k < c.blk_cap; k++) CHECK(h_blk[c.blk0 + k] == (u32)i);
+    }
+}
+
+// ---- an inflate batch
+static void check_inflate(const std::vector<ull> &rows, int nc, int sz, int nc_full)
+{
+    const int n = (int)rows.size();
+    std::vector<long> c_off(n), c_len(n), n_rows(n), out_off(n);
+    for (int i = 0; i < n; i++) { c_off[i] = 100l * i; c_len[i] = 50 + i; n_rows[i] = (long)rows[i]; out_off[i] = 4096l * i; }
+    const InflatePlan P(c_off.data(), c_len.data(), n_rows.data(), out_off.data(), n, nc, sz, nc_full, 24);
+    const ull row_bytes = (ull)(nc_full ? nc_full : nc) * sz;
+    bool too_big = false;
+    for (int i = 0; i < n; i++) too_big = too_big || rows[i] * row_bytes >= TWO31;
+    CHECK((P.error[0] != 0) == too_big);
+    if (too_big) return;
+    ull max_n = 0, max_rows = 0;
+    for (int i = 0; i < n; i++) {
+        const InfChunk &c = P.ic[i];
+        const ull bytes = rows[i] * row_bytes;
+        CHECK(c.c_off == (ull)c_off[i] && c.c_len == (ull)c_len[i] && c.n_expect == bytes);
+        const ull s_end = i + 1 < n ? P.ic[i + 1].stream_off : P.stream_bytes(), t_end = i + 1 < n ? P.ic[i + 1].tok_off : P.toff;
+        CHECK(c.stream_off % STREAM_ALIGN == 0 && c.stream_off + bytes + STREAM_PAD <= s_end);
+        CHECK(c.tok_off % 4 == 0 && c.tok_off + bytes + 2 <= t_end);                     // 16-byte aligned, room for n + 2 tokens
+        if (!nc_full) CHECK(c.n_need == 0);
+        else CHECK(c.n_need >= 1 && c.n_need == std::max<ull>(1, rows[i] * nc * sz) && c.n_need <= std::max<ull>(1, bytes));
+        CHECK(P.so[i] == c.stream_off && P.nn[i] == bytes && P.oo[i] == (ull)out_off[i] && P.rows[i] == rows[i]);
+        max_n = std::max(max_n, bytes); max_rows = std::max(max_rows, rows[i]);
+    }
+    CHECK(P.max_n == max_n && P.max_rows == max_rows && P.token_bytes() >= (P.toff + 64) * 4);
+    // descriptor regions: disjoint, 256-aligned, the host's part at the head
+    const size_t off[] = {P.o_ic, P.o_so, P.o_nn, P.o_oo, P.o_rows, P.o_res, P.o_status, P.o_end};
+    const size_t size[] = {sizeof(InfChunk) * n, 8ul * n, 4ul * n, 8ul * n, 4ul * n, 24ul * n, 4ul * n};
+    for (int r = 0; r < 7; r++) CHECK(off[r] % 256 == 0 && off[r] + size[r] <= off[r + 1]);
+    CHECK(P.o_ic == 0 && P.host_bytes == P.o_res);
+    std::vector<u8> h(P.host_bytes, 0);
+    P.fill(h.data());
+    CHECK(!memcmp(h.data() + P.o_ic, P.ic.data(), size[0]) && !memcmp(h.data() + P.o_so, P.so.data(), size[1]) && !memcmp(h.data() + P.o_nn, P.nn.data(), size[2]) &&
+          !memcmp(h.data() + P.o_oo, P.oo.data(), size[3]) && !memcmp(h.data() + P.o_rows, P.rows.data(), size[4]));
+}
+
+// ---- the sub-batch cut
+static void check_cut(const std::vector<size_t> &bytes, size_t budget, int max_chunks)
+{
+    const int n = (int)bytes.size();
+    const std::vector<int> b = cut_batches([&](int i) { return bytes[i]; }, n, budget, max_chunks);
+    CHECK(!b.empty() && b.front() == 0 && b.back() == n);
+    for (size_t k = 0; k + 1 < b.size(); k++) {
+        CHECK(b[k] < b[k + 1] && b[k + 1] - b[k] <= max_chunks);                         // in order, none empty, none too long
+        size_t sum = 0;
+        for (int i = b[k]; i < b[k + 1]; i++) sum += bytes[i];
+        CHECK(sum <= budget || b[k + 1] - b[k] == 1);                                    // over the budget only when alone
+        if (b[k + 1] < n) CHECK(sum + bytes[b[k + 1]] > budget || b[k + 1] - b[k] == max_chunks);   // maximal
+    }
+    if (n == 0) CHECK(b.size() == 1);
+}
+
+// ---- the phase width of levels 1..3
+static void check_phase_width(ull budget, int n_chunks, ull K, u32 max_n)
+{
+    const ull W = CompressPlan::phase_width(budget, n_chunks, K, max_n);
+    if (max_n == 0) return;                                                              // (nothing to walk: no lists are made)
+    CHECK(W >= 256 && W % 256 == 0);
+    CHECK(W == 256 || 2 * (ull)n_chunks * W * K * 4 <= budget);                          // both list buffers within the budget
+    const ull phases = (max_n + W - 1) / W;
+    CHECK(phases * W >= max_n && W <= std::max<ull>(256, align_up(max_n, 256)));         // the phases cover max_n, and no more than that
+    // at least 8 phases when max_n allows: wider than 1024 only up to an eighth of max_n (in whole granules of 256)
+    CHECK(W <= 1024 || W <= align_up((max_n + 7ull) / 8, 256));
+    if (max_n % 2048 == 0 && W > 1024) CHECK(phases >= 8);
+}
+
+// ---- staging: the copies carry every listed chunk's bytes to where the layout says, once
+struct Staged {
+    std::vector<int> writes;                                                             // per staging byte
+    std::vector<long> from;                                                              // ... and the caller's offset it came from
+    explicit Staged(ull ctot) : writes(ctot, 0), from(ctot, -1) {}
+    void apply(const std::vector<StageCopy> &cp)
+    {
+        for (const StageCopy &c : cp) {
+            CHECK(c.len > 0 && c.dst >= 0 && c.src >= 0 && (ull)c.dst + c.len <= writes.size());
+            for (ull b = 0; b < c.len; b++) { writes[c.dst + b]++; from[c.dst + b] = c.src + (long)b; }
+        }
+    }
+    void holds(long soff, long c_off, long c_len) const { for (long b = 0; b < c_len; b++) CHECK(writes[soff + b] == 1 && from[soff + b] == c_off + b); }
+};
+
+static void check_run_staging(const std::vector<long> &c_off, const std::vector<long> &c_len, const std::vector<int> &ids, int piece_chunks, bool expect_one_copy)
+{
+    const int n = (int)c_off.size(), m = (int)ids.size();
+    std::vector<long> soff(n, -1);
+    const ull ctot = stage_runs(c_off.data(), c_len.data(), ids.data(), m, soff.data());
+    ull end = 0;
+    for (int k = 0; k < m; k++) {
+        const int i = ids[k];
+        CHECK(soff[i] >= 0);
+        for (int q = 0; q < k; q++) { const int j = ids[q]; CHECK(soff[i] >= soff[j] + c_len[j] || soff[j] >= soff[i] + c_len[i]); }   // disjoint
+        if (k) {
+            const int p = ids[k - 1];
+            if (c_off[i] == c_off[p] + c_len[p]) CHECK(soff[i] == soff[p] + c_len[p]);   // back to back: the distance is kept
+            else CHECK(soff[i] % 16 == 0);                                               // a gap: the run starts 16-aligned
+        } else CHECK(soff[i] % 16 == 0);
+        end = std::max<ull>(end, soff[i] + c_len[i]);
+    }
+    CHECK(ctot >= end + 16);
+    // the copies, piece by piece (piece_chunks listed chunks each, the last chunk of a piece listed again in the next: a halo)
+    Staged S(ctot);
+    std::vector<char> done(n, 0);
+    ull moved = 0, want = 0;
+    for (int k0 = 0; k0 < m; k0 += piece_chunks) {
+        const int a = k0 ? k0 - 1 : 0, e = std::min(m, k0 + piece_chunks);
+        const std::vector<StageCopy> cp = run_copies(c_off.data(), c_len.data(), soff.data(), ids.data() + a, e - a, done.data());
+        if (expect_one_copy) CHECK(cp.size() == 1);
+        for (const StageCopy &c : cp) moved += c.len;
+        S.apply(cp);
+    }
+    for (int k = 0; k < m; k++) { S.holds(soff[ids[k]], c_off[ids[k]], c_len[ids[k]]); want += c_len[ids[k]]; }
+    CHECK(moved == want);                                                                // nothing but the chunks' bytes
+    // ... and all at once
+    Staged A(ctot);
+    A.apply(run_copies(c_off.data(), c_len.data(), soff.data(), ids.data(), m));
+    for (int k = 0; k < m; k++) A.holds(soff[ids[k]], c_off[ids[k]], c_len[ids[k]]);
+}
+
+static void check_range_staging(const std::vector<long> &c_off, const std::vector<long> &c_len, int piece_chunks, int expect_one_range /* -1: either */)
+{
+    const int n = (int)c_off.size();
+    RangeStaging S(c_off.data(), c_len.data(), n);
+    long lo = c_off[0], hi = c_off[0] + c_len[0];
+    ull sum = 0;
+    bool ascending = true;
+    for (int i = 0; i < n; i++) {
+        lo = std::min(lo, c_off[i]); hi = std::max(hi, c_off[i] + c_len[i]); sum += c_len[i];
+        if (i && c_off[i] < c_off[i - 1] + c_len[i - 1]) ascending = false;
+    }
+    CHECK(S.one_range == ((ull)(hi - lo) <= sum + sum / 4 + 4096));                      // a quarter of padding and 4096 bytes
+    if (expect_one_range >= 0) CHECK(S.one_range == (expect_one_range != 0));
+    CHECK(S.piecewise() == (!S.one_range || ascending));                                 // a range out of order is one piece
+    S.pb = {0};
+    if (S.piecewise()) for (int i = piece_chunks; i < n; i += piece_chunks) S.pb.push_back(i);
+    S.pb.push_back(n);
+    ull end = 0;
+    for (int i = 0; i < n; i++) {
+        for (int j = 0; j < i; j++) CHECK(S.coff[i] >= S.coff[j] + c_len[j] || S.coff[j] >= S.coff[i] + c_len[i]);
+        if (S.one_range) CHECK(S.coff[i] - S.coff[0] == c_off[i] - c_off[0]);            // the range as it is
+        else CHECK(S.coff[i] % 16 == 0);
+        end = std::max<ull>(end, S.coff[i] + c_len[i]);
+    }
+    // (behind the last chunk: 16 bytes of a range; a chunk staged alone has 8 behind it, as it had before the rules moved here)
+    CHECK(S.ctot >= end + (S.one_range ? 16 : 8));
+    Staged G(S.ctot);
+    for (size_t k = 0; k + 1 < S.pb.size(); k++) {
+        const std::vector<StageCopy> cp = S.copies((int)k);
+        if (S.one_range) CHECK(cp.size() <= 1);                                          // a piece of a range is one copy
+        else { size_t nz = 0; for (int i = S.pb[k]; i < S.pb[k + 1]; i++) nz += c_len[i] != 0; CHECK(cp.size() == nz); }
+        G.apply(cp);
+    }
+    for (int i = 0; i < n; i++) G.holds(S.coff[i], c_off[i], c_len[i]);
+}
+
+static void check_codec_plans()
+{
+    const ull edge[] = {0, 1, 2, 3, SEG - 1, SEG + 1, HALO - 1, HALO + 1, TILE - 1, TILE, TILE + 1, 2ull * TILE + 1};
+    std::mt19937 rng(77);
+    // compress: every edge size alone and in pairs; 2^31 - 1 accepted, 2^31 refused; 300 chunks of mixed sizes
+    for (int level : {1, 6}) for (int stream = 0; stream < 2; stream++) {
+        for (ull a : edge) {
+            g_case = "compress one chunk of " + std::to_string(a) + " level " + std::to_string(level) + " stream " + std::to_string(stream);
+            check_compress({a}, 1, stream, level);
+            for (ull b : edge) { g_case += " +" + std::to_string(b); check_compress({a, b}, 1, stream, level); }
+        }
+        g_case = "compress rows of 6 bytes, level " + std::to_string(level);
+        check_compress({0, 1, 171, (ull)TILE / 6, (ull)TILE / 6 + 1}, 6, false, level);
+        g_case = "compress 2^31 - 1 bytes, level " + std::to_string(level);
+        check_compress({TWO31 - 1}, 1, stream, level);
+        check_compress({3, TWO31 - 1}, 1, stream, level);
+        g_case = "compress 2^31 bytes";
+        check_compress({TWO31}, 1, stream, level);
+        check_compress({5, TWO31 / 2}, 2, false, level);
+        std::vector<ull> many(300);
+        for (ull &v : many) v = rng() % 4 == 0 ? edge[rng() % 8] : rng() % 5000;
+        g_case = "compress 300 chunks";
+        check_compress(many, 1, stream, level);
+    }
+    {   // an output slot that is not 16-byte aligned is refused, and named
+        g_case = "compress slot alignment";
+        const long bounds[3] = {0, 10, 20}, slots[2] = {0, 24};
+        const CompressPlan P(bounds, 2, 1, false, slots, 6, DIMS);
+        CHECK(strstr(P.error, "slot 1"));
+    }
+    // inflate
+    for (int nc_full : {0, 9}) {
+        for (ull a : edge) for (ull b : {0ull, 1ull, 7ull}) {
+            g_case = "inflate rows " + std::to_string(a) + ", " + std::to_string(b) + " nc_full " + std::to_string(nc_full);
+            check_inflate({a, b}, 1, 1, nc_full ? 3 : 0);
+            check_inflate({a}, 3, 2, nc_full);
+        }
+        std::vector<ull> many(300);
+        for (ull &v : many) v = rng() % 700;
+        g_case = "inflate 300 chunks nc_full " + std::to_string(nc_full);
+        check_inflate(many, 5, 2, nc_full);
+        g_case = "inflate 2^31";
+        check_inflate({TWO31 - 1}, 1, 1, 0);
+        check_inflate({1, TWO31 / 4}, 2, 2, 0);
+    }
+    // the sub-batch cut
+    for (int t = 0; t < 400; t++) {
+        const int n = t < 3 ? t : 1 + (int)(rng() % 40);
+        const size_t budget = t % 3 == 0 ? 1 : 1000 + rng() % 5000;
+        std::vector<size_t> bytes(n);
+        for (size_t &v : bytes) { const unsigned r = rng() % 10; v = r == 0 ? 0 : r == 1 ? budget + 1 + rng() % 100 : r == 2 ? budget : rng() % 2000; }
+        for (int max_chunks : {1, 3, 32768}) {
+            g_case = "cut_batches case " + std::to_string(t) + " budget " + std::to_string(budget) + " max_chunks " + std::to_string(max_chunks);
+            check_cut(bytes, budget, max_chunks);
+        }
+    }
+    g_case = "cut_batches zeros";
+    check_cut(std::vector<size_t>(50, 0), 1, 7);
+    // the phase width
+    for (ull budget : {1ull, 1ull << 20, 100ull << 20, 8ull << 30}) for (int n_chunks : {1, 7, 300, 32768}) for (ull K : {14ull, 26ull, 51ull})
+        for (u32 max_n : {0u, 1u, 255u, 256u, 257u, 5000u, 8192u, 8200u, 16384u, 1u << 20, (1u << 20) + 2048u, 23100000u, (u32)(TWO31 - 1)}) {
+            g_case = "phase_width budget " + std::to_string(budget) + " chunks " + std::to_string(n_chunks) + " K " + std::to_string(K) + " max_n " + std::to_string(max_n);
+            check_phase_width(budget, n_chunks, K, max_n);
+        }
+    // staging.  Tables of 1 .. 9 chunks: ascending back to back (a .cbin), two runs with a gap, every chunk apart, descending
+    for (int t = 0; t < 200; t++) {
+        const int n = 1 + t % 9, shape = t / 9 % 4;
+        std::vector<long> len(n), off(n);
+        for (long &v : len) v = 1 + rng() % 60;
+        long at = rng() % 30;
+        for (int i = 0; i < n; i++) {
+            if (shape == 1 && i == n / 2) at += 1 + rng() % 40;
+            if (shape == 2) at += 1 + rng() % 40;
+            off[i] = at; at += len[i];
+        }
+        if (shape == 3) { std::reverse(off.begin(), off.end()); std::reverse(len.begin(), len.end()); }
+        std::vector<int> all(n), some;
+        for (int i = 0; i < n; i++) { all[i] = i; if (rng() % 3) some.push_back(i); }
+        for (int piece_chunks : {1, 2, 100}) {
+            g_case = "run staging table " + std::to_string(t) + " shape " + std::to_string(shape) + " piece of " + std::to_string(piece_chunks);
+            check_run_staging(off, len, all, piece_chunks, shape == 0 && piece_chunks == 100);
+            g_case += " some resident";
+            check_run_staging(off, len, some, piece_chunks, false);
+            g_case = "range staging table " + std::to_string(t) + " shape " + std::to_string(shape) + " piece of " + std::to_string(piece_chunks);
+            check_range_staging(off, len, piece_chunks, shape == 0 || shape == 3 ? 1 : -1);
+            std::vector<long> len0 = len;                          // zero-length chunks (this caller allows them)
+            len0[rng() % n] = 0;
+            g_case += " with an empty chunk";
+            check_range_staging(off, len0, piece_chunks, -1);
+        }
+    }
+    {   // keys 0, 1, 3, 4 of a range missing, key 2 resident: two runs, two copies
+        g_case = "run staging two runs around a resident chunk";
+        const std::vector<long> off = {0, 100, 200, 300, 400}, len(5, 100);
+        check_run_staging(off, len, {0, 1, 3, 4}, 100, false);
+        std::vector<long> soff(5);
+        stage_runs(off.data(), len.data(), std::vector<int>{0, 1, 3, 4}.data(), 4, soff.data());
+        CHECK(run_copies(off.data(), len.data(), soff.data(), std::vector<int>{0, 1, 3, 4}.data(), 4).size() == 2);
+    }
+    // the slack of a range: 10 chunks of 40000 bytes, the padding between them just under and just over a quarter (+ 4096 bytes)
+    for (int over = 0; over < 2; over++) {
+        const long L = 40000, sum = 10 * L, span = sum + sum / 4 + 4096 + over, pad = span - sum;
+        std::vector<long> off(10), len(10, L);
+        for (int i = 0; i < 10; i++) off[i] = 7 + i * L + (i ? pad / 9 * i + (i == 9 ? pad % 9 : 0) : 0);
+        g_case = "range staging slack, over " + std::to_string(over);
+        check_range_staging(off, len, 3, !over);
+    }
+}
+
 int main()
 {
     long n_cases = 0;
@@ -291,6 +638,7 @@ int main()
             CHECK(G.layout() == T.n - 1);
         }
     }
-    printf("plan_check: %ld tables x pieces passed\n", n_cases);
+    check_codec_plans();
+    printf("plan_check: %ld tables x pieces and the codec's plans passed\n", n_cases);
     return 0;
 }

@@ -1,4 +1,5 @@
-"""The plans of the device reductions (csrc/reduce_plan.h: pieces, staging layout, tiles, halo tables) have no HIP in them.
+"""The plans of the device reductions (csrc/reduce_plan.h: pieces, staging layout, tiles, halo tables) and of the codec
+(csrc/codec_plan.h: batch geometry, sub-batch cut, phase width, staging rules) have no HIP in them.
 tests/plan_check.cpp sweeps them on the CPU, built with the address and undefined-behaviour sanitizers as a program of its own;
 this test builds it and runs it as a child process.  No GPU."""
 import subprocess

@@ -547,6 +547,109 @@ def test_host_entry_points_piece_by_piece(monkeypatch):
         src.free(); dst.free()
 
 
+_ELEVEN = None
+
+
+def _eleven_chunks():
+    """The chunks of test_host_entry_points_piece_by_piece and the reference's streams of them, made once."""
+    global _ELEVEN
+    if _ELEVEN is None:
+        r = np.random.RandomState(19)
+        chunks = [synth_rows(int(n), 64, 40 + k) for k, n in enumerate(r.randint(2400, 9600, size=11))]
+        _ELEVEN = (chunks, [c.shape[0] for c in chunks], [O.ref_compress_chunk(c) for c in chunks])
+    return _ELEVEN
+
+
+def _zlib_verdict(z, n):
+    """What the reference makes of a stream expected to inflate to n bytes."""
+    try:
+        out = zlib.decompress(z)
+    except zlib.error:
+        return hip.CHUNK_CORRUPT
+    return 0 if len(out) == n else hip.CHUNK_BADSIZE
+
+
+def test_decompress_chunks_from_one_buffer_out_of_order_and_padded(monkeypatch):
+    """mts_decompress_chunks given (buffer, offsets, lengths) in the arrangements test_host_entry_points_piece_by_piece does not hold:
+    the chunks in descending order of their offsets (one range, staged as it is, one piece whatever MTS_PIPE_BYTES says) and with
+    more than a quarter of padding between them (a copy per chunk, ~12 pieces of 300 kB), there also with a damaged chunk in a
+    middle piece.  The rows and the verdicts are the reference's."""
+    chunks, rows, want = _eleven_chunks()
+    monkeypatch.setenv('MTS_PIPE_BYTES', '300000')
+    lens = [len(w) for w in want]
+    # descending: chunk 10 first in the buffer, chunk 0 last
+    blob = b''.join(reversed(want)) + b'\0' * 16
+    ends = np.cumsum(lens[::-1])[::-1]
+    offs = [int(ends[i] - lens[i]) for i in range(11)]
+    assert offs[0] > offs[10] == 0 and blob[offs[3]:offs[3] + lens[3]] == want[3]
+    st, back = hip.decompress_chunks((blob, offs, lens), rows, 64, 'int16', 5)
+    assert st == [0] * 11 and all(np.array_equal(c, b) for c, b in zip(chunks, back))
+    # padded: half a chunk of other bytes behind each
+    parts, offs, at = [], [], 0
+    for w in want:
+        offs.append(at)
+        parts += [w, b'\xaa' * (len(w) // 2 + 500)]
+        at += len(parts[-2]) + len(parts[-1])
+    blob = b''.join(parts)
+    assert at - sum(lens) > sum(lens) // 4 + 4096
+    st, back = hip.decompress_chunks((blob, offs, lens), rows, 64, 'int16', 5)
+    assert st == [0] * 11 and all(np.array_equal(c, b) for c, b in zip(chunks, back))
+    bad = bytearray(blob)
+    bad[offs[5] + lens[5] // 2] ^= 0x40
+    verdict = _zlib_verdict(bytes(bad[offs[5]:offs[5] + lens[5]]), chunks[5].nbytes)
+    assert verdict != 0
+    st, back = hip.decompress_chunks((bytes(bad), offs, lens), rows, 64, 'int16', 5)
+    assert st == [verdict if k == 5 else 0 for k in range(11)], st
+    assert all(np.array_equal(c, b) for k, (c, b) in enumerate(zip(chunks, back)) if k != 5)
+
+
+def test_sub_batches_inside_pieces(monkeypatch):
+    """MTS_BATCH_BYTES and MTS_PIPE_BYTES of 1 MiB together: every piece of the host entry points is cut into sub-batches again.  The
+    reference's bytes, the rows back, and the stage times of the call list each stage once -- the stages of one undivided call."""
+    chunks, rows, want = _eleven_chunks()
+    bounds = np.concatenate(([0], np.cumsum(rows)))
+    x = np.concatenate(chunks, axis=0)
+    monkeypatch.delenv('MTS_BATCH_BYTES', raising=False)
+    monkeypatch.delenv('MTS_PIPE_BYTES', raising=False)
+    assert [bytes(z) for z in hip.compress_chunks(x, bounds, 5, 6)] == want
+    names_c = [n for n, _ in hip.last_stage_times()]
+    st, back = hip.decompress_chunks(want, rows, 64, 'int16', 5)
+    names_d = [n for n, _ in hip.last_stage_times()]
+    assert st == [0] * 11 and names_c and names_d and len(set(names_c)) == len(names_c) and len(set(names_d)) == len(names_d)
+    monkeypatch.setenv('MTS_BATCH_BYTES', '1048576')
+    monkeypatch.setenv('MTS_PIPE_BYTES', '1048576')
+    assert [bytes(z) for z in hip.compress_chunks(x, bounds, 5, 6)] == want
+    got_c = [n for n, _ in hip.last_stage_times()]
+    assert len(set(got_c)) == len(got_c) and set(got_c) == set(names_c), (got_c, names_c)
+    st, back = hip.decompress_chunks(want, rows, 64, 'int16', 5)
+    got_d = [n for n, _ in hip.last_stage_times()]
+    assert st == [0] * 11 and all(np.array_equal(c, b) for c, b in zip(chunks, back))
+    assert len(set(got_d)) == len(got_d) and set(got_d) == set(names_d), (got_d, names_d)
+
+
+def test_cache_read_two_runs_and_a_gap():
+    """A cache read whose missing chunks form two runs in the caller's buffer with a resident chunk between them (keys 0, 1, 3, 4
+    missing, key 2 resident: two staged copies), then all five missing and handed over in one range (one copy)."""
+    chunks, rows, want = _eleven_chunks()
+    chunks, rows, want = chunks[:5], rows[:5], want[:5]
+    x = np.concatenate(chunks, axis=0)
+    blob = b''.join(want)
+    lens = [len(w) for w in want]
+    offs = [int(o) for o in np.concatenate(([0], np.cumsum(lens)))[:-1]]
+    for resident in ([2], []):
+        cid = hip.cache_create(64 << 20)
+        try:
+            for k in resident:
+                st, got = hip.cache_read_rows(cid, [k], blob, [offs[k]], [lens[k]], [rows[k]], 64, np.int16, 5, 0, rows[k])
+                assert st == [0] and np.array_equal(got, chunks[k])
+            given = [0 if k in resident else lens[k] for k in range(5)]
+            st, got = hip.cache_read_rows(cid, list(range(5)), blob, offs, given, rows, 64, np.int16, 5, 0, x.shape[0])
+            assert st == [0] * 5 and np.array_equal(got, x), resident
+            assert list(hip.cache_query(cid, list(range(5))) > 0) == [True] * 5
+        finally:
+            hip.cache_destroy(cid)
+
+
 def test_inflate_full_size_streams_without_dynamic_blocks():
     """Chunks of the headline size (385 x 30000 int16 = 23.1 MB) whose streams give the block-start scan nothing to find:
     stored blocks (incompressible data, level 0) and fixed-Huffman blocks (Z_FIXED) go through the wave decoder, not one lane."""
