@@ -45,7 +45,7 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_welch, mts_gram and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_welch, mts_gram and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
 #define MTS_PROJECT_MAX_COLS 1024
 #define MTS_PROJECT_MAX_OUT  1024
@@ -57,6 +57,8 @@ extern "C" {
 #define MTS_GRAM_MAX_COLS 16384
 #define MTS_DETECT_MAX_EXCLUDE 255      /* mts_detect: rows either side in which a larger sample suppresses an event */
 #define MTS_DETECT_MAX_SPREAD 32        /* ... and column positions either side */
+#define MTS_WAVEFORMS_MAX_ROWS 4096     /* mts_waveforms: rows of a snippet (before + after) */
+#define MTS_WAVEFORMS_MAX_WIDTH 1024    /* ... and its column positions */
 #define MTS_DETECT_MAX_REF_COLS 1024    /* columns of a median reference: a row's order keys are sorted in 4 KiB of LDS by one wave */
 
 int mts_version(void);
@@ -303,6 +305,46 @@ int mts_detect(int device, long cache_id, int n_chunks, const long *chunk_keys, 
                int *out_pos, float *out_amp, long *n_events, int *chunk_status);
 
 /*
+ * Snippets around events and their extrema (an extension: the reference has no such call; its users pull Reader[...] across the bus,
+ * filter it and slice on the host).  Only the snippets and four numbers per event cross the bus.  Everything is float32 and a
+ * definition, not a tolerance:
+ *   z              exactly mts_detect's z: the filter y[t, j] = sum_k taps[k] * x[t + half - k, cols[j]] (mts_decimate with q = 1 and
+ *                  out_itemsize 4, bit for bit; x = 0 outside [valid_begin, valid_end)), and with reference 1 the float32 median over
+ *                  all n_cols columns of row t subtracted (np.sort's order, NaN last, 0.5f * (a + b) for an even n_cols)
+ *   snippet        event e at file row ev_row[e] with first column position ev_col0[e]: wave[e, tau, w] = z[ev_row[e] - before + tau,
+ *                  ev_col0[e] + w] for 0 <= tau < T = before + after, 0 <= w < width
+ *   fill           an entry whose row lies outside [valid_begin, valid_end) or whose column position lies outside [0, n_cols) is the
+ *                  quiet NaN 0x7fc00000; an entry whose z is a NaN is stored as the same bits (the sign and payload that float
+ *                  arithmetic gives a NaN differ from one processor to the next and are not part of the definition)
+ *   extrema        out_min / out_argmin / out_max / out_argmax per event, over the entries that are not NaN (fill entries and NaN data
+ *                  alike are ignored): arg* is the flat index tau * width + w of the first such entry in (tau, w) order; -0 and +0
+ *                  compare equal, so the first wins and its own bits are returned; an event without such an entry gives NaN and -1
+ *   events         n_events file rows on the host, ascending (repeats allowed), each in [valid_begin, valid_end); ev_col0 any int
+ *   outputs        out_wave (n_events, T, width) C order, or null: the extrema alone, the same bytes as with it.  The same bytes
+ *                  whatever the call, its pieces, its slabs, the gap setting, the cache or the device.
+ *   limits         1 <= T <= MTS_WAVEFORMS_MAX_ROWS, before and after >= 0; 1 <= width <= MTS_WAVEFORMS_MAX_WIDTH; 0 <= n_events <=
+ *                  2^40; taps and columns as mts_detect; with a reference n_cols <= MTS_DETECT_MAX_REF_COLS
+ *   chunks         as mts_decimate: adjacent, ascending, covering [ev_row[0] - before + half - n_taps + 1, ev_row[n_events - 1] + after
+ *                  + half) within [valid_begin, valid_end)
+ *   chunk_status   MTS_CHUNK_* per chunk; the snippets near a failed chunk are undefined
+ * mts_waveforms: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated piece by piece (MTS_PIPE_BYTES) in a
+ * transient workspace and NOT inserted; a piece owns the events whose rows lie in its chunks.  Within a piece the events go through
+ * the float workspace in slabs of at most 256 MiB (MTS_WAVEFORMS_SLAB_BYTES) that also end where the next event starts more than
+ * MTS_WAVEFORMS_GAP_ROWS rows (4096; negative: never) past the rows filtered so far.  The outputs are host memory.
+ * mts_dev_waveforms: device d_cdata and d_* outputs on `device`; ev_row, ev_col0 and chunk_status on the host; no cache.
+ * MTS_E_ARG with a message before anything is allocated or launched: ev_row not ascending or a row outside [valid_begin, valid_end),
+ * any argument outside the limits above, no extrema buffers, a tap that is not finite, chunks not adjacent or not covering the rows
+ * read.  n_events == 0 is MTS_OK without a launch.
+ */
+int mts_waveforms(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                  const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                  long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                  const long *ev_row, const int *ev_col0, int before, int after, int width,
+                  float *out_wave /* (n_events, T, width) C order or null */, float *out_min, int *out_argmin, float *out_max, int *out_argmax,
+                  int *chunk_status);
+
+/*
  * Per-channel power spectral density, Welch's method (an extension: the reference has no such call; its users run
  * scipy.signal.welch on Reader[...] on the host).  Only one float64 partial per (group, bin, column) crosses the bus.
  *   segments       segment s covers file rows [row_seg0 + s * step, row_seg0 + s * step + nperseg); the call computes segments
@@ -457,6 +499,12 @@ int mts_dev_detect(int device, void *stream, const unsigned char *d_cdata, const
                    long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols,
                    const float *threshold /* host */, int sign, int reference, int exclude_rows, int exclude_cols, long max_events,
                    long *d_row, int *d_pos, float *d_amp, long *n_events /* host */, int *chunk_status /* host */);
+int mts_dev_waveforms(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                      const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                      long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                      const long *ev_row /* host */, const int *ev_col0 /* host */, int before, int after, int width,
+                      float *d_wave /* (n_events, T, width) C order or null */, float *d_min, int *d_argmin, float *d_max, int *d_argmax,
+                      int *chunk_status /* host */);
 int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                   const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0,
                   long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,
@@ -491,6 +539,11 @@ int mts_dev_compare(int device, void *stream, const void *d_a, const void *d_b, 
 /* Kernel-stage timings (ms, HIP events on the launch stream) of the last dev_* call on `device`:
  * fills up to `cap` entries of (name, ms); returns the number of stages.  For bench.py / profiling. */
 int mts_last_stage_times(int device, const char **names, float *ms, int cap);
+
+/* What the last successful mts_waveforms / mts_dev_waveforms call on `device` did, for the tests and the benchmark: out[0] its pieces,
+ * out[1] its slabs, out[2] the slabs among them that were begun at a gap, out[3] the microseconds of its gather kernels (measured,
+ * with a wait per slab, only while MTS_WAVEFORMS_TIME is set; else 0). */
+int mts_waveforms_last_plan(int device, long *out /* 4 */);
 
 /* Debug/parity taps for the GPU tests (stage-by-stage comparison with the oracle); host buffers. */
 int mts_debug_match_tables(int device, const void *stream_bytes, long n, int level,

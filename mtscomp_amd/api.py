@@ -68,6 +68,8 @@ DETECT_CALL_BYTES = 1 << 30            # Reader.detect: compressed bytes per dev
 DETECT_GUESS_MIN = 4096                # Reader.detect: events a call's first buffer holds at least, and one more per this many samples:
 DETECT_GUESS_SAMPLES = 256             # a call that finds more says how many and is made once more
 DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per device call (a longer range is split at output-row boundaries)
+WAVEFORMS_CALL_BYTES = 1 << 30         # Reader.waveforms: compressed bytes per device call (a longer event list is split between events) ...
+WAVEFORMS_OUT_BYTES = 1 << 30          # ... and the bytes of a call's result
 PROJECT_CALL_BYTES = 1 << 30           # Reader.project: compressed bytes per device call (a longer range is split at chunk boundaries) ...
 PROJECT_OUT_BYTES = 1 << 30            # ... and the bytes of a call's result
 WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
@@ -380,6 +382,7 @@ class HipCodec:
     window_stats, rank_hist, decimate, detect, welch, gram = map(
         _lane_reduction, ('window_stats', 'rank_hist', 'decimate', 'detect', 'welch', 'gram'))
     project = _lane_reduction('project')
+    waveforms = _lane_reduction('waveforms')
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1831,6 +1834,120 @@ class Reader:
         pos = np.concatenate([f[1] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
         amp = np.concatenate([f[2] for f in found]).astype(np.float32) if found else np.zeros(0, np.float32)
         return Bunch(sample=row, channel=cols.astype(np.int64)[pos], amplitude=amp, threshold=thr, start=i0, stop=i1, channels=cols)
+
+    # -- snippets around events on the device (an extension: the reference's users filter Reader[...] and slice it on the host)
+    def _waveform_cuts(self, lo, hi, max_bytes, max_events):
+        """The calls of waveforms: the events (by ascending row; event i reads file rows [lo[i], hi[i])) cut where consecutive
+        events' chunk spans leave at least one whole chunk unread, where the compressed bytes of a call's chunks pass max_bytes,
+        and so that a call holds at most max_events.  -> the cut list, 0 first, the number of events last."""
+        n = int(lo.size)
+        bounds = np.asarray(self.chunk_bounds, dtype=np.int64)
+        k_lo = np.searchsorted(bounds, lo, side='right') - 1
+        k_hi = np.searchsorted(bounds, hi - 1, side='right') - 1
+        # the spans ascend with the events: only an event whose span differs from the one before it can start a call
+
+        def nbytes(a, b):
+            return self.chunk_offsets[b + 1] - self.chunk_offsets[a] if b >= a else 0
+        base, acc, top = [0], 0, -1                                 # top: the last chunk of the call so far
+        for i in np.concatenate(([0], np.flatnonzero((np.diff(k_lo) != 0) | (np.diff(k_hi) != 0)) + 1)).tolist():
+            a, b = int(k_lo[i]), int(k_hi[i])
+            new = nbytes(max(a, top + 1), b)
+            if i and (a > top + 1 or (new and acc + new > max_bytes)):
+                base.append(i)
+                acc, top, new = 0, -1, nbytes(a, b)
+            acc, top = acc + new, max(top, b)
+        base.append(n)
+        return [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, max_events)] + [n]
+
+    def waveforms(self, sample, channel=None, before=20, after=41, neighbours=None, channels=slice(None), taps=None, reference=None,
+                  waveforms=True):
+        """Snippets of the filtered rows around events, and their extrema, on the device: only they cross the bus.  All in float32.
+        z is detect's z: the bytes of decimate(1, taps=taps, edge='recording', dtype=float32) on `channels` (taps=None is [1.0]),
+        minus, with reference='median', the float32 median over all selected columns of each row.  Event e at file row sample[e]:
+        waveforms[e, tau, w] = z[sample[e] - before + tau, position[e] + w] for tau < T = before + after and w < W.
+        neighbours=None: W is the number of selected channels and position 0 (`channel` is not needed); neighbours=k >= 0: W =
+        2 k + 1 and position[e] = pos - k, pos the first position in `channels` that holds channel[e] (file channel numbers, as
+        detect returns them; a channel that is not selected is a ValueError).  An entry whose row lies outside the recording or
+        whose position lies outside the selection is NaN (every NaN entry, fill or data, has the bits 0x7fc00000).  trough / peak: the minimum / maximum over the entries that are not NaN
+        (the first one in (tau, w) order; -0 == +0), each a Bunch of value (float32; NaN for none), offset (int64, tau - before; 0
+        for none), channel (int64, the entry of `channels`; -1 for none) and index (int64, tau * W + w; -1 for none).  So
+        waveforms[e, before, pos - position[e]] is detect's amplitude of the event, bit for bit.  sample: ints in [0, n_samples),
+        any order, repeats allowed; the results come in that order.  waveforms=False: the extrema alone (the same bytes),
+        `waveforms` is None.  Returns a Bunch: waveforms (n, T, W), trough, peak, sample, position, before, after, channels.  T <=
+        4096, W <= 1024, a median over at most 1024 columns.  The same bytes whatever the lanes, calls, pieces or cache residency.
+        Only the chunks that the events' snippets and their filter support read are decoded: resident chunks are read where they
+        lie, the others in a transient workspace and NOT kept.  A damaged chunk in an event's support raises the IOError of
+        Reader[...]."""
+        self._need_codec('waveforms', 'waveforms', 'gathers')
+        if reference not in (None, 'median'):
+            raise ValueError("reference must be None or 'median', got %r" % (reference,))
+        for name, v in (('before', before), ('after', after)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0:
+                raise ValueError("%s must be an int >= 0, got %r" % (name, v))
+        before, after = int(before), int(after)
+        T = before + after
+        if not 1 <= T <= hip.WAVEFORMS_MAX_ROWS:
+            raise ValueError("before + after must be in [1, %d], got %d" % (hip.WAVEFORMS_MAX_ROWS, T))
+        if neighbours is not None and (not isinstance(neighbours, (int, np.integer)) or isinstance(neighbours, bool) or neighbours < 0):
+            raise ValueError("neighbours must be None or an int >= 0, got %r" % (neighbours,))
+        taps = _fir_taps([1.0] if taps is None else taps)
+        cols, _ = self._stats_channels(channels)
+        if not cols.size:
+            raise ValueError("waveforms needs at least one channel")
+        W = int(cols.size) if neighbours is None else 2 * int(neighbours) + 1
+        if W > hip.WAVEFORMS_MAX_WIDTH:
+            raise ValueError("a snippet holds at most %d positions, got %d" % (hip.WAVEFORMS_MAX_WIDTH, W))
+        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
+            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
+        rows = np.asarray(sample)
+        if rows.ndim != 1 or (rows.size and rows.dtype.kind not in 'iu'):
+            raise ValueError("sample must be a 1-D array of ints")
+        rows = rows.astype(np.int64)
+        n, N = int(rows.size), self.n_samples
+        if n and (rows.min() < 0 or rows.max() >= N):
+            raise ValueError("sample must lie in [0, %d)" % N)
+        if neighbours is None:
+            col0 = np.zeros(n, np.int64)
+        else:
+            if channel is None:
+                raise ValueError("neighbours=%d needs the events' channels" % neighbours)
+            ch = np.asarray(channel)
+            if ch.shape != rows.shape or (ch.size and ch.dtype.kind not in 'iu'):
+                raise ValueError("channel must hold one int per sample")
+            ch = ch.astype(np.int64)
+            first = np.full(self.n_channels, -1, np.int64)          # the first position in `channels` of every file channel
+            first[cols[::-1]] = np.arange(cols.size - 1, -1, -1)
+            if n and (ch.min() < 0 or ch.max() >= self.n_channels or (first[ch] < 0).any()):
+                raise ValueError("channel holds a channel that is not among `channels`")
+            col0 = first[ch] - int(neighbours)
+        order = np.argsort(rows, kind='stable')
+        s_rows, s_col0 = rows[order], col0[order]
+        ref_code, n_taps = 1 if reference else 0, int(taps.size)
+        half = (n_taps - 1) // 2
+        wave = np.empty((n, T, W), np.float32) if waveforms else None
+        ext = [np.empty(n, t) for t in (np.float32, np.int64, np.float32, np.int64)]
+        if n:
+            lo = np.maximum(0, s_rows - before + half - (n_taps - 1))  # the file rows an event reads
+            hi = np.minimum(N, s_rows + after + half)
+            cuts = self._waveform_cuts(lo, hi, WAVEFORMS_CALL_BYTES, max(1, WAVEFORMS_OUT_BYTES // (4 * T * W + 16)))
+
+            def part(a, b):
+                return (self._chunk_span(int(lo[a]), int(hi[b - 1])),
+                        (0, N, taps, cols, ref_code, s_rows[a:b], s_col0[a:b], before, after, W, bool(waveforms)))
+            in_order = bool((order[1:] > order[:-1]).all())          # (detect's events are: plain copies then)
+            for a, b, got in self._halo_parts(self.codec.waveforms, cuts, part):
+                where = slice(a, b) if in_order else order[a:b]
+                if waveforms:
+                    wave[where] = got[0]
+                for dst, src in zip(ext, got[1:]):
+                    dst[where] = src
+        out = {}
+        for name, value, index in (('trough', ext[0], ext[1]), ('peak', ext[2], ext[3])):
+            some = index >= 0
+            pos = np.where(some, col0 + index % W, 0)
+            out[name] = Bunch(value=value, offset=np.where(some, index // W - before, 0), channel=np.where(some, cols[pos], -1), index=index)
+        return Bunch(waveforms=wave, trough=out['trough'], peak=out['peak'], sample=rows, position=col0, before=before, after=after,
+                     channels=cols)
 
     # -- power spectral density on the device (an extension: the reference's users run scipy.signal.welch on Reader[...])
     def welch(self, nperseg=256, start=0, stop=None, channels=slice(None), noverlap=None, window='hann', detrend='constant',

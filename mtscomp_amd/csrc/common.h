@@ -128,6 +128,14 @@ int launch_detect_mask(hipStream_t st, const float *d_z, long ws_row0, long ws_r
 int launch_detect_emit(hipStream_t st, const u64 *d_bitmap, long n_words, u32 *d_counts, u64 *d_offsets, u64 *d_total, const float *d_z,
                        long ws_row0, int n_cols, long s0, long max_events, long *d_row, int *d_pos, float *d_amp);
 
+// waveforms.hip: snippets of the same workspace (mts_waveforms).  For the events e of [e0, e1): wave[e, tau, w] = z[ev_row[e] - before +
+// tau, ev_col0[e] + w] (tau < before + after, w < width; the quiet NaN 0x7fc00000 for a row outside [vb, ve) or the workspace and a
+// column position outside [0, n_cols), and for a z that is a NaN), and the first minimum and maximum over the entries that are not NaN with their flat indices
+// tau * width + w (NaN and -1 when there is none).  d_wave may be null: the stores are skipped, nothing else
+int launch_waveforms(hipStream_t st, const float *d_z, long ws_row0, long ws_rows, int n_cols, long vb, long ve, const long *d_ev_row,
+                     const int *d_ev_col0, long e0, long e1, int before, int after, int width, float *d_wave, float *d_min, int *d_argmin,
+                     float *d_max, int *d_argmax);
+
 // welch.hip: Welch PSD partials (mts_welch).  Segments s of blocks [block0, block0 + n_blocks) (block b: segments [b * B, (b + 1) * B)
 // ∩ [.., seg_end)) start at file row row_seg0 + s * step; d_part[(b - block0), k, c] = sum over the block's segments, in order, of
 // |X_k|^2 of column cols[c] (float64; X in the csize float type).  d_taper: 2^log2n values, d_tw: 2^log2n complex values

@@ -90,6 +90,12 @@ struct Engine {
     // peak detection: taps, columns, thresholds, segment tables, the filtered slab, its event bitmap, block counts and offsets,
     // the outputs of the host entry point
     DBuf det;
+    // snippets: taps, columns, segment tables, the events, the filtered slab, the outputs of the host entry point
+    DBuf wav;
+    // ... and what the last call did (mts_waveforms_last_plan): pieces, slabs, slabs begun at a gap, the gather kernel's microseconds
+    // (measured, slab by slab, only under MTS_WAVEFORMS_TIME)
+    long wav_plan[4] = {0, 0, 0, 0};
+    hipEvent_t wav_ev[2] = {nullptr, nullptr};
     // Welch PSD: taper, twiddles, columns, segment tables, block partials, group sums
     DBuf welch;
     // Gram matrices: columns, slab and group tables, slab partials, the accumulators of the host entry point
@@ -145,7 +151,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &welch, &gram, &proj};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &wav, &welch, &gram, &proj};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();

@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -26,7 +26,7 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, welch, gram): a unit of output (outputs, rows, blocks, groups -- the op gives HaloPlan its map
+//   halo (decimate, project, detect, waveforms, welch, gram): a unit of output (outputs, rows, events, blocks, groups -- the op gives HaloPlan its map
 //        from units to rows) reads rows of several adjacent chunks, so a piece reads chunks [c0, c1] through a table of segment bases
 //        and first rows, and decodes the missing ones among them -- a boundary chunk in both pieces (HaloPlan, HaloFeed).
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
@@ -731,6 +731,135 @@ static int detect_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, l
     return MTS_OK;
 }
 
+// ---- snippets around events (mts_waveforms, mts_dev_waveforms) -----------------------------------------------------------------
+// The unit is an event; the events come by ascending row.  Piece p owns the events whose rows lie in its chunks; event e reads
+// z[ev_row[e] - before, ev_row[e] + after), and that the filter's support: the events [u0, u1) read the file rows from
+// ev_row[u0] - before + half - (L - 1) to ev_row[u1 - 1] + after + half, within the valid range.  A piece's events go through the
+// float32 workspace in slabs (SnippetPlan: at most the slab bound, and cut where events lie further apart than the gap, so that the
+// rows between them are not filtered): filter -> median -> gather.  Every value is computed from the same rows in the same order
+// whatever the pieces, slabs and gap.
+static const u64 WAVEFORMS_SLAB_BYTES = 256ull << 20;
+static const long WAVEFORMS_GAP_ROWS = 4096;                        // (swept at 1024 / 4096 / 16384 / never: profiles/waveforms.json)
+
+static u64 waveforms_slab_bytes()
+{
+    const char *e = getenv("MTS_WAVEFORMS_SLAB_BYTES");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (u64)v : WAVEFORMS_SLAB_BYTES;
+}
+
+static long waveforms_gap_rows()                                     // (negative: never cut at a gap)
+{
+    const char *e = getenv("MTS_WAVEFORMS_GAP_ROWS");
+    return e && *e ? (long)atoll(e) : WAVEFORMS_GAP_ROWS;
+}
+
+static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, int n_taps, const double *taps, int n_cols,
+                         const int *cols, int reference, long n_events, const long *ev_row, const int *ev_col0, int before, int after, int width,
+                         float *out_wave, float *out_min, int *out_argmin, float *out_max, int *out_argmax, bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    int rc;
+    if (nc <= 0 || T.n_chunks < 0 || n_cols < 1 || n_cols > 64 * 65535 || !cols) { set_error("waveforms: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
+    if ((rc = check_taps("waveforms", n_taps, taps))) return rc;
+    if (reference < 0 || reference > 1) { set_error("waveforms: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
+    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("waveforms: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
+    const long n_snip = (long)before + (long)after;
+    if (before < 0 || after < 0 || n_snip < 1 || n_snip > MTS_WAVEFORMS_MAX_ROWS) {
+        set_error("waveforms: before %d, after %d (both >= 0, 1 .. %d rows in all)", before, after, MTS_WAVEFORMS_MAX_ROWS); return MTS_E_ARG;
+    }
+    if (width < 1 || width > MTS_WAVEFORMS_MAX_WIDTH) { set_error("waveforms: width %d (1 .. %d)", width, MTS_WAVEFORMS_MAX_WIDTH); return MTS_E_ARG; }
+    if (vb < 0 || ve < vb || ve > (1l << 60)) { set_error("waveforms: rows invalid"); return MTS_E_ARG; }
+    if (n_events < 0 || n_events > (1l << 40)) { set_error("waveforms: %ld events (0 .. 2^40)", n_events); return MTS_E_ARG; }
+    if (n_events && (!ev_row || !ev_col0)) { set_error("waveforms: no events"); return MTS_E_ARG; }
+    if (!out_min || !out_argmin || !out_max || !out_argmax) { set_error("waveforms: no extrema buffers"); return MTS_E_ARG; }
+    for (long e = 0; e < n_events; e++) {
+        if (ev_row[e] < vb || ev_row[e] >= ve) { set_error("waveforms: event %ld at row %ld outside [%ld, %ld)", e, ev_row[e], vb, ve); return MTS_E_ARG; }
+        if (e && ev_row[e] < ev_row[e - 1]) { set_error("waveforms: event %ld: the rows must ascend", e); return MTS_E_ARG; }
+    }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, T))) return rc;
+    const long half = (n_taps - 1) / 2;
+    // the rows that the events [u0, u1) read: their snippets' support ∩ valid range
+    auto rows = [&](long u0, long u1, long *lo, long *hi) {
+        *lo = std::max(vb, ev_row[u0] - before + half - (n_taps - 1)); *hi = std::min(ve, ev_row[u1 - 1] + after + half);
+    };
+    long need_lo = 0, need_hi = 0;
+    if (n_events) rows(0, n_events, &need_lo, &need_hi);
+    if ((rc = check_cover("waveforms", T, need_lo, need_hi))) return rc;
+    status_ok(T, status);
+    if (n_events == 0) return MTS_OK;
+
+    HaloFeed H(T, out_on_host);
+    // the first event at or after row r
+    if ((rc = H.plan(n_events, [&](long r) { return (long)(std::lower_bound(ev_row, ev_row + n_events, r) - ev_row); }, rows))) return rc;
+    // every piece's slabs: the workspace holds the longest
+    const long cap_rows = (long)std::min<u64>(waveforms_slab_bytes() / (4 * (u64)n_cols), (u64)1 << 40), gap_rows = waveforms_gap_rows();
+    std::vector<SnippetPlan> slabs;
+    long max_rows = 0, report[4] = {(long)H.P->pieces.size(), 0, 0, 0};
+    for (const FeedPiece &Pc : H.P->pieces) {
+        slabs.emplace_back(ev_row, Pc.u0, Pc.u1, before, after, vb, ve, cap_rows, gap_rows);
+        max_rows = std::max(max_rows, slabs.back().max_rows);
+        report[1] += (long)slabs.back().slabs.size(); report[2] += slabs.back().gap_cuts;
+    }
+    const bool timed = getenv("MTS_WAVEFORMS_TIME") != nullptr;   // the gather kernel's time, slab by slab (tools/waveforms_bench.py)
+    if (timed && !E.wav_ev[0]) { MTS_HIP(hipEventCreate(&E.wav_ev[0])); MTS_HIP(hipEventCreate(&E.wav_ev[1])); }
+    double gather_ms = 0;
+    // ---- workspace
+    const u64 n_item = (u64)n_snip * width;
+    WsLayout &L = H.L;
+    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_seg = L.take(H.table_bytes()), o_erow = L.take(8 * (u64)n_events),
+                 o_ecol = L.take(4 * (u64)n_events), o_y = L.take(4 * (u64)max_rows * n_cols),
+                 o_wave = out_wave ? L.take_out(4 * (u64)n_events * n_item) : 0, o_min = L.take_out(4 * (u64)n_events),
+                 o_amin = L.take_out(4 * (u64)n_events), o_max = L.take_out(4 * (u64)n_events), o_amax = L.take_out(4 * (u64)n_events);
+    if ((rc = H.place(E, st, E.wav, o_seg))) return rc;
+    u8 *ws = E.wav.as<u8>();
+    std::vector<float> h_taps(n_taps);
+    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
+    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_erow, ev_row, 8 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_ecol, ev_col0, 4 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    float *d_wave = out_wave ? L.out(ws, o_wave, out_wave) : nullptr;
+    float *d_min = L.out(ws, o_min, out_min), *d_max = L.out(ws, o_max, out_max);
+    int *d_amin = L.out(ws, o_amin, out_argmin), *d_amax = L.out(ws, o_amax, out_argmax);
+    float *d_y = (float *)(ws + o_y);
+    rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
+        int r = MTS_OK;
+        for (const SnippetSlab &S : slabs[&Pc - H.P->pieces.data()].slabs) {
+            // y[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k
+            r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half, S.a,
+                                S.b, Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
+            if (!r && reference) r = launch_row_median(st, d_y, S.b - S.a, n_cols);
+            if (!r && timed) (void)hipEventRecord(E.wav_ev[0], st);
+            if (!r) r = launch_waveforms(st, d_y, S.a, S.b - S.a, n_cols, vb, ve, (const long *)(ws + o_erow), (const int *)(ws + o_ecol), S.e0, S.e1,
+                                         before, after, width, d_wave, d_min, d_amin, d_max, d_amax);
+            if (!r && timed) {
+                float ms = 0;
+                (void)hipEventRecord(E.wav_ev[1], st);
+                (void)hipEventSynchronize(E.wav_ev[1]);
+                (void)hipEventElapsedTime(&ms, E.wav_ev[0], E.wav_ev[1]);
+                gather_ms += ms;
+            }
+            if (r) break;
+        }
+        return r;
+    });
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps has been read before it goes)
+    if (out_on_host) {
+        if (out_wave) MTS_HIP(hipMemcpyAsync(out_wave, d_wave, 4 * (size_t)n_events * n_item, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_min, d_min, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_argmin, d_amin, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_max, d_max, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_argmax, d_amax, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
+    }
+    MTS_HIP(hipStreamSynchronize(st));
+    report[3] = (long)(gather_ms * 1e3);
+    memcpy(E.wav_plan, report, sizeof report);
+    return MTS_OK;
+}
+
 // ---- Welch PSD (mts_welch, mts_dev_welch) ------------------------------------------------------------------------------------
 // The call's segments are cut into blocks of B (WELCH_BLOCK_SEGMENTS) and groups of G; the unit is a block.  Piece p owns the blocks
 // whose first row lies in its chunks.  A piece's blocks are launched in runs that keep the partial slab <= WELCH_SLAB_BYTES, each
@@ -1057,6 +1186,37 @@ int mts_dev_detect(int device, void *stream, const unsigned char *d_cdata, const
 {
     return DEV_ENTRY(detect_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, threshold, sign,
                      reference, exclude_rows, exclude_cols, max_events, d_row, d_pos, d_amp, false, n_events, chunk_status));
+}
+
+int mts_waveforms(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                  const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                  long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                  const long *ev_row, const int *ev_col0, int before, int after, int width, float *out_wave, float *out_min, int *out_argmin,
+                  float *out_max, int *out_argmax, int *chunk_status)
+{
+    return HOST_ENTRY(waveforms_run(E, nullptr, T, valid_begin, valid_end, n_taps, taps, n_cols, cols, reference, n_events, ev_row, ev_col0, before,
+                      after, width, out_wave, out_min, out_argmin, out_max, out_argmax, true, chunk_status));
+}
+
+int mts_dev_waveforms(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                      const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                      long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                      const long *ev_row, const int *ev_col0, int before, int after, int width, float *d_wave, float *d_min, int *d_argmin,
+                      float *d_max, int *d_argmax, int *chunk_status)
+{
+    return DEV_ENTRY(waveforms_run(E, (hipStream_t)stream, T, valid_begin, valid_end, n_taps, taps, n_cols, cols, reference, n_events, ev_row,
+                     ev_col0, before, after, width, d_wave, d_min, d_argmin, d_max, d_argmax, false, chunk_status));
+}
+
+int mts_waveforms_last_plan(int device, long *out)
+{
+    Engine *E;
+    if (!out) return MTS_E_ARG;
+    const int rc = get_engine(device, &E);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(E->mu);
+    memcpy(out, E->wav_plan, sizeof E->wav_plan);
+    return MTS_OK;
 }
 
 int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,

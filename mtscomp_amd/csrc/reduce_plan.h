@@ -1,7 +1,8 @@
 // How a reduction is fed: the part that decides and touches no device.  Which chunks go into which piece, where the compressed
 // bytes of the missing chunks lie in the staging buffer, where each of them is decoded to, which chunks a piece of the halo family
-// reads and what its segment table holds, how the tile family cuts and orders its tiles.  Addresses are plain integers here: the
-// header includes the C++ standard library only, so tests/plan_check.cpp sweeps these plans on the CPU.  reduce.hip puts the
+// reads and what its segment table holds, how the tile family cuts and orders its tiles, how the events of waveforms are cut into
+// slabs.  Addresses are plain integers here: the header includes the C++ standard library only, so tests/plan_check.cpp and
+// tests/snippet_plan_check.cpp sweep these plans on the CPU.  reduce.hip puts the
 // device side around them (ChunkFeed, feed_pieces, HaloFeed, TileFeed) and says there what every caller keeps to.
 #pragma once
 
@@ -146,6 +147,36 @@ struct HaloPlan {
             r[P.c1 - P.c0 + 1] = P.c1 >= P.c0 ? F.row0[P.c1] + F.n_rows[P.c1] : 0;
         }
         return seg;
+    }
+};
+
+// ---- snippets (waveforms): the events of one piece, by ascending file row, cut into slabs.  Event e reads the rows [row[e] - before,
+// row[e] + after) of the filtered workspace, within the recording [vb, ve).  Slab { e0, e1, a, b } owns the events [e0, e1) and holds
+// the rows [a, b) = [max(vb, row[e0] - before), min(ve, row[e1 - 1] + after)): every row of the recording that its events read.  A new
+// slab starts where the next event would take b - a past cap_rows (never less than before + after: one event always fits), and where
+// the next event's first row lies more than gap_rows past b, so that the rows between events far apart are not filtered
+// (gap_rows < 0: never).  The slabs partition the events in order; the results do not depend on them.
+struct SnippetSlab { long e0, e1, a, b; };
+
+struct SnippetPlan {
+    std::vector<SnippetSlab> slabs;
+    long max_rows = 0;                                        // of a slab
+    long gap_cuts = 0;                                        // slabs begun because of the gap
+
+    SnippetPlan(const long *row, long e0, long e1, long before, long after, long vb, long ve, long cap_rows, long gap_rows)
+    {
+        const long cap = std::max(cap_rows, before + after);
+        for (long e = e0; e < e1; e++) {
+            const long a = std::max(vb, row[e] - before), b = std::min(ve, row[e] + after);
+            if (!slabs.empty()) {
+                SnippetSlab &S = slabs.back();
+                const bool far = gap_rows >= 0 && a - S.b > gap_rows;
+                if (b - S.a <= cap && !far) { S.e1 = e + 1; S.b = std::max(S.b, b); continue; }
+                gap_cuts += far;
+            }
+            slabs.push_back({e, e + 1, a, b});
+        }
+        for (const SnippetSlab &S : slabs) max_rows = std::max(max_rows, S.b - S.a);
     }
 };
 

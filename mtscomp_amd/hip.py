@@ -107,11 +107,13 @@ def lib():
             ('decimate', [cl, cl, cl, cl, ci, ci, dp, ci, ci, ip], [vp, ip], None),
             ('project', [cl, cl, ci, ip, dp, ci, dp, ci], [vp, ip], None),
             ('detect', [cl, cl, cl, cl, ci, dp, ci, ip, fp, ci, ci, ci, ci, cl], [vp, vp, vp, lp, ip], None),
+            ('waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci], [vp, vp, vp, vp, vp, ip], None),
             ('welch', [cl, cl, cl, ci, cl, dp, ci, ci, ci, ip], [vp, ip], None),
             ('gram', [cl, cl, cl, cl, cl, ci, ip], [vp, vp, ip], None),
             ('rank_hist', [cl, cl, cl, ci, ip, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip], [vp, vp, vp, lp, ip])):
         getattr(L, 'mts_' + name).argtypes = host + mid + tail
         getattr(L, 'mts_dev_' + name).argtypes = dev + mid + (dev_tail or tail)
+    L.mts_waveforms_last_plan.argtypes = [C.c_int, lp]
     L.mts_release.restype = None
     _lib = L
     return L
@@ -125,6 +127,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
            'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_project', 'mts_dev_project', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
+           'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
 
 
@@ -702,6 +705,64 @@ def dev_detect(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_b
     if download:
         res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _DETECT_DTYPES]))
     return _status(status, n), int(n_ev[0]), res, out
+
+
+# -- snippets around events and their extrema
+WAVEFORMS_MAX_ROWS = 4096
+WAVEFORMS_MAX_WIDTH = 1024
+_WAVEFORMS_DTYPES = (np.float32, np.int32, np.float32, np.int32)       # min, argmin, max, argmax of an event
+
+
+def _wav_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width):
+    """-> (the op's own arguments of mts_waveforms, the events, the entries of a snippet)."""
+    taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).ravel())
+    cols = _cols32(cols)
+    ev_row = _longs(ev_row)
+    ev_col0 = np.ascontiguousarray(np.asarray(ev_col0, dtype=np.int32))
+    assert ev_row.ndim == 1 and ev_row.shape == ev_col0.shape
+    mid = (int(valid_begin), int(valid_end), int(taps.size), _dp(taps), int(cols.size), _ip(cols), int(reference), int(ev_row.size), _lp(ev_row),
+           _ip(ev_col0), int(before), int(after), int(width))
+    return mid, int(ev_row.size), max(int(before) + int(after), 0) * max(int(width), 0)
+
+
+def waveforms(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference, ev_row,
+              ev_col0, before, after, width, want_wave=True, device=0):
+    """mts_waveforms: the snippets (before + after rows x width positions) of the events at the ascending file rows ev_row with first
+    column positions ev_col0 (include/mtscomp_hip.h) from the adjacent chunks `keys`.  reference 0 / 1.  cache_id 0: no cache, every
+    chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, wave float32
+    (n, T, width) or None without want_wave, min float32, argmin int32, max float32, argmax int32)."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, n_ev, item = _wav_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width)
+    wave = np.empty((n_ev, int(before) + int(after), int(width)) if item else (n_ev, 0, 0), np.float32) if want_wave else None
+    res = [np.empty(n_ev, t) for t in _WAVEFORMS_DTYPES]
+    _check(lib().mts_waveforms(*head, *mid, _ptr(wave) if want_wave else None, *(_ptr(a) for a in res), _ip(status)), 'mts_waveforms')
+    return (_status(status, n), wave) + tuple(res)
+
+
+def dev_waveforms(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before,
+                  after, width, want_wave=True, out=None, download=True):
+    """mts_dev_waveforms on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the snippets and the four
+    extrema arrays (made when None; returned so that a caller timing repeated calls can pass it again).  Returns (status list,
+    (wave or None, min, argmin, max, argmax) or None, out)."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, n_ev, item = _wav_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width)
+    sizes = [4 * n_ev * item if want_wave else 0] + [4 * n_ev] * 4
+    out, ptrs, at = _dev_results(out, cbuf.device, sizes)
+    _check(lib().mts_dev_waveforms(*head, *mid, ptrs[0] if want_wave else None, *ptrs[1:], _ip(status)), 'mts_dev_waveforms')
+    res = None
+    if download:
+        wave = np.empty((n_ev, int(before) + int(after), int(width)), np.float32) if want_wave else np.empty(0, np.float32)
+        got = _dev_fetch(out, at, [wave] + [np.empty(n_ev, t) for t in _WAVEFORMS_DTYPES])
+        res = (got[0] if want_wave else None,) + tuple(got[1:])
+    return _status(status, n), res, out
+
+
+def waveforms_last_plan(device=0):
+    """What the last waveforms call on `device` did: a dict of pieces, slabs, gap_cuts (slabs begun at a gap) and gather_us (the gather
+    kernels' microseconds, measured only while MTS_WAVEFORMS_TIME is set)."""
+    out = np.zeros(4, np.int64)
+    _check(lib().mts_waveforms_last_plan(int(device), _lp(out)), 'mts_waveforms_last_plan')
+    return dict(zip(('pieces', 'slabs', 'gap_cuts', 'gather_us'), (int(v) for v in out)))
 
 
 # -- Welch power spectral density
