@@ -45,7 +45,7 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_welch, mts_gram and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_correlate, mts_welch, mts_gram and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
 #define MTS_PROJECT_MAX_COLS 1024
 #define MTS_PROJECT_MAX_OUT  1024
@@ -60,6 +60,9 @@ extern "C" {
 #define MTS_WAVEFORMS_MAX_ROWS 4096     /* mts_waveforms: rows of a snippet (before + after) */
 #define MTS_WAVEFORMS_MAX_WIDTH 1024    /* ... and its column positions */
 #define MTS_DETECT_MAX_REF_COLS 1024    /* columns of a median reference: a row's order keys are sorted in 4 KiB of LDS by one wave */
+#define MTS_CORRELATE_MAX_T 256         /* mts_correlate: rows of a template (its taus) */
+#define MTS_CORRELATE_MAX_OUT 1024      /* ... the templates of a call */
+#define MTS_CORRELATE_MAX_COLS 1024     /* ... and the columns of one */
 
 int mts_version(void);
 int mts_device_count(void);                 /* number of gfx950 devices visible; 0 if none */
@@ -345,6 +348,55 @@ int mts_waveforms(int device, long cache_id, int n_chunks, const long *chunk_key
                   int *chunk_status);
 
 /*
+ * Spatio-temporal template scores of filtered rows (an extension: the reference has no such call; its users pull Reader[...] across the
+ * bus, filter it and run a matched filter on the host).  Only the scores cross the bus.  Everything is float32 and a definition, not a
+ * tolerance:
+ *   z              exactly mts_detect's z: the filter y[t, j] = sum_k taps[k] * x[t + half - k, cols[j]] (mts_decimate with q = 1 and
+ *                  out_itemsize 4, bit for bit; x = 0 outside [valid_begin, valid_end)), and with reference 1 the float32 median over
+ *                  all n_cols columns of row t subtracted (np.sort's order, NaN last, 0.5f * (a + b) for an even n_cols).  z[r, j] =
+ *                  +0 for a row r outside [valid_begin, valid_end)
+ *   templates      n_out templates of T rows x n_cols columns: floats on the host, (n_out, T, n_cols) C order, all finite; template
+ *                  row `before` is laid on file row t, 0 <= before <= T
+ *   score          score[t, k] = sum_tau sum_j z[t - before + tau, j] * K[k, tau, j] for row_begin <= t < row_end, formed as this
+ *                  chain.  With n4 = n_cols rounded up to a multiple of 4, columns n_cols .. n4 - 1 of z and K are +0, and
+ *                      acc = +0
+ *                      for g in 0, 4, 8, .. < n4:              (column group, outermost)
+ *                          for tau in 0 .. T - 1:
+ *                              for j in g .. g + 3:
+ *                                  acc = fmaf(z[t - before + tau, j], K[k, tau, j], acc)
+ *                      score[t, k] = acc, or the bits 0x7fc00000 when acc is a NaN
+ *                  Each (g, tau) is one v_mfma_f32_16x16x4_f32 step; the order does not depend on any tile size.  Zero template
+ *                  entries are not skipped (inf * 0 is NaN); the sign and payload that float arithmetic gives a NaN differ from one
+ *                  processor to the next and are not part of the definition.  float32 subnormals are kept, as operands and as
+ *                  results.  score[t, k] depends on t, cols, taps, reference and template k alone: not on the other templates, the
+ *                  tile, the slab, the piece, the call, the lane, cache residency, the entry point or the device.
+ *   outputs        out (row_end - row_begin, n_out) float, C order
+ *   limits         1 <= T <= MTS_CORRELATE_MAX_T; 1 <= n_out <= MTS_CORRELATE_MAX_OUT; 1 <= n_cols <= MTS_CORRELATE_MAX_COLS channel
+ *                  indices, any order, repeats allowed; taps as mts_detect
+ *                  Every call repacks the templates on the host (n4 * T * n_out rounded up to 64 floats: 12 MB for 128 templates of
+ *                  61 x 385, 1 GiB at all three limits) and uploads them: a caller with many templates of many rows scores them in
+ *                  several calls, or over fewer columns
+ *   chunks         as mts_decimate: adjacent, ascending, covering [row_begin - before + half - n_taps + 1, row_end + T - before - 1 +
+ *                  half) within [valid_begin, valid_end); valid_begin <= row_begin <= row_end <= valid_end.  row_begin == row_end is
+ *                  MTS_OK with nothing written.
+ *   chunk_status   MTS_CHUNK_* per chunk; the scores near a failed chunk are undefined
+ * mts_correlate: host cdata; cache_id 0 or a decoded-chunk cache.  A chunk resident there (whole rows) is read where it lies --
+ * c_lengths[i] may then be 0 (MTS_E_MISS when it is not resident).  The others are inflated piece by piece (MTS_PIPE_BYTES) in a
+ * transient workspace and NOT inserted; a piece owns the rows of its chunks and a chunk in the halo of two pieces is inflated in
+ * both.  Within a piece the rows go through the float workspace in slabs of at most 256 MiB (MTS_CORRELATE_SLAB_BYTES; never less than
+ * one row and its T - 1 neighbours).  `out` is host memory.
+ * mts_dev_correlate: device d_cdata and d_out on `device`; templates and chunk_status on the host; no cache.
+ * MTS_E_ARG with a message before anything is allocated or launched: any argument outside the limits above, a template entry or a tap
+ * that is not finite, no templates, no output buffer, a column outside [0, n_channels), chunks not adjacent or not covering the rows
+ * read.
+ */
+int mts_correlate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                  const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                  long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                  int before, int T, int n_out, const float *templates /* (n_out, T, n_cols) C order */,
+                  float *out /* (row_end - row_begin, n_out) C order */, int *chunk_status);
+
+/*
  * Per-channel power spectral density, Welch's method (an extension: the reference has no such call; its users run
  * scipy.signal.welch on Reader[...] on the host).  Only one float64 partial per (group, bin, column) crosses the bus.
  *   segments       segment s covers file rows [row_seg0 + s * step, row_seg0 + s * step + nperseg); the call computes segments
@@ -505,6 +557,10 @@ int mts_dev_waveforms(int device, void *stream, const unsigned char *d_cdata, co
                       const long *ev_row /* host */, const int *ev_col0 /* host */, int before, int after, int width,
                       float *d_wave /* (n_events, T, width) C order or null */, float *d_min, int *d_argmin, float *d_max, int *d_argmax,
                       int *chunk_status /* host */);
+int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                      const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                      long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                      int before, int T, int n_out, const float *templates /* host */, float *d_out, int *chunk_status /* host */);
 int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                   const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0,
                   long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,

@@ -70,6 +70,8 @@ DETECT_GUESS_SAMPLES = 256             # a call that finds more says how many an
 DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per device call (a longer range is split at output-row boundaries)
 WAVEFORMS_CALL_BYTES = 1 << 30         # Reader.waveforms: compressed bytes per device call (a longer event list is split between events) ...
 WAVEFORMS_OUT_BYTES = 1 << 30          # ... and the bytes of a call's result
+CORRELATE_CALL_BYTES = 1 << 30         # Reader.correlate: compressed bytes per device call (a longer range is split at chunk boundaries) ...
+CORRELATE_OUT_BYTES = 1 << 30          # ... and the bytes of a call's result
 PROJECT_CALL_BYTES = 1 << 30           # Reader.project: compressed bytes per device call (a longer range is split at chunk boundaries) ...
 PROJECT_OUT_BYTES = 1 << 30            # ... and the bytes of a call's result
 WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
@@ -383,6 +385,7 @@ class HipCodec:
         _lane_reduction, ('window_stats', 'rank_hist', 'decimate', 'detect', 'welch', 'gram'))
     project = _lane_reduction('project')
     waveforms = _lane_reduction('waveforms')
+    correlate = _lane_reduction('correlate')
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1774,6 +1777,70 @@ class Reader:
             def part(a, b):
                 return self._chunk_span(a, b), (a, b, cols, off, w, out_dtype)
             for a, b, (y,) in self._halo_parts(self.codec.project, cuts, part):
+                out[a - i0:b - i0] = y
+        return out[:, 0] if squeeze else out
+
+    # -- template scores on the device (an extension: the reference's users filter Reader[...] and run a matched filter on the host)
+    def correlate(self, templates, start=0, stop=None, channels=slice(None), before=20, taps=None, reference=None):
+        """Spatio-temporal template scores of the filtered rows [start, stop), on the device: only the scores cross the bus.  All in
+        float32 on the matrix cores.  z is detect's z: the bytes of decimate(1, taps=taps, edge='recording', dtype=float32) on
+        `channels` (taps=None is [1.0]), minus, with reference='median', the float32 median over all selected columns of each row;
+        z is +0 outside the recording.  templates: (K, T, W) finite numbers, W the number of selected channels -- the shape of
+        waveforms(...).waveforms[e] with neighbours=None, so the mean of a unit's snippets is a template -- each rounded once to
+        float32.  Row i of the result is the score with template row `before` laid on file row start + i:
+        score[t, k] = sum_tau sum_j z[t - before + tau, j] * templates[k, tau, j], formed bit for bit as acc = fmaf(z, K, acc) from +0
+        over the column groups g = 0, 4, 8, .. (outermost; the columns padded with +0 to a multiple of 4), tau = 0 .. T - 1 and the
+        four columns of the group (innermost); a NaN score has the bits 0x7fc00000.  Zero template entries are not skipped (inf * 0
+        is NaN).  project is the T = 1 case.  The same bytes whatever the other templates, the lanes, calls, pieces, slabs or cache
+        residency, and correlate(a, b) followed by correlate(b, c) is correlate(a, c).  1 <= T <= 256, 0 <= before <= T (after = T
+        - before is implied), 1 <= K <= 1024, W <= 1024; a 2-D (T, W) array is one template and gives a 1-D result.  start / stop
+        follow Reader[...]; channels: an int, a slice with step >= 1, or a sequence of ints (repeats allowed).  Returns a (stop -
+        start, K) float32 array.  Chunks resident in the device cache are read where they lie; the others are decoded in a transient
+        workspace and NOT kept.  A damaged chunk in the support raises the IOError of Reader[...]."""
+        self._need_codec('correlate', 'correlate', 'correlates')
+        if reference not in (None, 'median'):
+            raise ValueError("reference must be None or 'median', got %r" % (reference,))
+        taps = _fir_taps([1.0] if taps is None else taps)
+        i0, i1 = self._row_range(start, stop)
+        cols, _ = self._stats_channels(channels)
+        k = np.asarray(templates)
+        if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
+            raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
+        squeeze = k.ndim == 2
+        with np.errstate(over='ignore'):
+            k = np.ascontiguousarray((k[None] if squeeze else k).astype(np.float32))
+        n_out, T, W = k.shape
+        if W != cols.size:
+            raise ValueError("templates have %d columns for %d selected channels" % (W, cols.size))
+        if not 1 <= W <= hip.CORRELATE_MAX_COLS:
+            raise ValueError("correlate takes 1 to %d columns, got %d" % (hip.CORRELATE_MAX_COLS, W))
+        if not 1 <= T <= hip.CORRELATE_MAX_T:
+            raise ValueError("templates have 1 to %d rows, got %d" % (hip.CORRELATE_MAX_T, T))
+        if not 1 <= n_out <= hip.CORRELATE_MAX_OUT:
+            raise ValueError("correlate takes 1 to %d templates, got %d" % (hip.CORRELATE_MAX_OUT, n_out))
+        if not isinstance(before, (int, np.integer)) or isinstance(before, bool) or not 0 <= before <= T:
+            raise ValueError("before must be an int in [0, %d], got %r" % (T, before))
+        if not np.isfinite(k).all():
+            raise ValueError("templates must be finite in float32")
+        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
+            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
+        before, n_taps, N = int(before), int(taps.size), self.n_samples
+        after, half, ref_code = T - before, (n_taps - 1) // 2, 1 if reference else 0
+        out = np.zeros((i1 - i0, n_out), np.float32)
+        if i1 > i0:
+            def support(a, b):                                      # the file rows that the scores of rows [a, b) read
+                return max(0, a - before + half - (n_taps - 1)), min(N, b + after - 1 + half)
+            # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they read pass CORRELATE_CALL_BYTES,
+            # and so that a call's result stays within CORRELATE_OUT_BYTES
+            rows = max(1, CORRELATE_OUT_BYTES // (4 * n_out))
+            base = self._halo_cuts(*support(i0, i1), CORRELATE_CALL_BYTES, i0, i1, lambda row: min(i1, max(i0, row)))
+            cuts = [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, rows)] + [i1]
+
+            def part(a, b):
+                lo, hi = support(a, b)
+                if lo < hi:                                         # (rows that read no row of the recording score +0)
+                    return self._chunk_span(lo, hi), (0, N, a, b, taps, cols, ref_code, before, k)
+            for a, b, (y,) in self._halo_parts(self.codec.correlate, cuts, part):
                 out[a - i0:b - i0] = y
         return out[:, 0] if squeeze else out
 

@@ -136,6 +136,18 @@ int launch_waveforms(hipStream_t st, const float *d_z, long ws_row0, long ws_row
                      const int *d_ev_col0, long e0, long e1, int before, int after, int width, float *d_wave, float *d_min, int *d_argmin,
                      float *d_max, int *d_argmax);
 
+// correlate.hip: template scores on the same workspace (mts_correlate).  out[(t - r_begin) * n_out + k] for file rows t of [r_begin,
+// r_end) = the chain of matrix steps over (g, tau), g = 0, 4, .. < n4 outermost and tau < T inside, of z[t - before + tau, g .. g + 3]
+// against the templates; z = +0 for a row outside [vb, ve) or the workspace; a NaN is stored as 0x7fc00000.  d_tpl: the templates
+// group-major, row (g / 4 * T + tau) * 4 + c = K[0 .. tpl_pitch, tau, g + c], zeros past n_cols and n_out; tpl_pitch: n_out rounded up
+// to CORRELATE_PAD
+constexpr int CORRELATE_MAX_T = MTS_CORRELATE_MAX_T;               // include/mtscomp_hip.h
+constexpr int CORRELATE_MAX_OUT = MTS_CORRELATE_MAX_OUT;
+constexpr int CORRELATE_MAX_COLS = MTS_CORRELATE_MAX_COLS;
+constexpr int CORRELATE_PAD = 64;
+int launch_correlate(hipStream_t st, const float *d_z, long ws_row0, long ws_rows, int n_cols, long vb, long ve, const float *d_tpl, int tpl_pitch,
+                     int T, int before, int n_out, long r_begin, long r_end, float *d_out);
+
 // welch.hip: Welch PSD partials (mts_welch).  Segments s of blocks [block0, block0 + n_blocks) (block b: segments [b * B, (b + 1) * B)
 // ∩ [.., seg_end)) start at file row row_seg0 + s * step; d_part[(b - block0), k, c] = sum over the block's segments, in order, of
 // |X_k|^2 of column cols[c] (float64; X in the csize float type).  d_taper: 2^log2n values, d_tw: 2^log2n complex values

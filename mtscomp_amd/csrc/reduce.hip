@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, correlate, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -26,7 +26,7 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, waveforms, welch, gram): a unit of output (outputs, rows, events, blocks, groups -- the op gives HaloPlan its map
+//   halo (decimate, project, detect, waveforms, correlate, welch, gram): a unit of output (outputs, rows, events, blocks, groups -- the op gives HaloPlan its map
 //        from units to rows) reads rows of several adjacent chunks, so a piece reads chunks [c0, c1] through a table of segment bases
 //        and first rows, and decodes the missing ones among them -- a boundary chunk in both pieces (HaloPlan, HaloFeed).
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
@@ -860,6 +860,103 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
     return MTS_OK;
 }
 
+// ---- template scores (mts_correlate, mts_dev_correlate) ------------------------------------------------------------------------
+// The unit is a row of [row_begin, row_end).  Piece p owns the rows in its chunks; their scores need z from `before` rows before to
+// T - before - 1 rows after, and that the filter's support: the rows [u0, u1) read the file rows from u0 - before + half - (L - 1) to
+// u1 + T - before - 1 + half, within the valid range.  A piece's rows go through the float32 workspace in slabs of owned rows that
+// keep it (own + T - 1 rows) <= the slab bound: filter -> median -> k_correlate.  The templates are repacked once per call into the
+// kernel's layout (correlate.hip: group-major, padded with zeros).  Every score is computed from the same rows in the same order
+// whatever the pieces and slabs.
+static const u64 CORRELATE_SLAB_BYTES = 256ull << 20;
+
+static u64 correlate_slab_bytes()
+{
+    const char *e = getenv("MTS_CORRELATE_SLAB_BYTES");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (u64)v : CORRELATE_SLAB_BYTES;
+}
+
+static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
+                         int n_cols, const int *cols, int reference, int before, int n_tau, int n_out, const float *templates, float *out,
+                         bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    int rc;
+    if (nc <= 0 || T.n_chunks < 0) { set_error("correlate: n_channels or n_chunks invalid"); return MTS_E_ARG; }
+    if (n_cols < 1 || n_cols > MTS_CORRELATE_MAX_COLS || !cols) { set_error("correlate: %d columns (1 .. %d)", n_cols, MTS_CORRELATE_MAX_COLS); return MTS_E_ARG; }
+    if ((rc = check_taps("correlate", n_taps, taps))) return rc;
+    if (reference < 0 || reference > 1) { set_error("correlate: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
+    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("correlate: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
+    if (n_tau < 1 || n_tau > MTS_CORRELATE_MAX_T) { set_error("correlate: templates of %d rows (1 .. %d)", n_tau, MTS_CORRELATE_MAX_T); return MTS_E_ARG; }
+    if (before < 0 || before > n_tau) { set_error("correlate: before %d (0 .. %d)", before, n_tau); return MTS_E_ARG; }
+    if (n_out < 1 || n_out > MTS_CORRELATE_MAX_OUT || !templates) { set_error("correlate: %d templates (1 .. %d)", n_out, MTS_CORRELATE_MAX_OUT); return MTS_E_ARG; }
+    const long per = (long)n_tau * n_cols;
+    for (long e = 0; e < (long)n_out * per; e++)
+        if (!std::isfinite(templates[e])) { set_error("correlate: template entry (%ld, %ld, %ld) is not finite", e / per, e % per / n_cols, e % n_cols); return MTS_E_ARG; }
+    if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve || row_end - row_begin > (1l << 40)) {
+        set_error("correlate: rows invalid"); return MTS_E_ARG;
+    }
+    if (row_end > row_begin && !out) { set_error("correlate: no output buffer"); return MTS_E_ARG; }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, T))) return rc;
+    const long half = (n_taps - 1) / 2, n_units = row_end - row_begin, after = n_tau - before;
+    // the rows that the scores of rows [u0, u1) read: (rows - before .. rows + after - 1)'s support ∩ valid range
+    auto rows = [&](long u0, long u1, long *lo, long *hi) {
+        *lo = std::max(vb, row_begin + u0 - before + half - (n_taps - 1)); *hi = std::min(ve, row_begin + u1 + after - 1 + half);
+    };
+    long need_lo = 0, need_hi = 0;
+    if (n_units) rows(0, n_units, &need_lo, &need_hi);
+    if ((rc = check_cover("correlate", T, need_lo, need_hi))) return rc;
+    status_ok(T, status);
+    if (!n_units) return MTS_OK;
+
+    HaloFeed H(T, out_on_host);
+    if ((rc = H.plan(n_units, [&](long r) { return r - row_begin; }, rows))) return rc;
+    // rows a slab owns: the workspace holds them and their T - 1 neighbours
+    const long cap_rows = (long)std::min<u64>(correlate_slab_bytes() / (4 * (u64)n_cols), (u64)1 << 40);
+    const long own = std::min(n_units, std::max(1l, cap_rows - (n_tau - 1)));
+    // ---- workspace: taps, columns, segment tables, templates (group-major: row (g / 4 * T + tau) * 4 + c holds K[., tau, g + c], zeros
+    // past n_cols and n_out), the filtered slab, the output
+    const int n4 = (int)align_up((u64)n_cols, 4), kp = (int)align_up((u64)n_out, CORRELATE_PAD);
+    const u64 tpl_items = (u64)n4 * n_tau * kp, n_items = (u64)n_units * n_out;
+    WsLayout &L = H.L;
+    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_seg = L.take(H.table_bytes()), o_tpl = L.take(4 * tpl_items),
+                 o_y = L.take(4 * (u64)(own + n_tau - 1) * n_cols), o_out = L.take_out(4 * n_items);
+    if ((rc = H.place(E, st, E.cor, o_seg))) return rc;
+    u8 *ws = E.cor.as<u8>();
+    std::vector<float> h_taps(n_taps), h_tpl(tpl_items, 0.0f);
+    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
+    for (int k = 0; k < n_out; k++)
+        for (int tau = 0; tau < n_tau; tau++) {
+            const float *src = templates + ((size_t)k * n_tau + tau) * n_cols;
+            for (int j = 0; j < n_cols; j++) h_tpl[(((size_t)(j >> 2) * n_tau + tau) * 4 + (j & 3)) * kp + k] = src[j];
+        }
+    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_tpl, h_tpl.data(), 4 * (size_t)tpl_items, hipMemcpyHostToDevice, st));
+    float *d_out = L.out(ws, o_out, out);
+    float *d_y = (float *)(ws + o_y);
+    rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
+        const long p0 = row_begin + Pc.u0, p1 = row_begin + Pc.u1;
+        int r = MTS_OK;
+        for (long s0 = p0; !r && s0 < p1; s0 += own) {
+            const long s1 = std::min(p1, s0 + own), a = std::max(vb, s0 - before), b = std::max(a, std::min(ve, s1 + after - 1));
+            // y[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k
+            if (b > a) r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half,
+                                           a, b, Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
+            if (!r && reference && b > a) r = launch_row_median(st, d_y, b - a, n_cols);
+            if (!r) r = launch_correlate(st, d_y, a, b - a, n_cols, vb, ve, (const float *)(ws + o_tpl), kp, n_tau, before, n_out, s0, s1,
+                                         d_out + (u64)(s0 - row_begin) * n_out);
+        }
+        return r;
+    });
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps and h_tpl have been read before they go)
+    if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, 4 * n_items, hipMemcpyDeviceToHost, st));
+    MTS_HIP(hipStreamSynchronize(st));
+    return MTS_OK;
+}
+
 // ---- Welch PSD (mts_welch, mts_dev_welch) ------------------------------------------------------------------------------------
 // The call's segments are cut into blocks of B (WELCH_BLOCK_SEGMENTS) and groups of G; the unit is a block.  Piece p owns the blocks
 // whose first row lies in its chunks.  A piece's blocks are launched in runs that keep the partial slab <= WELCH_SLAB_BYTES, each
@@ -1217,6 +1314,24 @@ int mts_waveforms_last_plan(int device, long *out)
     std::lock_guard<std::mutex> lk(E->mu);
     memcpy(out, E->wav_plan, sizeof E->wav_plan);
     return MTS_OK;
+}
+
+int mts_correlate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                  const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                  long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                  int before, int T_, int n_out, const float *templates, float *out, int *chunk_status)
+{
+    return HOST_ENTRY(correlate_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before, T_,
+                      n_out, templates, out, true, chunk_status));
+}
+
+int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                      const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                      long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                      int before, int T_, int n_out, const float *templates, float *d_out, int *chunk_status)
+{
+    return DEV_ENTRY(correlate_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference,
+                     before, T_, n_out, templates, d_out, false, chunk_status));
 }
 
 int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,

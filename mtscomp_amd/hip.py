@@ -108,6 +108,7 @@ def lib():
             ('project', [cl, cl, ci, ip, dp, ci, dp, ci], [vp, ip], None),
             ('detect', [cl, cl, cl, cl, ci, dp, ci, ip, fp, ci, ci, ci, ci, cl], [vp, vp, vp, lp, ip], None),
             ('waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci], [vp, vp, vp, vp, vp, ip], None),
+            ('correlate', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp], [vp, ip], None),
             ('welch', [cl, cl, cl, ci, cl, dp, ci, ci, ci, ip], [vp, ip], None),
             ('gram', [cl, cl, cl, cl, cl, ci, ip], [vp, vp, ip], None),
             ('rank_hist', [cl, cl, cl, ci, ip, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip], [vp, vp, vp, lp, ip])):
@@ -127,7 +128,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
            'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_project', 'mts_dev_project', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
-           'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan',
+           'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan', 'mts_correlate', 'mts_dev_correlate',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
 
 
@@ -763,6 +764,49 @@ def waveforms_last_plan(device=0):
     out = np.zeros(4, np.int64)
     _check(lib().mts_waveforms_last_plan(int(device), _lp(out)), 'mts_waveforms_last_plan')
     return dict(zip(('pieces', 'slabs', 'gap_cuts', 'gather_us'), (int(v) for v in out)))
+
+
+# -- spatio-temporal template scores
+CORRELATE_MAX_T = 256                  # MTS_CORRELATE_MAX_T
+CORRELATE_MAX_OUT = 1024               # MTS_CORRELATE_MAX_OUT
+CORRELATE_MAX_COLS = 1024              # MTS_CORRELATE_MAX_COLS
+
+
+def _cor_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates):
+    """-> (the op's own arguments of mts_correlate, the shape of the result, what the pointers point at)."""
+    taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).ravel())
+    cols = _cols32(cols)
+    with np.errstate(over='ignore'):
+        tpl = np.ascontiguousarray(np.asarray(templates).astype(np.float32))
+    assert tpl.ndim == 3 and tpl.shape[2] == cols.size, 'templates must be (n_out, T, n_cols)'
+    mid = (int(valid_begin), int(valid_end), int(row_begin), int(row_end), int(taps.size), _dp(taps), int(cols.size), _ip(cols), int(reference),
+           int(before), int(tpl.shape[1]), int(tpl.shape[0]), tpl.ctypes.data_as(C.POINTER(C.c_float)))
+    return mid, (max(int(row_end) - int(row_begin), 0), int(tpl.shape[0])), (taps, cols, tpl)
+
+
+def correlate(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols,
+              reference, before, templates, device=0):
+    """mts_correlate: score[t, k] of the templates (n_out, T, n_cols), template row `before` on file row t, for file rows [row_begin,
+    row_end) (include/mtscomp_hip.h) from the adjacent chunks `keys`.  reference 0 / 1.  cache_id 0: no cache, every chunk comes with
+    its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, (row_end - row_begin, n_out)
+    float32)."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, shape, _keep = _cor_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates)
+    out = np.empty(shape, np.float32)
+    _check(lib().mts_correlate(*head, *mid, _ptr(out), _ip(status)), 'mts_correlate')
+    return _status(status, n), out
+
+
+def dev_correlate(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, reference,
+                  before, templates, out=None, download=True):
+    """mts_dev_correlate on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the scores (made when None;
+    returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, shape, _keep = _cor_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates)
+    out, ptrs, at = _dev_results(out, cbuf.device, [4 * shape[0] * shape[1]])
+    _check(lib().mts_dev_correlate(*head, *mid, *ptrs, _ip(status)), 'mts_dev_correlate')
+    res = _dev_fetch(out, at, [np.empty(shape, np.float32)])[0] if download else None
+    return _status(status, n), res, out
 
 
 # -- Welch power spectral density
