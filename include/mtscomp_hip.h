@@ -45,7 +45,7 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_correlate, mts_welch, mts_gram and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_correlate, mts_match_templates, mts_welch, mts_gram and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
 #define MTS_PROJECT_MAX_COLS 1024
 #define MTS_PROJECT_MAX_OUT  1024
@@ -63,6 +63,7 @@ extern "C" {
 #define MTS_CORRELATE_MAX_T 256         /* mts_correlate: rows of a template (its taus) */
 #define MTS_CORRELATE_MAX_OUT 1024      /* ... the templates of a call */
 #define MTS_CORRELATE_MAX_COLS 1024     /* ... and the columns of one */
+#define MTS_TMATCH_MAX_EXCLUDE 255      /* mts_match_templates: rows either side in which a larger score suppresses an event */
 
 int mts_version(void);
 int mts_device_count(void);                 /* number of gfx950 devices visible; 0 if none */
@@ -397,6 +398,54 @@ int mts_correlate(int device, long cache_id, int n_chunks, const long *chunk_key
                   float *out /* (row_end - row_begin, n_out) C order */, int *chunk_status);
 
 /*
+ * Template-matching events: the peaks of mts_correlate's scores, at most one per neighbourhood in time, each given to the template that
+ * scored highest (an extension: the reference has no such call; its users pull the score matrix across the bus and pick its peaks on
+ * the host).  Only the events cross the bus.  Everything is float32 and a definition, not a tolerance:
+ *   score          score[t, k] is mts_correlate's, bit for bit, for the same templates, cols, before, taps and reference, for every
+ *                  file row t of [valid_begin, valid_end): z is mts_detect's and +0 outside the recording, the fmaf chain runs from
+ *                  +0 over column groups of 4, then tau, then the group's columns, a NaN is 0x7fc00000.  A row whose template window
+ *                  reads nothing of the recording scores +0.
+ *   event          (t, k) with row_begin <= t < row_end, score[t, k] > threshold[k] and no (t', k') that beats it: |t' - t| <=
+ *                  exclude_rows, any template k', valid_begin <= t' < valid_end -- inside or outside [row_begin, row_end).  It beats
+ *                  (t, k) when score[t', k'] > score[t, k], or they are equal and (t', k') precedes (t, k) in (row, template)
+ *                  order.  mts_detect's words with every template a neighbour: a NaN score is no event and beats nothing; a plateau
+ *                  gives one event, at its first row and lowest template; -0 equals +0; of two identical templates the lower index
+ *                  has the event; a row has at most one event.  Calls on [a, b) and [b, c) together give the events of [a, c).
+ *                  Equivalently: with b[t] the largest score of row t that is not a NaN and k*[t] the first template that attains
+ *                  it, row t is an event when b[t] > threshold[k*[t]], no earlier row within exclude_rows has b >= b[t] and no later
+ *                  one has b > b[t]; a row of NaNs has no b.
+ *   threshold      n_out finite floats on the host, of any sign
+ *   outputs        the events in ascending row order: out_row[i] = t (file row), out_template[i] = k, out_score[i] = the bits of
+ *                  score[t, k].  *n_events: the events found, which may exceed max_events; then the first max_events of them are
+ *                  written, nothing past them, and the call still answers MTS_OK (call again with room for *n_events).  max_events
+ *                  0: a count, the outputs may be null.  The same bytes whatever the call, its pieces, its slabs, the cache, the
+ *                  entry point or the device.
+ *   limits         exclude_rows <= MTS_TMATCH_MAX_EXCLUDE; T, n_out, n_cols, taps and the reference as mts_correlate
+ *   chunks         as mts_decimate: adjacent, ascending, covering [row_begin - exclude_rows - before + half - n_taps + 1, row_end +
+ *                  exclude_rows + T - before - 1 + half) within [valid_begin, valid_end); valid_begin <= row_begin <= row_end <=
+ *                  valid_end.  No chunks at all when that range is empty (every score near the rows is +0).  row_begin == row_end is
+ *                  MTS_OK with *n_events = 0.
+ *   chunk_status   MTS_CHUNK_* per chunk; the events near a failed chunk are undefined
+ * mts_match_templates: host cdata; cache_id 0 or a decoded-chunk cache, used as mts_correlate uses it; nothing is inserted.  A piece
+ * owns the rows of its chunks; within a piece the rows go through slabs of owned rows that keep both the float workspace (the owned
+ * rows, exclude_rows either side and their T - 1 neighbours) and the score slab (the owned rows and exclude_rows either side, n_out
+ * floats each) within 256 MiB (MTS_TMATCH_SLAB_BYTES; never less than one row with its neighbours): filter, median, k_correlate into
+ * the score slab, then the row maxima, the event bitmap and its compaction.  The scores never leave the device.  The outputs are host
+ * memory.
+ * mts_dev_match_templates: device d_cdata and d_* outputs on `device`; templates, threshold, n_events and chunk_status on the host; no
+ * cache.
+ * MTS_E_ARG with a message before anything is allocated or launched: any argument outside the limits above, a template entry, a
+ * threshold or a tap that is not finite, no templates, no thresholds, max_events < 0 or no output buffer for it, no n_events, a column
+ * outside [0, n_channels), chunks not adjacent or not covering the rows read.
+ */
+int mts_match_templates(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                        const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags,
+                        long valid_begin, long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols,
+                        const int *cols, int reference, int before, int T, int n_out, const float *templates /* (n_out, T, n_cols) C order */,
+                        const float *threshold /* n_out */, int exclude_rows, long max_events, long *out_row, int *out_template,
+                        float *out_score, long *n_events, int *chunk_status);
+
+/*
  * Per-channel power spectral density, Welch's method (an extension: the reference has no such call; its users run
  * scipy.signal.welch on Reader[...] on the host).  Only one float64 partial per (group, bin, column) crosses the bus.
  *   segments       segment s covers file rows [row_seg0 + s * step, row_seg0 + s * step + nperseg); the call computes segments
@@ -561,6 +610,12 @@ int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, co
                       const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
                       long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
                       int before, int T, int n_out, const float *templates /* host */, float *d_out, int *chunk_status /* host */);
+int mts_dev_match_templates(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                            const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags,
+                            long valid_begin, long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols,
+                            const int *cols, int reference, int before, int T, int n_out, const float *templates /* host */,
+                            const float *threshold /* host */, int exclude_rows, long max_events, long *d_row, int *d_template,
+                            float *d_score, long *n_events /* host */, int *chunk_status /* host */);
 int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                   const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0,
                   long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,

@@ -72,6 +72,9 @@ WAVEFORMS_CALL_BYTES = 1 << 30         # Reader.waveforms: compressed bytes per 
 WAVEFORMS_OUT_BYTES = 1 << 30          # ... and the bytes of a call's result
 CORRELATE_CALL_BYTES = 1 << 30         # Reader.correlate: compressed bytes per device call (a longer range is split at chunk boundaries) ...
 CORRELATE_OUT_BYTES = 1 << 30          # ... and the bytes of a call's result
+TMATCH_CALL_BYTES = 1 << 30            # Reader.match_templates: compressed bytes per device call (a longer range is split at chunk boundaries)
+TMATCH_GUESS_MIN = 4096                # Reader.match_templates: events a call's first buffer holds at least, and one more per this many samples:
+TMATCH_GUESS_SAMPLES = 64              # a call that finds more says how many and is made once more
 PROJECT_CALL_BYTES = 1 << 30           # Reader.project: compressed bytes per device call (a longer range is split at chunk boundaries) ...
 PROJECT_OUT_BYTES = 1 << 30            # ... and the bytes of a call's result
 WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
@@ -386,6 +389,7 @@ class HipCodec:
     project = _lane_reduction('project')
     waveforms = _lane_reduction('waveforms')
     correlate = _lane_reduction('correlate')
+    match_templates = _lane_reduction('match_templates')
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1843,6 +1847,85 @@ class Reader:
             for a, b, (y,) in self._halo_parts(self.codec.correlate, cuts, part):
                 out[a - i0:b - i0] = y
         return out[:, 0] if squeeze else out
+
+    # -- template-matching events on the device (an extension: the reference's users pick the peaks of a matched filter on the host)
+    def match_templates(self, templates, threshold, start=0, stop=None, channels=slice(None), before=20, taps=None, reference=None,
+                        exclude=None):
+        """The peaks of correlate's scores over the rows [start, stop), on the device: only the events cross the bus.  score[t, k] is
+        correlate(templates, channels=channels, before=before, taps=taps, reference=reference)'s, bit for bit, for every row t of
+        the recording.  (t, k) is an event when score[t, k] > threshold[k] and no score within `exclude` rows (any template, inside
+        the recording, inside or outside [start, stop)) beats it: score' > score, or score' == score at an earlier (row, template).
+        These are detect's words with every template a neighbour: a NaN score is no event and beats nothing, a plateau gives one
+        event (its first row and lowest template), -0 equals +0, of two identical templates the lower index has the event, a row
+        has at most one event, and match_templates(a, b) followed by match_templates(b, c) is match_templates(a, c).  templates,
+        channels, before, taps and reference as correlate takes them (a 2-D (T, W) array is one template); threshold: a finite
+        number or one per template, of any sign; exclude: 0 .. 255 rows, None is min(T - 1, 255) -- no two events closer than a
+        template.  Returns a Bunch: sample (int64 file rows, ascending), template (int64), score (float32, the bits of
+        correlate(...)[sample - start, template]), threshold (the float32 array used), start, stop, channels, exclude.  The same
+        bytes whatever the lanes, calls, pieces, slabs or cache residency.  Chunks resident in the device cache are read where they
+        lie; the others are decoded in a transient workspace and NOT kept.  A damaged chunk in the support raises the IOError of
+        Reader[...]."""
+        self._need_codec('match_templates', 'match_templates', 'matches templates')
+        if reference not in (None, 'median'):
+            raise ValueError("reference must be None or 'median', got %r" % (reference,))
+        taps = _fir_taps([1.0] if taps is None else taps)
+        i0, i1 = self._row_range(start, stop)
+        cols, _ = self._stats_channels(channels)
+        k = np.asarray(templates)
+        if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
+            raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
+        with np.errstate(over='ignore'):
+            k = np.ascontiguousarray((k[None] if k.ndim == 2 else k).astype(np.float32))
+        n_out, T, W = k.shape
+        if W != cols.size:
+            raise ValueError("templates have %d columns for %d selected channels" % (W, cols.size))
+        if not 1 <= W <= hip.CORRELATE_MAX_COLS:
+            raise ValueError("match_templates takes 1 to %d columns, got %d" % (hip.CORRELATE_MAX_COLS, W))
+        if not 1 <= T <= hip.CORRELATE_MAX_T:
+            raise ValueError("templates have 1 to %d rows, got %d" % (hip.CORRELATE_MAX_T, T))
+        if not 1 <= n_out <= hip.CORRELATE_MAX_OUT:
+            raise ValueError("match_templates takes 1 to %d templates, got %d" % (hip.CORRELATE_MAX_OUT, n_out))
+        if not isinstance(before, (int, np.integer)) or isinstance(before, bool) or not 0 <= before <= T:
+            raise ValueError("before must be an int in [0, %d], got %r" % (T, before))
+        if not np.isfinite(k).all():
+            raise ValueError("templates must be finite in float32")
+        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
+            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
+        if exclude is None:
+            exclude = min(T - 1, hip.TMATCH_MAX_EXCLUDE)
+        if not isinstance(exclude, (int, np.integer)) or isinstance(exclude, bool) or not 0 <= exclude <= hip.TMATCH_MAX_EXCLUDE:
+            raise ValueError("exclude must be an int in [0, %d], got %r" % (hip.TMATCH_MAX_EXCLUDE, exclude))
+        thr = np.asarray(threshold)
+        if thr.dtype.kind not in 'fiu' or thr.shape not in ((), (n_out,)):
+            raise ValueError("threshold must be a number or one per template (%d)" % n_out)
+        with np.errstate(over='ignore'):
+            thr = np.ascontiguousarray(np.broadcast_to(thr.astype(np.float32), (n_out,)))
+        if not np.isfinite(thr).all():
+            raise ValueError("threshold must be finite in float32")
+        before, R, n_taps, N = int(before), int(exclude), int(taps.size), self.n_samples
+        after, half, ref_code = T - before, (n_taps - 1) // 2, 1 if reference else 0
+        found = []                                                  # (row, template, score) of every part, in order
+        if i1 > i0:
+            def support(a, b):                                      # the file rows that the events of rows [a, b) read
+                return max(0, a - R - before + half - (n_taps - 1)), min(N, b + R + after - 1 + half)
+            # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they read pass TMATCH_CALL_BYTES
+            lo, hi = support(i0, i1)
+            cuts = self._halo_cuts(lo, hi, TMATCH_CALL_BYTES, i0, i1, lambda row: min(i1, max(i0, row))) if lo < hi else [i0, i1]
+
+            def part(a, b):
+                lo, hi = support(a, b)                              # (rows that read no row of the recording score +0: a call without chunks)
+                keys = self._chunk_span(lo, hi) if lo < hi else []
+                cap = max(TMATCH_GUESS_MIN, (b - a) // TMATCH_GUESS_SAMPLES)
+                return keys, (0, N, a, b, taps, cols, ref_code, before, k, thr, R, cap)
+
+            def again(out, args):                                   # the buffer was short: once more, with room for all
+                if out[1] > args[-1] and all(v == hip.CHUNK_OK for v in out[0]):
+                    return args[:-1] + (out[1],)
+            found = [ev[1:] for _, _, ev in self._halo_parts(self.codec.match_templates, cuts, part, again)]
+        row = np.concatenate([f[0] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
+        tpl = np.concatenate([f[1] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
+        val = np.concatenate([f[2] for f in found]).astype(np.float32) if found else np.zeros(0, np.float32)
+        return Bunch(sample=row, template=tpl, score=val, threshold=thr, start=i0, stop=i1, channels=cols, exclude=R)
 
     # -- peak detection on the device (an extension: the reference's users filter Reader[...] and look for peaks on the host)
     def detect(self, threshold, start=0, stop=None, channels=slice(None), taps=None, sign='neg', reference=None, exclude=0, spread=0):

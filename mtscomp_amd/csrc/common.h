@@ -148,6 +148,23 @@ constexpr int CORRELATE_PAD = 64;
 int launch_correlate(hipStream_t st, const float *d_z, long ws_row0, long ws_rows, int n_cols, long vb, long ve, const float *d_tpl, int tpl_pitch,
                      int T, int before, int n_out, long r_begin, long r_end, float *d_out);
 
+// tmatch.hip: the events of a slab of those scores (mts_match_templates).  d_score: score[t, k] of file rows [sc_row0, sc_row0 + sc_rows)
+// x n_out, every row of the recording within exclude_rows of [s0, s1).  launch_tmatch_best: per score row the largest score that is not
+// a NaN and the first template that attains it (NaN and -1 for a row of NaNs).  launch_tmatch_mask: one bit per row of [s0, s1), in
+// words of 64 rows (tmatch_bitmap_words): 1 = an event, best > d_thr[arg] and no row within exclude_rows that beats it; rows outside the
+// slab do not exist.  launch_tmatch_emit: the events of the bitmap in row order to d_row / d_tpl / d_score from position *d_total on,
+// those at positions >= max_events counted only; *d_total += the events of the bitmap (launch_bitmap_offsets, detect.hip: the counts
+// and offsets of any bitmap's blocks of DETECT_BLOCK_WORDS words, one entry per detect_blocks(n_words))
+constexpr int TMATCH_MAX_EXCLUDE = MTS_TMATCH_MAX_EXCLUDE;         // include/mtscomp_hip.h
+constexpr int DETECT_BLOCK_WORDS = 1024;
+int launch_bitmap_offsets(hipStream_t st, const u64 *d_bitmap, long n_words, u32 *d_counts, u64 *d_offsets, u64 *d_total);
+long tmatch_bitmap_words(long n_rows);
+int launch_tmatch_best(hipStream_t st, const float *d_score, long n_rows, int n_out, float *d_best, int *d_arg);
+int launch_tmatch_mask(hipStream_t st, const float *d_best, const int *d_arg, long sc_row0, long sc_rows, const float *d_thr, int exclude_rows,
+                       long s0, long s1, u64 *d_bitmap);
+int launch_tmatch_emit(hipStream_t st, const u64 *d_bitmap, long n_words, u32 *d_counts, u64 *d_offsets, u64 *d_total, const float *d_best,
+                       const int *d_arg, long sc_row0, long s0, long max_events, long *d_row, int *d_tpl, float *d_score);
+
 // welch.hip: Welch PSD partials (mts_welch).  Segments s of blocks [block0, block0 + n_blocks) (block b: segments [b * B, (b + 1) * B)
 // ∩ [.., seg_end)) start at file row row_seg0 + s * step; d_part[(b - block0), k, c] = sum over the block's segments, in order, of
 // |X_k|^2 of column cols[c] (float64; X in the csize float type).  d_taper: 2^log2n values, d_tw: 2^log2n complex values

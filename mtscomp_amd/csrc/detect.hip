@@ -239,6 +239,19 @@ int launch_detect_mask(hipStream_t st, const float *d_z, long ws_row0, long ws_r
     return MTS_OK;
 }
 
+// k_detect_count and k_detect_scan know nothing of what a bit stands for: the offsets of any bitmap's blocks (tmatch.hip emits by them)
+int launch_bitmap_offsets(hipStream_t st, const u64 *d_bitmap, long n_words, u32 *d_counts, u64 *d_offsets, u64 *d_total)
+{
+    static_assert(DETECT_BLOCK_WORDS == DET_BLOCK_WORDS, "common.h states the block of the bitmap kernels");
+    if (n_words <= 0) return MTS_OK;
+    const long nb = detect_blocks(n_words);
+    if (nb > 0x7fffffffl) { set_error("detect: too many rows in one launch"); return MTS_E_ARG; }
+    hipLaunchKernelGGL(k_detect_count, dim3((unsigned)nb), dim3(DET_THREADS), 0, st, d_bitmap, (u64)n_words, d_counts);
+    hipLaunchKernelGGL(k_detect_scan, dim3(1), dim3(DET_THREADS), 0, st, d_counts, nb, d_offsets, d_total);
+    MTS_HIP(hipGetLastError());
+    return MTS_OK;
+}
+
 int launch_detect_emit(hipStream_t st, const u64 *d_bitmap, long n_words, u32 *d_counts, u64 *d_offsets, u64 *d_total, const float *d_z,
                        long ws_row0, int n_cols, long s0, long max_events, long *d_row, int *d_pos, float *d_amp)
 {

@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, correlate, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, correlate, match_templates, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -26,7 +26,7 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, waveforms, correlate, welch, gram): a unit of output (outputs, rows, events, blocks, groups -- the op gives HaloPlan its map
+//   halo (decimate, project, detect, waveforms, correlate, match_templates, welch, gram): a unit of output (outputs, rows, events, blocks, groups -- the op gives HaloPlan its map
 //        from units to rows) reads rows of several adjacent chunks, so a piece reads chunks [c0, c1] through a table of segment bases
 //        and first rows, and decodes the missing ones among them -- a boundary chunk in both pieces (HaloPlan, HaloFeed).
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
@@ -876,6 +876,18 @@ static u64 correlate_slab_bytes()
     return v > 0 ? (u64)v : CORRELATE_SLAB_BYTES;
 }
 
+// the templates (n_out, T, n_cols) in k_correlate's layout: row (g / 4 * T + tau) * 4 + c holds K[0 .. kp, tau, g + c], +0 past n_cols and n_out
+static std::vector<float> repack_templates(const float *templates, int n_out, int n_tau, int n_cols, int kp)
+{
+    std::vector<float> h_tpl(align_up((u64)n_cols, 4) * n_tau * kp, 0.0f);
+    for (int k = 0; k < n_out; k++)
+        for (int tau = 0; tau < n_tau; tau++) {
+            const float *src = templates + ((size_t)k * n_tau + tau) * n_cols;
+            for (int j = 0; j < n_cols; j++) h_tpl[(((size_t)(j >> 2) * n_tau + tau) * 4 + (j & 3)) * kp + k] = src[j];
+        }
+    return h_tpl;
+}
+
 static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
                          int n_cols, const int *cols, int reference, int before, int n_tau, int n_out, const float *templates, float *out,
                          bool out_on_host, int *status)
@@ -925,13 +937,9 @@ static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
                  o_y = L.take(4 * (u64)(own + n_tau - 1) * n_cols), o_out = L.take_out(4 * n_items);
     if ((rc = H.place(E, st, E.cor, o_seg))) return rc;
     u8 *ws = E.cor.as<u8>();
-    std::vector<float> h_taps(n_taps), h_tpl(tpl_items, 0.0f);
+    std::vector<float> h_taps(n_taps);
     for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
-    for (int k = 0; k < n_out; k++)
-        for (int tau = 0; tau < n_tau; tau++) {
-            const float *src = templates + ((size_t)k * n_tau + tau) * n_cols;
-            for (int j = 0; j < n_cols; j++) h_tpl[(((size_t)(j >> 2) * n_tau + tau) * 4 + (j & 3)) * kp + k] = src[j];
-        }
+    const std::vector<float> h_tpl = repack_templates(templates, n_out, n_tau, n_cols, kp);
     MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_tpl, h_tpl.data(), 4 * (size_t)tpl_items, hipMemcpyHostToDevice, st));
@@ -954,6 +962,128 @@ static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
     if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps and h_tpl have been read before they go)
     if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, 4 * n_items, hipMemcpyDeviceToHost, st));
     MTS_HIP(hipStreamSynchronize(st));
+    return MTS_OK;
+}
+
+// ---- template events (mts_match_templates, mts_dev_match_templates) ------------------------------------------------------------
+// The unit is a row of [row_begin, row_end).  Piece p owns the rows in its chunks; their events need the scores R rows either side,
+// those z from `before` rows before to T - before - 1 rows after, and that the filter's support: the rows [u0, u1) read the file rows
+// from u0 - R - before + half - (L - 1) to u1 + R + T - before - 1 + half, within the valid range.  A piece's rows go through slabs of
+// owned rows [s0, s1): the scores of [sa, sb) = [max(vb, s0 - R), min(ve, s1 + R)) from z of [max(vb, sa - before), min(ve, sb + after
+// - 1)) -- filter -> median -> k_correlate into the score slab -> row maxima -> mask -> count / scan / emit, all on the stream; the
+// write position is carried on the device from slab to slab and piece to piece.  `own` keeps both the z slab and the score slab within
+// the slab bound, and is never less than one row with its neighbours.  launch_decimate, launch_row_median and launch_correlate are
+// correlate_run's, so every score has correlate's bits whatever the pieces and slabs.
+static const u64 TMATCH_SLAB_BYTES = 256ull << 20;
+static const long TMATCH_SLAB_MAX_ROWS = 1l << 22;                  // (bounds the row maxima and the bitmap of a call with few templates)
+
+static u64 tmatch_slab_bytes()
+{
+    const char *e = getenv("MTS_TMATCH_SLAB_BYTES");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (u64)v : TMATCH_SLAB_BYTES;
+}
+
+static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
+                      int n_cols, const int *cols, int reference, int before, int n_tau, int n_out, const float *templates, const float *threshold,
+                      int R, long max_events, long *out_row, int *out_tpl, float *out_score, bool out_on_host, long *n_events, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    int rc;
+    if (nc <= 0 || T.n_chunks < 0) { set_error("match_templates: n_channels or n_chunks invalid"); return MTS_E_ARG; }
+    if (n_cols < 1 || n_cols > MTS_CORRELATE_MAX_COLS || !cols) { set_error("match_templates: %d columns (1 .. %d)", n_cols, MTS_CORRELATE_MAX_COLS); return MTS_E_ARG; }
+    if ((rc = check_taps("match_templates", n_taps, taps))) return rc;
+    if (reference < 0 || reference > 1) { set_error("match_templates: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
+    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("match_templates: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
+    if (n_tau < 1 || n_tau > MTS_CORRELATE_MAX_T) { set_error("match_templates: templates of %d rows (1 .. %d)", n_tau, MTS_CORRELATE_MAX_T); return MTS_E_ARG; }
+    if (before < 0 || before > n_tau) { set_error("match_templates: before %d (0 .. %d)", before, n_tau); return MTS_E_ARG; }
+    if (n_out < 1 || n_out > MTS_CORRELATE_MAX_OUT || !templates) { set_error("match_templates: %d templates (1 .. %d)", n_out, MTS_CORRELATE_MAX_OUT); return MTS_E_ARG; }
+    const long per = (long)n_tau * n_cols;
+    for (long e = 0; e < (long)n_out * per; e++)
+        if (!std::isfinite(templates[e])) { set_error("match_templates: template entry (%ld, %ld, %ld) is not finite", e / per, e % per / n_cols, e % n_cols); return MTS_E_ARG; }
+    if (!threshold) { set_error("match_templates: no thresholds"); return MTS_E_ARG; }
+    for (int k = 0; k < n_out; k++)
+        if (!std::isfinite(threshold[k])) { set_error("match_templates: threshold %d is not finite", k); return MTS_E_ARG; }
+    if (R < 0 || R > MTS_TMATCH_MAX_EXCLUDE) { set_error("match_templates: exclude_rows %d (0 .. %d)", R, MTS_TMATCH_MAX_EXCLUDE); return MTS_E_ARG; }
+    if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve) { set_error("match_templates: rows invalid"); return MTS_E_ARG; }
+    if (max_events < 0 || max_events > (1l << 40) || !n_events) { set_error("match_templates: max_events invalid or no n_events"); return MTS_E_ARG; }
+    if (max_events && (!out_row || !out_tpl || !out_score)) { set_error("match_templates: no output buffers"); return MTS_E_ARG; }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, T))) return rc;
+    const long half = (n_taps - 1) / 2, n_units = row_end - row_begin, after = n_tau - before;
+    // the rows that the events of rows [u0, u1) read: ((rows + R either side) - before .. + after - 1)'s support ∩ valid range
+    auto rows = [&](long u0, long u1, long *lo, long *hi) {
+        *lo = std::max(vb, row_begin + u0 - R - before + half - (n_taps - 1)); *hi = std::min(ve, row_begin + u1 + R + after - 1 + half);
+    };
+    long need_lo = 0, need_hi = 0;
+    if (n_units) rows(0, n_units, &need_lo, &need_hi);
+    if ((rc = check_cover("match_templates", T, need_lo, need_hi))) return rc;
+    status_ok(T, status);
+    *n_events = 0;
+    if (!n_units) return MTS_OK;
+
+    HaloFeed H(T, out_on_host);
+    if ((rc = H.plan(n_units, [&](long r) { return r - row_begin; }, rows))) return rc;
+    // rows a slab owns: the z slab holds them, R either side and their T - 1 neighbours; the score slab them and R either side (reduce_plan.h)
+    const TmatchSlabs SL(n_units, R, before, n_tau, vb, ve, n_cols, n_out, tmatch_slab_bytes(), TMATCH_SLAB_MAX_ROWS);
+    const long own = SL.own, sc_rows = SL.sc_rows, z_rows = SL.z_rows;
+    const long max_words = tmatch_bitmap_words(own), max_blocks = detect_blocks(max_words);
+    // ---- workspace
+    const int n4 = (int)align_up((u64)n_cols, 4), kp = (int)align_up((u64)n_out, CORRELATE_PAD);
+    const u64 tpl_items = (u64)n4 * n_tau * kp;
+    WsLayout &L = H.L;
+    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_thr = L.take(4 * (u64)n_out), o_seg = L.take(H.table_bytes()),
+                 o_total = L.take(8), o_tpl = L.take(4 * tpl_items), o_y = L.take(4 * (u64)z_rows * n_cols), o_sc = L.take(4 * (u64)sc_rows * n_out),
+                 o_best = L.take(4 * (u64)sc_rows), o_arg = L.take(4 * (u64)sc_rows), o_bits = L.take(8 * (u64)max_words),
+                 o_cnt = L.take(4 * (u64)max_blocks), o_offs = L.take(8 * (u64)max_blocks), o_row = L.take_out(8 * (u64)max_events),
+                 o_k = L.take_out(4 * (u64)max_events), o_val = L.take_out(4 * (u64)max_events);
+    if ((rc = H.place(E, st, E.tm, o_seg))) return rc;
+    u8 *ws = E.tm.as<u8>();
+    std::vector<float> h_taps(n_taps);
+    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
+    const std::vector<float> h_tpl = repack_templates(templates, n_out, n_tau, n_cols, kp);
+    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_thr, threshold, 4 * (size_t)n_out, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_tpl, h_tpl.data(), 4 * (size_t)tpl_items, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemsetAsync(ws + o_total, 0, 8, st));
+    long *d_row = L.out(ws, o_row, out_row);
+    int *d_k = L.out(ws, o_k, out_tpl);
+    float *d_val = L.out(ws, o_val, out_score);
+    float *d_y = (float *)(ws + o_y), *d_sc = (float *)(ws + o_sc), *d_best = (float *)(ws + o_best);
+    int *d_arg = (int *)(ws + o_arg);
+    u64 *d_bits = (u64 *)(ws + o_bits), *d_total = (u64 *)(ws + o_total);
+    rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
+        const long p0 = row_begin + Pc.u0, p1 = row_begin + Pc.u1;
+        int r = MTS_OK;
+        for (long s0 = p0; !r && s0 < p1; s0 += own) {
+            const TmatchSlab S = SL.at(s0, p1);
+            const long s1 = S.s1, sa = S.sa, sb = S.sb, a = S.a, b = S.b;
+            // y[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k
+            if (b > a) r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half,
+                                           a, b, Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
+            if (!r && reference && b > a) r = launch_row_median(st, d_y, b - a, n_cols);
+            if (!r) r = launch_correlate(st, d_y, a, b - a, n_cols, vb, ve, (const float *)(ws + o_tpl), kp, n_tau, before, n_out, sa, sb, d_sc);
+            if (!r) r = launch_tmatch_best(st, d_sc, sb - sa, n_out, d_best, d_arg);
+            if (!r) r = launch_tmatch_mask(st, d_best, d_arg, sa, sb - sa, (const float *)(ws + o_thr), R, s0, s1, d_bits);
+            if (!r) r = launch_tmatch_emit(st, d_bits, tmatch_bitmap_words(s1 - s0), (u32 *)(ws + o_cnt), (u64 *)(ws + o_offs), d_total, d_best, d_arg,
+                                           sa, s0, max_events, d_row, d_k, d_val);
+        }
+        return r;
+    });
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps and h_tpl have been read before they go)
+    u64 total = 0;
+    MTS_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
+    MTS_HIP(hipStreamSynchronize(st));
+    *n_events = (long)total;
+    const size_t n_w = (size_t)std::min<u64>(total, (u64)max_events);
+    if (out_on_host && n_w) {
+        MTS_HIP(hipMemcpyAsync(out_row, d_row, 8 * n_w, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_tpl, d_k, 4 * n_w, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_score, d_val, 4 * n_w, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipStreamSynchronize(st));
+    }
     return MTS_OK;
 }
 
@@ -1332,6 +1462,28 @@ int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, co
 {
     return DEV_ENTRY(correlate_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference,
                      before, T_, n_out, templates, d_out, false, chunk_status));
+}
+
+int mts_match_templates(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                        const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags,
+                        long valid_begin, long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols,
+                        const int *cols, int reference, int before, int T_, int n_out, const float *templates, const float *threshold,
+                        int exclude_rows, long max_events, long *out_row, int *out_template, float *out_score, long *n_events,
+                        int *chunk_status)
+{
+    return HOST_ENTRY(tmatch_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before, T_, n_out,
+                      templates, threshold, exclude_rows, max_events, out_row, out_template, out_score, true, n_events, chunk_status));
+}
+
+int mts_dev_match_templates(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                            const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags,
+                            long valid_begin, long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols,
+                            const int *cols, int reference, int before, int T_, int n_out, const float *templates, const float *threshold,
+                            int exclude_rows, long max_events, long *d_row, int *d_template, float *d_score, long *n_events,
+                            int *chunk_status)
+{
+    return DEV_ENTRY(tmatch_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before,
+                     T_, n_out, templates, threshold, exclude_rows, max_events, d_row, d_template, d_score, false, n_events, chunk_status));
 }
 
 int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,

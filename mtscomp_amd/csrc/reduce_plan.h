@@ -1,8 +1,8 @@
 // How a reduction is fed: the part that decides and touches no device.  Which chunks go into which piece, where the compressed
 // bytes of the missing chunks lie in the staging buffer, where each of them is decoded to, which chunks a piece of the halo family
-// reads and what its segment table holds, how the tile family cuts and orders its tiles, how the events of waveforms are cut into
-// slabs.  Addresses are plain integers here: the header includes the C++ standard library only, so tests/plan_check.cpp and
-// tests/snippet_plan_check.cpp sweep these plans on the CPU.  reduce.hip puts the
+// reads and what its segment table holds, how the tile family cuts and orders its tiles, how the events of waveforms and the rows of match_templates
+// are cut into slabs.  Addresses are plain integers here: the header includes the C++ standard library only, so tests/plan_check.cpp,
+// tests/snippet_plan_check.cpp and tests/tmatch_plan_check.cpp sweep these plans on the CPU.  reduce.hip puts the
 // device side around them (ChunkFeed, feed_pieces, HaloFeed, TileFeed) and says there what every caller keeps to.
 #pragma once
 
@@ -177,6 +177,38 @@ struct SnippetPlan {
             slabs.push_back({e, e + 1, a, b});
         }
         for (const SnippetSlab &S : slabs) max_rows = std::max(max_rows, S.b - S.a);
+    }
+};
+
+// ---- template events (match_templates): the rows of one piece cut into slabs of `own` owned rows.  The events of the rows [s0, s1)
+// read the scores of [sa, sb) = [max(vb, s0 - R), min(ve, s1 + R)) -- every row of the recording within R -- and those the filtered rows
+// [a, b) = [max(vb, sa - before), min(ve, sb + after - 1)) (b == a: they read nothing of the recording and every score is +0).  `own` is
+// the largest count that keeps the score slab (sc_rows x n_out floats) and the z slab (z_rows x n_cols floats) within slab_bytes and the
+// z slab within max_rows rows, and is never less than one row with its neighbours; sc_rows and z_rows bound every slab's.
+struct TmatchSlab { long s0, s1, sa, sb, a, b; };
+
+struct TmatchSlabs {
+    long R, before, after, vb, ve, own, sc_rows, z_rows;
+
+    TmatchSlabs(long n_units, long R_, long before_, long n_tau, long vb_, long ve_, long n_cols, long n_out, uint64_t slab_bytes, long max_rows)
+        : R(R_), before(before_), after(n_tau - before_), vb(vb_), ve(ve_)
+    {
+        const long big = 1l << 40;
+        const long z_fit = (long)std::min<uint64_t>(slab_bytes / (4 * (uint64_t)n_cols), (uint64_t)std::min(max_rows, big));
+        const long sc_fit = (long)std::min<uint64_t>(slab_bytes / (4 * (uint64_t)n_out), (uint64_t)big);
+        own = std::max(1l, std::min(n_units, std::min(z_fit - 2 * R - (n_tau - 1), sc_fit - 2 * R)));
+        sc_rows = own + 2 * R;
+        z_rows = sc_rows + n_tau - 1;
+    }
+
+    // the slab that starts at row s0 of a piece that ends at p1
+    TmatchSlab at(long s0, long p1) const
+    {
+        TmatchSlab S;
+        S.s0 = s0; S.s1 = std::min(p1, s0 + own);
+        S.sa = std::max(vb, S.s0 - R); S.sb = std::min(ve, S.s1 + R);
+        S.a = std::max(vb, S.sa - before); S.b = std::max(S.a, std::min(ve, S.sb + after - 1));
+        return S;
     }
 };
 

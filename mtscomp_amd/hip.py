@@ -109,6 +109,7 @@ def lib():
             ('detect', [cl, cl, cl, cl, ci, dp, ci, ip, fp, ci, ci, ci, ci, cl], [vp, vp, vp, lp, ip], None),
             ('waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci], [vp, vp, vp, vp, vp, ip], None),
             ('correlate', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp], [vp, ip], None),
+            ('match_templates', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, fp, ci, cl], [vp, vp, vp, lp, ip], None),
             ('welch', [cl, cl, cl, ci, cl, dp, ci, ci, ci, ip], [vp, ip], None),
             ('gram', [cl, cl, cl, cl, cl, ci, ip], [vp, vp, ip], None),
             ('rank_hist', [cl, cl, cl, ci, ip, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip], [vp, vp, vp, lp, ip])):
@@ -129,6 +130,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
            'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_project', 'mts_dev_project', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
            'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan', 'mts_correlate', 'mts_dev_correlate',
+           'mts_match_templates', 'mts_dev_match_templates',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
 
 
@@ -807,6 +809,50 @@ def dev_correlate(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, vali
     _check(lib().mts_dev_correlate(*head, *mid, *ptrs, _ip(status)), 'mts_dev_correlate')
     res = _dev_fetch(out, at, [np.empty(shape, np.float32)])[0] if download else None
     return _status(status, n), res, out
+
+
+# -- template-matching events
+TMATCH_MAX_EXCLUDE = 255               # MTS_TMATCH_MAX_EXCLUDE
+_TMATCH_DTYPES = (np.int64, np.int32, np.float32)       # row, template, score of an event
+
+
+def _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows, max_events):
+    """-> (the op's own arguments of mts_match_templates, the events the buffers hold, the array for n_events, what the pointers point at)."""
+    mid, shape, keep = _cor_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates)
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(threshold, dtype=np.float32), (shape[1],)))
+    mid = mid + (thr.ctypes.data_as(C.POINTER(C.c_float)), int(exclude_rows), int(max_events))
+    return mid, max(int(max_events), 0), np.zeros(1, np.int64), keep + (thr,)
+
+
+def match_templates(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps,
+                    cols, reference, before, templates, threshold, exclude_rows, max_events, device=0):
+    """mts_match_templates: the template events of rows [row_begin, row_end) (include/mtscomp_hip.h) from the adjacent chunks `keys` (none
+    when the rows read nothing of the recording).  templates (n_out, T, n_cols), threshold a number or one per template, reference 0 / 1.
+    cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns
+    (status list, n_events, row int64, template int32, score float32): the first min(n_events, max_events) events."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, cap, n_ev, _keep = _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows,
+                                     max_events)
+    res = [np.empty(cap, t) for t in _TMATCH_DTYPES]
+    _check(lib().mts_match_templates(*head, *mid, *(_ptr(a) if cap else None for a in res), _lp(n_ev), _ip(status)), 'mts_match_templates')
+    k = min(int(n_ev[0]), cap)
+    return (_status(status, n), int(n_ev[0])) + tuple(a[:k] for a in res)
+
+
+def dev_match_templates(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, reference,
+                        before, templates, threshold, exclude_rows, max_events, out=None, download=True):
+    """mts_dev_match_templates on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the three event arrays (made
+    when None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, n_events, (row, template,
+    score) or None, out)."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, cap, n_ev, _keep = _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows,
+                                     max_events)
+    out, ptrs, at = _dev_results(out, cbuf.device, [cap * np.dtype(t).itemsize for t in _TMATCH_DTYPES])
+    _check(lib().mts_dev_match_templates(*head, *mid, *ptrs, _lp(n_ev), _ip(status)), 'mts_dev_match_templates')
+    res = None
+    if download:
+        res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _TMATCH_DTYPES]))
+    return _status(status, n), int(n_ev[0]), res, out
 
 
 # -- Welch power spectral density
