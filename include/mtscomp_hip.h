@@ -446,6 +446,60 @@ int mts_match_templates(int device, long cache_id, int n_chunks, const long *chu
                         float *out_score, long *n_events, int *chunk_status);
 
 /*
+ * Template peeling: the filtered rows with matched templates subtracted, and the template events of those rows (an extension: the
+ * reference has no such call; a template-matching sorter subtracts every matched template, scaled by its fitted amplitude, and
+ * matches again -- a spike that overlaps a stronger one within exclude_rows is invisible to the first pass).  Everything is float32
+ * and a definition, not a tolerance:
+ *   z              mts_detect's / mts_correlate's z for cols, taps and reference: the filtered rows, minus the row median with
+ *                  reference 1; defined for the file rows of [valid_begin, valid_end) only
+ *   events         n_sub entries (sub_row[e], sub_tpl[e], sub_amp[e]) on the host: valid_begin <= sub_row[e] < valid_end,
+ *                  non-decreasing in e (ties keep the caller's order), 0 <= sub_tpl[e] < n_out, sub_amp[e] finite.  Event e covers
+ *                  file row t when 0 <= tau < T, tau = t - sub_row[e] + before.  n_sub == 0: the three pointers may be null
+ *   residual       acc = z[t, j]; for every event e that covers t, in list order: acc = fmaf(-sub_amp[e], K[sub_tpl[e], tau, j], acc);
+ *                  z'[t, j] = acc.  An event that does not cover the row issues no step (a masked step would turn a -0 into +0);
+ *                  zero template entries are not skipped; rows outside the recording do not exist (mts_correlate's chain keeps
+ *                  reading them as +0).  A NaN is stored as 0x7fc00000, with an empty list too; every other entry of an empty
+ *                  list's result has z's bits.  z'[t, j] depends on t, cols[j], taps, reference and the events that cover t alone:
+ *                  not on the other events, the tile, the slab, the piece, the call, the lane, cache residency, the entry point or
+ *                  the device.  Calls on [a, b) and [b, c) together give the rows of [a, c).
+ *   mts_residual   out (row_end - row_begin, n_cols) float, C order: z' of the file rows [row_begin, row_end)
+ *   mts_match_residual   the events of mts_match_templates, for the same arguments, of the scores of z': score[t, k] is
+ *                  mts_correlate's chain on z', bit for bit, for every file row t of [valid_begin, valid_end).  With n_sub == 0 not
+ *                  one launch or byte differs from mts_match_templates.
+ *   limits         n_sub <= 2^30; T, n_out, n_cols, taps and the reference as mts_correlate; exclude_rows, threshold, max_events and
+ *                  the outputs as mts_match_templates
+ *   chunks         mts_residual: as mts_decimate with q = 1, adjacent, ascending, covering [row_begin + half - n_taps + 1, row_end +
+ *                  half) within [valid_begin, valid_end) -- the subtraction reads no row that the filter did not;
+ *                  mts_match_residual: as mts_match_templates.  valid_begin <= row_begin <= row_end <= valid_end; row_begin ==
+ *                  row_end is MTS_OK with nothing written.
+ *   chunk_status   MTS_CHUNK_* per chunk; the rows and events near a failed chunk are undefined
+ * mts_residual: host cdata; cache_id 0 or a decoded-chunk cache, used as mts_correlate uses it; nothing is inserted.  Within a piece
+ * the rows go through the float workspace in slabs of at most 256 MiB of owned rows (MTS_RESIDUAL_SLAB_BYTES; never less than a row):
+ * filter, median, then k_subtract -- a gather: every (row, column) belongs to one thread, which walks the events that cover its row
+ * in list order; the events of a tile of rows are one range of the sorted list, found by binary search -- writes the slab's rows of
+ * the output.  mts_match_residual runs the same kernel in place on mts_match_templates' z slab, between the median and k_correlate.
+ * The events and a plain (n_out, T, n_cols) copy of the templates are uploaded only when n_sub > 0.  `out` is host memory.
+ * mts_dev_residual, mts_dev_match_residual: device d_cdata and d_* outputs on `device`; templates, threshold, the events, n_events
+ * and chunk_status on the host; no cache.
+ * MTS_E_ARG with a message that names the offending entry, before anything is allocated or launched: as mts_correlate /
+ * mts_match_templates, and an event out of row order, at a row outside [valid_begin, valid_end), with a template index outside [0,
+ * n_out) or an amplitude that is not finite, n_sub outside [0, 2^30], or n_sub > 0 without the three arrays.
+ */
+int mts_residual(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                 const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                 long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                 int before, int T, int n_out, const float *templates /* (n_out, T, n_cols) C order */, long n_sub,
+                 const long *sub_row /* n_sub */, const int *sub_tpl /* n_sub */, const float *sub_amp /* n_sub */,
+                 float *out /* (row_end - row_begin, n_cols) C order */, int *chunk_status);
+int mts_match_residual(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                       const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags,
+                       long valid_begin, long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols,
+                       const int *cols, int reference, int before, int T, int n_out, const float *templates /* (n_out, T, n_cols) C order */,
+                       const float *threshold /* n_out */, int exclude_rows, long max_events, long n_sub, const long *sub_row /* n_sub */,
+                       const int *sub_tpl /* n_sub */, const float *sub_amp /* n_sub */, long *out_row, int *out_template, float *out_score,
+                       long *n_events, int *chunk_status);
+
+/*
  * Per-channel power spectral density, Welch's method (an extension: the reference has no such call; its users run
  * scipy.signal.welch on Reader[...] on the host).  Only one float64 partial per (group, bin, column) crosses the bus.
  *   segments       segment s covers file rows [row_seg0 + s * step, row_seg0 + s * step + nperseg); the call computes segments
@@ -616,6 +670,18 @@ int mts_dev_match_templates(int device, void *stream, const unsigned char *d_cda
                             const int *cols, int reference, int before, int T, int n_out, const float *templates /* host */,
                             const float *threshold /* host */, int exclude_rows, long max_events, long *d_row, int *d_template,
                             float *d_score, long *n_events /* host */, int *chunk_status /* host */);
+int mts_dev_residual(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                     const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                     long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                     int before, int T, int n_out, const float *templates /* host */, long n_sub, const long *sub_row /* host */,
+                     const int *sub_tpl /* host */, const float *sub_amp /* host */, float *d_out, int *chunk_status /* host */);
+int mts_dev_match_residual(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                           const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags,
+                           long valid_begin, long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols,
+                           const int *cols, int reference, int before, int T, int n_out, const float *templates /* host */,
+                           const float *threshold /* host */, int exclude_rows, long max_events, long n_sub, const long *sub_row /* host */,
+                           const int *sub_tpl /* host */, const float *sub_amp /* host */, long *d_row, int *d_template, float *d_score,
+                           long *n_events /* host */, int *chunk_status /* host */);
 int mts_dev_welch(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                   const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long row_seg0,
                   long seg_begin, long seg_end, int nperseg, long step, const double *taper, int detrend, int csize, int n_cols,

@@ -75,7 +75,9 @@ CORRELATE_OUT_BYTES = 1 << 30          # ... and the bytes of a call's result
 TMATCH_CALL_BYTES = 1 << 30            # Reader.match_templates: compressed bytes per device call (a longer range is split at chunk boundaries)
 TMATCH_GUESS_MIN = 4096                # Reader.match_templates: events a call's first buffer holds at least, and one more per this many samples:
 TMATCH_GUESS_SAMPLES = 64              # a call that finds more says how many and is made once more
-PROJECT_CALL_BYTES = 1 << 30           # Reader.project: compressed bytes per device call (a longer range is split at chunk boundaries) ...
+RESIDUAL_CALL_BYTES = 1 << 30          # Reader.residual: compressed bytes per device call (a longer range is split at chunk boundaries) ...
+RESIDUAL_OUT_BYTES = 1 << 30           # ... and the bytes of a call's result
+PROJECT_CALL_BYTES = 1 << 30          # Reader.project: compressed bytes per device call (a longer range is split at chunk boundaries) ...
 PROJECT_OUT_BYTES = 1 << 30            # ... and the bytes of a call's result
 WELCH_CALL_BYTES = 1 << 30             # Reader.welch: compressed bytes per device call (a longer range is split at group boundaries)
 GRAM_CALL_BYTES = 1 << 30              # Reader.cov: compressed bytes per device call (a longer range is split at group boundaries)
@@ -278,6 +280,57 @@ def whitening_weights(cov, eps=0.0):
     return 0.5 * (w + w.T)
 
 
+def template_amplitudes(score, template, templates):
+    """The least-squares amplitudes of matched templates: score[e] / sum(templates[template[e]] ** 2) -- the a that minimises
+    |z - a * K| when score is the matched filter's <z, K>.  The norms are summed in float64 from the templates rounded to float32 (what
+    the device multiplies by), the quotient is formed in float64 and rounded once to float32.  score, template: the arrays of a
+    match_templates result (or any of one shape); templates: (K, T, W), or (T, W) for one.  With ev = r.match_templates(K, thr),
+    r.match_templates(K, thr, subtract=(ev.sample, ev.template, template_amplitudes(ev.score, ev.template, K))) is the second pass of
+    a template-matching sorter.  ValueError for an index outside the templates or a template of zero norm."""
+    k = np.asarray(templates)
+    if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
+        raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
+    with np.errstate(over='ignore'):
+        k = (k[None] if k.ndim == 2 else k).astype(np.float32)
+    if not np.isfinite(k).all():
+        raise ValueError("templates must be finite in float32")
+    sc, tp = np.asarray(score), np.asarray(template)
+    if sc.dtype.kind not in 'fiu' or (tp.size and tp.dtype.kind not in 'iu') or sc.shape != tp.shape:
+        raise ValueError("score (numbers) and template (ints) must have one shape")
+    tp = tp.astype(np.int64)
+    if tp.size and not (0 <= tp.min() and tp.max() < k.shape[0]):
+        raise ValueError("template indices must lie in [0, %d)" % k.shape[0])
+    norm = (k.astype(np.float64) ** 2).reshape(k.shape[0], -1).sum(axis=1)
+    if tp.size and not (norm[tp] > 0).all():
+        raise ValueError("template %d has zero norm" % int(tp[norm[tp] <= 0].ravel()[0]))
+    with np.errstate(over='ignore'):
+        return (sc.astype(np.float64) / norm[tp]).astype(np.float32)
+
+
+def _sub_events(sample, template, amplitude, n_templates, n_samples):
+    """The events of Reader.residual / match_templates(subtract=) as (sample int64, template int32, amplitude float32), stable-sorted by
+    sample: three 1-D arrays of one length, 0 <= sample < n_samples, 0 <= template < n_templates, amplitudes finite in float32."""
+    sm, tp, am = np.asarray(sample), np.asarray(template), np.asarray(amplitude)
+    if sm.ndim != 1 or tp.ndim != 1 or am.ndim != 1 or not sm.size == tp.size == am.size:
+        raise ValueError("the subtracted events are three 1-D arrays of one length: sample, template, amplitude")
+    if sm.size > hip.RESIDUAL_MAX_EVENTS:
+        raise ValueError("at most %d subtracted events, got %d" % (hip.RESIDUAL_MAX_EVENTS, sm.size))
+    if sm.size == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32)
+    if sm.dtype.kind not in 'iu' or tp.dtype.kind not in 'iu' or am.dtype.kind not in 'fiu':
+        raise ValueError("sample and template must be ints and amplitude numbers")
+    if sm.min() < 0 or sm.max() >= n_samples:
+        raise ValueError("subtracted samples must lie in [0, %d)" % n_samples)
+    if tp.min() < 0 or tp.max() >= n_templates:
+        raise ValueError("subtracted template indices must lie in [0, %d)" % n_templates)
+    with np.errstate(over='ignore'):
+        am = am.astype(np.float32)
+    if not np.isfinite(am).all():
+        raise ValueError("subtracted amplitudes must be finite in float32")
+    order = np.argsort(sm, kind='stable')
+    return np.ascontiguousarray(sm.astype(np.int64)[order]), np.ascontiguousarray(tp.astype(np.int32)[order]), np.ascontiguousarray(am[order])
+
+
 def _window_rows(window, i0, i1):
     """The window of Reader.window_stats / quantile / cov over rows [i0, i1) as an int: None is one window over the range."""
     if window is None:
@@ -390,6 +443,8 @@ class HipCodec:
     waveforms = _lane_reduction('waveforms')
     correlate = _lane_reduction('correlate')
     match_templates = _lane_reduction('match_templates')
+    residual = _lane_reduction('residual')
+    match_residual = _lane_reduction('match_residual')
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1850,7 +1905,7 @@ class Reader:
 
     # -- template-matching events on the device (an extension: the reference's users pick the peaks of a matched filter on the host)
     def match_templates(self, templates, threshold, start=0, stop=None, channels=slice(None), before=20, taps=None, reference=None,
-                        exclude=None):
+                        exclude=None, subtract=None):
         """The peaks of correlate's scores over the rows [start, stop), on the device: only the events cross the bus.  score[t, k] is
         correlate(templates, channels=channels, before=before, taps=taps, reference=reference)'s, bit for bit, for every row t of
         the recording.  (t, k) is an event when score[t, k] > threshold[k] and no score within `exclude` rows (any template, inside
@@ -1864,8 +1919,16 @@ class Reader:
         correlate(...)[sample - start, template]), threshold (the float32 array used), start, stop, channels, exclude.  The same
         bytes whatever the lanes, calls, pieces, slabs or cache residency.  Chunks resident in the device cache are read where they
         lie; the others are decoded in a transient workspace and NOT kept.  A damaged chunk in the support raises the IOError of
-        Reader[...]."""
+        Reader[...].
+        subtract: None, or (sample, template, amplitude) as residual takes them -- the events of an earlier pass with their
+        template_amplitudes.  The scores are then correlate's chain, bit for bit, on residual's z' in place of z (for every row of
+        the recording, so the calls still stitch with the same list), and the events are the peaks that the subtracted templates
+        hid: a spike within `exclude` rows of a stronger one."""
         self._need_codec('match_templates', 'match_templates', 'matches templates')
+        if subtract is not None:
+            self._need_codec('match_templates(subtract=)', 'match_residual', 'subtracts templates')
+            if not isinstance(subtract, (tuple, list)) or len(subtract) != 3:
+                raise ValueError("subtract must be None or (sample, template, amplitude)")
         if reference not in (None, 'median'):
             raise ValueError("reference must be None or 'median', got %r" % (reference,))
         taps = _fir_taps([1.0] if taps is None else taps)
@@ -1904,6 +1967,7 @@ class Reader:
             raise ValueError("threshold must be finite in float32")
         before, R, n_taps, N = int(before), int(exclude), int(taps.size), self.n_samples
         after, half, ref_code = T - before, (n_taps - 1) // 2, 1 if reference else 0
+        sub = None if subtract is None else _sub_events(*subtract, n_out, N)
         found = []                                                  # (row, template, score) of every part, in order
         if i1 > i0:
             def support(a, b):                                      # the file rows that the events of rows [a, b) read
@@ -1916,16 +1980,87 @@ class Reader:
                 lo, hi = support(a, b)                              # (rows that read no row of the recording score +0: a call without chunks)
                 keys = self._chunk_span(lo, hi) if lo < hi else []
                 cap = max(TMATCH_GUESS_MIN, (b - a) // TMATCH_GUESS_SAMPLES)
-                return keys, (0, N, a, b, taps, cols, ref_code, before, k, thr, R, cap)
+                args = (0, N, a, b, taps, cols, ref_code, before, k, thr, R, cap)
+                if sub is None:
+                    return keys, args
+                # with every event whose window meets the rows that the call computes z for: [a - R - before, b + R + after - 1)
+                e0, e1 = np.searchsorted(sub[0], [a - R - T + 1, b + R + after - 1 + before])
+                return keys, args + tuple(v[e0:e1] for v in sub)
 
             def again(out, args):                                   # the buffer was short: once more, with room for all
-                if out[1] > args[-1] and all(v == hip.CHUNK_OK for v in out[0]):
-                    return args[:-1] + (out[1],)
-            found = [ev[1:] for _, _, ev in self._halo_parts(self.codec.match_templates, cuts, part, again)]
+                if out[1] > args[11] and all(v == hip.CHUNK_OK for v in out[0]):
+                    return args[:11] + (out[1],) + args[12:]
+            fn = self.codec.match_templates if sub is None else self.codec.match_residual
+            found = [ev[1:] for _, _, ev in self._halo_parts(fn, cuts, part, again)]
         row = np.concatenate([f[0] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
         tpl = np.concatenate([f[1] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
         val = np.concatenate([f[2] for f in found]).astype(np.float32) if found else np.zeros(0, np.float32)
         return Bunch(sample=row, template=tpl, score=val, threshold=thr, start=i0, stop=i1, channels=cols, exclude=R)
+
+    # -- template peeling on the device (an extension: the reference's users subtract matched templates from Reader[...] on the host)
+    def residual(self, sample, template, amplitude, templates, start=0, stop=None, channels=slice(None), before=20, taps=None, reference=None):
+        """The filtered rows [start, stop) with matched templates subtracted, on the device.  All in float32.  z is correlate's z
+        inside the recording: the bytes of decimate(1, taps=taps, edge='recording', dtype=float32) on `channels` (taps=None is
+        [1.0]), minus, with reference='median', the float32 median over all selected columns of each row.  The events (sample[e],
+        template[e], amplitude[e]) -- 1-D arrays of one length, 0 <= sample < n_samples in any order with repeats, template an index
+        into `templates`, amplitude finite -- are ordered by sample, equal samples in list order.  Event e covers file row t when 0 <=
+        tau = t - sample[e] + before < T, and row i of the result is, for t = start + i,
+        acc = z[t, j]; for every event that covers t, in that order: acc = fmaf(-amplitude[e], templates[template[e], tau, j], acc),
+        bit for bit; a NaN has the bits 0x7fc00000.  An event that does not cover a row does nothing to it (no masked step: -0
+        stays -0), zero template entries are not skipped, and an empty list returns z itself -- the referenced, filtered rows.
+        The same bytes whatever the lanes, calls, pieces, slabs, cache residency or the events that cover none of the rows asked
+        for, and residual(a, b) followed by residual(b, c) is residual(a, c).  templates, channels, before, taps and reference as
+        correlate takes them (a 2-D (T, W) array is one template).  With ev = match_templates(K, thr) and amp =
+        template_amplitudes(ev.score, ev.template, K), residual(ev.sample, ev.template, amp, K) is what a second pass,
+        match_templates(K, thr, subtract=(ev.sample, ev.template, amp)), scores.  start / stop follow Reader[...].  Returns a (stop
+        - start, W) float32 array.  Chunks resident in the device cache are read where they lie; the others are decoded in a
+        transient workspace and NOT kept.  A damaged chunk in the support raises the IOError of Reader[...]."""
+        self._need_codec('residual', 'residual', 'subtracts templates')
+        if reference not in (None, 'median'):
+            raise ValueError("reference must be None or 'median', got %r" % (reference,))
+        taps = _fir_taps([1.0] if taps is None else taps)
+        i0, i1 = self._row_range(start, stop)
+        cols, _ = self._stats_channels(channels)
+        k = np.asarray(templates)
+        if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
+            raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
+        with np.errstate(over='ignore'):
+            k = np.ascontiguousarray((k[None] if k.ndim == 2 else k).astype(np.float32))
+        n_out, T, W = k.shape
+        if W != cols.size:
+            raise ValueError("templates have %d columns for %d selected channels" % (W, cols.size))
+        if not 1 <= W <= hip.CORRELATE_MAX_COLS:
+            raise ValueError("residual takes 1 to %d columns, got %d" % (hip.CORRELATE_MAX_COLS, W))
+        if not 1 <= T <= hip.CORRELATE_MAX_T:
+            raise ValueError("templates have 1 to %d rows, got %d" % (hip.CORRELATE_MAX_T, T))
+        if not 1 <= n_out <= hip.CORRELATE_MAX_OUT:
+            raise ValueError("residual takes 1 to %d templates, got %d" % (hip.CORRELATE_MAX_OUT, n_out))
+        if not isinstance(before, (int, np.integer)) or isinstance(before, bool) or not 0 <= before <= T:
+            raise ValueError("before must be an int in [0, %d], got %r" % (T, before))
+        if not np.isfinite(k).all():
+            raise ValueError("templates must be finite in float32")
+        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
+            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
+        before, n_taps, N = int(before), int(taps.size), self.n_samples
+        half, ref_code = (n_taps - 1) // 2, 1 if reference else 0
+        sub = _sub_events(sample, template, amplitude, n_out, N)
+        out = np.empty((i1 - i0, W), np.float32)                    # (every row is inside the recording and written by a call)
+        if i1 > i0:
+            def support(a, b):                                      # the file rows that rows [a, b) read
+                return max(0, a + half - (n_taps - 1)), min(N, b + half)
+            # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they read pass RESIDUAL_CALL_BYTES,
+            # and so that a call's result stays within RESIDUAL_OUT_BYTES
+            rows = max(1, RESIDUAL_OUT_BYTES // (4 * W))
+            base = self._halo_cuts(*support(i0, i1), RESIDUAL_CALL_BYTES, i0, i1, lambda row: min(i1, max(i0, row)))
+            cuts = [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, rows)] + [i1]
+
+            def part(a, b):
+                # with every event whose window [sample - before, sample - before + T) meets the rows [a, b)
+                e0, e1 = np.searchsorted(sub[0], [a + before - T + 1, b + before])
+                return self._chunk_span(*support(a, b)), (0, N, a, b, taps, cols, ref_code, before, k) + tuple(v[e0:e1] for v in sub)
+            for a, b, (y,) in self._halo_parts(self.codec.residual, cuts, part):
+                out[a - i0:b - i0] = y
+        return out
 
     # -- peak detection on the device (an extension: the reference's users filter Reader[...] and look for peaks on the host)
     def detect(self, threshold, start=0, stop=None, channels=slice(None), taps=None, sign='neg', reference=None, exclude=0, spread=0):

@@ -165,6 +165,13 @@ int launch_tmatch_mask(hipStream_t st, const float *d_best, const int *d_arg, lo
 int launch_tmatch_emit(hipStream_t st, const u64 *d_bitmap, long n_words, u32 *d_counts, u64 *d_offsets, u64 *d_total, const float *d_best,
                        const int *d_arg, long sc_row0, long s0, long max_events, long *d_row, int *d_tpl, float *d_score);
 
+// subtract.hip: template subtraction on the same workspace (mts_residual, mts_match_residual).  For every row t of the workspace and
+// column j: acc = z[t, j]; for the events e with 0 <= tau = t - ev_row[e] + before < T, in list order: acc = fmaf(ev_namp[e],
+// K[ev_tpl[e], tau, j], acc); out[t - ws_row0, j] = acc, a NaN as 0x7fc00000.  d_ev_row ascending, d_ev_namp the negated amplitudes,
+// d_tpl the plain (K, T, n_cols) templates (none of the four is read when n_ev == 0); d_out may be d_z: in place
+int launch_subtract(hipStream_t st, const float *d_z, long ws_row0, long ws_rows, int n_cols, const long *d_ev_row, const int *d_ev_tpl,
+                    const float *d_ev_namp, long n_ev, const float *d_tpl, int T, int before, float *d_out);
+
 // welch.hip: Welch PSD partials (mts_welch).  Segments s of blocks [block0, block0 + n_blocks) (block b: segments [b * B, (b + 1) * B)
 // ∩ [.., seg_end)) start at file row row_seg0 + s * step; d_part[(b - block0), k, c] = sum over the block's segments, in order, of
 // |X_k|^2 of column cols[c] (float64; X in the csize float type).  d_taper: 2^log2n values, d_tw: 2^log2n complex values

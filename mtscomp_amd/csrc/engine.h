@@ -101,6 +101,9 @@ struct Engine {
     // template events: taps, columns, thresholds, segment tables, the repacked templates, the filtered slab, the score slab, its row
     // maxima, the event bitmap, block counts and offsets, the outputs of the host entry point
     DBuf tm;
+    // residuals: taps, columns, segment tables, the subtracted events, the plain templates, the filtered slab, the output of the host
+    // entry point
+    DBuf res;
     // Welch PSD: taper, twiddles, columns, segment tables, block partials, group sums
     DBuf welch;
     // Gram matrices: columns, slab and group tables, slab partials, the accumulators of the host entry point
@@ -156,7 +159,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &wav, &cor, &tm, &welch, &gram, &proj};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &wav, &cor, &tm, &res, &welch, &gram, &proj};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();

@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, correlate, match_templates, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, correlate, match_templates, residual, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -965,6 +965,142 @@ static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
     return MTS_OK;
 }
 
+// ---- subtracted events (mts_residual, mts_match_residual and their device variants) ---------------------------------------------
+// The list that both ops take: n_sub events (row, template, amplitude), non-decreasing in row.  Checked with the other arguments; on
+// the device as (row, template, -amplitude), beside the plain (K, T, n_cols) templates that k_subtract reads -- both only when there
+// is something to subtract.
+static int check_sub_events(const char *op, long n_sub, const long *sub_row, const int *sub_tpl, const float *sub_amp, long vb, long ve, int n_out)
+{
+    if (n_sub < 0 || n_sub > (1l << 30)) { set_error("%s: %ld subtracted events (0 .. 2^30)", op, n_sub); return MTS_E_ARG; }
+    if (n_sub && (!sub_row || !sub_tpl || !sub_amp)) { set_error("%s: no subtracted events given", op); return MTS_E_ARG; }
+    for (long e = 0; e < n_sub; e++) {
+        if (sub_row[e] < vb || sub_row[e] >= ve) { set_error("%s: subtracted event %ld at row %ld outside [%ld, %ld)", op, e, sub_row[e], vb, ve); return MTS_E_ARG; }
+        if (e && sub_row[e] < sub_row[e - 1]) { set_error("%s: subtracted event %ld at row %ld follows one at row %ld (rows must not decrease)", op, e, sub_row[e], sub_row[e - 1]); return MTS_E_ARG; }
+        if (sub_tpl[e] < 0 || sub_tpl[e] >= n_out) { set_error("%s: subtracted event %ld names template %d (%d templates)", op, e, sub_tpl[e], n_out); return MTS_E_ARG; }
+        if (!std::isfinite(sub_amp[e])) { set_error("%s: the amplitude of subtracted event %ld is not finite", op, e); return MTS_E_ARG; }
+    }
+    return MTS_OK;
+}
+
+struct SubEvents {
+    long n = 0;
+    size_t o_row = 0, o_tpl = 0, o_namp = 0, o_plain = 0;
+    std::vector<float> namp;                                  // (the source of an asynchronous copy: it lives as long as the call)
+    const long *d_row = nullptr;
+    const int *d_tpl = nullptr;
+    const float *d_namp = nullptr, *d_plain = nullptr;
+
+    // (no events: no bytes)
+    void take(WsLayout &L, long n_sub, u64 tpl_items)
+    {
+        n = n_sub;
+        o_row = L.take(8 * (u64)n); o_tpl = L.take(4 * (u64)n); o_namp = L.take(4 * (u64)n); o_plain = L.take(n ? 4 * tpl_items : 0);
+    }
+    int upload(hipStream_t st, u8 *ws, const long *sub_row, const int *sub_tpl, const float *sub_amp, const float *templates, u64 tpl_items)
+    {
+        if (!n) return MTS_OK;
+        namp.resize((size_t)n);
+        for (long e = 0; e < n; e++) namp[e] = -sub_amp[e];
+        d_row = (const long *)(ws + o_row); d_tpl = (const int *)(ws + o_tpl); d_namp = (const float *)(ws + o_namp); d_plain = (const float *)(ws + o_plain);
+        MTS_HIP(hipMemcpyAsync(ws + o_row, sub_row, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+        MTS_HIP(hipMemcpyAsync(ws + o_tpl, sub_tpl, 4 * (size_t)n, hipMemcpyHostToDevice, st));
+        MTS_HIP(hipMemcpyAsync(ws + o_namp, namp.data(), 4 * (size_t)n, hipMemcpyHostToDevice, st));
+        MTS_HIP(hipMemcpyAsync(ws + o_plain, templates, 4 * (size_t)tpl_items, hipMemcpyHostToDevice, st));
+        return MTS_OK;
+    }
+};
+
+// ---- residual (mts_residual, mts_dev_residual) ---------------------------------------------------------------------------------
+// The unit is a row of [row_begin, row_end) and the halo is the filter's support alone: the rows [u0, u1) read the file rows from u0 +
+// half - (L - 1) to u1 + half, within the valid range -- decimate with q = 1.  A piece's rows go through the float32 workspace in
+// slabs of owned rows with no neighbours: filter -> median -> k_subtract, which writes the slab's rows of the output (a NaN as
+// 0x7fc00000, with an empty list too).  The subtraction reads no row of the recording: whatever the pieces and slabs, every entry is
+// the same chain over the same events.
+static const u64 RESIDUAL_SLAB_BYTES = 256ull << 20;
+
+static u64 residual_slab_bytes()
+{
+    const char *e = getenv("MTS_RESIDUAL_SLAB_BYTES");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (u64)v : RESIDUAL_SLAB_BYTES;
+}
+
+static int residual_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
+                        int n_cols, const int *cols, int reference, int before, int n_tau, int n_out, const float *templates, long n_sub,
+                        const long *sub_row, const int *sub_tpl, const float *sub_amp, float *out, bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    int rc;
+    if (nc <= 0 || T.n_chunks < 0) { set_error("residual: n_channels or n_chunks invalid"); return MTS_E_ARG; }
+    if (n_cols < 1 || n_cols > MTS_CORRELATE_MAX_COLS || !cols) { set_error("residual: %d columns (1 .. %d)", n_cols, MTS_CORRELATE_MAX_COLS); return MTS_E_ARG; }
+    if ((rc = check_taps("residual", n_taps, taps))) return rc;
+    if (reference < 0 || reference > 1) { set_error("residual: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
+    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("residual: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
+    if (n_tau < 1 || n_tau > MTS_CORRELATE_MAX_T) { set_error("residual: templates of %d rows (1 .. %d)", n_tau, MTS_CORRELATE_MAX_T); return MTS_E_ARG; }
+    if (before < 0 || before > n_tau) { set_error("residual: before %d (0 .. %d)", before, n_tau); return MTS_E_ARG; }
+    if (n_out < 1 || n_out > MTS_CORRELATE_MAX_OUT || !templates) { set_error("residual: %d templates (1 .. %d)", n_out, MTS_CORRELATE_MAX_OUT); return MTS_E_ARG; }
+    const long per = (long)n_tau * n_cols;
+    for (long e = 0; e < (long)n_out * per; e++)
+        if (!std::isfinite(templates[e])) { set_error("residual: template entry (%ld, %ld, %ld) is not finite", e / per, e % per / n_cols, e % n_cols); return MTS_E_ARG; }
+    if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve || row_end - row_begin > (1l << 40)) {
+        set_error("residual: rows invalid"); return MTS_E_ARG;
+    }
+    if ((rc = check_sub_events("residual", n_sub, sub_row, sub_tpl, sub_amp, vb, ve, n_out))) return rc;
+    if (row_end > row_begin && !out) { set_error("residual: no output buffer"); return MTS_E_ARG; }
+    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_chunk_table(true, T))) return rc;
+    const long half = (n_taps - 1) / 2, n_units = row_end - row_begin;
+    // the rows that the rows [u0, u1) read: their filter support ∩ valid range
+    auto rows = [&](long u0, long u1, long *lo, long *hi) {
+        *lo = std::max(vb, row_begin + u0 + half - (n_taps - 1)); *hi = std::min(ve, row_begin + u1 + half);
+    };
+    long need_lo = 0, need_hi = 0;
+    if (n_units) rows(0, n_units, &need_lo, &need_hi);
+    if ((rc = check_cover("residual", T, need_lo, need_hi))) return rc;
+    status_ok(T, status);
+    if (!n_units) return MTS_OK;
+
+    HaloFeed H(T, out_on_host);
+    if ((rc = H.plan(n_units, [&](long r) { return r - row_begin; }, rows))) return rc;
+    // rows a slab owns: the workspace holds them and nothing else
+    const long own = std::min(n_units, std::max(1l, (long)std::min<u64>(residual_slab_bytes() / (4 * (u64)n_cols), (u64)1 << 40)));
+    // ---- workspace: taps, columns, segment tables, the events, the plain templates, the filtered slab, the output
+    const u64 tpl_items = (u64)n_out * per, n_items = (u64)n_units * n_cols;
+    WsLayout &L = H.L;
+    SubEvents SE;
+    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_seg = L.take(H.table_bytes());
+    SE.take(L, n_sub, tpl_items);
+    const size_t o_y = L.take(4 * (u64)own * n_cols), o_out = L.take_out(4 * n_items);
+    if ((rc = H.place(E, st, E.res, o_seg))) return rc;
+    u8 *ws = E.res.as<u8>();
+    std::vector<float> h_taps(n_taps);
+    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
+    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    if ((rc = SE.upload(st, ws, sub_row, sub_tpl, sub_amp, templates, tpl_items))) { (void)hipStreamSynchronize(st); return rc; }
+    float *d_out = L.out(ws, o_out, out);
+    float *d_y = (float *)(ws + o_y);
+    rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
+        const long p0 = row_begin + Pc.u0, p1 = row_begin + Pc.u1;
+        int r = MTS_OK;
+        for (long s0 = p0; !r && s0 < p1; s0 += own) {
+            const long s1 = std::min(p1, s0 + own);
+            // y[t] for t in [s0, s1): output k = t of a decimation by 1 whose newest row is half + k
+            r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half, s0, s1,
+                                Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
+            if (!r && reference) r = launch_row_median(st, d_y, s1 - s0, n_cols);
+            if (!r) r = launch_subtract(st, d_y, s0, s1 - s0, n_cols, SE.d_row, SE.d_tpl, SE.d_namp, SE.n, SE.d_plain, n_tau, before,
+                                        d_out + (u64)(s0 - row_begin) * n_cols);
+        }
+        return r;
+    });
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps and the events have been read before they go)
+    if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, 4 * n_items, hipMemcpyDeviceToHost, st));
+    MTS_HIP(hipStreamSynchronize(st));
+    return MTS_OK;
+}
+
 // ---- template events (mts_match_templates, mts_dev_match_templates) ------------------------------------------------------------
 // The unit is a row of [row_begin, row_end).  Piece p owns the rows in its chunks; their events need the scores R rows either side,
 // those z from `before` rows before to T - before - 1 rows after, and that the filter's support: the rows [u0, u1) read the file rows
@@ -973,7 +1109,8 @@ static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
 // - 1)) -- filter -> median -> k_correlate into the score slab -> row maxima -> mask -> count / scan / emit, all on the stream; the
 // write position is carried on the device from slab to slab and piece to piece.  `own` keeps both the z slab and the score slab within
 // the slab bound, and is never less than one row with its neighbours.  launch_decimate, launch_row_median and launch_correlate are
-// correlate_run's, so every score has correlate's bits whatever the pieces and slabs.
+// correlate_run's, so every score has correlate's bits whatever the pieces and slabs.  With subtracted events (mts_match_residual, n_sub
+// > 0) k_subtract works in place on the z slab between the median and k_correlate; without them nothing differs.
 static const u64 TMATCH_SLAB_BYTES = 256ull << 20;
 static const long TMATCH_SLAB_MAX_ROWS = 1l << 22;                  // (bounds the row maxima and the bitmap of a call with few templates)
 
@@ -986,7 +1123,8 @@ static u64 tmatch_slab_bytes()
 
 static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
                       int n_cols, const int *cols, int reference, int before, int n_tau, int n_out, const float *templates, const float *threshold,
-                      int R, long max_events, long *out_row, int *out_tpl, float *out_score, bool out_on_host, long *n_events, int *status)
+                      int R, long max_events, long *out_row, int *out_tpl, float *out_score, bool out_on_host, long *n_events, int *status,
+                      long n_sub = 0, const long *sub_row = nullptr, const int *sub_tpl = nullptr, const float *sub_amp = nullptr)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
     const int nc = T.nc, sz = T.sz, flags = T.flags;
@@ -1009,6 +1147,7 @@ static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, l
     if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve) { set_error("match_templates: rows invalid"); return MTS_E_ARG; }
     if (max_events < 0 || max_events > (1l << 40) || !n_events) { set_error("match_templates: max_events invalid or no n_events"); return MTS_E_ARG; }
     if (max_events && (!out_row || !out_tpl || !out_score)) { set_error("match_templates: no output buffers"); return MTS_E_ARG; }
+    if ((rc = check_sub_events("match_templates", n_sub, sub_row, sub_tpl, sub_amp, vb, ve, n_out))) return rc;
     if ((rc = check_columns(cols, n_cols, nc))) return rc;
     if ((rc = check_chunk_table(true, T))) return rc;
     const long half = (n_taps - 1) / 2, n_units = row_end - row_begin, after = n_tau - before;
@@ -1038,6 +1177,8 @@ static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, l
                  o_best = L.take(4 * (u64)sc_rows), o_arg = L.take(4 * (u64)sc_rows), o_bits = L.take(8 * (u64)max_words),
                  o_cnt = L.take(4 * (u64)max_blocks), o_offs = L.take(8 * (u64)max_blocks), o_row = L.take_out(8 * (u64)max_events),
                  o_k = L.take_out(4 * (u64)max_events), o_val = L.take_out(4 * (u64)max_events);
+    SubEvents SE;
+    SE.take(L, n_sub, (u64)n_out * per);
     if ((rc = H.place(E, st, E.tm, o_seg))) return rc;
     u8 *ws = E.tm.as<u8>();
     std::vector<float> h_taps(n_taps);
@@ -1048,6 +1189,7 @@ static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, l
     MTS_HIP(hipMemcpyAsync(ws + o_thr, threshold, 4 * (size_t)n_out, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_tpl, h_tpl.data(), 4 * (size_t)tpl_items, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemsetAsync(ws + o_total, 0, 8, st));
+    if ((rc = SE.upload(st, ws, sub_row, sub_tpl, sub_amp, templates, (u64)n_out * per))) { (void)hipStreamSynchronize(st); return rc; }
     long *d_row = L.out(ws, o_row, out_row);
     int *d_k = L.out(ws, o_k, out_tpl);
     float *d_val = L.out(ws, o_val, out_score);
@@ -1064,6 +1206,7 @@ static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, l
             if (b > a) r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half,
                                            a, b, Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
             if (!r && reference && b > a) r = launch_row_median(st, d_y, b - a, n_cols);
+            if (!r && SE.n && b > a) r = launch_subtract(st, d_y, a, b - a, n_cols, SE.d_row, SE.d_tpl, SE.d_namp, SE.n, SE.d_plain, n_tau, before, d_y);
             if (!r) r = launch_correlate(st, d_y, a, b - a, n_cols, vb, ve, (const float *)(ws + o_tpl), kp, n_tau, before, n_out, sa, sb, d_sc);
             if (!r) r = launch_tmatch_best(st, d_sc, sb - sa, n_out, d_best, d_arg);
             if (!r) r = launch_tmatch_mask(st, d_best, d_arg, sa, sb - sa, (const float *)(ws + o_thr), R, s0, s1, d_bits);
@@ -1484,6 +1627,50 @@ int mts_dev_match_templates(int device, void *stream, const unsigned char *d_cda
 {
     return DEV_ENTRY(tmatch_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before,
                      T_, n_out, templates, threshold, exclude_rows, max_events, d_row, d_template, d_score, false, n_events, chunk_status));
+}
+
+int mts_residual(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                 const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                 long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                 int before, int T_, int n_out, const float *templates, long n_sub, const long *sub_row, const int *sub_tpl, const float *sub_amp,
+                 float *out, int *chunk_status)
+{
+    return HOST_ENTRY(residual_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before, T_,
+                      n_out, templates, n_sub, sub_row, sub_tpl, sub_amp, out, true, chunk_status));
+}
+
+int mts_dev_residual(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                     const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                     long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                     int before, int T_, int n_out, const float *templates, long n_sub, const long *sub_row, const int *sub_tpl,
+                     const float *sub_amp, float *d_out, int *chunk_status)
+{
+    return DEV_ENTRY(residual_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference,
+                     before, T_, n_out, templates, n_sub, sub_row, sub_tpl, sub_amp, d_out, false, chunk_status));
+}
+
+int mts_match_residual(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                       const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags,
+                       long valid_begin, long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols,
+                       const int *cols, int reference, int before, int T_, int n_out, const float *templates, const float *threshold,
+                       int exclude_rows, long max_events, long n_sub, const long *sub_row, const int *sub_tpl, const float *sub_amp,
+                       long *out_row, int *out_template, float *out_score, long *n_events, int *chunk_status)
+{
+    return HOST_ENTRY(tmatch_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before, T_, n_out,
+                      templates, threshold, exclude_rows, max_events, out_row, out_template, out_score, true, n_events, chunk_status, n_sub,
+                      sub_row, sub_tpl, sub_amp));
+}
+
+int mts_dev_match_residual(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                           const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags,
+                           long valid_begin, long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols,
+                           const int *cols, int reference, int before, int T_, int n_out, const float *templates, const float *threshold,
+                           int exclude_rows, long max_events, long n_sub, const long *sub_row, const int *sub_tpl, const float *sub_amp,
+                           long *d_row, int *d_template, float *d_score, long *n_events, int *chunk_status)
+{
+    return DEV_ENTRY(tmatch_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before,
+                     T_, n_out, templates, threshold, exclude_rows, max_events, d_row, d_template, d_score, false, n_events, chunk_status, n_sub,
+                     sub_row, sub_tpl, sub_amp));
 }
 
 int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,

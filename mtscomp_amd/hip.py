@@ -110,6 +110,8 @@ def lib():
             ('waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci], [vp, vp, vp, vp, vp, ip], None),
             ('correlate', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp], [vp, ip], None),
             ('match_templates', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, fp, ci, cl], [vp, vp, vp, lp, ip], None),
+            ('residual', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, cl, lp, ip, fp], [vp, ip], None),
+            ('match_residual', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, fp, ci, cl, cl, lp, ip, fp], [vp, vp, vp, lp, ip], None),
             ('welch', [cl, cl, cl, ci, cl, dp, ci, ci, ci, ip], [vp, ip], None),
             ('gram', [cl, cl, cl, cl, cl, ci, ip], [vp, vp, ip], None),
             ('rank_hist', [cl, cl, cl, ci, ip, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip], [vp, vp, vp, lp, ip])):
@@ -131,6 +133,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_project', 'mts_dev_project', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
            'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan', 'mts_correlate', 'mts_dev_correlate',
            'mts_match_templates', 'mts_dev_match_templates',
+           'mts_residual', 'mts_dev_residual', 'mts_match_residual', 'mts_dev_match_residual',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
 
 
@@ -849,6 +852,81 @@ def dev_match_templates(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags
                                      max_events)
     out, ptrs, at = _dev_results(out, cbuf.device, [cap * np.dtype(t).itemsize for t in _TMATCH_DTYPES])
     _check(lib().mts_dev_match_templates(*head, *mid, *ptrs, _lp(n_ev), _ip(status)), 'mts_dev_match_templates')
+    res = None
+    if download:
+        res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _TMATCH_DTYPES]))
+    return _status(status, n), int(n_ev[0]), res, out
+
+
+# -- template peeling: the filtered rows minus matched templates, and the template events of those rows
+RESIDUAL_MAX_EVENTS = 1 << 30          # n_sub of mts_residual and mts_match_residual
+
+
+def _sub_args(sub_row, sub_tpl, sub_amp):
+    """-> (n_sub and the three pointers of mts_residual / mts_match_residual, what they point at).  The events in row order."""
+    row = _longs(sub_row)
+    tpl = np.ascontiguousarray(np.asarray(sub_tpl, dtype=np.int32))
+    amp = np.ascontiguousarray(np.asarray(sub_amp, dtype=np.float32))
+    assert row.ndim == 1 and row.shape == tpl.shape == amp.shape, 'the events are three 1-D arrays of one length'
+    n = int(row.size)
+    return (n, _lp(row) if n else None, _ip(tpl) if n else None, amp.ctypes.data_as(C.POINTER(C.c_float)) if n else None), (row, tpl, amp)
+
+
+def _res_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, sub_row, sub_tpl, sub_amp):
+    """-> (the op's own arguments of mts_residual, the shape of the result, what the pointers point at)."""
+    mid, shape, keep = _cor_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates)
+    sub, keep_sub = _sub_args(sub_row, sub_tpl, sub_amp)
+    return mid + sub, (shape[0], int(keep[1].size)), keep + keep_sub
+
+
+def residual(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols,
+             reference, before, templates, sub_row, sub_tpl, sub_amp, device=0):
+    """mts_residual: z' of file rows [row_begin, row_end) (include/mtscomp_hip.h) -- the filtered, referenced rows minus sub_amp[e] times
+    template sub_tpl[e] laid with its row `before` on file row sub_row[e], for the events in ascending row order -- from the adjacent
+    chunks `keys`.  templates (n_out, T, n_cols), reference 0 / 1.  cache_id 0: no cache, every chunk comes with its bytes; else chunks
+    with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, (row_end - row_begin, n_cols) float32)."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, shape, _keep = _res_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, sub_row, sub_tpl, sub_amp)
+    out = np.empty(shape, np.float32)
+    _check(lib().mts_residual(*head, *mid, _ptr(out), _ip(status)), 'mts_residual')
+    return _status(status, n), out
+
+
+def dev_residual(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, reference,
+                 before, templates, sub_row, sub_tpl, sub_amp, out=None, download=True):
+    """mts_dev_residual on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the rows (made when None;
+    returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, shape, _keep = _res_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, sub_row, sub_tpl, sub_amp)
+    out, ptrs, at = _dev_results(out, cbuf.device, [4 * shape[0] * shape[1]])
+    _check(lib().mts_dev_residual(*head, *mid, *ptrs, _ip(status)), 'mts_dev_residual')
+    res = _dev_fetch(out, at, [np.empty(shape, np.float32)])[0] if download else None
+    return _status(status, n), res, out
+
+
+def match_residual(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps,
+                   cols, reference, before, templates, threshold, exclude_rows, max_events, sub_row, sub_tpl, sub_amp, device=0):
+    """mts_match_residual: match_templates on z' -- the events (sub_row, sub_tpl, sub_amp), in ascending row order, subtracted from the
+    filtered rows before they are scored (include/mtscomp_hip.h).  Arguments and result as match_templates."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, cap, n_ev, _keep = _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows,
+                                     max_events)
+    sub, _keep_sub = _sub_args(sub_row, sub_tpl, sub_amp)
+    res = [np.empty(cap, t) for t in _TMATCH_DTYPES]
+    _check(lib().mts_match_residual(*head, *mid, *sub, *(_ptr(a) if cap else None for a in res), _lp(n_ev), _ip(status)), 'mts_match_residual')
+    k = min(int(n_ev[0]), cap)
+    return (_status(status, n), int(n_ev[0])) + tuple(a[:k] for a in res)
+
+
+def dev_match_residual(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, reference,
+                       before, templates, threshold, exclude_rows, max_events, sub_row, sub_tpl, sub_amp, out=None, download=True):
+    """mts_dev_match_residual on a DevBuffer of compressed chunks (offsets into it); `out` and the result as dev_match_templates."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, cap, n_ev, _keep = _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows,
+                                     max_events)
+    sub, _keep_sub = _sub_args(sub_row, sub_tpl, sub_amp)
+    out, ptrs, at = _dev_results(out, cbuf.device, [cap * np.dtype(t).itemsize for t in _TMATCH_DTYPES])
+    _check(lib().mts_dev_match_residual(*head, *mid, *sub, *ptrs, _lp(n_ev), _ip(status)), 'mts_dev_match_residual')
     res = None
     if download:
         res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _TMATCH_DTYPES]))
