@@ -24,6 +24,7 @@ constexpr u32 REL_MASK = (1u << REL_BITS) - 1;
 struct LevelCfg { int good, lazy, nice, chain; };
 
 // per-block record produced by the tree stage
+#define MTS_PACK_RANGES 8    // ranges of token indices the block packer's waves take (deflate.hip: PACK_RANGES)
 struct BlockRec {
     u32 tok0, ntok;          // token range (chunk-relative)
     u32 in_start, in_len;    // input byte range
@@ -31,6 +32,7 @@ struct BlockRec {
     u32 btype;               // 0 stored 1 fixed 2 dynamic
     u32 hdr_bits;            // dynamic: bits of the tree header (after the 3-bit block header)
     u32 last;
+    u32 range_bits[MTS_PACK_RANGES];   // fixed / dynamic: code bits of the token indices [r * 16384 / MTS_PACK_RANGES, ..) (index ntok = the end-of-block code): where the packer's waves start
     u64 bit_start;           // bit offset in the chunk's zlib stream
 };
 

@@ -22,7 +22,8 @@
 //                      speculative entry, iterated to a fixed point (walks re-converge after a few
 //                      tokens); then count + emit tokens (LDS rows, written out coalesced).
 //   T  k_block_trees   per 16383-token block: symbol histogram (LDS atomics) and zlib's exact
-//                      build_tree / gen_bitlen / scan_tree by one lane; stored/fixed/dynamic choice.
+//                      build_tree / gen_bitlen / scan_tree by one lane; stored/fixed/dynamic choice; the
+//                      code bits of each eighth of the block's token indices (where the packer's waves start).
 //   L  k_block_layout  per chunk: bit offsets of the blocks, stream size, adler32.
 //   B  k_block_pack    per block: codes OR-ed into an LDS image of the block at scanned bit positions,
 //                      image written out as whole words.
@@ -31,6 +32,7 @@
 #include <mutex>
 
 #include "deflate_dev.h"
+#include "op_rank.h"
 
 namespace mts {
 
@@ -309,7 +311,7 @@ __global__ __launch_bounds__(SORT_NT) void k_hash_sort(const u8 *__restrict__ st
 //                 random data) or fewer than OP_MIN_KEYS keys are left to the two-pass kernel
 //   k_op_count    per slice: keys per bucket                                                    [2 LDS reads + 1 atomic per key]
 //   k_op_scan     per tile: bucket starts, and per slice and bucket the keys of earlier slices
-//   k_op_scatter  per slice: per-wave counts, then rank and store                               [~8 LDS operations per key]
+//   k_op_scatter  per slice: per-wave counts whose atomic also ranks the key, then store            [~7 LDS operations per key, ONE of them an atomic]
 // The 64 workgroups of a tile's slices run on ONE XCD, like the match stage's (blockIdx -> tile as there): the tile's 1 MB of
 // sorted keys, written four bytes at a time, and the counts between the kernels stay in that XCD's L2 until they are complete.
 // Scratch: an OpTile per tile (8 KB) and, in the tile's part of the two-pass kernel's first-pass buffer, 6 KB per slice.
@@ -494,11 +496,19 @@ __global__ __launch_bounds__(OP_NT) void k_op_scatter(const u8 *__restrict__ str
 #pragma unroll
     for (int k = 0; k < OP_KPL; k++) v[k] = gld_u32_unaligned(s, min(beg + 64u * k + lane, td.wlen - 1));
     __syncthreads();
-    u32 id[OP_KPL];
+    // ONE atomic per key: the counting one returns the word as it was, and the key's half of that is its rank among the wave's
+    // earlier keys of the bucket (lane-ordered inside an instruction, program order between the wave's instructions: ascending with
+    // k and the lane).  It stays in the register beside the bucket number (op_rank.h) until the scan below has made the counters
+    // the wave's first places; a second atomic on the same word -- as contended as the first: a recording's few popular buckets take
+    // most lanes of an instruction, and the LDS serves same-address lanes one after the other -- is then a plain read, which
+    // same-address lanes get as a broadcast.
+    static_assert(OP_LMAX <= (1 << OP_ID_BITS) && OP_KPL * 64 <= (1 << (32 - OP_ID_BITS)), "bucket and rank share a word");
+    u32 idr[OP_KPL];
 #pragma unroll
     for (int k = 0; k < OP_KPL; k++) {
-        id[k] = op_bucket(bp, sort_hash(v[k]));
-        if (beg + 64u * k + lane < end) atomicAdd(&cw[wave][id[k] >> 1], 1u << (16 * (id[k] & 1)));
+        const u32 id = op_bucket(bp, sort_hash(v[k]));
+        idr[k] = id;                                               // (a key at or past `end` takes no rank and adds nothing)
+        if (beg + 64u * k + lane < end) idr[k] = op_pack_rank(id, atomicAdd(&cw[wave][op_cw_word(id)], op_cw_one(id)));
     }
     __syncthreads();
     {   // thread j: buckets 2 j and 2 j + 1.  Their first places in the slice (an exclusive scan over the buckets), and per wave
@@ -528,9 +538,9 @@ __global__ __launch_bounds__(OP_NT) void k_op_scatter(const u8 *__restrict__ str
     for (int k = 0; k < OP_KPL; k++) {
         const u32 i = beg + 64u * k + lane;
         if (i < end) {
-            const u32 sh = 16 * (id[k] & 1);
-            const u32 slot = (atomicAdd(&cw[wave][id[k] >> 1], 1u << sh) >> sh) & 0xffffu;      // lane-ordered: earlier lanes get lower places
-            S[slot] = i | (id[k] << REL_BITS);
+            const u32 id = op_rank_id(idr[k]);
+            const u32 slot = op_slot(idr[k], cw[wave][op_cw_word(id)]);      // the wave's first place of the bucket + the key's rank behind it
+            S[slot] = i | (id << REL_BITS);
         }
     }
     __syncthreads();
@@ -1980,6 +1990,21 @@ __device__ __forceinline__ u32 slides_at(u32 q, u32 n)
     return k;
 }
 
+// The packer's waves take a block's token indices in PACK_RANGES consecutive ranges of PACK_WTOK (index ntok is the end-of-block
+// code); a wave's first bit is the header's end plus the bits of the ranges before its own.  Those totals are dot products of a
+// range's symbol histogram with the code lengths: k_block_trees, which counts the block's symbols anyway and ends with the code
+// lengths in LDS, counts them per range and leaves the totals with the block (BlockRec::range_bits), so that the packer does not
+// have to load and encode every token once more just to add up lengths.
+#ifndef MTS_PACK_THREADS
+#define MTS_PACK_THREADS 512
+#endif
+constexpr int PACK_THREADS = MTS_PACK_THREADS;              // 256: 1.19 ms, 512: 1.01, 1024: 1.60 (the image's LDS lets four workgroups share a CU)
+constexpr int PACK_RANGES = MTS_PACK_RANGES;                // common.h: the words of BlockRec::range_bits
+constexpr int PACK_WTOK = 16384 / PACK_RANGES;              // token indices per range = per wave of the packer (together >= 16383 tokens + end-of-block)
+static_assert(PACK_THREADS / 64 == PACK_RANGES, "a wave of the packer per range");
+static_assert(PACK_RANGES % 2 == 0 && PACK_WTOK % 256 == 0 && PACK_WTOK < 65536, "two 16-bit range counters a word; a load step of 256 tokens lies in one range");
+constexpr int RC_SYMS = L_CODES + 2 + D_CODES + 2;          // a range's counters: literal/length symbols, then distance codes
+
 __global__ __launch_bounds__(64) void k_block_trees(const ChunkDesc *__restrict__ chunks, const u32 *__restrict__ blk_chunk,
                                                     int total_blk_cap, const u32 *__restrict__ tokens,
                                                     const u32 *__restrict__ blk_in_start, const ChunkOut *__restrict__ cout,
@@ -1999,23 +2024,30 @@ __global__ __launch_bounds__(64) void k_block_trees(const ChunkDesc *__restrict_
     const u32 last = bi == nblk - 1;
     const u32 in_start = nt ? blk_in_start[b] : ch.n;
     const u32 in_end = tok0 + nt < ntok_c ? blk_in_start[b + 1] : ch.n;
+    // The symbol histogram per range of the packer: ranges 2 q and 2 q + 1 in the halves of rc[q][symbol] (a range has at most
+    // PACK_WTOK tokens).  It is counted in the tree builder's storage, which nothing uses yet, and then lives in registers -- lane l
+    // keeps the counters of the symbols l, l + 64, ..: 5 x 4 words -- so that the kernel's LDS, which is what limits its waves
+    // per CU, stays what it was.  The trees take the sums over the ranges; the ranges' bits are taken once the block's type is known.
+    __shared__ union TreeOrCounts { TreeWS tw; u32 rc[PACK_RANGES / 2][RC_SYMS]; } tc;
+    static_assert(sizeof(TreeWS) >= sizeof(u32) * (PACK_RANGES / 2) * RC_SYMS, "the counters fit the tree builder's storage");
+    TreeWS &tw = tc.tw;
+    u32 (&rc)[PACK_RANGES / 2][RC_SYMS] = tc.rc;
     __shared__ u32 dfreq[D_CODES + 2];
-    __shared__ TreeWS tw;
     __shared__ u16 llen_s[L_CODES + 2], dlen_s[D_CODES + 2];
-    u32 *lfreq = tw.hp;                              // the literal/length histogram lives in the heap's storage until it is copied out
     const int lane = threadIdx.x;
-    for (int i = lane; i < L_CODES + 2; i += 64) lfreq[i] = 0;
-    if (lane < D_CODES + 2) dfreq[lane] = 0;
+    for (int i = lane; i < (PACK_RANGES / 2) * RC_SYMS; i += 64) (&rc[0][0])[i] = 0;
     __syncthreads();
     const u32 *tk = tokens + ch.tok_off + tok0;
     {
         typedef u32 tok4 __attribute__((ext_vector_type(4), aligned(4)));
-        auto count = [&](u32 t) {
+        auto count = [&](u32 t, u32 *row /* the range's counter words */, u32 one /* 1 in its half */) {
             const u32 dist = t & 0xffff, lc = t >> 16;
             u32 ex;
-            if (dist == 0) atomicAdd(&lfreq[lc], 1u);
-            else { atomicAdd(&lfreq[257 + len_code(lc, ex)], 1u); atomicAdd(&dfreq[dist_code(dist - 1, ex)], 1u); }
+            if (dist == 0) atomicAdd(&row[lc], one);
+            else { atomicAdd(&row[257 + len_code(lc, ex)], one); atomicAdd(&row[L_CODES + 2 + dist_code(dist - 1, ex)], one); }
         };
+        auto row_of = [&](u32 i) { return &rc[(i / PACK_WTOK) >> 1][0]; };
+        auto one_of = [&](u32 i) { return 1u << (16 * ((i / PACK_WTOK) & 1)); };
         const u32 nt4 = nt & ~3u;
         constexpr int TA = 4;                                   // 16-byte loads in flight per lane
         for (u32 i0 = (u32)lane * 4; i0 < nt4; i0 += 256 * TA) {
@@ -2023,14 +2055,32 @@ __global__ __launch_bounds__(64) void k_block_trees(const ChunkDesc *__restrict_
 #pragma unroll
             for (int a = 0; a < TA; a++) { const u32 i = i0 + 256 * a; q[a] = i < nt4 ? *(const tok4 *)(tk + i) : tok4{0, 0, 0, 0}; }
 #pragma unroll
-            for (int a = 0; a < TA; a++) if (i0 + 256 * a < nt4) { count(q[a].x); count(q[a].y); count(q[a].z); count(q[a].w); }
+            for (int a = 0; a < TA; a++)
+                if (i0 + 256 * a < nt4) {
+                    const u32 i = i0 + 256 * a;                  // (the four tokens from i on, like the 256 of the step, lie in one range)
+                    u32 *row = row_of(i);
+                    const u32 one = one_of(i);
+                    count(q[a].x, row, one); count(q[a].y, row, one); count(q[a].z, row, one); count(q[a].w, row, one);
+                }
         }
-        if ((u32)lane < nt - nt4) count(tk[nt4 + lane]);
+        if ((u32)lane < nt - nt4) count(tk[nt4 + lane], row_of(nt4), one_of(nt4));
+        if (lane == 0) atomicAdd(&row_of(nt)[256], one_of(nt));     // the end-of-block code: the packer's token index nt (zlib gives it frequency 1)
     }
     __syncthreads();
+    constexpr int RC_STEPS = RC_SYMS / 64;
+    static_assert(RC_SYMS % 64 == 0 && L_CODES + 2 == 64 * (RC_STEPS - 1) + 32, "a lane's symbols: lane + 64 i; the distance codes are the last step's lanes 32 ..");
+    u32 cnt[RC_STEPS][PACK_RANGES / 2];
+#pragma unroll
+    for (int i = 0; i < RC_STEPS; i++)
+#pragma unroll
+        for (int q = 0; q < PACK_RANGES / 2; q++) cnt[i][q] = rc[q][lane + 64 * i];
+    __syncthreads();                                            // (the counters are read: the storage is the tree builder's from here on)
+    auto cnt_sum = [&](int i) { u32 x = 0; for (int q = 0; q < PACK_RANGES / 2; q++) x += cnt[i][q]; return (x & 0xffffu) + (x >> 16); };      // (a block has < 65536 tokens: the halves do not carry)
     long opt_len = 0, static_len = 0;
     // literal/length tree
-    for (int i = lane; i < L_CODES; i += 64) tw.freq[i] = i == 256 ? (u16)1 : (u16)lfreq[i];
+#pragma unroll
+    for (int i = 0; i < RC_STEPS; i++) if (lane + 64 * i < L_CODES) tw.freq[lane + 64 * i] = (u16)cnt_sum(i);
+    if (lane >= 32) dfreq[lane - 32] = cnt_sum(RC_STEPS - 1);
     __syncthreads();
     tw_build(tw, 0, lane, opt_len, static_len);
     const int l_max = tw.max_code;
@@ -2123,6 +2173,30 @@ __global__ __launch_bounds__(64) void k_block_trees(const ChunkDesc *__restrict_
         __syncthreads();
         for (int i = lane; i < BLK_HDR_WORDS; i += 64) hw[i] = hdr_img[i];
         r.hdr_bits = hb;
+    }
+    // the bits of the packer's ranges: a lane per symbol, its count in each range times the symbol's code length and extra bits
+    // (the static lengths or this block's: whichever the block is written with), summed over the wave
+#pragma unroll
+    for (int k = 0; k < PACK_RANGES; k++) r.range_bits[k] = 0;
+    if (r.btype != 0) {
+        u32 acc[PACK_RANGES];
+#pragma unroll
+        for (int k = 0; k < PACK_RANGES; k++) acc[k] = 0;
+#pragma unroll
+        for (int i = 0; i < RC_STEPS; i++) {
+            const int sym = lane + 64 * i;
+            const int d = sym - (L_CODES + 2);
+            u32 cost = 0;
+            if (sym < L_CODES) cost = (r.btype == 1 ? static_llen((u32)sym) : sym <= l_max ? (u32)llen_s[sym] : 0u) + (sym > 256 ? (u32)c_extra_lbits[sym - 257] : 0u);
+            else if (d >= 0 && d < D_CODES) cost = (r.btype == 1 ? 5u : d <= d_max ? (u32)dlen_s[d] : 0u) + (u32)c_extra_dbits[d];
+#pragma unroll
+            for (int q = 0; q < PACK_RANGES / 2; q++) {
+                const u32 w = cnt[i][q];
+                acc[2 * q] += (w & 0xffffu) * cost; acc[2 * q + 1] += (w >> 16) * cost;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < PACK_RANGES; k++) r.range_bits[k] = (u32)__builtin_amdgcn_readlane((int)wave_incl_scan_dpp(acc[k]), 63);
     }
     if (lane != 0) return;
     blocks[b] = r;
@@ -2237,16 +2311,12 @@ __device__ __forceinline__ u64 token_code(u32 t, const u32 *lc_tab, const u32 *d
 }
 
 // One workgroup per block.  The bits of the block are assembled in LDS and leave as whole words, coalesced:
-// a wave owns 2048 consecutive tokens and takes them 64 at a time (one coalesced load), a wave scan of
+// a wave owns 2048 consecutive tokens (a range: PACK_WTOK, above k_block_trees, which leaves every range's bits with the
+// block: the wave's first bit) and takes them 64 at a time (one coalesced load), a wave scan of
 // the code lengths gives every token its bit position, and the code is OR-ed into the (zeroed) LDS image.
 // Only the first and the last word of the image can be shared with the neighbouring blocks: those two are
 // OR-ed into the (zeroed) output, the rest is stored.  A block too large for the image (it holds 16 bits
 // per token; zlib needs 9-10 on this kind of data) ORs the overhang straight into the output.
-#ifndef MTS_PACK_THREADS
-#define MTS_PACK_THREADS 512
-#endif
-constexpr int PACK_THREADS = MTS_PACK_THREADS;              // 256: 1.19 ms, 512: 1.01, 1024: 1.60 (the image's LDS lets four workgroups share a CU)
-constexpr int PACK_WTOK = 16384 / (PACK_THREADS / 64);      // token indices per wave (together >= 16383 tokens + end-of-block)
 constexpr int PACK_IMG_WORDS = 8192;
 
 __global__ __launch_bounds__(PACK_THREADS) void k_block_pack(const u8 *__restrict__ stream, const ChunkDesc *__restrict__ chunks,
@@ -2265,7 +2335,6 @@ __global__ __launch_bounds__(PACK_THREADS) void k_block_pack(const u8 *__restric
     const BlockRec r = blocks[b];
     u32 *out = (u32 *)(outb + ch.out_off);
     __shared__ u32 codes[BLK_CODE_WORDS];
-    __shared__ u32 wsum[PACK_THREADS / 64];
     __shared__ u32 img[PACK_IMG_WORDS];
     const int tid = threadIdx.x;
     if (r.btype == 0) {
@@ -2331,17 +2400,6 @@ __global__ __launch_bounds__(PACK_THREADS) void k_block_pack(const u8 *__restric
         nb = 0;
         return 0;
     };
-    u32 mybits = 0;
-    for (u32 i0 = i_beg; i0 < i_end; i0 += 64 * PACK_AHEAD) {
-        u32 t[PACK_AHEAD];
-#pragma unroll
-        for (int a = 0; a < PACK_AHEAD; a++) { const u32 i = i0 + 64 * a + lane; t[a] = i < r.ntok ? tk[i] : 0u; }
-#pragma unroll
-        for (int a = 0; a < PACK_AHEAD; a++) { const u32 i = i0 + 64 * a + lane; u32 nb; if (i < i_end) { code_of(i, t[a], nb); mybits += nb; } }
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) mybits += __shfl_xor(mybits, o, 64);
-    if (lane == 0) wsum[wave] = mybits;
     // zlib header, block header, code-length header
     if (tid == 0) {
         if (bi == 0) or_bits(0, zhdr, 16);
@@ -2355,9 +2413,10 @@ __global__ __launch_bounds__(PACK_THREADS) void k_block_pack(const u8 *__restric
             or_bits(r.bit_start + 3 + 32 * k, left >= 32 ? hw[k] : hw[k] & ((1u << left) - 1), left >= 32 ? 32 : left);
         }
     }
-    __syncthreads();
+    // the wave's first bit: behind the headers and the ranges before its own (their bits come with the block: k_block_trees)
     u64 pos = r.bit_start + 3 + r.hdr_bits;
-    for (int w = 0; w < wave; w++) pos += wsum[w];
+#pragma unroll
+    for (int w = 0; w < PACK_RANGES - 1; w++) if (w < wave) pos += r.range_bits[w];
     for (u32 i0 = i_beg; i0 < i_end; i0 += 64 * PACK_AHEAD) {
         u32 t[PACK_AHEAD];
 #pragma unroll
