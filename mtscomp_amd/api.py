@@ -280,6 +280,54 @@ def whitening_weights(cov, eps=0.0):
     return 0.5 * (w + w.T)
 
 
+_DETECT_CAP_AT = 11                     # where max_events stands among the op's own arguments of codec.detect ...
+_TMATCH_CAP_AT = 11                     # ... and of codec.match_templates / match_residual (the subtracted events follow it)
+
+
+def _templates32(templates):
+    """templates as a C-contiguous float32 (K, T, W) array, and whether one 2-D (T, W) template was given."""
+    k = np.asarray(templates)
+    if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
+        raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
+    with np.errstate(over='ignore'):
+        return np.ascontiguousarray((k[None] if k.ndim == 2 else k).astype(np.float32)), k.ndim == 2
+
+
+def _template_args(templates, before, cols, op):
+    """The templates and `before` of Reader.correlate / match_templates / residual (`op`, for the messages) on the columns `cols`
+    -> (the float32 (K, T, W) templates, whether one 2-D template was given, before as an int)."""
+    k, squeeze = _templates32(templates)
+    n_out, T, W = k.shape
+    if W != cols.size:
+        raise ValueError("templates have %d columns for %d selected channels" % (W, cols.size))
+    if not 1 <= W <= hip.CORRELATE_MAX_COLS:
+        raise ValueError("%s takes 1 to %d columns, got %d" % (op, hip.CORRELATE_MAX_COLS, W))
+    if not 1 <= T <= hip.CORRELATE_MAX_T:
+        raise ValueError("templates have 1 to %d rows, got %d" % (hip.CORRELATE_MAX_T, T))
+    if not 1 <= n_out <= hip.CORRELATE_MAX_OUT:
+        raise ValueError("%s takes 1 to %d templates, got %d" % (op, hip.CORRELATE_MAX_OUT, n_out))
+    if not isinstance(before, (int, np.integer)) or isinstance(before, bool) or not 0 <= before <= T:
+        raise ValueError("before must be an int in [0, %d], got %r" % (T, before))
+    if not np.isfinite(k).all():
+        raise ValueError("templates must be finite in float32")
+    return k, squeeze, int(before)
+
+
+def _event_arrays(found):
+    """The (row, index, value) arrays of the parts of detect / match_templates, in order, as one int64, int64 and float32 array."""
+    return tuple(np.concatenate([f[j] for f in found]).astype(t) if found else np.zeros(0, t)
+                 for j, t in enumerate((np.int64, np.int64, np.float32)))
+
+
+def _again_with_room(cap_at):
+    """The `again` of _halo_parts for detect / match_templates: a part whose buffer (args[cap_at] events) was short is sent once more
+    with room for all the events it counted."""
+    def again(out, args):
+        if out[1] > args[cap_at] and all(v == hip.CHUNK_OK for v in out[0]):
+            return args[:cap_at] + (out[1],) + args[cap_at + 1:]
+    return again
+
+
 def template_amplitudes(score, template, templates):
     """The least-squares amplitudes of matched templates: score[e] / sum(templates[template[e]] ** 2) -- the a that minimises
     |z - a * K| when score is the matched filter's <z, K>.  The norms are summed in float64 from the templates rounded to float32 (what
@@ -287,11 +335,7 @@ def template_amplitudes(score, template, templates):
     match_templates result (or any of one shape); templates: (K, T, W), or (T, W) for one.  With ev = r.match_templates(K, thr),
     r.match_templates(K, thr, subtract=(ev.sample, ev.template, template_amplitudes(ev.score, ev.template, K))) is the second pass of
     a template-matching sorter.  ValueError for an index outside the templates or a template of zero norm."""
-    k = np.asarray(templates)
-    if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
-        raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
-    with np.errstate(over='ignore'):
-        k = (k[None] if k.ndim == 2 else k).astype(np.float32)
+    k, _ = _templates32(templates)
     if not np.isfinite(k).all():
         raise ValueError("templates must be finite in float32")
     sc, tp = np.asarray(score), np.asarray(template)
@@ -1416,6 +1460,34 @@ class Reader:
         """The adjacent chunks that hold rows [lo, hi), lo < hi, as a list of keys."""
         return list(range(bisect.bisect_right(self.chunk_bounds, lo) - 1, bisect.bisect_right(self.chunk_bounds, hi - 1)))
 
+    def _budget_cuts(self, lo, hi, max_bytes, i0, i1, row_bytes, out_bytes):
+        """The calls of project, correlate and residual: rows [i0, i1) cut at the chunk boundaries where the compressed bytes of the
+        chunks of the rows [lo, hi) they read pass max_bytes, and again so that a call's result (row_bytes a row) stays within
+        out_bytes.  -> the cut list, i0 first, i1 last."""
+        rows = max(1, out_bytes // row_bytes)
+        base = self._halo_cuts(lo, hi, max_bytes, i0, i1, lambda row: min(i1, max(i0, row)))
+        return [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, rows)] + [i1]
+
+    def _support(self, a, b, R, before, after, n_taps):
+        """The file rows [lo, hi) that the results of rows [a, b) read: the rows themselves and R either side (an exclusion), from
+        `before` rows before to after - 1 rows after each of those (a template; 0 and 1: the row alone), and the filter's support of
+        all of them, inside the recording."""
+        half = (n_taps - 1) // 2
+        return max(0, a - R - before + half - (n_taps - 1)), min(self.n_samples, b + R + after - 1 + half)
+
+    def _filter_args(self, taps, reference, channels, then=None):
+        """The arguments that detect, waveforms, correlate, match_templates and residual filter by -> (taps as float64, default [1.0];
+        the columns; reference as the library's code; then(cols)).  `then` holds the checks that an op makes of its own arguments
+        against the columns: they come before the median's column limit, as they always did."""
+        if reference not in (None, 'median'):
+            raise ValueError("reference must be None or 'median', got %r" % (reference,))
+        taps = _fir_taps([1.0] if taps is None else taps)
+        cols, _ = self._stats_channels(channels)
+        more = then(cols) if then else None
+        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
+            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
+        return taps, cols, 1 if reference else 0, more
+
     def _halo_parts(self, fn, cuts, part, again=None):
         """The halo family's calls (decimate, detect, welch, gram): every [cuts[i], cuts[i + 1]) of the op's unit axis (outputs, rows,
         groups) is one round of calls, split into contiguous parts [a, b), one per lane (a part's halo is decoded by that part alone).
@@ -1829,9 +1901,7 @@ class Reader:
             out = np.empty((i1 - i0, n_out), out_dtype)             # (every row is written by a call)
             # calls: cut the rows at the chunk boundaries where the compressed bytes pass PROJECT_CALL_BYTES, and so that a call's
             # result stays within PROJECT_OUT_BYTES
-            rows = max(1, PROJECT_OUT_BYTES // (n_out * out_dtype.itemsize))
-            base = self._halo_cuts(i0, i1, PROJECT_CALL_BYTES, i0, i1, lambda row: row)
-            cuts = [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, rows)] + [i1]
+            cuts = self._budget_cuts(i0, i1, PROJECT_CALL_BYTES, i0, i1, n_out * out_dtype.itemsize, PROJECT_OUT_BYTES)
 
             def part(a, b):
                 return self._chunk_span(a, b), (a, b, cols, off, w, out_dtype)
@@ -1857,43 +1927,17 @@ class Reader:
         start, K) float32 array.  Chunks resident in the device cache are read where they lie; the others are decoded in a transient
         workspace and NOT kept.  A damaged chunk in the support raises the IOError of Reader[...]."""
         self._need_codec('correlate', 'correlate', 'correlates')
-        if reference not in (None, 'median'):
-            raise ValueError("reference must be None or 'median', got %r" % (reference,))
-        taps = _fir_taps([1.0] if taps is None else taps)
         i0, i1 = self._row_range(start, stop)
-        cols, _ = self._stats_channels(channels)
-        k = np.asarray(templates)
-        if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
-            raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
-        squeeze = k.ndim == 2
-        with np.errstate(over='ignore'):
-            k = np.ascontiguousarray((k[None] if squeeze else k).astype(np.float32))
-        n_out, T, W = k.shape
-        if W != cols.size:
-            raise ValueError("templates have %d columns for %d selected channels" % (W, cols.size))
-        if not 1 <= W <= hip.CORRELATE_MAX_COLS:
-            raise ValueError("correlate takes 1 to %d columns, got %d" % (hip.CORRELATE_MAX_COLS, W))
-        if not 1 <= T <= hip.CORRELATE_MAX_T:
-            raise ValueError("templates have 1 to %d rows, got %d" % (hip.CORRELATE_MAX_T, T))
-        if not 1 <= n_out <= hip.CORRELATE_MAX_OUT:
-            raise ValueError("correlate takes 1 to %d templates, got %d" % (hip.CORRELATE_MAX_OUT, n_out))
-        if not isinstance(before, (int, np.integer)) or isinstance(before, bool) or not 0 <= before <= T:
-            raise ValueError("before must be an int in [0, %d], got %r" % (T, before))
-        if not np.isfinite(k).all():
-            raise ValueError("templates must be finite in float32")
-        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
-            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
-        before, n_taps, N = int(before), int(taps.size), self.n_samples
-        after, half, ref_code = T - before, (n_taps - 1) // 2, 1 if reference else 0
+        taps, cols, ref_code, (k, squeeze, before) = self._filter_args(
+            taps, reference, channels, lambda cols: _template_args(templates, before, cols, 'correlate'))
+        (n_out, T, _), n_taps, N = k.shape, int(taps.size), self.n_samples
         out = np.zeros((i1 - i0, n_out), np.float32)
         if i1 > i0:
             def support(a, b):                                      # the file rows that the scores of rows [a, b) read
-                return max(0, a - before + half - (n_taps - 1)), min(N, b + after - 1 + half)
+                return self._support(a, b, 0, before, T - before, n_taps)
             # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they read pass CORRELATE_CALL_BYTES,
             # and so that a call's result stays within CORRELATE_OUT_BYTES
-            rows = max(1, CORRELATE_OUT_BYTES // (4 * n_out))
-            base = self._halo_cuts(*support(i0, i1), CORRELATE_CALL_BYTES, i0, i1, lambda row: min(i1, max(i0, row)))
-            cuts = [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, rows)] + [i1]
+            cuts = self._budget_cuts(*support(i0, i1), CORRELATE_CALL_BYTES, i0, i1, 4 * n_out, CORRELATE_OUT_BYTES)
 
             def part(a, b):
                 lo, hi = support(a, b)
@@ -1929,31 +1973,10 @@ class Reader:
             self._need_codec('match_templates(subtract=)', 'match_residual', 'subtracts templates')
             if not isinstance(subtract, (tuple, list)) or len(subtract) != 3:
                 raise ValueError("subtract must be None or (sample, template, amplitude)")
-        if reference not in (None, 'median'):
-            raise ValueError("reference must be None or 'median', got %r" % (reference,))
-        taps = _fir_taps([1.0] if taps is None else taps)
         i0, i1 = self._row_range(start, stop)
-        cols, _ = self._stats_channels(channels)
-        k = np.asarray(templates)
-        if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
-            raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
-        with np.errstate(over='ignore'):
-            k = np.ascontiguousarray((k[None] if k.ndim == 2 else k).astype(np.float32))
-        n_out, T, W = k.shape
-        if W != cols.size:
-            raise ValueError("templates have %d columns for %d selected channels" % (W, cols.size))
-        if not 1 <= W <= hip.CORRELATE_MAX_COLS:
-            raise ValueError("match_templates takes 1 to %d columns, got %d" % (hip.CORRELATE_MAX_COLS, W))
-        if not 1 <= T <= hip.CORRELATE_MAX_T:
-            raise ValueError("templates have 1 to %d rows, got %d" % (hip.CORRELATE_MAX_T, T))
-        if not 1 <= n_out <= hip.CORRELATE_MAX_OUT:
-            raise ValueError("match_templates takes 1 to %d templates, got %d" % (hip.CORRELATE_MAX_OUT, n_out))
-        if not isinstance(before, (int, np.integer)) or isinstance(before, bool) or not 0 <= before <= T:
-            raise ValueError("before must be an int in [0, %d], got %r" % (T, before))
-        if not np.isfinite(k).all():
-            raise ValueError("templates must be finite in float32")
-        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
-            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
+        taps, cols, ref_code, (k, _, before) = self._filter_args(
+            taps, reference, channels, lambda cols: _template_args(templates, before, cols, 'match_templates'))
+        n_out, T, _ = k.shape
         if exclude is None:
             exclude = min(T - 1, hip.TMATCH_MAX_EXCLUDE)
         if not isinstance(exclude, (int, np.integer)) or isinstance(exclude, bool) or not 0 <= exclude <= hip.TMATCH_MAX_EXCLUDE:
@@ -1965,13 +1988,12 @@ class Reader:
             thr = np.ascontiguousarray(np.broadcast_to(thr.astype(np.float32), (n_out,)))
         if not np.isfinite(thr).all():
             raise ValueError("threshold must be finite in float32")
-        before, R, n_taps, N = int(before), int(exclude), int(taps.size), self.n_samples
-        after, half, ref_code = T - before, (n_taps - 1) // 2, 1 if reference else 0
+        R, n_taps, N, after = int(exclude), int(taps.size), self.n_samples, T - before
         sub = None if subtract is None else _sub_events(*subtract, n_out, N)
         found = []                                                  # (row, template, score) of every part, in order
         if i1 > i0:
             def support(a, b):                                      # the file rows that the events of rows [a, b) read
-                return max(0, a - R - before + half - (n_taps - 1)), min(N, b + R + after - 1 + half)
+                return self._support(a, b, R, before, after, n_taps)
             # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they read pass TMATCH_CALL_BYTES
             lo, hi = support(i0, i1)
             cuts = self._halo_cuts(lo, hi, TMATCH_CALL_BYTES, i0, i1, lambda row: min(i1, max(i0, row))) if lo < hi else [i0, i1]
@@ -1980,21 +2002,16 @@ class Reader:
                 lo, hi = support(a, b)                              # (rows that read no row of the recording score +0: a call without chunks)
                 keys = self._chunk_span(lo, hi) if lo < hi else []
                 cap = max(TMATCH_GUESS_MIN, (b - a) // TMATCH_GUESS_SAMPLES)
-                args = (0, N, a, b, taps, cols, ref_code, before, k, thr, R, cap)
+                args = (0, N, a, b, taps, cols, ref_code, before, k, thr, R, cap)          # (cap at _TMATCH_CAP_AT)
                 if sub is None:
                     return keys, args
                 # with every event whose window meets the rows that the call computes z for: [a - R - before, b + R + after - 1)
                 e0, e1 = np.searchsorted(sub[0], [a - R - T + 1, b + R + after - 1 + before])
                 return keys, args + tuple(v[e0:e1] for v in sub)
 
-            def again(out, args):                                   # the buffer was short: once more, with room for all
-                if out[1] > args[11] and all(v == hip.CHUNK_OK for v in out[0]):
-                    return args[:11] + (out[1],) + args[12:]
             fn = self.codec.match_templates if sub is None else self.codec.match_residual
-            found = [ev[1:] for _, _, ev in self._halo_parts(fn, cuts, part, again)]
-        row = np.concatenate([f[0] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
-        tpl = np.concatenate([f[1] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
-        val = np.concatenate([f[2] for f in found]).astype(np.float32) if found else np.zeros(0, np.float32)
+            found = [ev[1:] for _, _, ev in self._halo_parts(fn, cuts, part, _again_with_room(_TMATCH_CAP_AT))]
+        row, tpl, val = _event_arrays(found)
         return Bunch(sample=row, template=tpl, score=val, threshold=thr, start=i0, stop=i1, channels=cols, exclude=R)
 
     # -- template peeling on the device (an extension: the reference's users subtract matched templates from Reader[...] on the host)
@@ -2016,43 +2033,18 @@ class Reader:
         - start, W) float32 array.  Chunks resident in the device cache are read where they lie; the others are decoded in a
         transient workspace and NOT kept.  A damaged chunk in the support raises the IOError of Reader[...]."""
         self._need_codec('residual', 'residual', 'subtracts templates')
-        if reference not in (None, 'median'):
-            raise ValueError("reference must be None or 'median', got %r" % (reference,))
-        taps = _fir_taps([1.0] if taps is None else taps)
         i0, i1 = self._row_range(start, stop)
-        cols, _ = self._stats_channels(channels)
-        k = np.asarray(templates)
-        if k.dtype.kind not in 'fiu' or k.ndim not in (2, 3):
-            raise ValueError("templates must be a (K, T, W) or (T, W) array of numbers")
-        with np.errstate(over='ignore'):
-            k = np.ascontiguousarray((k[None] if k.ndim == 2 else k).astype(np.float32))
-        n_out, T, W = k.shape
-        if W != cols.size:
-            raise ValueError("templates have %d columns for %d selected channels" % (W, cols.size))
-        if not 1 <= W <= hip.CORRELATE_MAX_COLS:
-            raise ValueError("residual takes 1 to %d columns, got %d" % (hip.CORRELATE_MAX_COLS, W))
-        if not 1 <= T <= hip.CORRELATE_MAX_T:
-            raise ValueError("templates have 1 to %d rows, got %d" % (hip.CORRELATE_MAX_T, T))
-        if not 1 <= n_out <= hip.CORRELATE_MAX_OUT:
-            raise ValueError("residual takes 1 to %d templates, got %d" % (hip.CORRELATE_MAX_OUT, n_out))
-        if not isinstance(before, (int, np.integer)) or isinstance(before, bool) or not 0 <= before <= T:
-            raise ValueError("before must be an int in [0, %d], got %r" % (T, before))
-        if not np.isfinite(k).all():
-            raise ValueError("templates must be finite in float32")
-        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
-            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
-        before, n_taps, N = int(before), int(taps.size), self.n_samples
-        half, ref_code = (n_taps - 1) // 2, 1 if reference else 0
+        taps, cols, ref_code, (k, _, before) = self._filter_args(
+            taps, reference, channels, lambda cols: _template_args(templates, before, cols, 'residual'))
+        (n_out, T, W), n_taps, N = k.shape, int(taps.size), self.n_samples
         sub = _sub_events(sample, template, amplitude, n_out, N)
         out = np.empty((i1 - i0, W), np.float32)                    # (every row is inside the recording and written by a call)
         if i1 > i0:
-            def support(a, b):                                      # the file rows that rows [a, b) read
-                return max(0, a + half - (n_taps - 1)), min(N, b + half)
+            def support(a, b):                                      # the file rows that rows [a, b) read: their filter support
+                return self._support(a, b, 0, 0, 1, n_taps)
             # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they read pass RESIDUAL_CALL_BYTES,
             # and so that a call's result stays within RESIDUAL_OUT_BYTES
-            rows = max(1, RESIDUAL_OUT_BYTES // (4 * W))
-            base = self._halo_cuts(*support(i0, i1), RESIDUAL_CALL_BYTES, i0, i1, lambda row: min(i1, max(i0, row)))
-            cuts = [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, rows)] + [i1]
+            cuts = self._budget_cuts(*support(i0, i1), RESIDUAL_CALL_BYTES, i0, i1, 4 * W, RESIDUAL_OUT_BYTES)
 
             def part(a, b):
                 # with every event whose window [sample - before, sample - before + T) meets the rows [a, b)
@@ -2081,43 +2073,33 @@ class Reader:
         self._need_codec('detect', 'detect', 'detects')
         if sign not in hip.DETECT_SIGNS:
             raise ValueError("sign must be 'neg', 'pos' or 'both', got %r" % (sign,))
-        if reference not in (None, 'median'):
-            raise ValueError("reference must be None or 'median', got %r" % (reference,))
         for name, v, top in (('exclude', exclude, hip.DETECT_MAX_EXCLUDE), ('spread', spread, hip.DETECT_MAX_SPREAD)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= v <= top:
                 raise ValueError("%s must be an int in [0, %d], got %r" % (name, top, v))
-        taps = _fir_taps([1.0] if taps is None else taps)
         i0, i1 = self._row_range(start, stop)
-        cols, _ = self._stats_channels(channels)
-        thr = np.asarray(threshold)
-        if thr.dtype.kind not in 'fiu' or thr.shape not in ((), (cols.size,)):
-            raise ValueError("threshold must be a number or one per column (%d)" % cols.size)
-        with np.errstate(over='ignore'):
-            thr = np.ascontiguousarray(np.broadcast_to(thr.astype(np.float32), (cols.size,)))
-        if not (np.isfinite(thr) & (thr > 0)).all():
-            raise ValueError("threshold must be positive and finite in float32")
-        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
-            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
-        R, S, n_taps, N = int(exclude), int(spread), int(taps.size), self.n_samples
-        half = (n_taps - 1) // 2
-        sign_code, ref_code = hip.DETECT_SIGNS[sign], 1 if reference else 0
+
+        def thresholds(cols):
+            thr = np.asarray(threshold)
+            if thr.dtype.kind not in 'fiu' or thr.shape not in ((), (cols.size,)):
+                raise ValueError("threshold must be a number or one per column (%d)" % cols.size)
+            with np.errstate(over='ignore'):
+                thr = np.ascontiguousarray(np.broadcast_to(thr.astype(np.float32), (cols.size,)))
+            if not (np.isfinite(thr) & (thr > 0)).all():
+                raise ValueError("threshold must be positive and finite in float32")
+            return thr
+        taps, cols, ref_code, thr = self._filter_args(taps, reference, channels, thresholds)
+        R, S, n_taps, N, sign_code = int(exclude), int(spread), int(taps.size), self.n_samples, hip.DETECT_SIGNS[sign]
         found = []                                                  # (row, pos, amp) of every part, in order
         if i1 > i0 and cols.size:
             # calls: cut the rows at the chunk boundaries where the compressed bytes of the chunks they lie in pass DETECT_CALL_BYTES
             cuts = self._halo_cuts(i0, i1, DETECT_CALL_BYTES, i0, i1, lambda row: row)
 
             def part(a, b):
-                keys = self._chunk_span(max(0, a - R + half - (n_taps - 1)), min(N, b + R + half))
+                keys = self._chunk_span(*self._support(a, b, R, 0, 1, n_taps))
                 cap = max(DETECT_GUESS_MIN, (b - a) * cols.size // DETECT_GUESS_SAMPLES)
-                return keys, (0, N, a, b, taps, cols, thr, sign_code, ref_code, R, S, cap)
-
-            def again(out, args):                                   # the buffer was short: once more, with room for all
-                if out[1] > args[-1] and all(v == hip.CHUNK_OK for v in out[0]):
-                    return args[:-1] + (out[1],)
-            found = [ev[1:] for _, _, ev in self._halo_parts(self.codec.detect, cuts, part, again)]
-        row = np.concatenate([f[0] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
-        pos = np.concatenate([f[1] for f in found]).astype(np.int64) if found else np.zeros(0, np.int64)
-        amp = np.concatenate([f[2] for f in found]).astype(np.float32) if found else np.zeros(0, np.float32)
+                return keys, (0, N, a, b, taps, cols, thr, sign_code, ref_code, R, S, cap)     # (cap at _DETECT_CAP_AT)
+            found = [ev[1:] for _, _, ev in self._halo_parts(self.codec.detect, cuts, part, _again_with_room(_DETECT_CAP_AT))]
+        row, pos, amp = _event_arrays(found)
         return Bunch(sample=row, channel=cols.astype(np.int64)[pos], amplitude=amp, threshold=thr, start=i0, stop=i1, channels=cols)
 
     # -- snippets around events on the device (an extension: the reference's users filter Reader[...] and slice it on the host)
@@ -2164,8 +2146,6 @@ class Reader:
         lie, the others in a transient workspace and NOT kept.  A damaged chunk in an event's support raises the IOError of
         Reader[...]."""
         self._need_codec('waveforms', 'waveforms', 'gathers')
-        if reference not in (None, 'median'):
-            raise ValueError("reference must be None or 'median', got %r" % (reference,))
         for name, v in (('before', before), ('after', after)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0:
                 raise ValueError("%s must be an int >= 0, got %r" % (name, v))
@@ -2175,15 +2155,14 @@ class Reader:
             raise ValueError("before + after must be in [1, %d], got %d" % (hip.WAVEFORMS_MAX_ROWS, T))
         if neighbours is not None and (not isinstance(neighbours, (int, np.integer)) or isinstance(neighbours, bool) or neighbours < 0):
             raise ValueError("neighbours must be None or an int >= 0, got %r" % (neighbours,))
-        taps = _fir_taps([1.0] if taps is None else taps)
-        cols, _ = self._stats_channels(channels)
-        if not cols.size:
-            raise ValueError("waveforms needs at least one channel")
-        W = int(cols.size) if neighbours is None else 2 * int(neighbours) + 1
-        if W > hip.WAVEFORMS_MAX_WIDTH:
-            raise ValueError("a snippet holds at most %d positions, got %d" % (hip.WAVEFORMS_MAX_WIDTH, W))
-        if reference and cols.size > hip.DETECT_MAX_REF_COLS:
-            raise ValueError("a median reference takes at most %d columns, got %d" % (hip.DETECT_MAX_REF_COLS, cols.size))
+        def width(cols):
+            if not cols.size:
+                raise ValueError("waveforms needs at least one channel")
+            W = int(cols.size) if neighbours is None else 2 * int(neighbours) + 1
+            if W > hip.WAVEFORMS_MAX_WIDTH:
+                raise ValueError("a snippet holds at most %d positions, got %d" % (hip.WAVEFORMS_MAX_WIDTH, W))
+            return W
+        taps, cols, ref_code, W = self._filter_args(taps, reference, channels, width)
         rows = np.asarray(sample)
         if rows.ndim != 1 or (rows.size and rows.dtype.kind not in 'iu'):
             raise ValueError("sample must be a 1-D array of ints")
@@ -2207,7 +2186,7 @@ class Reader:
             col0 = first[ch] - int(neighbours)
         order = np.argsort(rows, kind='stable')
         s_rows, s_col0 = rows[order], col0[order]
-        ref_code, n_taps = 1 if reference else 0, int(taps.size)
+        n_taps = int(taps.size)
         half = (n_taps - 1) // 2
         wave = np.empty((n, T, W), np.float32) if waveforms else None
         ext = [np.empty(n, t) for t in (np.float32, np.int64, np.float32, np.int64)]

@@ -26,9 +26,11 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, waveforms, correlate, match_templates, welch, gram): a unit of output (outputs, rows, events, blocks, groups -- the op gives HaloPlan its map
-//        from units to rows) reads rows of several adjacent chunks, so a piece reads chunks [c0, c1] through a table of segment bases
-//        and first rows, and decodes the missing ones among them -- a boundary chunk in both pieces (HaloPlan, HaloFeed).
+//   halo (decimate, project, detect, waveforms, correlate, match_templates, residual, welch, gram): a unit of output (outputs, rows,
+//        events, blocks, groups -- the op gives HaloPlan its map from units to rows) reads rows of several adjacent chunks, so a piece
+//        reads chunks [c0, c1] through a table of segment bases and first rows, and decodes the missing ones among them -- a boundary
+//        chunk in both pieces (HaloPlan, HaloFeed).  Five of them (detect, waveforms, correlate, match_templates, residual) start from
+//        one filtered signal z: their checks, uploads, filter stage and tails are the z family's shared parts below.
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
 //   - An allocation that fails empties this device's caches before it tries again (DBuf::ensure -> drop_device_caches: hipFree,
 //     which waits for the kernels already launched -- earlier reads are done).  So every allocation of the call (the op's own DBuf,
@@ -123,13 +125,54 @@ int check_chunk_table(bool adjacent, const ChunkTable &T, long row_begin = 0, lo
     return MTS_OK;
 }
 
-// the FIR taps of decimate and detect
+// the FIR taps of decimate and the z family
 int check_taps(const char *op, int n_taps, const double *taps)
 {
     if (n_taps < 1 || n_taps > MTS_DECIMATE_MAX_TAPS || !taps) { set_error("%s: %d taps (1 .. %d)", op, n_taps, MTS_DECIMATE_MAX_TAPS); return MTS_E_ARG; }
     for (int j = 0; j < n_taps; j++)
         if (!std::isfinite(taps[j])) { set_error("%s: tap %d is not finite", op, j); return MTS_E_ARG; }
     return MTS_OK;
+}
+
+// what the z family (detect, waveforms, correlate, match_templates, residual) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
+// in float32, x = 0 outside [vb, ve), minus the row's median over the columns with reference 1.  `op` names the entry in every message.
+struct ZArgs { const char *op; long vb, ve; int n_taps; const double *taps; int n_cols; const int *cols; int reference; };
+
+// the first checks of the z family.  max_cols 0: as many columns as a grid holds, in one message with the table (detect, waveforms);
+// else that many, the count named (the template ops)
+int check_zargs(const ChunkTable &T, const ZArgs &Z, int max_cols = 0)
+{
+    const bool bad_table = T.nc <= 0 || T.n_chunks < 0, bad_cols = Z.n_cols < 1 || Z.n_cols > (max_cols ? max_cols : 64 * 65535) || !Z.cols;
+    if (!max_cols && (bad_table || bad_cols)) { set_error("%s: n_channels, n_chunks or columns invalid", Z.op); return MTS_E_ARG; }
+    if (bad_table) { set_error("%s: n_channels or n_chunks invalid", Z.op); return MTS_E_ARG; }
+    if (bad_cols) { set_error("%s: %d columns (1 .. %d)", Z.op, Z.n_cols, max_cols); return MTS_E_ARG; }
+    if (const int rc = check_taps(Z.op, Z.n_taps, Z.taps)) return rc;
+    if (Z.reference < 0 || Z.reference > 1) { set_error("%s: reference %d (0 none, 1 median)", Z.op, Z.reference); return MTS_E_ARG; }
+    if (Z.reference && Z.n_cols > MTS_DETECT_MAX_REF_COLS) {
+        set_error("%s: a median reference over %d columns (<= %d)", Z.op, Z.n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG;
+    }
+    if (Z.vb < 0 || Z.ve < Z.vb || Z.ve > (1l << 60)) { set_error("%s: rows invalid", Z.op); return MTS_E_ARG; }
+    return MTS_OK;
+}
+
+// the templates (n_out, n_tau, n_cols) of correlate, match_templates and residual, row `before` of each laid on the event's row
+int check_templates(const char *op, int n_cols, int before, int n_tau, int n_out, const float *templates)
+{
+    if (n_tau < 1 || n_tau > MTS_CORRELATE_MAX_T) { set_error("%s: templates of %d rows (1 .. %d)", op, n_tau, MTS_CORRELATE_MAX_T); return MTS_E_ARG; }
+    if (before < 0 || before > n_tau) { set_error("%s: before %d (0 .. %d)", op, before, n_tau); return MTS_E_ARG; }
+    if (n_out < 1 || n_out > MTS_CORRELATE_MAX_OUT || !templates) { set_error("%s: %d templates (1 .. %d)", op, n_out, MTS_CORRELATE_MAX_OUT); return MTS_E_ARG; }
+    const long per = (long)n_tau * n_cols;
+    for (long e = 0; e < (long)n_out * per; e++)
+        if (!std::isfinite(templates[e])) { set_error("%s: template entry (%ld, %ld, %ld) is not finite", op, e / per, e % per / n_cols, e % n_cols); return MTS_E_ARG; }
+    return MTS_OK;
+}
+
+// a slab bound from the environment (MTS_<OP>_SLAB_BYTES: tests and tools set them); anything but a positive number is the default
+u64 env_bytes(const char *name, u64 otherwise)
+{
+    const char *e = getenv(name);
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (u64)v : otherwise;
 }
 
 // the (adjacent) chunks hold the rows [lo, hi) that the op reads; nothing to hold when the range is empty
@@ -295,6 +338,88 @@ struct HaloFeed {
         });
     }
 };
+
+// ---- z family: what detect, waveforms, correlate, match_templates and residual share around their own slab loops.  Each run reads
+// top to bottom as the halo family's sequence: plan -> regions (ZStage first, the op's, EventTail's) -> StreamGuard -> place ->
+// uploads -> run -> tail.
+//
+// The rule for leaving early, for all five: from the first asynchronous upload out of host memory that the call owns (HaloFeed::seg,
+// ZStage::h_taps, the repacked templates, SubEvents::namp) no path returns before the stream has been waited for -- a failed
+// H.run, a failed MTS_HIP.  The guard is declared after those vectors and before H.place, so it goes before they do; the tails'
+// own wait() disarms it, so the normal path waits no more often than it has to.
+struct StreamGuard {
+    hipStream_t st;
+    bool waited = false;
+    ~StreamGuard() { if (!waited) (void)hipStreamSynchronize(st); }
+    int wait() { MTS_HIP(hipStreamSynchronize(st)); waited = true; return MTS_OK; }
+};
+
+// the filter stage: the taps (rounded once to float32) and the columns on the device, and z of the rows [a, b) into a float32 slab --
+// the same launches with the same arguments in every op, so the same bytes
+struct ZStage {
+    const ZArgs &Z;
+    const long half;
+    const size_t o_taps, o_cols;
+    std::vector<float> h_taps;                                // (the source of an asynchronous copy: it lives as long as the call)
+    const void *d_taps = nullptr;
+    const int *d_cols = nullptr;
+
+    // (the first two regions of the op's workspace)
+    ZStage(const ZArgs &Z_, WsLayout &L) : Z(Z_), half((Z_.n_taps - 1) / 2), o_taps(L.take(4 * (u64)Z_.n_taps)), o_cols(L.take(4 * (u64)Z_.n_cols)) {}
+
+    // (after H.place: ws is the op's workspace)
+    int upload(hipStream_t st, u8 *ws)
+    {
+        h_taps.resize((size_t)Z.n_taps);
+        for (int j = 0; j < Z.n_taps; j++) h_taps[j] = (float)Z.taps[j];
+        d_taps = ws + o_taps; d_cols = (const int *)(ws + o_cols);
+        MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)Z.n_taps, hipMemcpyHostToDevice, st));
+        MTS_HIP(hipMemcpyAsync(ws + o_cols, Z.cols, 4 * (size_t)Z.n_cols, hipMemcpyHostToDevice, st));
+        return MTS_OK;
+    }
+
+    // d_y[t - a] = z[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k (nothing valid to read,
+    // ns == 0: every row is 0), then the median
+    int filter(hipStream_t st, const ChunkTable &T, const PieceSegs &Sg, long a, long b, float *d_y) const
+    {
+        const int r = launch_decimate(st, T.sz, T.flags, 4, Sg.base, Sg.row0, Sg.ns, T.nc, d_cols, Z.n_cols, d_taps, Z.n_taps, 1, half, a, b,
+                                      Sg.ns ? Z.vb : 0, Sg.ns ? Z.ve : 0, d_y);
+        return !r && Z.reference ? launch_row_median(st, d_y, b - a, Z.n_cols) : r;
+    }
+};
+
+// the events of detect and match_templates: their count on the device, carried from slab to slab and piece to piece, and the first
+// max_events of them in three arrays of 8-, 4- and 4-byte items
+struct EventTail {
+    const size_t o_total;
+    u64 *d_total = nullptr;
+
+    explicit EventTail(WsLayout &L) : o_total(L.take(8)) {}
+    int begin(hipStream_t st, u8 *ws) { d_total = (u64 *)(ws + o_total); MTS_HIP(hipMemsetAsync(d_total, 0, 8, st)); return MTS_OK; }
+    int finish(StreamGuard &G, long max_events, bool out_on_host, long *n_events, void *out8, const void *d8, void *out4a, const void *d4a, void *out4b,
+               const void *d4b)
+    {
+        u64 total = 0;
+        MTS_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, G.st));
+        if (const int rc = G.wait()) return rc;
+        *n_events = (long)total;
+        const size_t n_w = (size_t)std::min<u64>(total, (u64)max_events);
+        if (out_on_host && n_w) {
+            MTS_HIP(hipMemcpyAsync(out8, d8, 8 * n_w, hipMemcpyDeviceToHost, G.st));
+            MTS_HIP(hipMemcpyAsync(out4a, d4a, 4 * n_w, hipMemcpyDeviceToHost, G.st));
+            MTS_HIP(hipMemcpyAsync(out4b, d4b, 4 * n_w, hipMemcpyDeviceToHost, G.st));
+            MTS_HIP(hipStreamSynchronize(G.st));
+        }
+        return MTS_OK;
+    }
+};
+
+// the dense float32 result of correlate and residual
+int dense_tail(StreamGuard &G, bool out_on_host, float *out, const float *d_out, u64 n_items)
+{
+    if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, 4 * n_items, hipMemcpyDeviceToHost, G.st));
+    return G.wait();
+}
 
 // ---- tile family: what the two ops share between their checks and their outputs, in three steps with the op's own regions,
 // uploads and kernel between them:  plan() -> the op takes its regions from L ->  place()  -> the op's uploads ->  run(launch).
@@ -634,40 +759,30 @@ static int project_run(Engine &E, hipStream_t st, const ChunkTable &T, long row_
 static const u64 DETECT_SLAB_BYTES = 256ull << 20;
 static const long DETECT_SLAB_MAX_ROWS = 1l << 22;                  // (bounds the bitmap of narrow selections: <= 32 MiB up to 64 columns)
 
-static u64 detect_slab_bytes()
-{
-    const char *e = getenv("MTS_DETECT_SLAB_BYTES");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (u64)v : DETECT_SLAB_BYTES;
-}
-
-static int detect_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
-                      int n_cols, const int *cols, const float *threshold, int sign, int reference, int R, int S, long max_events, long *out_row,
-                      int *out_pos, float *out_amp, bool out_on_host, long *n_events, int *status)
+static int detect_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long row_begin, long row_end, const float *threshold, int sign,
+                      int R, int S, long max_events, long *out_row, int *out_pos, float *out_amp, bool out_on_host, long *n_events, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols;
     int rc;
-    if (nc <= 0 || T.n_chunks < 0 || n_cols < 1 || n_cols > 64 * 65535 || !cols) { set_error("detect: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
-    if ((rc = check_taps("detect", n_taps, taps))) return rc;
+    if ((rc = check_zargs(T, Z))) return rc;
     if (!threshold) { set_error("detect: no thresholds"); return MTS_E_ARG; }
     for (int j = 0; j < n_cols; j++)
         if (!std::isfinite(threshold[j]) || !(threshold[j] > 0)) { set_error("detect: threshold %d is not a finite positive number", j); return MTS_E_ARG; }
     if (sign < 0 || sign > 2) { set_error("detect: sign %d (0 neg, 1 pos, 2 both)", sign); return MTS_E_ARG; }
-    if (reference < 0 || reference > 1) { set_error("detect: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
-    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("detect: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
     if (R < 0 || R > MTS_DETECT_MAX_EXCLUDE || S < 0 || S > MTS_DETECT_MAX_SPREAD) {
         set_error("detect: exclude_rows %d (0 .. %d) or exclude_cols %d (0 .. %d)", R, MTS_DETECT_MAX_EXCLUDE, S, MTS_DETECT_MAX_SPREAD); return MTS_E_ARG;
     }
-    if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve) { set_error("detect: rows invalid"); return MTS_E_ARG; }
+    if (row_begin < vb || row_end < row_begin || row_end > ve) { set_error("detect: rows invalid"); return MTS_E_ARG; }
     if (max_events < 0 || max_events > (1l << 40) || !n_events) { set_error("detect: max_events invalid or no n_events"); return MTS_E_ARG; }
     if (max_events && (!out_row || !out_pos || !out_amp)) { set_error("detect: no output buffers"); return MTS_E_ARG; }
-    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_columns(Z.cols, n_cols, T.nc))) return rc;
     if ((rc = check_chunk_table(true, T))) return rc;
-    const long half = (n_taps - 1) / 2, n_units = row_end - row_begin;
+    const long half = (Z.n_taps - 1) / 2, n_units = row_end - row_begin;
     // the rows that the events of rows [u0, u1) read: (rows + R either side)'s support ∩ valid range
     auto rows = [&](long u0, long u1, long *lo, long *hi) {
-        *lo = std::max(vb, row_begin + u0 - R + half - (n_taps - 1)); *hi = std::min(ve, row_begin + u1 + R + half);
+        *lo = std::max(vb, row_begin + u0 - R + half - (Z.n_taps - 1)); *hi = std::min(ve, row_begin + u1 + R + half);
     };
     long need_lo = 0, need_hi = 0;
     if (n_units) rows(0, n_units, &need_lo, &need_hi);
@@ -679,56 +794,42 @@ static int detect_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, l
     HaloFeed H(T, out_on_host);
     if ((rc = H.plan(n_units, [&](long r) { return r - row_begin; }, rows))) return rc;
     // rows a slab owns: the workspace holds them and R rows either side
-    const long cap_rows = (long)std::min<u64>(detect_slab_bytes() / (4 * (u64)n_cols), (u64)DETECT_SLAB_MAX_ROWS);
+    const long cap_rows = (long)std::min<u64>(env_bytes("MTS_DETECT_SLAB_BYTES", DETECT_SLAB_BYTES) / (4 * (u64)n_cols), (u64)DETECT_SLAB_MAX_ROWS);
     const long own = std::min(n_units, std::max(1l, cap_rows - 2l * R));
     const long max_words = detect_bitmap_words(own, n_cols), max_blocks = detect_blocks(max_words);
     // ---- workspace
     WsLayout &L = H.L;
-    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_thr = L.take(4 * (u64)n_cols), o_seg = L.take(H.table_bytes()),
-                 o_total = L.take(8), o_y = L.take(4 * (u64)(own + 2l * R) * n_cols), o_bits = L.take(8 * (u64)max_words),
-                 o_cnt = L.take(4 * (u64)max_blocks), o_offs = L.take(8 * (u64)max_blocks), o_row = L.take_out(8 * (u64)max_events),
-                 o_pos = L.take_out(4 * (u64)max_events), o_amp = L.take_out(4 * (u64)max_events);
+    ZStage F(Z, L);
+    const size_t o_thr = L.take(4 * (u64)n_cols), o_seg = L.take(H.table_bytes());
+    EventTail EV(L);
+    const size_t o_y = L.take(4 * (u64)(own + 2l * R) * n_cols), o_bits = L.take(8 * (u64)max_words), o_cnt = L.take(4 * (u64)max_blocks),
+                 o_offs = L.take(8 * (u64)max_blocks), o_row = L.take_out(8 * (u64)max_events), o_pos = L.take_out(4 * (u64)max_events),
+                 o_amp = L.take_out(4 * (u64)max_events);
+    StreamGuard G{st};
     if ((rc = H.place(E, st, E.det, o_seg))) return rc;
     u8 *ws = E.det.as<u8>();
-    std::vector<float> h_taps(n_taps);
-    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
-    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
-    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    if ((rc = F.upload(st, ws))) return rc;
     MTS_HIP(hipMemcpyAsync(ws + o_thr, threshold, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
-    MTS_HIP(hipMemsetAsync(ws + o_total, 0, 8, st));
+    if ((rc = EV.begin(st, ws))) return rc;
     long *d_row = L.out(ws, o_row, out_row);
     int *d_pos = L.out(ws, o_pos, out_pos);
     float *d_amp = L.out(ws, o_amp, out_amp);
     float *d_y = (float *)(ws + o_y);
-    u64 *d_bits = (u64 *)(ws + o_bits), *d_total = (u64 *)(ws + o_total);
+    u64 *d_bits = (u64 *)(ws + o_bits);
     rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
         const long p0 = row_begin + Pc.u0, p1 = row_begin + Pc.u1;
         int r = MTS_OK;
         for (long s0 = p0; !r && s0 < p1; s0 += own) {
             const long s1 = std::min(p1, s0 + own), a = std::max(vb, s0 - R), b = std::min(ve, s1 + R);
-            // y[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k
-            r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half, a, b,
-                                Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
-            if (!r && reference) r = launch_row_median(st, d_y, b - a, n_cols);
+            r = F.filter(st, T, Sg, a, b, d_y);
             if (!r) r = launch_detect_mask(st, d_y, a, b - a, n_cols, (const float *)(ws + o_thr), sign, R, S, s0, s1, d_bits);
-            if (!r) r = launch_detect_emit(st, d_bits, detect_bitmap_words(s1 - s0, n_cols), (u32 *)(ws + o_cnt), (u64 *)(ws + o_offs), d_total, d_y,
+            if (!r) r = launch_detect_emit(st, d_bits, detect_bitmap_words(s1 - s0, n_cols), (u32 *)(ws + o_cnt), (u64 *)(ws + o_offs), EV.d_total, d_y,
                                            a, n_cols, s0, max_events, d_row, d_pos, d_amp);
         }
         return r;
     });
     if (rc) return rc;
-    u64 total = 0;
-    MTS_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
-    MTS_HIP(hipStreamSynchronize(st));
-    *n_events = (long)total;
-    const size_t n_w = (size_t)std::min<u64>(total, (u64)max_events);
-    if (out_on_host && n_w) {
-        MTS_HIP(hipMemcpyAsync(out_row, d_row, 8 * n_w, hipMemcpyDeviceToHost, st));
-        MTS_HIP(hipMemcpyAsync(out_pos, d_pos, 4 * n_w, hipMemcpyDeviceToHost, st));
-        MTS_HIP(hipMemcpyAsync(out_amp, d_amp, 4 * n_w, hipMemcpyDeviceToHost, st));
-        MTS_HIP(hipStreamSynchronize(st));
-    }
-    return MTS_OK;
+    return EV.finish(G, max_events, out_on_host, n_events, out_row, d_row, out_pos, d_pos, out_amp, d_amp);
 }
 
 // ---- snippets around events (mts_waveforms, mts_dev_waveforms) -----------------------------------------------------------------
@@ -741,36 +842,26 @@ static int detect_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, l
 static const u64 WAVEFORMS_SLAB_BYTES = 256ull << 20;
 static const long WAVEFORMS_GAP_ROWS = 4096;                        // (swept at 1024 / 4096 / 16384 / never: profiles/waveforms.json)
 
-static u64 waveforms_slab_bytes()
-{
-    const char *e = getenv("MTS_WAVEFORMS_SLAB_BYTES");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (u64)v : WAVEFORMS_SLAB_BYTES;
-}
-
 static long waveforms_gap_rows()                                     // (negative: never cut at a gap)
 {
     const char *e = getenv("MTS_WAVEFORMS_GAP_ROWS");
     return e && *e ? (long)atoll(e) : WAVEFORMS_GAP_ROWS;
 }
 
-static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, int n_taps, const double *taps, int n_cols,
-                         const int *cols, int reference, long n_events, const long *ev_row, const int *ev_col0, int before, int after, int width,
-                         float *out_wave, float *out_min, int *out_argmin, float *out_max, int *out_argmax, bool out_on_host, int *status)
+static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long n_events, const long *ev_row, const int *ev_col0,
+                         int before, int after, int width, float *out_wave, float *out_min, int *out_argmin, float *out_max, int *out_argmax,
+                         bool out_on_host, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols, n_taps = Z.n_taps;
     int rc;
-    if (nc <= 0 || T.n_chunks < 0 || n_cols < 1 || n_cols > 64 * 65535 || !cols) { set_error("waveforms: n_channels, n_chunks or columns invalid"); return MTS_E_ARG; }
-    if ((rc = check_taps("waveforms", n_taps, taps))) return rc;
-    if (reference < 0 || reference > 1) { set_error("waveforms: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
-    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("waveforms: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
+    if ((rc = check_zargs(T, Z))) return rc;
     const long n_snip = (long)before + (long)after;
     if (before < 0 || after < 0 || n_snip < 1 || n_snip > MTS_WAVEFORMS_MAX_ROWS) {
         set_error("waveforms: before %d, after %d (both >= 0, 1 .. %d rows in all)", before, after, MTS_WAVEFORMS_MAX_ROWS); return MTS_E_ARG;
     }
     if (width < 1 || width > MTS_WAVEFORMS_MAX_WIDTH) { set_error("waveforms: width %d (1 .. %d)", width, MTS_WAVEFORMS_MAX_WIDTH); return MTS_E_ARG; }
-    if (vb < 0 || ve < vb || ve > (1l << 60)) { set_error("waveforms: rows invalid"); return MTS_E_ARG; }
     if (n_events < 0 || n_events > (1l << 40)) { set_error("waveforms: %ld events (0 .. 2^40)", n_events); return MTS_E_ARG; }
     if (n_events && (!ev_row || !ev_col0)) { set_error("waveforms: no events"); return MTS_E_ARG; }
     if (!out_min || !out_argmin || !out_max || !out_argmax) { set_error("waveforms: no extrema buffers"); return MTS_E_ARG; }
@@ -778,7 +869,7 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
         if (ev_row[e] < vb || ev_row[e] >= ve) { set_error("waveforms: event %ld at row %ld outside [%ld, %ld)", e, ev_row[e], vb, ve); return MTS_E_ARG; }
         if (e && ev_row[e] < ev_row[e - 1]) { set_error("waveforms: event %ld: the rows must ascend", e); return MTS_E_ARG; }
     }
-    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_columns(Z.cols, n_cols, T.nc))) return rc;
     if ((rc = check_chunk_table(true, T))) return rc;
     const long half = (n_taps - 1) / 2;
     // the rows that the events [u0, u1) read: their snippets' support ∩ valid range
@@ -795,7 +886,8 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
     // the first event at or after row r
     if ((rc = H.plan(n_events, [&](long r) { return (long)(std::lower_bound(ev_row, ev_row + n_events, r) - ev_row); }, rows))) return rc;
     // every piece's slabs: the workspace holds the longest
-    const long cap_rows = (long)std::min<u64>(waveforms_slab_bytes() / (4 * (u64)n_cols), (u64)1 << 40), gap_rows = waveforms_gap_rows();
+    const long cap_rows = (long)std::min<u64>(env_bytes("MTS_WAVEFORMS_SLAB_BYTES", WAVEFORMS_SLAB_BYTES) / (4 * (u64)n_cols), (u64)1 << 40);
+    const long gap_rows = waveforms_gap_rows();
     std::vector<SnippetPlan> slabs;
     long max_rows = 0, report[4] = {(long)H.P->pieces.size(), 0, 0, 0};
     for (const FeedPiece &Pc : H.P->pieces) {
@@ -809,16 +901,15 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
     // ---- workspace
     const u64 n_item = (u64)n_snip * width;
     WsLayout &L = H.L;
-    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_seg = L.take(H.table_bytes()), o_erow = L.take(8 * (u64)n_events),
-                 o_ecol = L.take(4 * (u64)n_events), o_y = L.take(4 * (u64)max_rows * n_cols),
-                 o_wave = out_wave ? L.take_out(4 * (u64)n_events * n_item) : 0, o_min = L.take_out(4 * (u64)n_events),
-                 o_amin = L.take_out(4 * (u64)n_events), o_max = L.take_out(4 * (u64)n_events), o_amax = L.take_out(4 * (u64)n_events);
+    ZStage F(Z, L);
+    const size_t o_seg = L.take(H.table_bytes()), o_erow = L.take(8 * (u64)n_events), o_ecol = L.take(4 * (u64)n_events),
+                 o_y = L.take(4 * (u64)max_rows * n_cols), o_wave = out_wave ? L.take_out(4 * (u64)n_events * n_item) : 0,
+                 o_min = L.take_out(4 * (u64)n_events), o_amin = L.take_out(4 * (u64)n_events), o_max = L.take_out(4 * (u64)n_events),
+                 o_amax = L.take_out(4 * (u64)n_events);
+    StreamGuard G{st};
     if ((rc = H.place(E, st, E.wav, o_seg))) return rc;
     u8 *ws = E.wav.as<u8>();
-    std::vector<float> h_taps(n_taps);
-    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
-    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
-    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    if ((rc = F.upload(st, ws))) return rc;
     MTS_HIP(hipMemcpyAsync(ws + o_erow, ev_row, 8 * (size_t)n_events, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_ecol, ev_col0, 4 * (size_t)n_events, hipMemcpyHostToDevice, st));
     float *d_wave = out_wave ? L.out(ws, o_wave, out_wave) : nullptr;
@@ -828,10 +919,7 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
     rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
         int r = MTS_OK;
         for (const SnippetSlab &S : slabs[&Pc - H.P->pieces.data()].slabs) {
-            // y[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k
-            r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half, S.a,
-                                S.b, Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
-            if (!r && reference) r = launch_row_median(st, d_y, S.b - S.a, n_cols);
+            r = F.filter(st, T, Sg, S.a, S.b, d_y);
             if (!r && timed) (void)hipEventRecord(E.wav_ev[0], st);
             if (!r) r = launch_waveforms(st, d_y, S.a, S.b - S.a, n_cols, vb, ve, (const long *)(ws + o_erow), (const int *)(ws + o_ecol), S.e0, S.e1,
                                          before, after, width, d_wave, d_min, d_amin, d_max, d_amax);
@@ -846,7 +934,7 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
         }
         return r;
     });
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps has been read before it goes)
+    if (rc) return rc;
     if (out_on_host) {
         if (out_wave) MTS_HIP(hipMemcpyAsync(out_wave, d_wave, 4 * (size_t)n_events * n_item, hipMemcpyDeviceToHost, st));
         MTS_HIP(hipMemcpyAsync(out_min, d_min, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
@@ -854,7 +942,7 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
         MTS_HIP(hipMemcpyAsync(out_max, d_max, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
         MTS_HIP(hipMemcpyAsync(out_argmax, d_amax, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
     }
-    MTS_HIP(hipStreamSynchronize(st));
+    if ((rc = G.wait())) return rc;
     report[3] = (long)(gather_ms * 1e3);
     memcpy(E.wav_plan, report, sizeof report);
     return MTS_OK;
@@ -869,13 +957,6 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
 // whatever the pieces and slabs.
 static const u64 CORRELATE_SLAB_BYTES = 256ull << 20;
 
-static u64 correlate_slab_bytes()
-{
-    const char *e = getenv("MTS_CORRELATE_SLAB_BYTES");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (u64)v : CORRELATE_SLAB_BYTES;
-}
-
 // the templates (n_out, T, n_cols) in k_correlate's layout: row (g / 4 * T + tau) * 4 + c holds K[0 .. kp, tau, g + c], +0 past n_cols and n_out
 static std::vector<float> repack_templates(const float *templates, int n_out, int n_tau, int n_cols, int kp)
 {
@@ -888,29 +969,18 @@ static std::vector<float> repack_templates(const float *templates, int n_out, in
     return h_tpl;
 }
 
-static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
-                         int n_cols, const int *cols, int reference, int before, int n_tau, int n_out, const float *templates, float *out,
-                         bool out_on_host, int *status)
+static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long row_begin, long row_end, int before, int n_tau,
+                         int n_out, const float *templates, float *out, bool out_on_host, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols, n_taps = Z.n_taps;
     int rc;
-    if (nc <= 0 || T.n_chunks < 0) { set_error("correlate: n_channels or n_chunks invalid"); return MTS_E_ARG; }
-    if (n_cols < 1 || n_cols > MTS_CORRELATE_MAX_COLS || !cols) { set_error("correlate: %d columns (1 .. %d)", n_cols, MTS_CORRELATE_MAX_COLS); return MTS_E_ARG; }
-    if ((rc = check_taps("correlate", n_taps, taps))) return rc;
-    if (reference < 0 || reference > 1) { set_error("correlate: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
-    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("correlate: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
-    if (n_tau < 1 || n_tau > MTS_CORRELATE_MAX_T) { set_error("correlate: templates of %d rows (1 .. %d)", n_tau, MTS_CORRELATE_MAX_T); return MTS_E_ARG; }
-    if (before < 0 || before > n_tau) { set_error("correlate: before %d (0 .. %d)", before, n_tau); return MTS_E_ARG; }
-    if (n_out < 1 || n_out > MTS_CORRELATE_MAX_OUT || !templates) { set_error("correlate: %d templates (1 .. %d)", n_out, MTS_CORRELATE_MAX_OUT); return MTS_E_ARG; }
-    const long per = (long)n_tau * n_cols;
-    for (long e = 0; e < (long)n_out * per; e++)
-        if (!std::isfinite(templates[e])) { set_error("correlate: template entry (%ld, %ld, %ld) is not finite", e / per, e % per / n_cols, e % n_cols); return MTS_E_ARG; }
-    if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve || row_end - row_begin > (1l << 40)) {
-        set_error("correlate: rows invalid"); return MTS_E_ARG;
-    }
+    if ((rc = check_zargs(T, Z, MTS_CORRELATE_MAX_COLS))) return rc;
+    if ((rc = check_templates("correlate", n_cols, before, n_tau, n_out, templates))) return rc;
+    if (row_begin < vb || row_end < row_begin || row_end > ve || row_end - row_begin > (1l << 40)) { set_error("correlate: rows invalid"); return MTS_E_ARG; }
     if (row_end > row_begin && !out) { set_error("correlate: no output buffer"); return MTS_E_ARG; }
-    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_columns(Z.cols, n_cols, T.nc))) return rc;
     if ((rc = check_chunk_table(true, T))) return rc;
     const long half = (n_taps - 1) / 2, n_units = row_end - row_begin, after = n_tau - before;
     // the rows that the scores of rows [u0, u1) read: (rows - before .. rows + after - 1)'s support ∩ valid range
@@ -926,22 +996,21 @@ static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
     HaloFeed H(T, out_on_host);
     if ((rc = H.plan(n_units, [&](long r) { return r - row_begin; }, rows))) return rc;
     // rows a slab owns: the workspace holds them and their T - 1 neighbours
-    const long cap_rows = (long)std::min<u64>(correlate_slab_bytes() / (4 * (u64)n_cols), (u64)1 << 40);
+    const long cap_rows = (long)std::min<u64>(env_bytes("MTS_CORRELATE_SLAB_BYTES", CORRELATE_SLAB_BYTES) / (4 * (u64)n_cols), (u64)1 << 40);
     const long own = std::min(n_units, std::max(1l, cap_rows - (n_tau - 1)));
     // ---- workspace: taps, columns, segment tables, templates (group-major: row (g / 4 * T + tau) * 4 + c holds K[., tau, g + c], zeros
     // past n_cols and n_out), the filtered slab, the output
     const int n4 = (int)align_up((u64)n_cols, 4), kp = (int)align_up((u64)n_out, CORRELATE_PAD);
     const u64 tpl_items = (u64)n4 * n_tau * kp, n_items = (u64)n_units * n_out;
     WsLayout &L = H.L;
-    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_seg = L.take(H.table_bytes()), o_tpl = L.take(4 * tpl_items),
-                 o_y = L.take(4 * (u64)(own + n_tau - 1) * n_cols), o_out = L.take_out(4 * n_items);
+    ZStage F(Z, L);
+    const size_t o_seg = L.take(H.table_bytes()), o_tpl = L.take(4 * tpl_items), o_y = L.take(4 * (u64)(own + n_tau - 1) * n_cols),
+                 o_out = L.take_out(4 * n_items);
+    const std::vector<float> h_tpl = repack_templates(templates, n_out, n_tau, n_cols, kp);
+    StreamGuard G{st};
     if ((rc = H.place(E, st, E.cor, o_seg))) return rc;
     u8 *ws = E.cor.as<u8>();
-    std::vector<float> h_taps(n_taps);
-    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
-    const std::vector<float> h_tpl = repack_templates(templates, n_out, n_tau, n_cols, kp);
-    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
-    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    if ((rc = F.upload(st, ws))) return rc;
     MTS_HIP(hipMemcpyAsync(ws + o_tpl, h_tpl.data(), 4 * (size_t)tpl_items, hipMemcpyHostToDevice, st));
     float *d_out = L.out(ws, o_out, out);
     float *d_y = (float *)(ws + o_y);
@@ -950,19 +1019,14 @@ static int correlate_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb
         int r = MTS_OK;
         for (long s0 = p0; !r && s0 < p1; s0 += own) {
             const long s1 = std::min(p1, s0 + own), a = std::max(vb, s0 - before), b = std::max(a, std::min(ve, s1 + after - 1));
-            // y[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k
-            if (b > a) r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half,
-                                           a, b, Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
-            if (!r && reference && b > a) r = launch_row_median(st, d_y, b - a, n_cols);
+            if (b > a) r = F.filter(st, T, Sg, a, b, d_y);
             if (!r) r = launch_correlate(st, d_y, a, b - a, n_cols, vb, ve, (const float *)(ws + o_tpl), kp, n_tau, before, n_out, s0, s1,
                                          d_out + (u64)(s0 - row_begin) * n_out);
         }
         return r;
     });
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps and h_tpl have been read before they go)
-    if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, 4 * n_items, hipMemcpyDeviceToHost, st));
-    MTS_HIP(hipStreamSynchronize(st));
-    return MTS_OK;
+    if (rc) return rc;
+    return dense_tail(G, out_on_host, out, d_out, n_items);
 }
 
 // ---- subtracted events (mts_residual, mts_match_residual and their device variants) ---------------------------------------------
@@ -1018,37 +1082,20 @@ struct SubEvents {
 // the same chain over the same events.
 static const u64 RESIDUAL_SLAB_BYTES = 256ull << 20;
 
-static u64 residual_slab_bytes()
-{
-    const char *e = getenv("MTS_RESIDUAL_SLAB_BYTES");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (u64)v : RESIDUAL_SLAB_BYTES;
-}
-
-static int residual_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
-                        int n_cols, const int *cols, int reference, int before, int n_tau, int n_out, const float *templates, long n_sub,
-                        const long *sub_row, const int *sub_tpl, const float *sub_amp, float *out, bool out_on_host, int *status)
+static int residual_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long row_begin, long row_end, int before, int n_tau,
+                        int n_out, const float *templates, long n_sub, const long *sub_row, const int *sub_tpl, const float *sub_amp, float *out,
+                        bool out_on_host, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols, n_taps = Z.n_taps;
     int rc;
-    if (nc <= 0 || T.n_chunks < 0) { set_error("residual: n_channels or n_chunks invalid"); return MTS_E_ARG; }
-    if (n_cols < 1 || n_cols > MTS_CORRELATE_MAX_COLS || !cols) { set_error("residual: %d columns (1 .. %d)", n_cols, MTS_CORRELATE_MAX_COLS); return MTS_E_ARG; }
-    if ((rc = check_taps("residual", n_taps, taps))) return rc;
-    if (reference < 0 || reference > 1) { set_error("residual: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
-    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("residual: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
-    if (n_tau < 1 || n_tau > MTS_CORRELATE_MAX_T) { set_error("residual: templates of %d rows (1 .. %d)", n_tau, MTS_CORRELATE_MAX_T); return MTS_E_ARG; }
-    if (before < 0 || before > n_tau) { set_error("residual: before %d (0 .. %d)", before, n_tau); return MTS_E_ARG; }
-    if (n_out < 1 || n_out > MTS_CORRELATE_MAX_OUT || !templates) { set_error("residual: %d templates (1 .. %d)", n_out, MTS_CORRELATE_MAX_OUT); return MTS_E_ARG; }
-    const long per = (long)n_tau * n_cols;
-    for (long e = 0; e < (long)n_out * per; e++)
-        if (!std::isfinite(templates[e])) { set_error("residual: template entry (%ld, %ld, %ld) is not finite", e / per, e % per / n_cols, e % n_cols); return MTS_E_ARG; }
-    if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve || row_end - row_begin > (1l << 40)) {
-        set_error("residual: rows invalid"); return MTS_E_ARG;
-    }
+    if ((rc = check_zargs(T, Z, MTS_CORRELATE_MAX_COLS))) return rc;
+    if ((rc = check_templates("residual", n_cols, before, n_tau, n_out, templates))) return rc;
+    if (row_begin < vb || row_end < row_begin || row_end > ve || row_end - row_begin > (1l << 40)) { set_error("residual: rows invalid"); return MTS_E_ARG; }
     if ((rc = check_sub_events("residual", n_sub, sub_row, sub_tpl, sub_amp, vb, ve, n_out))) return rc;
     if (row_end > row_begin && !out) { set_error("residual: no output buffer"); return MTS_E_ARG; }
-    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_columns(Z.cols, n_cols, T.nc))) return rc;
     if ((rc = check_chunk_table(true, T))) return rc;
     const long half = (n_taps - 1) / 2, n_units = row_end - row_begin;
     // the rows that the rows [u0, u1) read: their filter support ∩ valid range
@@ -1064,21 +1111,21 @@ static int residual_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb,
     HaloFeed H(T, out_on_host);
     if ((rc = H.plan(n_units, [&](long r) { return r - row_begin; }, rows))) return rc;
     // rows a slab owns: the workspace holds them and nothing else
-    const long own = std::min(n_units, std::max(1l, (long)std::min<u64>(residual_slab_bytes() / (4 * (u64)n_cols), (u64)1 << 40)));
+    const u64 cap_rows = std::min<u64>(env_bytes("MTS_RESIDUAL_SLAB_BYTES", RESIDUAL_SLAB_BYTES) / (4 * (u64)n_cols), (u64)1 << 40);
+    const long own = std::min(n_units, std::max(1l, (long)cap_rows));
     // ---- workspace: taps, columns, segment tables, the events, the plain templates, the filtered slab, the output
-    const u64 tpl_items = (u64)n_out * per, n_items = (u64)n_units * n_cols;
+    const u64 tpl_items = (u64)n_out * n_tau * n_cols, n_items = (u64)n_units * n_cols;
     WsLayout &L = H.L;
+    ZStage F(Z, L);
+    const size_t o_seg = L.take(H.table_bytes());
     SubEvents SE;
-    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_seg = L.take(H.table_bytes());
     SE.take(L, n_sub, tpl_items);
     const size_t o_y = L.take(4 * (u64)own * n_cols), o_out = L.take_out(4 * n_items);
+    StreamGuard G{st};
     if ((rc = H.place(E, st, E.res, o_seg))) return rc;
     u8 *ws = E.res.as<u8>();
-    std::vector<float> h_taps(n_taps);
-    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
-    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
-    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
-    if ((rc = SE.upload(st, ws, sub_row, sub_tpl, sub_amp, templates, tpl_items))) { (void)hipStreamSynchronize(st); return rc; }
+    if ((rc = F.upload(st, ws))) return rc;
+    if ((rc = SE.upload(st, ws, sub_row, sub_tpl, sub_amp, templates, tpl_items))) return rc;
     float *d_out = L.out(ws, o_out, out);
     float *d_y = (float *)(ws + o_y);
     rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
@@ -1086,19 +1133,14 @@ static int residual_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb,
         int r = MTS_OK;
         for (long s0 = p0; !r && s0 < p1; s0 += own) {
             const long s1 = std::min(p1, s0 + own);
-            // y[t] for t in [s0, s1): output k = t of a decimation by 1 whose newest row is half + k
-            r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half, s0, s1,
-                                Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
-            if (!r && reference) r = launch_row_median(st, d_y, s1 - s0, n_cols);
+            r = F.filter(st, T, Sg, s0, s1, d_y);
             if (!r) r = launch_subtract(st, d_y, s0, s1 - s0, n_cols, SE.d_row, SE.d_tpl, SE.d_namp, SE.n, SE.d_plain, n_tau, before,
                                         d_out + (u64)(s0 - row_begin) * n_cols);
         }
         return r;
     });
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps and the events have been read before they go)
-    if (out_on_host) MTS_HIP(hipMemcpyAsync(out, d_out, 4 * n_items, hipMemcpyDeviceToHost, st));
-    MTS_HIP(hipStreamSynchronize(st));
-    return MTS_OK;
+    if (rc) return rc;
+    return dense_tail(G, out_on_host, out, d_out, n_items);
 }
 
 // ---- template events (mts_match_templates, mts_dev_match_templates) ------------------------------------------------------------
@@ -1114,41 +1156,26 @@ static int residual_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb,
 static const u64 TMATCH_SLAB_BYTES = 256ull << 20;
 static const long TMATCH_SLAB_MAX_ROWS = 1l << 22;                  // (bounds the row maxima and the bitmap of a call with few templates)
 
-static u64 tmatch_slab_bytes()
-{
-    const char *e = getenv("MTS_TMATCH_SLAB_BYTES");
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (u64)v : TMATCH_SLAB_BYTES;
-}
-
-static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, long ve, long row_begin, long row_end, int n_taps, const double *taps,
-                      int n_cols, const int *cols, int reference, int before, int n_tau, int n_out, const float *templates, const float *threshold,
-                      int R, long max_events, long *out_row, int *out_tpl, float *out_score, bool out_on_host, long *n_events, int *status,
-                      long n_sub = 0, const long *sub_row = nullptr, const int *sub_tpl = nullptr, const float *sub_amp = nullptr)
+static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long row_begin, long row_end, int before, int n_tau, int n_out,
+                      const float *templates, const float *threshold, int R, long max_events, long *out_row, int *out_tpl, float *out_score,
+                      bool out_on_host, long *n_events, int *status, long n_sub = 0, const long *sub_row = nullptr, const int *sub_tpl = nullptr,
+                      const float *sub_amp = nullptr)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
-    const int nc = T.nc, sz = T.sz, flags = T.flags;
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols, n_taps = Z.n_taps;
     int rc;
-    if (nc <= 0 || T.n_chunks < 0) { set_error("match_templates: n_channels or n_chunks invalid"); return MTS_E_ARG; }
-    if (n_cols < 1 || n_cols > MTS_CORRELATE_MAX_COLS || !cols) { set_error("match_templates: %d columns (1 .. %d)", n_cols, MTS_CORRELATE_MAX_COLS); return MTS_E_ARG; }
-    if ((rc = check_taps("match_templates", n_taps, taps))) return rc;
-    if (reference < 0 || reference > 1) { set_error("match_templates: reference %d (0 none, 1 median)", reference); return MTS_E_ARG; }
-    if (reference && n_cols > MTS_DETECT_MAX_REF_COLS) { set_error("match_templates: a median reference over %d columns (<= %d)", n_cols, MTS_DETECT_MAX_REF_COLS); return MTS_E_ARG; }
-    if (n_tau < 1 || n_tau > MTS_CORRELATE_MAX_T) { set_error("match_templates: templates of %d rows (1 .. %d)", n_tau, MTS_CORRELATE_MAX_T); return MTS_E_ARG; }
-    if (before < 0 || before > n_tau) { set_error("match_templates: before %d (0 .. %d)", before, n_tau); return MTS_E_ARG; }
-    if (n_out < 1 || n_out > MTS_CORRELATE_MAX_OUT || !templates) { set_error("match_templates: %d templates (1 .. %d)", n_out, MTS_CORRELATE_MAX_OUT); return MTS_E_ARG; }
-    const long per = (long)n_tau * n_cols;
-    for (long e = 0; e < (long)n_out * per; e++)
-        if (!std::isfinite(templates[e])) { set_error("match_templates: template entry (%ld, %ld, %ld) is not finite", e / per, e % per / n_cols, e % n_cols); return MTS_E_ARG; }
+    if ((rc = check_zargs(T, Z, MTS_CORRELATE_MAX_COLS))) return rc;
+    if ((rc = check_templates("match_templates", n_cols, before, n_tau, n_out, templates))) return rc;
     if (!threshold) { set_error("match_templates: no thresholds"); return MTS_E_ARG; }
     for (int k = 0; k < n_out; k++)
         if (!std::isfinite(threshold[k])) { set_error("match_templates: threshold %d is not finite", k); return MTS_E_ARG; }
     if (R < 0 || R > MTS_TMATCH_MAX_EXCLUDE) { set_error("match_templates: exclude_rows %d (0 .. %d)", R, MTS_TMATCH_MAX_EXCLUDE); return MTS_E_ARG; }
-    if (vb < 0 || ve < vb || ve > (1l << 60) || row_begin < vb || row_end < row_begin || row_end > ve) { set_error("match_templates: rows invalid"); return MTS_E_ARG; }
+    if (row_begin < vb || row_end < row_begin || row_end > ve) { set_error("match_templates: rows invalid"); return MTS_E_ARG; }
     if (max_events < 0 || max_events > (1l << 40) || !n_events) { set_error("match_templates: max_events invalid or no n_events"); return MTS_E_ARG; }
     if (max_events && (!out_row || !out_tpl || !out_score)) { set_error("match_templates: no output buffers"); return MTS_E_ARG; }
     if ((rc = check_sub_events("match_templates", n_sub, sub_row, sub_tpl, sub_amp, vb, ve, n_out))) return rc;
-    if ((rc = check_columns(cols, n_cols, nc))) return rc;
+    if ((rc = check_columns(Z.cols, n_cols, T.nc))) return rc;
     if ((rc = check_chunk_table(true, T))) return rc;
     const long half = (n_taps - 1) / 2, n_units = row_end - row_begin, after = n_tau - before;
     // the rows that the events of rows [u0, u1) read: ((rows + R either side) - before .. + after - 1)'s support ∩ valid range
@@ -1165,69 +1192,55 @@ static int tmatch_run(Engine &E, hipStream_t st, const ChunkTable &T, long vb, l
     HaloFeed H(T, out_on_host);
     if ((rc = H.plan(n_units, [&](long r) { return r - row_begin; }, rows))) return rc;
     // rows a slab owns: the z slab holds them, R either side and their T - 1 neighbours; the score slab them and R either side (reduce_plan.h)
-    const TmatchSlabs SL(n_units, R, before, n_tau, vb, ve, n_cols, n_out, tmatch_slab_bytes(), TMATCH_SLAB_MAX_ROWS);
+    const TmatchSlabs SL(n_units, R, before, n_tau, vb, ve, n_cols, n_out, env_bytes("MTS_TMATCH_SLAB_BYTES", TMATCH_SLAB_BYTES), TMATCH_SLAB_MAX_ROWS);
     const long own = SL.own, sc_rows = SL.sc_rows, z_rows = SL.z_rows;
     const long max_words = tmatch_bitmap_words(own), max_blocks = detect_blocks(max_words);
     // ---- workspace
     const int n4 = (int)align_up((u64)n_cols, 4), kp = (int)align_up((u64)n_out, CORRELATE_PAD);
-    const u64 tpl_items = (u64)n4 * n_tau * kp;
+    const u64 tpl_items = (u64)n4 * n_tau * kp, plain_items = (u64)n_out * n_tau * n_cols;
     WsLayout &L = H.L;
-    const size_t o_taps = L.take(4 * (u64)n_taps), o_cols = L.take(4 * (u64)n_cols), o_thr = L.take(4 * (u64)n_out), o_seg = L.take(H.table_bytes()),
-                 o_total = L.take(8), o_tpl = L.take(4 * tpl_items), o_y = L.take(4 * (u64)z_rows * n_cols), o_sc = L.take(4 * (u64)sc_rows * n_out),
+    ZStage F(Z, L);
+    const size_t o_thr = L.take(4 * (u64)n_out), o_seg = L.take(H.table_bytes());
+    EventTail EV(L);
+    const size_t o_tpl = L.take(4 * tpl_items), o_y = L.take(4 * (u64)z_rows * n_cols), o_sc = L.take(4 * (u64)sc_rows * n_out),
                  o_best = L.take(4 * (u64)sc_rows), o_arg = L.take(4 * (u64)sc_rows), o_bits = L.take(8 * (u64)max_words),
                  o_cnt = L.take(4 * (u64)max_blocks), o_offs = L.take(8 * (u64)max_blocks), o_row = L.take_out(8 * (u64)max_events),
                  o_k = L.take_out(4 * (u64)max_events), o_val = L.take_out(4 * (u64)max_events);
     SubEvents SE;
-    SE.take(L, n_sub, (u64)n_out * per);
+    SE.take(L, n_sub, plain_items);
+    const std::vector<float> h_tpl = repack_templates(templates, n_out, n_tau, n_cols, kp);
+    StreamGuard G{st};
     if ((rc = H.place(E, st, E.tm, o_seg))) return rc;
     u8 *ws = E.tm.as<u8>();
-    std::vector<float> h_taps(n_taps);
-    for (int j = 0; j < n_taps; j++) h_taps[j] = (float)taps[j];
-    const std::vector<float> h_tpl = repack_templates(templates, n_out, n_tau, n_cols, kp);
-    MTS_HIP(hipMemcpyAsync(ws + o_taps, h_taps.data(), 4 * (size_t)n_taps, hipMemcpyHostToDevice, st));
-    MTS_HIP(hipMemcpyAsync(ws + o_cols, cols, 4 * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    if ((rc = F.upload(st, ws))) return rc;
     MTS_HIP(hipMemcpyAsync(ws + o_thr, threshold, 4 * (size_t)n_out, hipMemcpyHostToDevice, st));
     MTS_HIP(hipMemcpyAsync(ws + o_tpl, h_tpl.data(), 4 * (size_t)tpl_items, hipMemcpyHostToDevice, st));
-    MTS_HIP(hipMemsetAsync(ws + o_total, 0, 8, st));
-    if ((rc = SE.upload(st, ws, sub_row, sub_tpl, sub_amp, templates, (u64)n_out * per))) { (void)hipStreamSynchronize(st); return rc; }
+    if ((rc = EV.begin(st, ws))) return rc;
+    if ((rc = SE.upload(st, ws, sub_row, sub_tpl, sub_amp, templates, plain_items))) return rc;
     long *d_row = L.out(ws, o_row, out_row);
     int *d_k = L.out(ws, o_k, out_tpl);
     float *d_val = L.out(ws, o_val, out_score);
     float *d_y = (float *)(ws + o_y), *d_sc = (float *)(ws + o_sc), *d_best = (float *)(ws + o_best);
     int *d_arg = (int *)(ws + o_arg);
-    u64 *d_bits = (u64 *)(ws + o_bits), *d_total = (u64 *)(ws + o_total);
+    u64 *d_bits = (u64 *)(ws + o_bits);
     rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
         const long p0 = row_begin + Pc.u0, p1 = row_begin + Pc.u1;
         int r = MTS_OK;
         for (long s0 = p0; !r && s0 < p1; s0 += own) {
             const TmatchSlab S = SL.at(s0, p1);
             const long s1 = S.s1, sa = S.sa, sb = S.sb, a = S.a, b = S.b;
-            // y[t] for t in [a, b): output k = t of a decimation by 1 whose newest row is half + k
-            if (b > a) r = launch_decimate(st, sz, flags, 4, Sg.base, Sg.row0, Sg.ns, nc, (const int *)(ws + o_cols), n_cols, ws + o_taps, n_taps, 1, half,
-                                           a, b, Sg.ns ? vb : 0, Sg.ns ? ve : 0, d_y);
-            if (!r && reference && b > a) r = launch_row_median(st, d_y, b - a, n_cols);
+            if (b > a) r = F.filter(st, T, Sg, a, b, d_y);
             if (!r && SE.n && b > a) r = launch_subtract(st, d_y, a, b - a, n_cols, SE.d_row, SE.d_tpl, SE.d_namp, SE.n, SE.d_plain, n_tau, before, d_y);
             if (!r) r = launch_correlate(st, d_y, a, b - a, n_cols, vb, ve, (const float *)(ws + o_tpl), kp, n_tau, before, n_out, sa, sb, d_sc);
             if (!r) r = launch_tmatch_best(st, d_sc, sb - sa, n_out, d_best, d_arg);
             if (!r) r = launch_tmatch_mask(st, d_best, d_arg, sa, sb - sa, (const float *)(ws + o_thr), R, s0, s1, d_bits);
-            if (!r) r = launch_tmatch_emit(st, d_bits, tmatch_bitmap_words(s1 - s0), (u32 *)(ws + o_cnt), (u64 *)(ws + o_offs), d_total, d_best, d_arg,
+            if (!r) r = launch_tmatch_emit(st, d_bits, tmatch_bitmap_words(s1 - s0), (u32 *)(ws + o_cnt), (u64 *)(ws + o_offs), EV.d_total, d_best, d_arg,
                                            sa, s0, max_events, d_row, d_k, d_val);
         }
         return r;
     });
-    if (rc) { (void)hipStreamSynchronize(st); return rc; }   // (h_taps and h_tpl have been read before they go)
-    u64 total = 0;
-    MTS_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
-    MTS_HIP(hipStreamSynchronize(st));
-    *n_events = (long)total;
-    const size_t n_w = (size_t)std::min<u64>(total, (u64)max_events);
-    if (out_on_host && n_w) {
-        MTS_HIP(hipMemcpyAsync(out_row, d_row, 8 * n_w, hipMemcpyDeviceToHost, st));
-        MTS_HIP(hipMemcpyAsync(out_tpl, d_k, 4 * n_w, hipMemcpyDeviceToHost, st));
-        MTS_HIP(hipMemcpyAsync(out_score, d_val, 4 * n_w, hipMemcpyDeviceToHost, st));
-        MTS_HIP(hipStreamSynchronize(st));
-    }
-    return MTS_OK;
+    if (rc) return rc;
+    return EV.finish(G, max_events, out_on_host, n_events, out_row, d_row, out_tpl, d_k, out_score, d_val);
 }
 
 // ---- Welch PSD (mts_welch, mts_dev_welch) ------------------------------------------------------------------------------------
@@ -1463,6 +1476,8 @@ static int gram_run(Engine &E, hipStream_t st, const ChunkTable &T, long range_b
 #define DEV_ENTRY(call)                                                                                                                      \
     reduce_entry(device, 0, dev_table(d_cdata, c_offsets, c_lengths, chunk_row0, n_rows, n_chunks, n_channels, itemsize, flags, chunk_status), \
               [&](Engine &E, const ChunkTable &T) { return call; })
+// (so have the filter arguments in every entry of the z family)
+#define Z_ARGS(op) ZArgs{op, valid_begin, valid_end, n_taps, taps, n_cols, cols, reference}
 
 extern "C" {
 
@@ -1544,8 +1559,8 @@ int mts_detect(int device, long cache_id, int n_chunks, const long *chunk_keys, 
                const float *threshold, int sign, int reference, int exclude_rows, int exclude_cols, long max_events, long *out_row,
                int *out_pos, float *out_amp, long *n_events, int *chunk_status)
 {
-    return HOST_ENTRY(detect_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, threshold, sign, reference,
-                      exclude_rows, exclude_cols, max_events, out_row, out_pos, out_amp, true, n_events, chunk_status));
+    return HOST_ENTRY(detect_run(E, nullptr, T, Z_ARGS("detect"), row_begin, row_end, threshold, sign, exclude_rows, exclude_cols, max_events,
+                      out_row, out_pos, out_amp, true, n_events, chunk_status));
 }
 
 int mts_dev_detect(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
@@ -1554,8 +1569,8 @@ int mts_dev_detect(int device, void *stream, const unsigned char *d_cdata, const
                    const float *threshold, int sign, int reference, int exclude_rows, int exclude_cols, long max_events, long *d_row,
                    int *d_pos, float *d_amp, long *n_events, int *chunk_status)
 {
-    return DEV_ENTRY(detect_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, threshold, sign,
-                     reference, exclude_rows, exclude_cols, max_events, d_row, d_pos, d_amp, false, n_events, chunk_status));
+    return DEV_ENTRY(detect_run(E, (hipStream_t)stream, T, Z_ARGS("detect"), row_begin, row_end, threshold, sign, exclude_rows, exclude_cols,
+                     max_events, d_row, d_pos, d_amp, false, n_events, chunk_status));
 }
 
 int mts_waveforms(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
@@ -1564,8 +1579,8 @@ int mts_waveforms(int device, long cache_id, int n_chunks, const long *chunk_key
                   const long *ev_row, const int *ev_col0, int before, int after, int width, float *out_wave, float *out_min, int *out_argmin,
                   float *out_max, int *out_argmax, int *chunk_status)
 {
-    return HOST_ENTRY(waveforms_run(E, nullptr, T, valid_begin, valid_end, n_taps, taps, n_cols, cols, reference, n_events, ev_row, ev_col0, before,
-                      after, width, out_wave, out_min, out_argmin, out_max, out_argmax, true, chunk_status));
+    return HOST_ENTRY(waveforms_run(E, nullptr, T, Z_ARGS("waveforms"), n_events, ev_row, ev_col0, before, after, width, out_wave, out_min,
+                      out_argmin, out_max, out_argmax, true, chunk_status));
 }
 
 int mts_dev_waveforms(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
@@ -1574,8 +1589,8 @@ int mts_dev_waveforms(int device, void *stream, const unsigned char *d_cdata, co
                       const long *ev_row, const int *ev_col0, int before, int after, int width, float *d_wave, float *d_min, int *d_argmin,
                       float *d_max, int *d_argmax, int *chunk_status)
 {
-    return DEV_ENTRY(waveforms_run(E, (hipStream_t)stream, T, valid_begin, valid_end, n_taps, taps, n_cols, cols, reference, n_events, ev_row,
-                     ev_col0, before, after, width, d_wave, d_min, d_argmin, d_max, d_argmax, false, chunk_status));
+    return DEV_ENTRY(waveforms_run(E, (hipStream_t)stream, T, Z_ARGS("waveforms"), n_events, ev_row, ev_col0, before, after, width, d_wave, d_min,
+                     d_argmin, d_max, d_argmax, false, chunk_status));
 }
 
 int mts_waveforms_last_plan(int device, long *out)
@@ -1594,8 +1609,7 @@ int mts_correlate(int device, long cache_id, int n_chunks, const long *chunk_key
                   long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
                   int before, int T_, int n_out, const float *templates, float *out, int *chunk_status)
 {
-    return HOST_ENTRY(correlate_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before, T_,
-                      n_out, templates, out, true, chunk_status));
+    return HOST_ENTRY(correlate_run(E, nullptr, T, Z_ARGS("correlate"), row_begin, row_end, before, T_, n_out, templates, out, true, chunk_status));
 }
 
 int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
@@ -1603,8 +1617,8 @@ int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, co
                       long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
                       int before, int T_, int n_out, const float *templates, float *d_out, int *chunk_status)
 {
-    return DEV_ENTRY(correlate_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference,
-                     before, T_, n_out, templates, d_out, false, chunk_status));
+    return DEV_ENTRY(correlate_run(E, (hipStream_t)stream, T, Z_ARGS("correlate"), row_begin, row_end, before, T_, n_out, templates, d_out, false,
+                     chunk_status));
 }
 
 int mts_match_templates(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
@@ -1614,8 +1628,8 @@ int mts_match_templates(int device, long cache_id, int n_chunks, const long *chu
                         int exclude_rows, long max_events, long *out_row, int *out_template, float *out_score, long *n_events,
                         int *chunk_status)
 {
-    return HOST_ENTRY(tmatch_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before, T_, n_out,
-                      templates, threshold, exclude_rows, max_events, out_row, out_template, out_score, true, n_events, chunk_status));
+    return HOST_ENTRY(tmatch_run(E, nullptr, T, Z_ARGS("match_templates"), row_begin, row_end, before, T_, n_out, templates, threshold, exclude_rows,
+                      max_events, out_row, out_template, out_score, true, n_events, chunk_status));
 }
 
 int mts_dev_match_templates(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
@@ -1625,8 +1639,8 @@ int mts_dev_match_templates(int device, void *stream, const unsigned char *d_cda
                             int exclude_rows, long max_events, long *d_row, int *d_template, float *d_score, long *n_events,
                             int *chunk_status)
 {
-    return DEV_ENTRY(tmatch_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before,
-                     T_, n_out, templates, threshold, exclude_rows, max_events, d_row, d_template, d_score, false, n_events, chunk_status));
+    return DEV_ENTRY(tmatch_run(E, (hipStream_t)stream, T, Z_ARGS("match_templates"), row_begin, row_end, before, T_, n_out, templates, threshold,
+                     exclude_rows, max_events, d_row, d_template, d_score, false, n_events, chunk_status));
 }
 
 int mts_residual(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
@@ -1635,8 +1649,8 @@ int mts_residual(int device, long cache_id, int n_chunks, const long *chunk_keys
                  int before, int T_, int n_out, const float *templates, long n_sub, const long *sub_row, const int *sub_tpl, const float *sub_amp,
                  float *out, int *chunk_status)
 {
-    return HOST_ENTRY(residual_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before, T_,
-                      n_out, templates, n_sub, sub_row, sub_tpl, sub_amp, out, true, chunk_status));
+    return HOST_ENTRY(residual_run(E, nullptr, T, Z_ARGS("residual"), row_begin, row_end, before, T_, n_out, templates, n_sub, sub_row, sub_tpl,
+                      sub_amp, out, true, chunk_status));
 }
 
 int mts_dev_residual(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
@@ -1645,8 +1659,8 @@ int mts_dev_residual(int device, void *stream, const unsigned char *d_cdata, con
                      int before, int T_, int n_out, const float *templates, long n_sub, const long *sub_row, const int *sub_tpl,
                      const float *sub_amp, float *d_out, int *chunk_status)
 {
-    return DEV_ENTRY(residual_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference,
-                     before, T_, n_out, templates, n_sub, sub_row, sub_tpl, sub_amp, d_out, false, chunk_status));
+    return DEV_ENTRY(residual_run(E, (hipStream_t)stream, T, Z_ARGS("residual"), row_begin, row_end, before, T_, n_out, templates, n_sub, sub_row,
+                     sub_tpl, sub_amp, d_out, false, chunk_status));
 }
 
 int mts_match_residual(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
@@ -1656,9 +1670,8 @@ int mts_match_residual(int device, long cache_id, int n_chunks, const long *chun
                        int exclude_rows, long max_events, long n_sub, const long *sub_row, const int *sub_tpl, const float *sub_amp,
                        long *out_row, int *out_template, float *out_score, long *n_events, int *chunk_status)
 {
-    return HOST_ENTRY(tmatch_run(E, nullptr, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before, T_, n_out,
-                      templates, threshold, exclude_rows, max_events, out_row, out_template, out_score, true, n_events, chunk_status, n_sub,
-                      sub_row, sub_tpl, sub_amp));
+    return HOST_ENTRY(tmatch_run(E, nullptr, T, Z_ARGS("match_templates"), row_begin, row_end, before, T_, n_out, templates, threshold, exclude_rows,
+                      max_events, out_row, out_template, out_score, true, n_events, chunk_status, n_sub, sub_row, sub_tpl, sub_amp));
 }
 
 int mts_dev_match_residual(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
@@ -1668,9 +1681,8 @@ int mts_dev_match_residual(int device, void *stream, const unsigned char *d_cdat
                            int exclude_rows, long max_events, long n_sub, const long *sub_row, const int *sub_tpl, const float *sub_amp,
                            long *d_row, int *d_template, float *d_score, long *n_events, int *chunk_status)
 {
-    return DEV_ENTRY(tmatch_run(E, (hipStream_t)stream, T, valid_begin, valid_end, row_begin, row_end, n_taps, taps, n_cols, cols, reference, before,
-                     T_, n_out, templates, threshold, exclude_rows, max_events, d_row, d_template, d_score, false, n_events, chunk_status, n_sub,
-                     sub_row, sub_tpl, sub_amp));
+    return DEV_ENTRY(tmatch_run(E, (hipStream_t)stream, T, Z_ARGS("match_templates"), row_begin, row_end, before, T_, n_out, templates, threshold,
+                     exclude_rows, max_events, d_row, d_template, d_score, false, n_events, chunk_status, n_sub, sub_row, sub_tpl, sub_amp));
 }
 
 int mts_welch(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,

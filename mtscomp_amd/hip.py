@@ -416,6 +416,48 @@ def _dev_fetch(out, at, arrays):
     return arrays
 
 
+# -- the tails of the two result kinds that detect, correlate, match_templates, residual and match_residual return.  `what` names the
+# entry, chunks is (head, n, status) of _host_chunks / _dev_chunks, mid the op's own arguments; the caller keeps what mid points at.
+_EVENT_DTYPES = (np.int64, np.int32, np.float32)        # row; position or template; amplitude or score
+
+
+def _host_events(what, chunks, mid, cap, n_ev):
+    """-> (status list, n_events, the first min(n_events, cap) events as three arrays)."""
+    head, n, status = chunks
+    res = [np.empty(cap, t) for t in _EVENT_DTYPES]
+    _check(getattr(lib(), what)(*head, *mid, *(_ptr(a) if cap else None for a in res), _lp(n_ev), _ip(status)), what)
+    k = min(int(n_ev[0]), cap)
+    return (_status(status, n), int(n_ev[0])) + tuple(a[:k] for a in res)
+
+
+def _dev_events(what, cbuf, chunks, mid, cap, n_ev, out, download):
+    """-> (status list, n_events, the three arrays or None, out)."""
+    head, n, status = chunks
+    out, ptrs, at = _dev_results(out, cbuf.device, [cap * np.dtype(t).itemsize for t in _EVENT_DTYPES])
+    _check(getattr(lib(), what)(*head, *mid, *ptrs, _lp(n_ev), _ip(status)), what)
+    res = None
+    if download:
+        res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _EVENT_DTYPES]))
+    return _status(status, n), int(n_ev[0]), res, out
+
+
+def _host_dense(what, chunks, mid, shape):
+    """-> (status list, the float32 result of `shape`)."""
+    head, n, status = chunks
+    out = np.empty(shape, np.float32)
+    _check(getattr(lib(), what)(*head, *mid, _ptr(out), _ip(status)), what)
+    return _status(status, n), out
+
+
+def _dev_dense(what, cbuf, chunks, mid, shape, out, download):
+    """-> (status list, the float32 result of `shape` or None, out)."""
+    head, n, status = chunks
+    out, ptrs, at = _dev_results(out, cbuf.device, [4 * shape[0] * shape[1]])
+    _check(getattr(lib(), what)(*head, *mid, *ptrs, _ip(status)), what)
+    res = _dev_fetch(out, at, [np.empty(shape, np.float32)])[0] if download else None
+    return _status(status, n), res, out
+
+
 # -- per-window statistics
 def stats_exact(dtype):
     """1- and 2-byte integers: the sum of squares is the exact uint64 sum (converted to float64 once, by the caller)."""
@@ -670,7 +712,6 @@ DETECT_MAX_EXCLUDE = 255
 DETECT_MAX_SPREAD = 32
 DETECT_MAX_REF_COLS = 1024
 DETECT_SIGNS = {'neg': 0, 'pos': 1, 'both': 2}
-_DETECT_DTYPES = (np.int64, np.int32, np.float32)       # row, pos, amp of an event
 
 
 def _det_args(valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign, reference, exclude_rows, exclude_cols, max_events):
@@ -688,13 +729,9 @@ def detect(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, f
     """mts_detect: the events of rows [row_begin, row_end) (include/mtscomp_hip.h) from the adjacent chunks `keys`.  sign 0 / 1 / 2,
     reference 0 / 1.  cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError
     E_MISS).  Returns (status list, n_events, row int64, pos int32, amp float32): the first min(n_events, max_events) events."""
-    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
     mid, cap, n_ev = _det_args(valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign, reference, exclude_rows, exclude_cols,
                                max_events)
-    res = [np.empty(cap, t) for t in _DETECT_DTYPES]
-    _check(lib().mts_detect(*head, *mid, *(_ptr(a) if cap else None for a in res), _lp(n_ev), _ip(status)), 'mts_detect')
-    k = min(int(n_ev[0]), cap)
-    return (_status(status, n), int(n_ev[0])) + tuple(a[:k] for a in res)
+    return _host_events('mts_detect', _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags), mid, cap, n_ev)
 
 
 def dev_detect(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign,
@@ -702,15 +739,9 @@ def dev_detect(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_b
     """mts_dev_detect on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the three event arrays (made when
     None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, n_events, (row, pos, amp) or None,
     out)."""
-    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
     mid, cap, n_ev = _det_args(valid_begin, valid_end, row_begin, row_end, taps, cols, threshold, sign, reference, exclude_rows, exclude_cols,
                                max_events)
-    out, ptrs, at = _dev_results(out, cbuf.device, [cap * np.dtype(t).itemsize for t in _DETECT_DTYPES])
-    _check(lib().mts_dev_detect(*head, *mid, *ptrs, _lp(n_ev), _ip(status)), 'mts_dev_detect')
-    res = None
-    if download:
-        res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _DETECT_DTYPES]))
-    return _status(status, n), int(n_ev[0]), res, out
+    return _dev_events('mts_dev_detect', cbuf, _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags), mid, cap, n_ev, out, download)
 
 
 # -- snippets around events and their extrema
@@ -795,28 +826,20 @@ def correlate(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype
     row_end) (include/mtscomp_hip.h) from the adjacent chunks `keys`.  reference 0 / 1.  cache_id 0: no cache, every chunk comes with
     its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, (row_end - row_begin, n_out)
     float32)."""
-    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
     mid, shape, _keep = _cor_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates)
-    out = np.empty(shape, np.float32)
-    _check(lib().mts_correlate(*head, *mid, _ptr(out), _ip(status)), 'mts_correlate')
-    return _status(status, n), out
+    return _host_dense('mts_correlate', _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags), mid, shape)
 
 
 def dev_correlate(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, reference,
                   before, templates, out=None, download=True):
     """mts_dev_correlate on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the scores (made when None;
     returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
-    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
     mid, shape, _keep = _cor_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates)
-    out, ptrs, at = _dev_results(out, cbuf.device, [4 * shape[0] * shape[1]])
-    _check(lib().mts_dev_correlate(*head, *mid, *ptrs, _ip(status)), 'mts_dev_correlate')
-    res = _dev_fetch(out, at, [np.empty(shape, np.float32)])[0] if download else None
-    return _status(status, n), res, out
+    return _dev_dense('mts_dev_correlate', cbuf, _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags), mid, shape, out, download)
 
 
 # -- template-matching events
 TMATCH_MAX_EXCLUDE = 255               # MTS_TMATCH_MAX_EXCLUDE
-_TMATCH_DTYPES = (np.int64, np.int32, np.float32)       # row, template, score of an event
 
 
 def _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows, max_events):
@@ -833,13 +856,10 @@ def match_templates(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels,
     when the rows read nothing of the recording).  templates (n_out, T, n_cols), threshold a number or one per template, reference 0 / 1.
     cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns
     (status list, n_events, row int64, template int32, score float32): the first min(n_events, max_events) events."""
-    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
     mid, cap, n_ev, _keep = _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows,
                                      max_events)
-    res = [np.empty(cap, t) for t in _TMATCH_DTYPES]
-    _check(lib().mts_match_templates(*head, *mid, *(_ptr(a) if cap else None for a in res), _lp(n_ev), _ip(status)), 'mts_match_templates')
-    k = min(int(n_ev[0]), cap)
-    return (_status(status, n), int(n_ev[0])) + tuple(a[:k] for a in res)
+    return _host_events('mts_match_templates', _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags), mid,
+                        cap, n_ev)
 
 
 def dev_match_templates(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, reference,
@@ -847,15 +867,10 @@ def dev_match_templates(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags
     """mts_dev_match_templates on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the three event arrays (made
     when None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, n_events, (row, template,
     score) or None, out)."""
-    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
     mid, cap, n_ev, _keep = _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows,
                                      max_events)
-    out, ptrs, at = _dev_results(out, cbuf.device, [cap * np.dtype(t).itemsize for t in _TMATCH_DTYPES])
-    _check(lib().mts_dev_match_templates(*head, *mid, *ptrs, _lp(n_ev), _ip(status)), 'mts_dev_match_templates')
-    res = None
-    if download:
-        res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _TMATCH_DTYPES]))
-    return _status(status, n), int(n_ev[0]), res, out
+    return _dev_events('mts_dev_match_templates', cbuf, _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags), mid, cap, n_ev, out,
+                       download)
 
 
 # -- template peeling: the filtered rows minus matched templates, and the template events of those rows
@@ -885,52 +900,37 @@ def residual(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype,
     template sub_tpl[e] laid with its row `before` on file row sub_row[e], for the events in ascending row order -- from the adjacent
     chunks `keys`.  templates (n_out, T, n_cols), reference 0 / 1.  cache_id 0: no cache, every chunk comes with its bytes; else chunks
     with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, (row_end - row_begin, n_cols) float32)."""
-    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
     mid, shape, _keep = _res_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, sub_row, sub_tpl, sub_amp)
-    out = np.empty(shape, np.float32)
-    _check(lib().mts_residual(*head, *mid, _ptr(out), _ip(status)), 'mts_residual')
-    return _status(status, n), out
+    return _host_dense('mts_residual', _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags), mid, shape)
 
 
 def dev_residual(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, reference,
                  before, templates, sub_row, sub_tpl, sub_amp, out=None, download=True):
     """mts_dev_residual on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the rows (made when None;
     returned so that a caller timing repeated calls can pass it again).  Returns (status list, numpy array or None, out)."""
-    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
     mid, shape, _keep = _res_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, sub_row, sub_tpl, sub_amp)
-    out, ptrs, at = _dev_results(out, cbuf.device, [4 * shape[0] * shape[1]])
-    _check(lib().mts_dev_residual(*head, *mid, *ptrs, _ip(status)), 'mts_dev_residual')
-    res = _dev_fetch(out, at, [np.empty(shape, np.float32)])[0] if download else None
-    return _status(status, n), res, out
+    return _dev_dense('mts_dev_residual', cbuf, _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags), mid, shape, out, download)
 
 
 def match_residual(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps,
                    cols, reference, before, templates, threshold, exclude_rows, max_events, sub_row, sub_tpl, sub_amp, device=0):
     """mts_match_residual: match_templates on z' -- the events (sub_row, sub_tpl, sub_amp), in ascending row order, subtracted from the
     filtered rows before they are scored (include/mtscomp_hip.h).  Arguments and result as match_templates."""
-    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
     mid, cap, n_ev, _keep = _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows,
                                      max_events)
     sub, _keep_sub = _sub_args(sub_row, sub_tpl, sub_amp)
-    res = [np.empty(cap, t) for t in _TMATCH_DTYPES]
-    _check(lib().mts_match_residual(*head, *mid, *sub, *(_ptr(a) if cap else None for a in res), _lp(n_ev), _ip(status)), 'mts_match_residual')
-    k = min(int(n_ev[0]), cap)
-    return (_status(status, n), int(n_ev[0])) + tuple(a[:k] for a in res)
+    return _host_events('mts_match_residual', _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags),
+                        mid + sub, cap, n_ev)
 
 
 def dev_match_residual(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, row_begin, row_end, taps, cols, reference,
                        before, templates, threshold, exclude_rows, max_events, sub_row, sub_tpl, sub_amp, out=None, download=True):
     """mts_dev_match_residual on a DevBuffer of compressed chunks (offsets into it); `out` and the result as dev_match_templates."""
-    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
     mid, cap, n_ev, _keep = _tm_args(valid_begin, valid_end, row_begin, row_end, taps, cols, reference, before, templates, threshold, exclude_rows,
                                      max_events)
     sub, _keep_sub = _sub_args(sub_row, sub_tpl, sub_amp)
-    out, ptrs, at = _dev_results(out, cbuf.device, [cap * np.dtype(t).itemsize for t in _TMATCH_DTYPES])
-    _check(lib().mts_dev_match_residual(*head, *mid, *sub, *ptrs, _lp(n_ev), _ip(status)), 'mts_dev_match_residual')
-    res = None
-    if download:
-        res = tuple(_dev_fetch(out, at, [np.empty(min(int(n_ev[0]), cap), t) for t in _TMATCH_DTYPES]))
-    return _status(status, n), int(n_ev[0]), res, out
+    return _dev_events('mts_dev_match_residual', cbuf, _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags), mid + sub, cap, n_ev,
+                       out, download)
 
 
 # -- Welch power spectral density

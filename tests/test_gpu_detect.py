@@ -15,6 +15,7 @@ from mtscomp_amd import api, hip
 from mtscomp_amd.synth import synth_int16
 from tests.codec_oracle import OracleCodec
 from tests.detect_oracle import SIGNS, detect_events, filtered, tied_events
+from tests.zfamily_errors import filter_errors, wide_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -329,6 +330,13 @@ def test_c_abi_argument_errors():
             rc, st, ne = call(dev=dev, **bad)
             assert rc == -1, bad                                       # MTS_E_ARG ...
             assert st == 99 and ne == -7, bad                          # ... before anything ran
+        # a shared argument, one bad at a time: the text is the one the library gave before the five ops shared their checks
+        for bad, text in filter_errors('detect') + wide_errors('detect'):
+            if 'cols' in bad:
+                bad = dict(bad, thr=[1.0] * len(bad['cols']))          # (a threshold per column)
+            rc, st, ne = call(dev=dev, **bad)
+            assert (rc, st, ne) == (-1, 99, -7), bad
+            assert hip.lib().mts_last_error().decode() == text, bad
     d_out.free()
     cbuf.free()
 

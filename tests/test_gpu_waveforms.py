@@ -18,6 +18,7 @@ from mtscomp_amd.synth import synth_int16
 from tests.codec_oracle import OracleCodec
 from tests.detect_oracle import detect_events
 from tests.waveforms_oracle import BASE_COUNTS, FILL, edge_counts, waveforms
+from tests.zfamily_errors import filter_errors, wide_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -402,16 +403,18 @@ def test_c_abi_arguments():
         assert (rc, st) == (0, 0) and (o[1] == 5).all()
         assert call(dev=dev, n_ev=0, events=False)[:2] == (0, 0)
         assert call(dev=dev, before=0, after=1, width=1)[:2] == (0, 0) and call(dev=dev, before=4096, after=0, width=1, wave=False)[:2] == (0, 0)
-        for bad in (dict(ev=(10, 9, 50)), dict(ev=(10, 10, 100)), dict(ev=(-1, 10, 50)), dict(vb=20), dict(ve=40), dict(vb=50, ve=20),
-                    dict(before=-1), dict(after=-1), dict(before=0, after=0), dict(before=4096, after=1), dict(before=2 ** 31 - 1, after=2),
-                    dict(width=0), dict(width=-3), dict(width=1025), dict(n_ev=-1), dict(n_ev=(1 << 40) + 1), dict(events=False),
-                    dict(ext=(0, 1, 1, 1)), dict(ext=(1, 0, 1, 1)), dict(ext=(1, 1, 0, 1)), dict(ext=(1, 1, 1, 0)), dict(ext=(0, 0, 0, 0)),
-                    dict(ref=2), dict(ref=-1), dict(ref=1, cols=[0] * 1025), dict(taps=()), dict(taps=(np.nan,)), dict(taps=(np.inf, 1.0)),
-                    dict(taps=np.ones(8193)), dict(cols=(0, 4)), dict(cols=(-1,)), dict(cols=()), dict(row0=10), dict(rows=50), dict(itemsize=3),
-                    dict(flags=hip.FLAG_FLOAT, itemsize=2)):
+        others = (dict(ev=(10, 9, 50)), dict(ev=(10, 10, 100)), dict(ev=(-1, 10, 50)), dict(vb=20), dict(ve=40),
+                  dict(before=-1), dict(after=-1), dict(before=0, after=0), dict(before=4096, after=1), dict(before=2 ** 31 - 1, after=2),
+                  dict(width=0), dict(width=-3), dict(width=1025), dict(n_ev=-1), dict(n_ev=(1 << 40) + 1), dict(events=False),
+                  dict(ext=(0, 1, 1, 1)), dict(ext=(1, 0, 1, 1)), dict(ext=(1, 1, 0, 1)), dict(ext=(1, 1, 1, 0)), dict(ext=(0, 0, 0, 0)),
+                  dict(taps=(np.inf, 1.0)), dict(cols=(0, 4)), dict(cols=(-1,)), dict(row0=10), dict(rows=50), dict(itemsize=3),
+                  dict(flags=hip.FLAG_FLOAT, itemsize=2))
+        # (a shared argument, one bad at a time: the text is the one the library gave before the five ops shared their checks)
+        for bad, text in [(b, None) for b in others] + filter_errors('waveforms', rows_too=False) + wide_errors('waveforms'):
             rc, st, o = call(dev=dev, **bad)
             assert rc == -1, bad                                       # MTS_E_ARG ...
             assert st == 99 and (dev or all((v == 5).all() for v in o)), bad       # ... before anything ran
-            assert hip.lib().mts_last_error(), bad
+            said = hip.lib().mts_last_error().decode()
+            assert said and text in (None, said), (bad, said)
     d_out.free()
     cbuf.free()
