@@ -34,14 +34,19 @@ static int compress_batch(Engine &E, hipStream_t st, const u8 *d_raw, bool raw_i
 {
     const LevelCfg cfg = LEVELS[level];
     // ---- plan ----
-    static const CompressDims dims = {hash_sort_ws_bytes, parse_marks_words, parse_cp_words(), sizeof(BlockRec), sizeof(ChunkOut), BLK_CODE_WORDS,
-                                      BLK_HDR_WORDS, MATCH_SINK_BYTES};
+    static const CompressDims dims = {hash_sort_ws_bytes, parse_marks_words, parse_cp_words(), sizeof(BlockRec), sizeof(ChunkOut), BLK_CODE_WORDS, BLK_HDR_WORDS, MATCH_SINK_BYTES};
     const CompressPlan P(bounds, n_chunks, (u64)nc * sz, raw_is_stream, slot_off, level, dims);
     if (P.error[0]) { set_error("%s", P.error); return MTS_E_ARG; }
     const std::vector<ChunkDesc> &cd = P.cd;
     const std::vector<TileDesc> &tiles = P.tiles;
     const u32 nseg = P.nseg, nblk = P.nblk, max_rows = P.max_rows, max_n = P.max_n, max_nseg = P.max_nseg;
     const size_t table_words = P.table_words;
+    // ---- environment (per batch, but for the flag print) ----
+    int force_ballot = getenv("MTS_SORT_INJECT_DISORDER") ? 2 : 0;      // (test hook: the first sort of the call is deliberately mis-ranked)
+    const char *be = getenv("MTS_FAST_LIST_BYTES");           // (tests: a tiny budget = many phases)
+    const u64 fast_list_budget = be ? strtoull(be, nullptr, 10) : (u64)8 << 30;
+    const bool debug_addr = getenv("MTS_DEBUG_ADDR") != nullptr;        // (tools/m5_addr_times.py: does the match stage's time follow where its buffers lie?)
+    static const bool debug_flags = getenv("MTS_DEBUG_FLAGS") != nullptr;      // (read once)
     // ---- workspace ----
     int rc;
     if (!raw_is_stream) { if ((rc = E.stream.ensure(P.stream_bytes))) return rc; }
@@ -62,19 +67,14 @@ static int compress_batch(Engine &E, hipStream_t st, const u8 *d_raw, bool raw_i
     ChunkDesc *d_chunks = (ChunkDesc *)(dp + P.o_chunks);
     TileDesc *d_tiles = (TileDesc *)(dp + P.o_tiles);
     ChunkOut *d_cout = (ChunkOut *)(dp + P.o_cout);
-    // per-segment arrays
+    // per-segment arrays, the flag words, block arrays: where the plan says
     u32 *sg = E.segbuf.as<u32>();
-    ParseBufs pb;
-    const size_t SN = (size_t)nseg + 64;
-    pb.entry = sg; pb.exit_a = sg + SN; pb.exit_b = sg + 2 * SN; pb.cnt = sg + 3 * SN; pb.tokbase = sg + 4 * SN;
-    pb.seg_chunk = sg + 5 * SN; pb.seg_start = sg + 6 * SN;
-    pb.cp = sg + 7 * SN;
-    pb.changed = (int *)(E.adler.as<u8>() + sizeof(u64) * 2 * n_chunks);
-    pb.marks = E.sort_a.as<u32>();
-    // block arrays
-    BlockRec *d_blocks = E.blk.as<BlockRec>();
-    u32 *d_blk_chunk = (u32 *)(d_blocks + nblk + 1);
-    u32 *d_blk_in_start = d_blk_chunk + nblk + 1;
+    u8 *ad = E.adler.as<u8>(), *bk = E.blk.as<u8>();
+    const ParseBufs pb = {sg + P.seg.entry, sg + P.seg.exit_a, sg + P.seg.exit_b, sg + P.seg.cnt, sg + P.seg.tokbase, sg + P.seg.cp, E.sort_a.as<u32>(),
+                          sg + P.seg.seg_chunk, sg + P.seg.seg_start, (int *)(ad + P.ad.changed)};
+    u32 *d_flags = (u32 *)(ad + P.ad.flags);                  // [0] bit 0: the match stage found a hash run out of position order
+    BlockRec *d_blocks = (BlockRec *)(bk + P.bk.blocks);
+    u32 *d_blk_chunk = (u32 *)(bk + P.bk.chunk), *d_blk_in_start = (u32 *)(bk + P.bk.in_start);
 
     // ---- upload ----
     MTS_HIP(hipMemcpyAsync(d_chunks, cd.data(), sizeof(ChunkDesc) * n_chunks, hipMemcpyHostToDevice, st));
@@ -113,7 +113,7 @@ static int compress_batch(Engine &E, hipStream_t st, const u8 *d_raw, bool raw_i
         d_stream = d_raw;
         for (int i = 0; i < n_chunks; i++) { so[i] = cd[i].stream_off; nn[i] = cd[i].n; }
         if ((rc = E.misc.ensure(P.misc))) return rc;
-        u64 *d_so = E.misc.as<u64>(); u32 *d_nn = (u32 *)(d_so + n_chunks);
+        u64 *d_so = (u64 *)(E.misc.as<u8>() + P.mi.so); u32 *d_nn = (u32 *)(E.misc.as<u8>() + P.mi.nn);
         MTS_HIP(hipMemcpyAsync(d_so, so.data(), 8 * (size_t)n_chunks, hipMemcpyHostToDevice, st));
         MTS_HIP(hipMemcpyAsync(d_nn, nn.data(), 4 * (size_t)n_chunks, hipMemcpyHostToDevice, st));
         if ((rc = launch_adler_stream(st, d_stream, d_so, d_nn, n_chunks, max_n, d_adler, nullptr, 0))) return rc;
@@ -124,9 +124,7 @@ static int compress_batch(Engine &E, hipStream_t st, const u8 *d_raw, bool raw_i
     E.t_mark(st, "delta_transpose");
     u32 *tmp_k = E.sort_a.as<u32>(), *srt_k = E.sort_b.as<u32>();
     u32 *d_tables = E.tables.as<u32>(), *d_quarter = d_tables + table_words;
-    u32 *d_flags = (u32 *)(pb.changed + 1);                   // [0] bit 0: the match stage found a hash run out of position order
     u32 *d_tokens = E.tokens.as<u32>();
-    int force_ballot = getenv("MTS_SORT_INJECT_DISORDER") ? 2 : 0;      // (test hook: the first sort of the call is deliberately mis-ranked)
     const bool fast = level < 4;                              // deflate_fast: no candidate tables, the walk itself searches (deflate.hip, section F)
     u32 *d_inv = (u32 *)d_tables;                             // levels 1..3: the inverse map lives where the other levels keep the candidate tables
     int fix_rounds = 0;                                       // parallel fix rounds of the parse that counted (they say where the exits are)
@@ -140,11 +138,9 @@ static int compress_batch(Engine &E, hipStream_t st, const u8 *d_raw, bool raw_i
             if ((rc = launch_inverse_map(st, d_stream, d_tiles, (int)tiles.size(), srt_k, d_inv, d_flags))) return rc;
             E.t_mark(st, "inverse_map");
             const u64 K = (u64)fast_list_rows(level);
-            const char *be = getenv("MTS_FAST_LIST_BYTES");      // (tests: a tiny budget = many phases)
-            const u64 budget = be ? strtoull(be, nullptr, 10) : (u64)8 << 30;
             // two list buffers: the lists of phase k + 1 are made on a second stream while phase k is walked (the walk keeps
             // one wave per chunk busy, the rest of the device is free)
-            const u64 W = CompressPlan::phase_width(budget, n_chunks, K, max_n);
+            const u64 W = CompressPlan::phase_width(fast_list_budget, n_chunks, K, max_n);
             if (max_n) {
                 const size_t list_words = (size_t)n_chunks * W * K;
                 if ((rc = E.fast_lists.ensure(2 * list_words * 4))) return rc;
@@ -169,7 +165,7 @@ static int compress_batch(Engine &E, hipStream_t st, const u8 *d_raw, bool raw_i
             MTS_HIP(hipStreamSynchronize(st));
             if (hflags[1] & 1) resort = true;
         } else {
-        if (getenv("MTS_DEBUG_ADDR"))                                 // (tools/m5_addr_times.py: does the match stage's time follow where its buffers lie?)
+        if (debug_addr)
             fprintf(stderr, "[addr] stream %p sorted %p tables %p quarter %p tiles %zu\n", (void *)d_stream, (void *)srt_k, (void *)d_tables, (void *)d_quarter, tiles.size());
         if ((rc = launch_match(st, d_stream, d_tiles, (int)tiles.size(), srt_k, d_tables, d_quarter, cfg, d_flags, tap && tap->t_full ? 1 : 0))) return rc;
         E.t_mark(st, "match");
@@ -180,7 +176,6 @@ static int compress_batch(Engine &E, hipStream_t st, const u8 *d_raw, bool raw_i
             int hflags[2] = {0, 0};                              // {changed, match-stage flags}
             MTS_HIP(hipMemcpyAsync(hflags, pb.changed, 8, hipMemcpyDeviceToHost, st));
             MTS_HIP(hipStreamSynchronize(st));
-            static const bool debug_flags = getenv("MTS_DEBUG_FLAGS") != nullptr;      // (read once)
             if (debug_flags) fprintf(stderr, "[flags] level %d round %d changed %d match-flags %d force_ballot %d\n", level, round, hflags[0], hflags[1], force_ballot);
             if (hflags[1] & 1) { resort = true; break; }
             if (!hflags[0]) break;
@@ -299,10 +294,11 @@ static int decompress_batch(Engine &E, hipStream_t st, const u8 *d_cdata, const 
     // ---- plan ----
     const InflatePlan P(c_off, c_len, n_rows, out_off, n_chunks, nc, sz, nc_full, sizeof(InfResult));
     if (P.error[0]) { set_error("%s", P.error); return MTS_E_ARG; }
-    const std::vector<InfChunk> &ic = P.ic;
+    const InflateKnobs K = inflate_knobs();
+    const InflateScratch L = inflate_scratch(P, K);
     const std::vector<u64> &so = P.so;
     const std::vector<u32> &nn = P.nn;
-    const u32 max_n = P.max_n, max_rows = P.max_rows;
+    const u32 max_rows = P.max_rows;
     // ---- workspace ----
     int rc;
     if ((rc = E.stream.ensure(P.stream_bytes()))) return rc;
@@ -311,6 +307,7 @@ static int decompress_batch(Engine &E, hipStream_t st, const u8 *d_cdata, const 
     if ((rc = E.adler.ensure(sizeof(u64) * 2 * n_chunks + 256))) return rc;
     if ((rc = E.segsums.ensure(cumsum_scratch_bytes(n_chunks, max_rows, nc)))) return rc;
     if ((rc = E.init_events())) return rc;
+    if ((rc = E.inf_scratch.ensure(L.end + 256))) return rc;      // (a batch's last allocation: where buffers lie has shown in stage times)
     u8 *dp = E.inf_desc.as<u8>();
     InfChunk *d_ic = (InfChunk *)(dp + P.o_ic);
     InfResult *d_res = (InfResult *)(dp + P.o_res);
@@ -318,11 +315,6 @@ static int decompress_batch(Engine &E, hipStream_t st, const u8 *d_cdata, const 
     u64 *d_oo = (u64 *)(dp + P.o_oo);
     u32 *d_rows = (u32 *)(dp + P.o_rows);
     int *d_status = (int *)(dp + P.o_status);
-    {
-        std::vector<u64> clens(n_chunks);
-        for (int i = 0; i < n_chunks; i++) clens[i] = ic[i].c_len;
-        if ((rc = E.inf_scratch.ensure(inflate_scratch_bytes(n_chunks, clens.data(), nn.data())))) return rc;
-    }
     // ---- upload (what the host fills lies in a row: one copy) ----
     {
         std::vector<u8> &hst = E.host_stage[0];
@@ -332,8 +324,7 @@ static int decompress_batch(Engine &E, hipStream_t st, const u8 *d_cdata, const 
     }
     // ---- launch ----
     E.t_begin(st);
-    if ((rc = launch_inflate(st, d_cdata, d_ic, ic.data(), n_chunks, E.stream.as<u8>(), E.tokens.as<u32>(), d_res, E.adler.as<u64>(),
-                             max_n, d_status, E.inf_scratch.p, &E))) return rc;
+    if ((rc = launch_inflate(E, st, d_cdata, d_ic, P, L, K, E.stream.as<u8>(), E.tokens.as<u32>(), d_res, E.adler.as<u64>(), d_status))) return rc;
     if (d_out) {
         if ((rc = launch_cumsum_transpose(st, E.stream.p, d_out, d_so, d_oo, d_rows, d_status, n_chunks, max_rows, nc, sz, flags,
                                           E.segsums.p))) return rc;
@@ -369,9 +360,6 @@ static int decompress_batch(Engine &E, hipStream_t st, const u8 *d_cdata, const 
     }
     return MTS_OK;
 }
-
-void inflate_mark(void *engine, hipStream_t st, const char *name) { ((Engine *)engine)->t_mark(st, name); }
-u8 *inflate_host_stage(void *engine, size_t bytes) { auto &v = ((Engine *)engine)->host_stage[1]; v.assign(bytes, 0); return v.data(); }
 
 int dev_decompress(Engine &E, hipStream_t st, const u8 *d_cdata, const long *c_off, const long *c_len, const long *n_rows,
                    int n_chunks, int nc, int sz, int flags, u8 *d_out, const long *out_off, int *status, int nc_full, bool add_times)

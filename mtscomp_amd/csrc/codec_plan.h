@@ -1,7 +1,7 @@
 // How the codec is fed: the part that decides and touches no device.  The descriptors the kernels read, where a batch's streams,
-// tokens, tiles, segments and block slots lie (CompressPlan, InflatePlan), how a call is cut into sub-batches (cut_batches), how a
-// workspace is carved (WsLayout), and where the compressed bytes of a call lie in the staging buffer (stage_runs / run_copies,
-// RangeStaging).  The header includes the C/C++ standard library only, so tests/plan_check.cpp sweeps all of it on the CPU;
+// tokens, tiles, segments and block slots lie and which arrays share a compress workspace (CompressPlan, InflatePlan), every region of
+// the inflate kernels' scratch (InflateScratch), how a call is cut into sub-batches (cut_batches), how a workspace is carved (WsLayout),
+// and where the compressed bytes of a call lie in the staging buffer (stage_runs / run_copies, RangeStaging).  The header includes the C/C++ standard library only, so tests/plan_check.cpp sweeps all of it on the CPU;
 // codec.hip and cache.hip allocate, copy and launch around it.
 #pragma once
 
@@ -56,6 +56,15 @@ constexpr int TILE = MTS_TILE;             // positions a match-stage workgroup 
 static_assert(TILE > 0 && TILE + HALO <= WIN && TILE % 64 == 0, "a tile and its history fit the window");
 
 constexpr int SEG = 1024;                  // parse segment (positions per speculative walker); measured 512: 9.0, 1024: 8.5, 2048: 8.9, 4096: 9.3 ms (fixpoint + emit)
+
+// The match stage's sink, where its lanes that own no position store (match.hip): behind the flag words of the adler workspace, from
+// word MATCH_SINK_WORD0 after the first flag word (256 bytes in) on, a line of MATCH_SINK_LINE_WORDS words per workgroup, the workgroups
+// taking the MATCH_SINK_LINES lines in turn
+constexpr int MATCH_SINK_BYTES = 65536;
+constexpr int MATCH_SINK_WORD0 = 63;
+constexpr int MATCH_SINK_LINE_WORDS = 64;
+constexpr int MATCH_SINK_LINES = MATCH_SINK_BYTES / (4 * MATCH_SINK_LINE_WORDS);
+static_assert((MATCH_SINK_LINES & (MATCH_SINK_LINES - 1)) == 0, "a workgroup finds its line with a mask");
 
 // one match-stage tile
 struct TileDesc {
@@ -137,14 +146,15 @@ std::vector<int> cut_batches(BytesOf &&bytes_of, int n, size_t budget, int max_c
 struct CompressDims {
     size_t (*hash_sort_ws_bytes)(int n_tiles);
     size_t (*parse_marks_words)(size_t n_segs);
-    size_t parse_cp_words, block_rec_bytes, chunk_out_bytes, blk_code_words, blk_hdr_words, match_sink_bytes;
+    size_t parse_cp_words, block_rec_bytes, chunk_out_bytes, blk_code_words, blk_hdr_words, match_sink_bytes;      // (the last: MATCH_SINK_BYTES)
 };
 
 // Chunk i's stream lies at cd[i].stream_off (STREAM_ALIGN-aligned, >= STREAM_PAD bytes behind it before the next begins or the
 // buffer ends), its tokens at tok_off (room for n + 1), its raw rows at raw_off, its segments [seg0, seg0 + ceil(n / SEG)), its block
 // slots [blk0, blk0 + n / BLOCK_TOKENS + 2), its tiles from tile0.  A chunk's tiles own [a, own_end) = TILE positions each, in order,
 // and hash the window [w, w + wlen): HALO positions of history, then the owned positions that still have three bytes (<= n - 3).
-// Each tile's sorted window is a 64-aligned region of the sort buffers.
+// Each tile's sorted window is a 64-aligned region of the sort buffers.  segbuf, blk, adler and misc each hold several arrays one
+// behind the other: seg, bk, ad and mi say where (they are not re-aligned: the match stage's time has followed buffer placement).
 struct MTS_LOCAL CompressPlan {
     char error[96] = "";                                      // not empty: a bad argument, nothing else is valid
     std::vector<ChunkDesc> cd;
@@ -155,6 +165,10 @@ struct MTS_LOCAL CompressPlan {
     // workspaces, in bytes
     size_t sort_a = 0, sort_b = 0, sort_ws = 0, tables = 0, tokens = 0, segbuf = 0, blk = 0, blkcodes = 0, blkhdr = 0, desc = 0, adler = 0, misc = 0;
     size_t o_chunks = 0, o_tiles = 0, o_cout = 0;             // the regions of desc
+    struct { size_t entry, exit_a, exit_b, cnt, tokbase, seg_chunk, seg_start, cp, end; } seg = {};      // segbuf, in words: nseg + 64 entries each, cp parse_cp_words per entry
+    struct { size_t blocks, chunk, in_start, end; } bk = {};      // blk, in bytes: nblk + 1 records, then as many words for the slot's chunk and its first input byte
+    struct { size_t sums, changed, flags, sink, end; } ad = {};   // adler, in bytes: two sums per chunk, the parse's flag word, the match stage's, its sink
+    struct { size_t so, nn, end; } mi = {};                       // misc, in bytes (raw_is_stream: the streams' offsets and sizes for the check value)
 
     CompressPlan(const long *bounds, int n_chunks, u64 row_bytes, bool raw_is_stream, const long *slot_off, int level, const CompressDims &D) : cd(n_chunks)
     {
@@ -202,15 +216,21 @@ struct MTS_LOCAL CompressPlan {
         table_words = align_up(stream_bytes + 64, 64);
         tables = table_words * 4 * (level < 4 ? 1 : 2);
         tokens = (tok_words + 64) * 4;
-        segbuf = ((size_t)nseg + 64) * 4 * (7 + D.parse_cp_words) + 256;
-        blk = ((size_t)nblk + 1) * (D.block_rec_bytes + 8) + 256;
+        const size_t SN = (size_t)nseg + 64, BN = (size_t)nblk + 1;
+        seg = {0, SN, 2 * SN, 3 * SN, 4 * SN, 5 * SN, 6 * SN, 7 * SN, (7 + D.parse_cp_words) * SN};
+        segbuf = seg.end * 4 + 256;
+        bk = {0, BN * D.block_rec_bytes, BN * (D.block_rec_bytes + 4), BN * (D.block_rec_bytes + 8)};
+        blk = bk.end + 256;
         blkcodes = ((size_t)nblk + 1) * D.blk_code_words * 4;
         blkhdr = ((size_t)nblk + 1) * D.blk_hdr_words * 4;
         WsLayout L{false};
         o_chunks = L.take(sizeof(ChunkDesc) * n_chunks); o_tiles = L.take(sizeof(TileDesc) * (tiles.size() + 1)); o_cout = L.take(D.chunk_out_bytes * n_chunks);
         desc = L.end;
-        adler = sizeof(u64) * 2 * n_chunks + 256 + D.match_sink_bytes;      // + the flag words and the match stage's sink behind them
-        misc = 12 * (size_t)n_chunks + 64;                    // (raw_is_stream: the streams' offsets and sizes for the check value)
+        ad.sums = 0; ad.changed = sizeof(u64) * 2 * n_chunks; ad.flags = ad.changed + 4; ad.sink = ad.flags + 4 * MATCH_SINK_WORD0;
+        ad.end = ad.sink + D.match_sink_bytes;
+        adler = ad.changed + 256 + D.match_sink_bytes;
+        mi = {0, 8 * (size_t)n_chunks, 12 * (size_t)n_chunks};
+        misc = mi.end + 64;
     }
 
     // the index arrays, which depend on the chunk sizes only: per segment its chunk, then its start position; per block slot its chunk
@@ -280,6 +300,108 @@ struct MTS_LOCAL InflatePlan {
         const size_t n = ic.size();
         memcpy(h + o_ic, ic.data(), sizeof(InfChunk) * n); memcpy(h + o_so, so.data(), 8 * n); memcpy(h + o_nn, nn.data(), 4 * n);
         memcpy(h + o_oo, oo.data(), 8 * n); memcpy(h + o_rows, rows.data(), 4 * n);
+    }
+};
+
+// ---- the scratch of an inflate batch ----------------------------------------------------------------------------------------------------
+// per-chunk bookkeeping of the fast path (a device array the host fills, one entry per chunk)
+struct InfFast {
+    u64 cand_off;                // first slot of this chunk in the candidate arrays
+    u32 cand_cap;
+    u32 true_off;                // first slot in the true-block array
+    u32 true_cap;
+    u32 pad;
+};
+static_assert(sizeof(InfFast) == 24 && offsetof(InfFast, cand_cap) == 8 && offsetof(InfFast, true_off) == 12 && offsetof(InfFast, true_cap) == 16, "InfFast layout");
+
+// what the scratch plan takes from inflate.hip: sizes of records it does not look into, and the constants that size a region
+struct InflateDims {
+    size_t cand_res_bytes, true_blk_bytes, lz_plan_bytes;     // sizeof(CandRes), sizeof(TrueBlk), sizeof(LzPlan)
+    u32 subcap, rowcap, rounds_max, gs_tile, lz_maxseg, lz_win, lz_flush, lz_flushers;
+};
+
+// Every region of the inflate kernels' scratch, 256-aligned, one behind the other in the order of the members.  Per chunk: cand_cap
+// candidate slots from cand_off and twice as many true-block slots from true_off (fast), groups_of(n) group bases from gb[i] in gbase,
+// tiles_of(n) tile bases from tb[i] in tile_base.  What the host fills -- so, nn, fast, gb_off, tb_off -- lies in a row at host_off:
+// host_bytes, one copy (fill).  The resolver clears clear[0] and clear[1] before it runs: gflag and seg_adler, which lie in a row.
+struct MTS_LOCAL InflateScratch {
+    struct Region { const char *name; size_t off, bytes; };
+    const InflatePlan &P;
+    std::vector<Region> regions;                              // every take, in order: the sweep's view
+    size_t so, nn, fast, gb_off, tb_off, cand_cnt, true_cnt, seq_flag, slot_chunk, tslot_chunk, cand_pos, cand_tmp, cres, tblk, subs, gbase, tile_base, surv,
+        surv_cnt, plan, win;
+    size_t rows_cells;           // pass A's token rows (u32) until pass B and k_inf_move_rows have run, then the resolver's cells (u16): the rows are dead by then
+    size_t round_row, row_ctr, gflag, seg_adler, end;
+    size_t host_off, host_bytes;
+    struct { size_t off, bytes; } clear[2];
+    u32 total_cand = 0, total_true = 0, surv_cap, rounds_cap, max_groups = 1;
+    u64 max_clen = 0;
+    int nseg;                    // segments the resolver cuts every chunk into (1: none)
+    std::vector<InfFast> h_fast;
+    std::vector<u64> gb, tb;
+
+    static u32 cand_cap_of(u64 c_len) { return (u32)(c_len / 4096 + 64); }
+    static u64 rows_rounds_of(u64 c_len) { return c_len * 8 / (64 * 640) + 32; }          // pool share of a chunk, in rounds
+    static u64 groups_of(u32 n) { return ((u64)n + 2 + 63) / 64 + 2; }                    // groups of 64 tokens; tokens <= bytes + 1
+    static u64 tiles_of(u32 n, u32 gs_tile) { return groups_of(n) / gs_tile + 2; }
+
+    // lz_segs: 0, or MTS_LZ_SEGS; row_rounds: < 0, or MTS_INF_ROW_ROUNDS (tests: a pool that runs out)
+    InflateScratch(const InflatePlan &P_, const InflateDims &D, int lz_segs, long row_rounds) : P(P_), h_fast(P_.ic.size()), gb(P_.ic.size()), tb(P_.ic.size())
+    {
+        const size_t n = P.ic.size();
+        u64 cand = 0, ng = 0, nt = 0, cbits = 0, cells = 0, rounds = 0;
+        for (size_t i = 0; i < n; i++) {
+            const u64 c_len = P.ic[i].c_len;
+            const u32 cap = cand_cap_of(c_len);
+            h_fast[i] = {cand, cap, (u32)(2 * cand), 2 * cap, 0};
+            gb[i] = ng; tb[i] = nt;
+            cand += cap; ng += groups_of(P.nn[i]); nt += tiles_of(P.nn[i], D.gs_tile);
+            cbits += 8 * c_len; rounds += rows_rounds_of(c_len);
+            cells += align_up((u64)P.nn[i] + STREAM_PAD, STREAM_ALIGN);
+            if (c_len > max_clen) max_clen = c_len;
+            if (groups_of(P.nn[i]) - 2 > max_groups) max_groups = (u32)(groups_of(P.nn[i]) - 2);
+        }
+        total_cand = (u32)cand; total_true = (u32)(2 * cand);
+        // with fewer chunks than CUs the resolver cuts a chunk into segments (inflate.hip: LzPlan); cells and windows live here
+        nseg = lz_segs ? lz_segs : n < 128 ? (int)(256 / (n ? n : 1)) : 1;
+        if (nseg > (int)D.lz_maxseg) nseg = (int)D.lz_maxseg;
+        if (row_rounds >= 0) rounds = (u64)row_rounds;
+        if (rounds > 0x3ffffffull) rounds = 0x3ffffffull;     // (row ids are 32 bits)
+        rounds_cap = (u32)rounds;
+        surv_cap = (u32)(cbits / 256 + 65536);                // ~0.1 % of the bit offsets pass the cheap filters
+        const bool cut = nseg > 1;
+        const size_t row_bytes = (size_t)rounds * 64 * D.rowcap * 4 + 256, cell_bytes = cut ? 2 * cells + 4096 : 0;
+        const size_t seg_adler_bytes = cut ? n * D.lz_maxseg * D.lz_flushers * 16 : 0;
+
+        WsLayout L{false};
+        regions.reserve(32);
+        auto take = [&](const char *name, size_t bytes) { regions.push_back({name, L.end, bytes}); return L.take(bytes); };
+        so = take("so", 8 * n); nn = take("nn", 4 * n); fast = take("fast", sizeof(InfFast) * n); gb_off = take("gb_off", 8 * n); tb_off = take("tb_off", 8 * n);
+        host_off = so; host_bytes = L.end - so;
+        cand_cnt = take("cand_cnt", 4 * n); true_cnt = take("true_cnt", 4 * n); seq_flag = take("seq_flag", 4 * n);
+        slot_chunk = take("slot_chunk", 4 * (size_t)total_cand); tslot_chunk = take("tslot_chunk", 4 * (size_t)total_true);
+        cand_pos = take("cand_pos", 8 * (size_t)total_cand); cand_tmp = take("cand_tmp", 8 * (size_t)total_cand);
+        cres = take("cres", D.cand_res_bytes * total_cand); tblk = take("tblk", D.true_blk_bytes * total_true);
+        subs = take("subs", 8 * (size_t)D.subcap * total_cand);
+        gbase = take("gbase", 4 * ng);
+        tile_base = take("tile_base", 4 * (ng / D.gs_tile + 2 * n + 16));
+        surv = take("surv", 8 * (size_t)surv_cap); surv_cnt = take("surv_cnt", 256);
+        plan = take("plan", D.lz_plan_bytes * n);
+        win = take("win", cut ? n * D.lz_maxseg * D.lz_win : 0);
+        rows_cells = take("rows_cells", row_bytes > cell_bytes ? row_bytes : cell_bytes);
+        round_row = take("round_row", 4 * (size_t)D.rounds_max * total_cand); row_ctr = take("row_ctr", 256);
+        gflag = take("gflag", cut ? cells / D.lz_flush + n + 64 : 0);
+        seg_adler = take("seg_adler", seg_adler_bytes);
+        clear[0] = {gflag, seg_adler - gflag}; clear[1] = {seg_adler, seg_adler_bytes};
+        end = L.end;
+    }
+
+    void fill(u8 *h) const                                    // host_bytes zeroed bytes
+    {
+        const size_t n = P.ic.size();
+        auto put = [&](size_t off, const void *src, size_t bytes) { memcpy(h + (off - host_off), src, bytes); };
+        put(so, P.so.data(), 8 * n); put(nn, P.nn.data(), 4 * n); put(fast, h_fast.data(), sizeof(InfFast) * n);
+        put(gb_off, gb.data(), 8 * n); put(tb_off, tb.data(), 8 * n);
     }
 };
 

@@ -218,9 +218,8 @@ int launch_project(hipStream_t st, int itemsize, int flags, int out_itemsize, co
 size_t hash_sort_ws_bytes(int n_tiles);                            // the one-pass sort's per-tile records
 int launch_hash_sort(hipStream_t st, const u8 *d_stream, const TileDesc *d_tiles, int n_tiles, u32 *d_tmp, u32 *d_sorted,
                      int force_ballot, void *d_ws);
-constexpr int MATCH_SINK_BYTES = 65536;         // behind the flag words, 256 bytes after the first: where the lanes of the match stage that own no position store (match.hip)
 int launch_match(hipStream_t st, const u8 *d_stream, const TileDesc *d_tiles, int n_tiles, const u32 *d_sorted, u32 *d_tables, u32 *d_quarter,
-                 LevelCfg cfg, u32 *d_flags /* [0] |= 1: a hash run out of position order; [63 ...]: MATCH_SINK_BYTES of sink */,
+                 LevelCfg cfg, u32 *d_flags /* [0] |= 1: a hash run out of position order; [MATCH_SINK_WORD0 ...]: MATCH_SINK_BYTES of sink (codec_plan.h) */,
                  int all_quarters /* debug tap: write the side table for every position */);
 struct ParseBufs {
     u32 *entry, *exit_a, *exit_b, *cnt, *tokbase;   // per segment
@@ -275,11 +274,18 @@ struct InfResult {
     u32 adler_stored;
     u64 end_bit;
 };
-int launch_inflate(hipStream_t st, const u8 *d_cdata, const InfChunk *d_chunks, const InfChunk *h_chunks, int n_chunks,
-                   u8 *d_stream, u32 *d_tokens, InfResult *d_res, u64 *d_adler_acc, u32 max_n, int *d_status_out,
-                   void *d_scratch, void *engine);
-size_t inflate_scratch_bytes(int n_chunks, const u64 *c_lens, const u32 *n_expect);
-void inflate_mark(void *engine, hipStream_t st, const char *name);   // stage timing hook (codec.hip)
-u8 *inflate_host_stage(void *engine, size_t bytes);                    // zeroed host bytes the engine keeps until the next batch (codec.hip)
+struct InflateKnobs {      // the MTS_* environment of an inflate batch (inflate_knobs reads it, per batch)
+    int lz_segs = 0;             // MTS_LZ_SEGS: segments per chunk of the LZ resolver, 1 .. LZ_MAXSEG (0: not set)
+    long row_rounds = -1;        // MTS_INF_ROW_ROUNDS: pass A's row pool, in rounds (< 0: not set)
+    bool seq = false;            // MTS_INFLATE_SEQ: every chunk through the block-after-block decoder
+    int lz_workers = 0;          // MTS_LZ_WORKERS: worker waves of the LZ resolver
+    u64 final_zone_bits = 0;     // MTS_SCAN_FINAL_ZONE (bytes): where the scan looks at candidates with BFINAL = 1
+    bool no_rows = false, force_retry = false, lz_prof = false, debug_status = false;      // MTS_INF_NO_ROWS, MTS_LZ_FORCE_RETRY, MTS_LZ_PROF, MTS_DEBUG_STATUS
+};
+struct Engine;             // engine.h
+InflateKnobs inflate_knobs() MTS_LOCAL;
+InflateScratch inflate_scratch(const InflatePlan &P, const InflateKnobs &K) MTS_LOCAL;      // every region of the engine's inf_scratch
+int launch_inflate(Engine &E, hipStream_t st, const u8 *d_cdata, const InfChunk *d_chunks, const InflatePlan &P, const InflateScratch &L,
+                   const InflateKnobs &K, u8 *d_stream, u32 *d_tokens, InfResult *d_res, u64 *d_adler_acc, int *d_status_out) MTS_LOCAL;
 
 }  // namespace mts

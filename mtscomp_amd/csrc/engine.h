@@ -54,7 +54,7 @@ struct Engine {
     std::mutex mu;
     hipStream_t own = nullptr;
     // compress workspace
-    DBuf stream, sort_a, sort_b, sort_ws, tables, tokens, marks, segbuf, blk, blkcodes, blkhdr, desc, adler, misc;
+    DBuf stream, sort_a, sort_b, sort_ws, tables, tokens, segbuf, blk, blkcodes, blkhdr, desc, adler, misc;
     DBuf fast_lists, fast_state;         // levels 1..3: candidate lists of two phases, per-chunk state of the in-order walk
     hipStream_t fast_st = nullptr;       // ... and the stream the lists are made on, with its events (lists ready x2, lists read x2, inputs ready)
     hipEvent_t fast_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -158,7 +158,7 @@ struct Engine {
     }
     void release_all()
     {
-        DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &marks, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
+        DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
                        &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &wav, &cor, &tm, &res, &welch, &gram, &proj};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)

@@ -16,7 +16,7 @@
 
 #include <vector>
 
-#include "common.h"
+#include "engine.h"
 
 namespace mts {
 
@@ -855,13 +855,7 @@ __device__ __forceinline__ int vh_step(VhState &s)
     return 1;
 }
 
-struct InfFast {                 // per-chunk bookkeeping of the fast path (device arrays, one entry per chunk)
-    u64 cand_off;                // first slot of this chunk in the candidate arrays
-    u32 cand_cap;
-    u32 true_off;                // first slot in the true-block array
-    u32 true_cap;
-    u32 pad;
-};
+// (InfFast, the per-chunk bookkeeping of the fast path, is in codec_plan.h: the host plan fills it)
 struct CandRes {                 // result of decoding one candidate block (pass A)
     u64 end_bit;                 // position after the end-of-block symbol
     u32 ntok, nout, nsub;
@@ -898,7 +892,6 @@ constexpr u32 SUB_MIN = 256;
 #endif
 constexpr u32 ROWCAP = MTS_INF_ROWCAP;
 constexpr int ROUNDS_MAX = (SUBCAP + 63) / 64;          // rounds of a block (all but the last have 64 sub-sequences)
-static inline u64 rows_rounds_of(u64 c_len) { return c_len * 8 / (64 * 640) + 32; }      // pool share of a chunk, in rounds
 
 #ifndef MTS_SCAN_SPANS
 #define MTS_SCAN_SPANS 1
@@ -2888,72 +2881,52 @@ __global__ __launch_bounds__(256) void k_inf_fill_slots(const InfFast *__restric
     for (u32 k = threadIdx.x; k < f.true_cap; k += 256) tslot_chunk[f.true_off + k] = blockIdx.x;
 }
 
-static inline u32 cand_cap_of(u64 c_len) { return (u32)(c_len / 4096 + 64); }
+// what the scratch plan (codec_plan.h: InflateScratch, every region of d_scratch) takes from this file
+static const InflateDims INF_DIMS = {sizeof(CandRes), sizeof(TrueBlk), sizeof(LzPlan), SUBCAP, ROWCAP, ROUNDS_MAX, GS_TILE, LZ_MAXSEG, LZ_WIN, LZ_FLUSH, LZ_FLUSHERS};
+constexpr u32 LZ_PLAN_WORDS = sizeof(LzPlan) / 4;
 
-// scratch layout (all 256-B aligned): [so u64 n][nn u32 n][fast n][cand_cnt n][true_cnt n][seq_flag n]
-//   [slot_chunk total_cand][tslot_chunk total_true][cand_pos][cand_tmp][cres][tblk][subs]
-struct InfLayout {
-    size_t so, nn, fast, cand_cnt, true_cnt, seq_flag, slot_chunk, tslot_chunk, cand_pos, cand_tmp, cres, tblk, subs, gb_off, gbase, tb_off, tile_base, surv, surv_cnt, plan, win, sym, rows,
-        round_row, row_ctr, gflag, seg_adler, end;
-    u32 total_cand, total_true, surv_cap, rounds_cap;
-    int nseg;                // segments the resolver cuts every chunk into (1: none)
-};
-static InfLayout inf_layout(int n_chunks, const u64 *c_lens, const u32 *n_expect)
+// the environment, read per batch (the tests change these between calls of one process)
+InflateKnobs inflate_knobs()
 {
-    InfLayout l;
-    u64 tc = 0;
-    for (int i = 0; i < n_chunks; i++) tc += cand_cap_of(c_lens[i]);
-    l.total_cand = (u32)tc;
-    l.total_true = (u32)(2 * tc);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t r = o; o += align_up(bytes, 256); return r; };
-    // (what the host fills -- so, nn, fast, gb_off, tb_off -- lies in a row: one copy)
-    l.so = take(8 * (size_t)n_chunks); l.nn = take(4 * (size_t)n_chunks); l.fast = take(sizeof(InfFast) * (size_t)n_chunks);
-    l.gb_off = take(8 * (size_t)n_chunks); l.tb_off = take(8 * (size_t)n_chunks);
-    l.cand_cnt = take(4 * (size_t)n_chunks); l.true_cnt = take(4 * (size_t)n_chunks); l.seq_flag = take(4 * (size_t)n_chunks);
-    l.slot_chunk = take(4 * (size_t)l.total_cand); l.tslot_chunk = take(4 * (size_t)l.total_true);
-    l.cand_pos = take(8 * (size_t)l.total_cand); l.cand_tmp = take(8 * (size_t)l.total_cand);
-    l.cres = take(sizeof(CandRes) * (size_t)l.total_cand); l.tblk = take(sizeof(TrueBlk) * (size_t)l.total_true);
-    l.subs = take(sizeof(uint2) * (size_t)SUBCAP * l.total_cand);
-    size_t ng = 0;
-    for (int i = 0; i < n_chunks; i++) ng += ((size_t)n_expect[i] + 2 + 63) / 64 + 2;       // tokens <= bytes + 1
-    l.gbase = take(4 * ng);
-    l.tile_base = take(4 * (ng / GS_TILE + 2 * (size_t)n_chunks + 16));
-    u64 cbits = 0;
-    for (int i = 0; i < n_chunks; i++) cbits += 8 * c_lens[i];
-    l.surv_cap = (u32)(cbits / 256 + 65536);          // ~0.1 % of the bit offsets pass the cheap filters
-    l.surv = take(8 * (size_t)l.surv_cap);
-    l.surv_cnt = take(256);
-    // LZ resolver: with fewer chunks than CUs a chunk is cut into segments (see LzPlan); cells and windows live here
-    l.nseg = 1;
-    if (n_chunks < 128) { l.nseg = 256 / n_chunks; if (l.nseg > LZ_MAXSEG) l.nseg = LZ_MAXSEG; }
-    if (const char *e = getenv("MTS_LZ_SEGS")) { l.nseg = atoi(e); if (l.nseg < 1) l.nseg = 1; if (l.nseg > LZ_MAXSEG) l.nseg = LZ_MAXSEG; }
-    l.plan = take(sizeof(LzPlan) * (size_t)n_chunks);
-    l.win = take(l.nseg > 1 ? (size_t)n_chunks * LZ_MAXSEG * LZ_WIN : 0);
-    size_t cells = 0;
-    for (int i = 0; i < n_chunks; i++) cells += align_up((u64)n_expect[i] + STREAM_PAD, STREAM_ALIGN);
-    // pass A's token rows are dead once pass B has run, the resolver's cells are written after that: one region for both
-    u64 rounds = 0;
-    for (int i = 0; i < n_chunks; i++) rounds += rows_rounds_of(c_lens[i]);
-    if (const char *e = getenv("MTS_INF_ROW_ROUNDS")) rounds = (u64)atoll(e);      // (tests: a pool that runs out)
-    if (rounds > 0x3ffffffull) rounds = 0x3ffffffull;                               // (row ids are 32 bits)
-    l.rounds_cap = (u32)rounds;
-    const size_t row_bytes = (size_t)rounds * 64 * ROWCAP * 4 + 256, sym_bytes = l.nseg > 1 ? 2 * cells + 4096 : 0;
-    l.sym = take(row_bytes > sym_bytes ? row_bytes : sym_bytes);
-    l.rows = l.sym;
-    l.round_row = take(4 * (size_t)ROUNDS_MAX * l.total_cand);
-    l.row_ctr = take(256);
-    l.gflag = take(l.nseg > 1 ? cells / LZ_FLUSH + (size_t)n_chunks + 64 : 0);
-    l.seg_adler = take(l.nseg > 1 ? (size_t)n_chunks * LZ_MAXSEG * LZ_FLUSHERS * 16 : 0);
-    l.end = o;
-    return l;
+    InflateKnobs K;
+    if (const char *e = getenv("MTS_LZ_SEGS")) K.lz_segs = std::min(std::max(atoi(e), 1), LZ_MAXSEG);
+    if (const char *e = getenv("MTS_INF_ROW_ROUNDS")) K.row_rounds = (long)std::min<u64>((u64)atoll(e), 0x3ffffffull);      // (tests: a pool that runs out)
+    K.seq = getenv("MTS_INFLATE_SEQ") != nullptr;
+    K.lz_workers = LZ_WORKERS;
+    if (const char *e = getenv("MTS_LZ_WORKERS")) K.lz_workers = std::min(std::max(atoi(e), 1), LZ_WORKERS);
+    K.final_zone_bits = SCAN_FINAL_ZONE_BITS;                        // (MTS_SCAN_FINAL_ZONE = bytes: the tests shrink it below a block's length)
+    if (const char *e = getenv("MTS_SCAN_FINAL_ZONE")) K.final_zone_bits = 8ull * (u64)atoll(e);
+    K.no_rows = getenv("MTS_INF_NO_ROWS") != nullptr;                // (A/B: pass B decodes every block again)
+    K.force_retry = getenv("MTS_LZ_FORCE_RETRY") != nullptr;         // (tests: pretend every chunk's first run gave up, so that the retry pass does the work)
+    K.lz_prof = getenv("MTS_LZ_PROF") != nullptr;                    // per-wave cycle counters of the resolver, printed to stderr
+    K.debug_status = getenv("MTS_DEBUG_STATUS") != nullptr;
+    return K;
 }
 
-size_t inflate_scratch_bytes(int n_chunks, const u64 *c_lens, const u32 *n_expect) { return inf_layout(n_chunks, c_lens, n_expect).end + 256; }
+InflateScratch inflate_scratch(const InflatePlan &P, const InflateKnobs &K) { return InflateScratch(P, INF_DIMS, K.lz_segs, K.row_rounds); }
+
+// ---- MTS_DEBUG_STATUS: what went in, and every chunk's result after a stage
+static void dbg_cdata(hipStream_t st, const u8 *d_cdata, const std::vector<InfChunk> &ic)
+{
+    for (size_t i = 0; i < ic.size(); i++) {
+        std::vector<u8> hb(ic[i].c_len);
+        (void)hipStreamSynchronize(st);
+        (void)hipMemcpy(hb.data(), d_cdata + ic[i].c_off, hb.size(), hipMemcpyDeviceToHost);
+        u32 a = 1, b2 = 0;
+        for (u8 v : hb) { a = (a + v) % 65521u; b2 = (b2 + a) % 65521u; }
+        fprintf(stderr, "[chunk %d] device copy of the compressed bytes: adler32 %08x\n", (int)i, (b2 << 16) | a);
+    }
+}
+
+static void dbg_chunks(const std::vector<InfChunk> &ic)
+{
+    for (size_t i = 0; i < ic.size(); i++)
+        fprintf(stderr, "[chunk %d] c_off %llu c_len %llu n_expect %u n_need %u stream_off %llu tok_off %llu\n", (int)i, (unsigned long long)ic[i].c_off,
+                (unsigned long long)ic[i].c_len, ic[i].n_expect, ic[i].n_need, (unsigned long long)ic[i].stream_off, (unsigned long long)ic[i].tok_off);
+}
 
 static void dbg_status(hipStream_t st, const InfResult *d_res, int n_chunks, const char *where)
 {
-    if (!getenv("MTS_DEBUG_STATUS")) return;
     std::vector<InfResult> h(n_chunks);
     (void)hipStreamSynchronize(st);
     (void)hipMemcpy(h.data(), d_res, sizeof(InfResult) * n_chunks, hipMemcpyDeviceToHost);
@@ -2962,161 +2935,123 @@ static void dbg_status(hipStream_t st, const InfResult *d_res, int n_chunks, con
     fprintf(stderr, "\n");
 }
 
-int launch_inflate(hipStream_t st, const u8 *d_cdata, const InfChunk *d_chunks, const InfChunk *h_chunks, int n_chunks,
-                   u8 *d_stream, u32 *d_tokens, InfResult *d_res, u64 *d_adler_acc, u32 max_n, int *d_status_out,
-                   void *d_scratch, void *engine)
+// ---- MTS_LZ_PROF: the resolver's counters, 16 waves x 8 words per chunk
+static size_t lz_prof_bytes(int n_chunks) { return (size_t)n_chunks * 16 * 8 * 8; }
+static int lz_prof_report(hipStream_t st, u64 *d_prof, int n_chunks)
 {
+    std::vector<u64> hp((size_t)n_chunks * 16 * 8);
+    MTS_HIP(hipStreamSynchronize(st));
+    MTS_HIP(hipMemcpy(hp.data(), d_prof, hp.size() * 8, hipMemcpyDeviceToHost));
+    MTS_HIP(hipFree(d_prof));
+    u64 a[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nw = 0;
+    for (int c = 0; c < n_chunks; c++) for (int w = 0; w < 16; w++) { const u64 *q = &hp[((size_t)c * 16 + w) * 8]; if (!q[5]) continue; nw++; for (int k = 0; k < 8; k++) a[k] += q[k]; }
+    if (nw) fprintf(stderr, "[lz prof] waves %d  per wave: total %.0f  wait %.0f  pre %.0f  loop %.0f cycles; groups %.0f  iters/group %.2f  cycles/group %.0f  vmwait %.0f  sleeps %.0f\n", nw,
+                    (double)a[0] / nw, (double)a[1] / nw, (double)a[2] / nw, (double)a[3] / nw, (double)a[5] / nw, (double)a[4] / a[5], (double)a[0] / a[5], (double)a[6] / nw, (double)a[7] / nw);
+    return MTS_OK;
+}
+
+// One batch, in launch order.  P: the batch (its descriptors are at d_chunks), L: the regions of E.inf_scratch, K: the environment.
+int launch_inflate(Engine &E, hipStream_t st, const u8 *d_cdata, const InfChunk *d_chunks, const InflatePlan &P, const InflateScratch &L,
+                   const InflateKnobs &K, u8 *d_stream, u32 *d_tokens, InfResult *d_res, u64 *d_adler_acc, int *d_status_out)
+{
+    const int n_chunks = (int)P.ic.size();
+    const u32 max_n = P.max_n;
     if (n_chunks == 0) return MTS_OK;
     MTS_LDS_ATTR(k_inf_lz, LZ_LDS);
     MTS_LDS_ATTR(k_inf_lz_seg, LZ2_LDS);
-    std::vector<u64> lens(n_chunks), so(n_chunks);
-    std::vector<u32> nn(n_chunks);
-    u64 max_clen = 0;
-    for (int i = 0; i < n_chunks; i++) {
-        lens[i] = h_chunks[i].c_len; so[i] = h_chunks[i].stream_off; nn[i] = h_chunks[i].n_expect;
-        if (lens[i] > max_clen) max_clen = lens[i];
-    }
-    const InfLayout l = inf_layout(n_chunks, lens.data(), nn.data());
-    if (getenv("MTS_DEBUG_STATUS"))
-        for (int i = 0; i < n_chunks; i++) {
-            std::vector<u8> hb(h_chunks[i].c_len);
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpy(hb.data(), d_cdata + h_chunks[i].c_off, hb.size(), hipMemcpyDeviceToHost);
-            u32 a = 1, b2 = 0;
-            for (u8 v : hb) { a = (a + v) % 65521u; b2 = (b2 + a) % 65521u; }
-            fprintf(stderr, "[chunk %d] device copy of the compressed bytes: adler32 %08x\n", i, (b2 << 16) | a);
-        }
-    if (getenv("MTS_DEBUG_STATUS"))
-        for (int i = 0; i < n_chunks; i++)
-            fprintf(stderr, "[chunk %d] c_off %llu c_len %llu n_expect %u n_need %u stream_off %llu tok_off %llu\n", i, (unsigned long long)h_chunks[i].c_off,
-                    (unsigned long long)h_chunks[i].c_len, h_chunks[i].n_expect, h_chunks[i].n_need, (unsigned long long)h_chunks[i].stream_off, (unsigned long long)h_chunks[i].tok_off);
-    // the per-chunk index arrays go to the device in ONE copy (they lie in a row in the scratch area, see inf_layout); which chunk a
-    // candidate / true-block slot belongs to -- ~6000 words per chunk -- is filled in on the device (the 60-chunk batch spent
+    // ---- the regions of the scratch, typed
+    u8 *S = E.inf_scratch.as<u8>();
+    const u64 *d_so = (const u64 *)(S + L.so), *d_gb_off = (const u64 *)(S + L.gb_off), *d_tb_off = (const u64 *)(S + L.tb_off);
+    const u32 *d_nn = (const u32 *)(S + L.nn);
+    const InfFast *d_fast = (const InfFast *)(S + L.fast);
+    u32 *d_cand_cnt = (u32 *)(S + L.cand_cnt), *d_true_cnt = (u32 *)(S + L.true_cnt), *d_slot_chunk = (u32 *)(S + L.slot_chunk), *d_tslot_chunk = (u32 *)(S + L.tslot_chunk);
+    int *d_seq = (int *)(S + L.seq_flag);
+    u64 *d_cand_pos = (u64 *)(S + L.cand_pos), *d_cand_tmp = (u64 *)(S + L.cand_tmp), *d_surv = (u64 *)(S + L.surv), *d_seg_adler = (u64 *)(S + L.seg_adler);
+    CandRes *d_cres = (CandRes *)(S + L.cres);
+    TrueBlk *d_tblk = (TrueBlk *)(S + L.tblk);
+    uint2 *d_subs = (uint2 *)(S + L.subs);
+    u32 *d_gbase = (u32 *)(S + L.gbase), *d_tile_base = (u32 *)(S + L.tile_base), *d_surv_cnt = (u32 *)(S + L.surv_cnt);
+    LzPlan *d_plan = (LzPlan *)(S + L.plan);
+    const u32 *d_plan_words = (const u32 *)(S + L.plan);
+    u8 *d_win = S + L.win, *d_gflag = S + L.gflag;
+    u32 *d_rows = (u32 *)(S + L.rows_cells), *d_round_row = (u32 *)(S + L.round_row), *d_row_ctr = (u32 *)(S + L.row_ctr);
+    u16 *d_cells = (u16 *)(S + L.rows_cells);                 // (the rows' region, once pass B has run: InflateScratch::rows_cells)
+    const bool cut = L.nseg > 1 && max_n > 0;                 // the resolver cuts the chunks into segments
+    const int use_rows = K.no_rows ? 0 : 1, first_pass = K.force_retry ? 2 : 0;
+
+    if (K.debug_status) { dbg_cdata(st, d_cdata, P.ic); dbg_chunks(P.ic); }
+    // the per-chunk index arrays go to the device in ONE copy (they lie in a row in the scratch area: InflateScratch::host_off); which
+    // chunk a candidate / true-block slot belongs to -- ~6000 words per chunk -- is filled in on the device (the 60-chunk batch spent
     // 0.9 ms of host time and a 1.5 MB pageable copy on it before its first kernel)
-    u8 *S = (u8 *)d_scratch;
-    const size_t hst_bytes = l.cand_cnt - l.so;
-    u8 *hst = inflate_host_stage(engine, hst_bytes);          // (kept by the engine until the next batch: the copy below is asynchronous)
-    u64 *h_so = (u64 *)(hst + (l.so - l.so)), *h_gb = (u64 *)(hst + (l.gb_off - l.so)), *h_tb = (u64 *)(hst + (l.tb_off - l.so));
-    u32 *h_nn = (u32 *)(hst + (l.nn - l.so));
-    InfFast *h_fast = (InfFast *)(hst + (l.fast - l.so));
-    {
-        u64 a = 0, b2 = 0, co = 0;
-        u32 to = 0;
-        for (int i = 0; i < n_chunks; i++) {
-            const u64 ng1 = ((u64)nn[i] + 2 + 63) / 64 + 2;
-            h_gb[i] = a; a += ng1;
-            h_tb[i] = b2; b2 += ng1 / GS_TILE + 2;
-            h_so[i] = so[i]; h_nn[i] = nn[i];
-            h_fast[i].cand_off = co; h_fast[i].cand_cap = cand_cap_of(lens[i]);
-            h_fast[i].true_off = to; h_fast[i].true_cap = 2 * h_fast[i].cand_cap; h_fast[i].pad = 0;
-            co += h_fast[i].cand_cap; to += h_fast[i].true_cap;
-        }
-    }
-    MTS_HIP(hipMemcpyAsync(S + l.so, hst, hst_bytes, hipMemcpyHostToDevice, st));
-    MTS_HIP(hipMemsetAsync(S + l.cand_cnt, 0, 4 * (size_t)n_chunks, st));
-    hipLaunchKernelGGL(k_inf_fill_slots, dim3(n_chunks), dim3(256), 0, st, (const InfFast *)(S + l.fast), (u32 *)(S + l.slot_chunk), (u32 *)(S + l.tslot_chunk));
-    const InfFast *d_fast = (const InfFast *)(S + l.fast);
-    u64 *d_cand_pos = (u64 *)(S + l.cand_pos), *d_cand_tmp = (u64 *)(S + l.cand_tmp);
-    u32 *d_cand_cnt = (u32 *)(S + l.cand_cnt), *d_true_cnt = (u32 *)(S + l.true_cnt);
-    int *d_seq = (int *)(S + l.seq_flag);
-    CandRes *d_cres = (CandRes *)(S + l.cres);
-    TrueBlk *d_tblk = (TrueBlk *)(S + l.tblk);
-    uint2 *d_subs = (uint2 *)(S + l.subs);
-    const bool fast_path = getenv("MTS_INFLATE_SEQ") == nullptr;
-    int lz_workers = LZ_WORKERS;
-    if (const char *e = getenv("MTS_LZ_WORKERS")) { lz_workers = atoi(e); if (lz_workers < 1) lz_workers = 1; if (lz_workers > LZ_WORKERS) lz_workers = LZ_WORKERS; }
-    if (fast_path) {
-        const u64 max_bits = 8 * max_clen + 32;
+    std::vector<u8> &hst = E.host_stage[1];                   // (kept by the engine until the next batch: the copy below is asynchronous)
+    hst.assign(L.host_bytes, 0);
+    L.fill(hst.data());
+    MTS_HIP(hipMemcpyAsync(S + L.host_off, hst.data(), L.host_bytes, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemsetAsync(d_cand_cnt, 0, 4 * (size_t)n_chunks, st));
+    hipLaunchKernelGGL(k_inf_fill_slots, dim3(n_chunks), dim3(256), 0, st, d_fast, d_slot_chunk, d_tslot_chunk);
+    if (!K.seq) {
+        const u64 max_bits = 8 * L.max_clen + 32;
         dim3 gscan((unsigned)((max_bits + (u64)SCAN_SPANS * SCAN_SPAN_BITS - 1) / ((u64)SCAN_SPANS * SCAN_SPAN_BITS)), n_chunks);
-        u64 *d_surv = (u64 *)(S + l.surv);
-        u32 *d_surv_cnt = (u32 *)(S + l.surv_cnt);
         MTS_HIP(hipMemsetAsync(d_surv_cnt, 0, 4, st));
-        u64 final_zone_bits = SCAN_FINAL_ZONE_BITS;                  // (MTS_SCAN_FINAL_ZONE = bytes: the tests shrink it below a block's length)
-        if (const char *e = getenv("MTS_SCAN_FINAL_ZONE")) final_zone_bits = 8ull * (u64)atoll(e);
         hipLaunchKernelGGL(k_inf_scan, gscan, dim3(SCAN_THREADS), 0, st, d_cdata, d_chunks, d_fast, d_cand_pos, d_cand_cnt, d_surv,
-                           d_surv_cnt, l.surv_cap, final_zone_bits);
-        hipLaunchKernelGGL(k_inf_validate, dim3(std::min((l.surv_cap + 255) / 256, 2048u)), dim3(256), 0, st, d_cdata, d_chunks, d_fast, d_surv,
-                           d_surv_cnt, l.surv_cap, d_cand_pos, d_cand_cnt);
+                           d_surv_cnt, L.surv_cap, K.final_zone_bits);
+        hipLaunchKernelGGL(k_inf_validate, dim3(std::min((L.surv_cap + 255) / 256, 2048u)), dim3(256), 0, st, d_cdata, d_chunks, d_fast, d_surv,
+                           d_surv_cnt, L.surv_cap, d_cand_pos, d_cand_cnt);
         hipLaunchKernelGGL(k_inf_sortc, dim3(n_chunks), dim3(256), 0, st, d_fast, d_cand_pos, d_cand_tmp, d_cand_cnt);
-        inflate_mark(engine, st, "inflate_scan");
-        const int use_rows = getenv("MTS_INF_NO_ROWS") ? 0 : 1;      // (A/B: pass B decodes every block again)
-        MTS_HIP(hipMemsetAsync(S + l.row_ctr, 0, 4, st));
-        hipLaunchKernelGGL(k_inf_passA, dim3(l.total_cand), dim3(64), 0, st, d_cdata, d_chunks, d_fast, (const u32 *)(S + l.slot_chunk),
-                           d_cand_pos, d_cand_cnt, d_cres, d_subs, (u32 *)(S + l.rows), (u32 *)(S + l.row_ctr), use_rows ? l.rounds_cap : 0u,
-                           (u32 *)(S + l.round_row));
-        inflate_mark(engine, st, "inflate_passA");
+        E.t_mark(st, "inflate_scan");
+        MTS_HIP(hipMemsetAsync(d_row_ctr, 0, 4, st));
+        hipLaunchKernelGGL(k_inf_passA, dim3(L.total_cand), dim3(64), 0, st, d_cdata, d_chunks, d_fast, d_slot_chunk, d_cand_pos, d_cand_cnt,
+                           d_cres, d_subs, d_rows, d_row_ctr, use_rows ? L.rounds_cap : 0u, d_round_row);
+        E.t_mark(st, "inflate_passA");
         hipLaunchKernelGGL(k_inf_chain, dim3(n_chunks), dim3(64), 0, st, d_cdata, d_chunks, d_fast, d_cand_pos, d_cand_cnt, d_cres,
                            d_tblk, d_true_cnt, d_res, d_seq);
-        inflate_mark(engine, st, "inflate_chain");
-        hipLaunchKernelGGL(k_inf_passB, dim3(l.total_true), dim3(64 * PASSB_WAVES), 0, st, d_cdata, d_chunks, d_fast, (const u32 *)(S + l.tslot_chunk),
+        E.t_mark(st, "inflate_chain");
+        hipLaunchKernelGGL(k_inf_passB, dim3(L.total_true), dim3(64 * PASSB_WAVES), 0, st, d_cdata, d_chunks, d_fast, d_tslot_chunk,
                            d_tblk, d_true_cnt, d_cres, d_subs, d_tokens, d_res, use_rows);
         if (use_rows)
-            hipLaunchKernelGGL(k_inf_move_rows, dim3(l.total_true), dim3(MOVE_THREADS), 0, st, d_chunks, d_fast, (const u32 *)(S + l.tslot_chunk), d_tblk,
-                               d_true_cnt, d_cres, d_subs, (const u32 *)(S + l.rows), (const u32 *)(S + l.round_row), d_tokens);
-        inflate_mark(engine, st, "inflate_passB");
+            hipLaunchKernelGGL(k_inf_move_rows, dim3(L.total_true), dim3(MOVE_THREADS), 0, st, d_chunks, d_fast, d_tslot_chunk, d_tblk,
+                               d_true_cnt, d_cres, d_subs, d_rows, d_round_row, d_tokens);
+        E.t_mark(st, "inflate_passB");
     }
-    hipLaunchKernelGGL(k_inf_wave, dim3(n_chunks), dim3(WV_NT), 0, st, d_cdata, d_chunks, n_chunks, d_tokens, d_res, fast_path ? d_seq : nullptr);
-    inflate_mark(engine, st, "inflate_wave_decoder");
-    dbg_status(st, d_res, n_chunks, "after decode");
-    {
-        u32 max_groups = 1;
-        for (int i = 0; i < n_chunks; i++) { const u32 gmax = (u32)(((u64)nn[i] + 2 + 63) / 64); if (gmax > max_groups) max_groups = gmax; }
-        dim3 gg((max_groups + GS_TILE - 1) / GS_TILE, n_chunks);
-        hipLaunchKernelGGL(k_inf_gsum, gg, dim3(GS_TILE), 0, st, d_tokens, d_chunks, d_res, (const u64 *)(S + l.gb_off),
-                           (const u64 *)(S + l.tb_off), (u32 *)(S + l.gbase), (u32 *)(S + l.tile_base));
-        hipLaunchKernelGGL(k_inf_gscan, dim3(n_chunks), dim3(64), 0, st, d_res, (const u64 *)(S + l.tb_off), (u32 *)(S + l.tile_base));
-        hipLaunchKernelGGL(k_inf_plan, dim3((n_chunks + 63) / 64), dim3(64), 0, st, d_res, (const u64 *)(S + l.gb_off), (const u64 *)(S + l.tb_off),
-                           (const u32 *)(S + l.gbase), (const u32 *)(S + l.tile_base), n_chunks, l.nseg, (LzPlan *)(S + l.plan));
-    }
-    inflate_mark(engine, st, "inflate_offsets");
-    u64 *d_prof = nullptr;                   // MTS_LZ_PROF=1: per-wave cycle counters of the resolver, printed to stderr
-    if (getenv("MTS_LZ_PROF")) { MTS_HIP(hipMalloc(&d_prof, (size_t)n_chunks * 16 * 8 * 8)); MTS_HIP(hipMemsetAsync(d_prof, 0, (size_t)n_chunks * 16 * 8 * 8, st)); }
-    const int first_pass = getenv("MTS_LZ_FORCE_RETRY") ? 2 : 0;    // (tests: pretend every chunk's first run gave up, so that the retry pass does the work)
-    hipLaunchKernelGGL(k_inf_lz, dim3(n_chunks), dim3(LZ_THREADS), LZ_LDS, st, d_tokens, d_chunks, d_res, (const u64 *)(S + l.gb_off),
-                       (const u64 *)(S + l.tb_off), (const u32 *)(S + l.gbase), (const u32 *)(S + l.tile_base), d_stream, lz_workers,
-                       d_prof, (const LzPlan *)(S + l.plan), first_pass);
-    hipLaunchKernelGGL(k_inf_lz, dim3(n_chunks), dim3(LZ_THREADS), LZ_LDS, st, d_tokens, d_chunks, d_res, (const u64 *)(S + l.gb_off),
-                       (const u64 *)(S + l.tb_off), (const u32 *)(S + l.gbase), (const u32 *)(S + l.tile_base), d_stream, 1,
-                       nullptr, (const LzPlan *)(S + l.plan), 1);                                  // (retry pass: returns at once unless a wait expired)
-    if (l.nseg > 1 && max_n > 0) {
-        MTS_HIP(hipMemsetAsync(S + l.gflag, 0, l.seg_adler - l.gflag, st));
-        MTS_HIP(hipMemsetAsync(S + l.seg_adler, 0, (size_t)n_chunks * LZ_MAXSEG * LZ_FLUSHERS * 16, st));
+    hipLaunchKernelGGL(k_inf_wave, dim3(n_chunks), dim3(WV_NT), 0, st, d_cdata, d_chunks, n_chunks, d_tokens, d_res, K.seq ? nullptr : d_seq);
+    E.t_mark(st, "inflate_wave_decoder");
+    if (K.debug_status) dbg_status(st, d_res, n_chunks, "after decode");
+    hipLaunchKernelGGL(k_inf_gsum, dim3((L.max_groups + GS_TILE - 1) / GS_TILE, n_chunks), dim3(GS_TILE), 0, st, d_tokens, d_chunks, d_res, d_gb_off,
+                       d_tb_off, d_gbase, d_tile_base);
+    hipLaunchKernelGGL(k_inf_gscan, dim3(n_chunks), dim3(64), 0, st, d_res, d_tb_off, d_tile_base);
+    hipLaunchKernelGGL(k_inf_plan, dim3((n_chunks + 63) / 64), dim3(64), 0, st, d_res, d_gb_off, d_tb_off, d_gbase, d_tile_base, n_chunks, L.nseg, d_plan);
+    E.t_mark(st, "inflate_offsets");
+    u64 *d_prof = nullptr;
+    if (K.lz_prof) { MTS_HIP(hipMalloc(&d_prof, lz_prof_bytes(n_chunks))); MTS_HIP(hipMemsetAsync(d_prof, 0, lz_prof_bytes(n_chunks), st)); }
+    hipLaunchKernelGGL(k_inf_lz, dim3(n_chunks), dim3(LZ_THREADS), LZ_LDS, st, d_tokens, d_chunks, d_res, d_gb_off, d_tb_off, d_gbase, d_tile_base,
+                       d_stream, K.lz_workers, d_prof, d_plan, first_pass);
+    hipLaunchKernelGGL(k_inf_lz, dim3(n_chunks), dim3(LZ_THREADS), LZ_LDS, st, d_tokens, d_chunks, d_res, d_gb_off, d_tb_off, d_gbase, d_tile_base,
+                       d_stream, 1, nullptr, d_plan, 1);      // (retry pass: returns at once unless a wait expired)
+    if (cut) {
+        MTS_HIP(hipMemsetAsync(S + L.clear[0].off, 0, L.clear[0].bytes, st));
+        MTS_HIP(hipMemsetAsync(S + L.clear[1].off, 0, L.clear[1].bytes, st));
         for (int pass = 0; pass < 2; pass++)
-            hipLaunchKernelGGL(k_inf_lz_seg, dim3(l.nseg, n_chunks), dim3(LZ_THREADS), LZ2_LDS, st, d_tokens, d_chunks, d_res,
-                               (const u64 *)(S + l.gb_off), (const u64 *)(S + l.tb_off), (const u32 *)(S + l.gbase), (const u32 *)(S + l.tile_base),
-                               (const LzPlan *)(S + l.plan), (u16 *)(S + l.sym), pass ? 1 : lz_workers, pass ? 1 : first_pass, d_stream,
-                               (u8 *)(S + l.gflag), (u64 *)(S + l.seg_adler));
+            hipLaunchKernelGGL(k_inf_lz_seg, dim3(L.nseg, n_chunks), dim3(LZ_THREADS), LZ2_LDS, st, d_tokens, d_chunks, d_res, d_gb_off, d_tb_off, d_gbase,
+                               d_tile_base, d_plan, d_cells, pass ? 1 : K.lz_workers, pass ? 1 : first_pass, d_stream, d_gflag, d_seg_adler);
     }
     hipLaunchKernelGGL(k_inf_lz_settle, dim3((n_chunks + 63) / 64), dim3(64), 0, st, d_res, n_chunks);
     MTS_HIP(hipMemsetAsync(d_adler_acc, 0, sizeof(u64) * 2 * n_chunks, st));      // (the translation of segmented chunks adds their byte sums)
-    if (l.nseg > 1 && max_n > 0) {
-        hipLaunchKernelGGL(k_inf_windows, dim3(n_chunks), dim3(1024), 0, st, d_chunks, d_res, (const LzPlan *)(S + l.plan),
-                           (const u16 *)(S + l.sym), (u8 *)(S + l.win), d_stream, (const u8 *)(S + l.gflag));
-        hipLaunchKernelGGL(k_inf_translate, dim3((max_n + 16383) / 16384, n_chunks), dim3(256), 0, st, d_chunks, d_res,
-                           (const LzPlan *)(S + l.plan), (const u16 *)(S + l.sym), (const u8 *)(S + l.win), d_stream, d_adler_acc, (const u8 *)(S + l.gflag));
+    if (cut) {
+        hipLaunchKernelGGL(k_inf_windows, dim3(n_chunks), dim3(1024), 0, st, d_chunks, d_res, d_plan, d_cells, d_win, d_stream, d_gflag);
+        hipLaunchKernelGGL(k_inf_translate, dim3((max_n + 16383) / 16384, n_chunks), dim3(256), 0, st, d_chunks, d_res, d_plan, d_cells, d_win,
+                           d_stream, d_adler_acc, d_gflag);
     }
     MTS_HIP(hipGetLastError());
-    if (d_prof) {
-        std::vector<u64> hp((size_t)n_chunks * 16 * 8);
-        MTS_HIP(hipStreamSynchronize(st));
-        MTS_HIP(hipMemcpy(hp.data(), d_prof, hp.size() * 8, hipMemcpyDeviceToHost));
-        MTS_HIP(hipFree(d_prof));
-        u64 a[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nw = 0;
-        for (int c = 0; c < n_chunks; c++) for (int w = 0; w < 16; w++) { const u64 *q = &hp[((size_t)c * 16 + w) * 8]; if (!q[5]) continue; nw++; for (int k = 0; k < 8; k++) a[k] += q[k]; }
-        if (nw) fprintf(stderr, "[lz prof] waves %d  per wave: total %.0f  wait %.0f  pre %.0f  loop %.0f cycles; groups %.0f  iters/group %.2f  cycles/group %.0f  vmwait %.0f  sleeps %.0f\n", nw,
-                        (double)a[0] / nw, (double)a[1] / nw, (double)a[2] / nw, (double)a[3] / nw, (double)a[5] / nw, (double)a[4] / a[5], (double)a[0] / a[5], (double)a[6] / nw, (double)a[7] / nw);
-    }
-    inflate_mark(engine, st, "inflate_lz");
-    dbg_status(st, d_res, n_chunks, "after lz");
+    if (d_prof) { if (int rc = lz_prof_report(st, d_prof, n_chunks)) return rc; }
+    E.t_mark(st, "inflate_lz");
+    if (K.debug_status) dbg_status(st, d_res, n_chunks, "after lz");
     // byte sums of the chunks that did not go through the translation (resolved as bytes by k_inf_lz)
-    int rc = launch_adler_stream(st, d_stream, (const u64 *)(S + l.so), (const u32 *)(S + l.nn), n_chunks, max_n, d_adler_acc,
-                                 (const u32 *)(S + l.plan), (u32)(sizeof(LzPlan) / 4));
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_inf_finish, dim3((n_chunks + 63) / 64), dim3(64), 0, st, d_chunks, d_res, d_adler_acc, n_chunks,
-                       d_status_out, l.nseg > 1 && max_n > 0 ? (const u64 *)(S + l.seg_adler) : nullptr);
+    if (int rc = launch_adler_stream(st, d_stream, d_so, d_nn, n_chunks, max_n, d_adler_acc, d_plan_words, LZ_PLAN_WORDS)) return rc;
+    hipLaunchKernelGGL(k_inf_finish, dim3((n_chunks + 63) / 64), dim3(64), 0, st, d_chunks, d_res, d_adler_acc, n_chunks, d_status_out,
+                       cut ? d_seg_adler : nullptr);
     MTS_HIP(hipGetLastError());
-    inflate_mark(engine, st, "adler32");
-    dbg_status(st, d_res, n_chunks, "after adler");
+    E.t_mark(st, "adler32");
+    if (K.debug_status) dbg_status(st, d_res, n_chunks, "after adler");
     return MTS_OK;
 }
 

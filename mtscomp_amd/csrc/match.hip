@@ -202,7 +202,7 @@ __global__ __launch_bounds__(M5W * 64) void k_match5(const u8 *__restrict__ stre
     auto ring_x = [&](u32 o8) -> u64 { return *(lds_u64p)(size_t)(((o8 & (M5_RING * 8 - 8)) | se_base) + M5W * M5_RING * 8); };
 #endif
     u32 *T = tables + td.stream_off, *TQ = quarter + td.stream_off;
-    u32 *sink = flags + 63 + (blockIdx.x & (MATCH_SINK_BYTES / 256 - 1)) * 64 + (threadIdx.x & 63);      // (this lane's word of a line per workgroup)
+    u32 *sink = flags + MATCH_SINK_WORD0 + (blockIdx.x & (MATCH_SINK_LINES - 1)) * MATCH_SINK_LINE_WORDS + (threadIdx.x & 63);      // (this lane's word of a line per workgroup)
     if (threadIdx.x < 2 && slice == 0) {
         const u32 hashed_end = td.w + td.wlen;
         const u32 p = hashed_end + threadIdx.x;

@@ -3,8 +3,9 @@
 // tests/test_feed_plan.py.  Reductions: small chunk tables, every residency mask, compressed bytes with and without gaps, five piece
 // sizes; the staging layout, the tile family's plan and, through a stand-in for each op's map from units to rows, the halo family's.
 // Codec: the compress and inflate batch geometry at every size where the arithmetic turns (0 .. 3 bytes, a segment, the history, a
-// tile, 2^31), the sub-batch cut, the phase width of levels 1..3 and both staging rules, each property stated from what the kernels and
-// the copies need, not from the code.  Exits 1 with the case printed at the first property that fails.
+// tile, 2^31), the arrays inside the compress workspaces and the match stage's sink, every region of the inflate kernels' scratch with
+// its per-chunk capacities, the sub-batch cut, the phase width of levels 1..3 and both staging rules, each property stated from what the
+// kernels and the copies need, not from the code.  Exits 1 with the case printed at the first property that fails.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -244,7 +245,7 @@ static void check_halo_ops(const Table &T, const FeedPlan &F, size_t piece, long
 typedef unsigned long long ull;
 static size_t dim_sort_ws(int n_tiles) { return (size_t)(n_tiles + 1) * 48; }
 static size_t dim_marks(size_t n_segs) { return (n_segs + 64) / 64 * 64 * 4; }
-static const CompressDims DIMS = {dim_sort_ws, dim_marks, 14, 40, 24, 320, 96, 65536};
+static const CompressDims DIMS = {dim_sort_ws, dim_marks, 14, 40, 24, 320, 96, MATCH_SINK_BYTES};
 static const ull TWO31 = 1ull << 31;
 
 // ---- a compress batch: chunk i is n[i] bytes (raw_is_stream: bounds in bytes; else rows of row_bytes)
@@ -306,6 +307,27 @@ static void check_compress(const std::vector<ull> &rows, ull row_bytes, bool raw
     CHECK(P.blkcodes >= (blk + 1) * 320 * 4 && P.blkhdr >= (blk + 1) * 96 * 4 && P.adler >= 16ull * nc + 8 + 65536 && P.misc >= 12ull * nc);
     CHECK(P.o_chunks % 256 == 0 && P.o_tiles % 256 == 0 && P.o_cout % 256 == 0);
     CHECK(P.o_chunks + sizeof(ChunkDesc) * nc <= P.o_tiles && P.o_tiles + sizeof(TileDesc) * (tile + 1) <= P.o_cout && P.o_cout + 24ull * nc <= P.desc);
+    // the arrays inside segbuf, blk, adler and misc: apart, and inside the bytes the plan asks for
+    {
+        struct Sub { size_t off, bytes; };
+        auto apart = [&](std::vector<Sub> v, size_t cap) {
+            std::sort(v.begin(), v.end(), [](const Sub &a, const Sub &b) { return a.off < b.off; });
+            for (size_t k = 0; k < v.size(); k++) CHECK(v[k].off + v[k].bytes <= (k + 1 < v.size() ? v[k + 1].off : cap));
+        };
+        const size_t SN = (seg + 64) * 4, BN = blk + 1;                                 // a per-segment array in bytes; block slots and one more
+        apart({{P.seg.entry * 4, SN}, {P.seg.exit_a * 4, SN}, {P.seg.exit_b * 4, SN}, {P.seg.cnt * 4, SN}, {P.seg.tokbase * 4, SN}, {P.seg.seg_chunk * 4, SN},
+               {P.seg.seg_start * 4, SN}, {P.seg.cp * 4, SN * DIMS.parse_cp_words}}, P.segbuf);
+        apart({{P.bk.blocks, BN * DIMS.block_rec_bytes}, {P.bk.chunk, BN * 4}, {P.bk.in_start, BN * 4}}, P.blk);
+        CHECK(P.bk.blocks % 8 == 0 && P.bk.chunk % 4 == 0 && P.bk.in_start % 4 == 0);
+        // the match stage's sink: MATCH_SINK_LINES lines of MATCH_SINK_LINE_WORDS words from word MATCH_SINK_WORD0 behind the first flag word;
+        // a workgroup's line is its index under the mask, a lane's word its number in the wave
+        const size_t sink_words = (size_t)MATCH_SINK_WORD0 + (size_t)(MATCH_SINK_LINES - 1) * MATCH_SINK_LINE_WORDS + 63 + 1;
+        CHECK(P.ad.sink == P.ad.flags + 4 * (size_t)MATCH_SINK_WORD0 && P.ad.flags + 4 * sink_words <= P.adler);
+        apart({{P.ad.sums, 16ul * nc}, {P.ad.changed, 4}, {P.ad.flags, 4}, {P.ad.sink, 4 * sink_words - 4 * (size_t)MATCH_SINK_WORD0}}, P.adler);
+        CHECK(P.ad.flags == P.ad.changed + 4 && P.ad.changed % 4 == 0);                // (the two flag words are cleared and read as one 8-byte range)
+        apart({{P.mi.so, 8ul * nc}, {P.mi.nn, 4ul * nc}}, P.misc);
+        CHECK(P.mi.so % 8 == 0 && P.mi.nn % 4 == 0);
+    }
     // the index arrays agree with cd
     std::vector<u32> h_seg, h_blk;
     P.index_arrays(h_seg, h_blk);
@@ -352,6 +374,88 @@ static void check_inflate(const std::vector<ull> &rows, int nc, int sz, int nc_f
     P.fill(h.data());
     CHECK(!memcmp(h.data() + P.o_ic, P.ic.data(), size[0]) && !memcmp(h.data() + P.o_so, P.so.data(), size[1]) && !memcmp(h.data() + P.o_nn, P.nn.data(), size[2]) &&
           !memcmp(h.data() + P.o_oo, P.oo.data(), size[3]) && !memcmp(h.data() + P.o_rows, P.rows.data(), size[4]));
+}
+
+// ---- the scratch of an inflate batch: chunk i is c_len[i] compressed bytes that inflate to n[i]
+static long n_scratch = 0;
+static const InflateDims IDIMS ={32, 24, 268, 512, 192, 8, 256, 32, 32768, 4096, 2};      // (inflate.hip's records and constants)
+
+static void check_inflate_scratch(const std::vector<ull> &n, const std::vector<ull> &c_len, int lz_segs, long row_rounds)
+{
+    const int nc = (int)n.size();
+    std::vector<long> c_off(nc), c_l(nc), n_rows(nc), out_off(nc);
+    for (int i = 0; i < nc; i++) { c_off[i] = 5000l * i; c_l[i] = (long)c_len[i]; n_rows[i] = (long)n[i]; out_off[i] = 0; }
+    const InflatePlan P(c_off.data(), c_l.data(), n_rows.data(), out_off.data(), nc, 1, 1, 0, 24);
+    CHECK(!P.error[0]);
+    const InflateScratch L(P, IDIMS, lz_segs, row_rounds);
+    // a direct recount of what the kernels index with
+    const ull GS = IDIMS.gs_tile;
+    std::vector<ull> cap(nc), cand0(nc + 1, 0), g(nc), g0(nc + 1, 0), t0(nc + 1, 0);
+    ull cbits = 0, cells = 0, share = 0, max_clen = 0, max_groups = 1;
+    for (int i = 0; i < nc; i++) {
+        cap[i] = c_len[i] / 4096 + 64; cand0[i + 1] = cand0[i] + cap[i];
+        g[i] = (n[i] + 2 + 63) / 64 + 2;                                                 // groups of 64 tokens (tokens <= bytes + 1), and two more
+        g0[i + 1] = g0[i] + g[i]; t0[i + 1] = t0[i] + g[i] / GS + 2;
+        cbits += 8 * c_len[i]; cells += up256(n[i] + STREAM_PAD); share += c_len[i] * 8 / (64 * 640) + 32;
+        max_clen = std::max(max_clen, c_len[i]); max_groups = std::max(max_groups, (n[i] + 2 + 63) / 64);
+    }
+    const ull tc = cand0[nc], tt = 2 * tc;
+    const int nseg = std::min(lz_segs ? lz_segs : nc < 128 ? 256 / nc : 1, (int)IDIMS.lz_maxseg);
+    const ull rounds = std::min<ull>(row_rounds >= 0 ? (ull)row_rounds : share, 0x3ffffffull);
+    CHECK(L.nseg == nseg && L.rounds_cap == rounds && L.total_cand == tc && L.total_true == tt && tt < (1ull << 32));
+    CHECK(L.surv_cap == cbits / 256 + 65536 && L.max_clen == max_clen && L.max_groups == max_groups);
+    // every region: 256-aligned, in the order of the members, disjoint, inside [0, end)
+    const struct { const char *name; size_t off; } members[] = {
+        {"so", L.so}, {"nn", L.nn}, {"fast", L.fast}, {"gb_off", L.gb_off}, {"tb_off", L.tb_off}, {"cand_cnt", L.cand_cnt}, {"true_cnt", L.true_cnt},
+        {"seq_flag", L.seq_flag}, {"slot_chunk", L.slot_chunk}, {"tslot_chunk", L.tslot_chunk}, {"cand_pos", L.cand_pos}, {"cand_tmp", L.cand_tmp},
+        {"cres", L.cres}, {"tblk", L.tblk}, {"subs", L.subs}, {"gbase", L.gbase}, {"tile_base", L.tile_base}, {"surv", L.surv}, {"surv_cnt", L.surv_cnt},
+        {"plan", L.plan}, {"win", L.win}, {"rows_cells", L.rows_cells}, {"round_row", L.round_row}, {"row_ctr", L.row_ctr}, {"gflag", L.gflag},
+        {"seg_adler", L.seg_adler}};
+    const size_t NR = sizeof members / sizeof members[0];
+    CHECK(L.regions.size() == NR && L.regions[0].off == 0);
+    auto bytes_of = [&](const char *name) { for (const auto &r : L.regions) if (!strcmp(r.name, name)) return r.bytes; CHECK(!"region"); return (size_t)0; };
+    for (size_t r = 0; r < NR; r++) {
+        CHECK(!strcmp(L.regions[r].name, members[r].name) && L.regions[r].off == members[r].off && members[r].off % 256 == 0);
+        CHECK(members[r].off + L.regions[r].bytes <= (r + 1 < NR ? members[r + 1].off : L.end));
+    }
+    CHECK(L.end % 256 == 0);
+    // what each region must hold
+    const ull un = (ull)nc;
+    CHECK(bytes_of("so") >= 8 * un && bytes_of("nn") >= 4 * un && bytes_of("fast") >= 24 * un && bytes_of("gb_off") >= 8 * un && bytes_of("tb_off") >= 8 * un);
+    CHECK(bytes_of("cand_cnt") >= 4 * un && bytes_of("true_cnt") >= 4 * un && bytes_of("seq_flag") >= 4 * un && bytes_of("plan") >= IDIMS.lz_plan_bytes * un);
+    CHECK(bytes_of("slot_chunk") >= 4 * tc && bytes_of("tslot_chunk") >= 4 * tt && bytes_of("cand_pos") >= 8 * tc && bytes_of("cand_tmp") >= 8 * tc);
+    CHECK(bytes_of("cres") >= IDIMS.cand_res_bytes * tc && bytes_of("tblk") >= IDIMS.true_blk_bytes * tt && bytes_of("subs") >= 8ull * IDIMS.subcap * tc);
+    CHECK(bytes_of("round_row") >= 4ull * IDIMS.rounds_max * tc && bytes_of("row_ctr") >= 4 && bytes_of("surv_cnt") >= 4 && bytes_of("surv") >= 8ull * L.surv_cap);
+    CHECK(bytes_of("gbase") >= 4 * g0[nc] && bytes_of("tile_base") >= 4 * t0[nc]);
+    // the per-chunk ranges partition their regions: candidate slots, twice as many true-block slots, group bases, tile bases
+    for (int i = 0; i < nc; i++) {
+        const InfFast &f = L.h_fast[i];
+        CHECK(f.cand_off == cand0[i] && f.cand_cap == cap[i] && f.true_off == 2 * cand0[i] && f.true_cap == 2 * cap[i] && f.pad == 0);
+        CHECK(L.gb[i] == g0[i] && L.tb[i] == t0[i]);
+        CHECK(InflateScratch::groups_of((u32)n[i]) == g[i] && InflateScratch::tiles_of((u32)n[i], IDIMS.gs_tile) == g[i] / GS + 2);
+        CHECK(g[i] * 64 >= n[i] + 1 + 2 * 64 && (g[i] / GS + 2) * GS >= g[i] + GS);     // room for every token, and slack of two groups / a tile
+    }
+    // the host row: five regions in a row at the head, one copy; fill writes them and nothing else
+    CHECK(L.host_off == L.so && L.host_off + L.host_bytes == L.cand_cnt && L.so < L.nn && L.nn < L.fast && L.fast < L.gb_off && L.gb_off < L.tb_off);
+    std::vector<u8> h(L.host_bytes, 0xEE), want(L.host_bytes, 0xEE);
+    L.fill(h.data());
+    memcpy(want.data() + (L.so - L.host_off), P.so.data(), 8 * un); memcpy(want.data() + (L.nn - L.host_off), P.nn.data(), 4 * un);
+    memcpy(want.data() + (L.gb_off - L.host_off), g0.data(), 8 * un); memcpy(want.data() + (L.tb_off - L.host_off), t0.data(), 8 * un);
+    for (int i = 0; i < nc; i++) {
+        const InfFast f = {cand0[i], (u32)cap[i], (u32)(2 * cand0[i]), (u32)(2 * cap[i]), 0};
+        memcpy(want.data() + (L.fast - L.host_off) + sizeof f * i, &f, sizeof f);
+    }
+    CHECK(h == want);
+    // the range the resolver zeroes: gflag and seg_adler, in two clears that meet, and nothing else (they are the last two regions)
+    CHECK(L.clear[0].off == L.gflag && L.clear[0].off + L.clear[0].bytes == L.clear[1].off && L.clear[1].off == L.seg_adler);
+    CHECK(L.clear[0].bytes >= bytes_of("gflag") && L.clear[1].bytes == bytes_of("seg_adler") && L.clear[1].off + L.clear[1].bytes <= L.end);
+    CHECK(L.gflag > L.row_ctr && L.seg_adler >= L.gflag && (nseg > 1 || L.clear[0].bytes + L.clear[1].bytes == 0));
+    // one region for pass A's token rows and the resolver's cells: it holds the larger
+    CHECK(bytes_of("rows_cells") >= rounds * 64 * IDIMS.rowcap * 4 && bytes_of("rows_cells") >= (nseg > 1 ? 2 * cells : 0));
+    // windows, flags and check sums: there exactly when the chunks are cut
+    CHECK((bytes_of("win") == 0) == (nseg == 1) && (bytes_of("gflag") == 0) == (nseg == 1) && (bytes_of("seg_adler") == 0) == (nseg == 1));
+    if (nseg > 1) CHECK(bytes_of("win") >= un * IDIMS.lz_maxseg * IDIMS.lz_win && bytes_of("gflag") >= cells / IDIMS.lz_flush + un &&
+                        bytes_of("seg_adler") >= un * IDIMS.lz_maxseg * IDIMS.lz_flushers * 16);
 }
 
 // ---- the sub-batch cut
@@ -517,6 +621,24 @@ static void check_codec_plans()
         check_inflate({TWO31 - 1}, 1, 1, 0);
         check_inflate({1, TWO31 / 4}, 2, 2, 0);
     }
+    // inflate scratch: chunk counts around the segment rule's 128; sizes either side of a whole number of groups (n + 2 a multiple of 64), of
+    // GS_TILE groups (a chunk's tile count, the grid of the group sums); compressed lengths around a candidate slot's 4096 bytes; both overrides
+    {
+        const ull sizes[] = {0, 1, 61, 62, 63, 126, 127, 16189, 16190, 16191, 16192, 16381, 16382, 16383, 16384}, clens[] = {0, 1, 4095, 4096, 4097};
+        const int NS = sizeof sizes / sizeof sizes[0], NL = sizeof clens / sizeof clens[0];
+        for (int nc : {1, 2, 3, 5, 127, 128, 129, 300}) for (int segs : {0, 1, 4, 40}) for (long rounds : {-1l, 0l, 3l, (1l << 26) + 5}) {
+            const std::string base = "inflate scratch chunks " + std::to_string(nc) + " segs " + std::to_string(segs) + " rounds " + std::to_string(rounds);
+            std::vector<ull> n(nc), cl(nc);
+            for (int a = 0; a < NS; a++) for (int b = 0; b < NL; b++) {
+                g_case = base + " mixed from size " + std::to_string(sizes[a]) + " c_len " + std::to_string(clens[b]);
+                for (int i = 0; i < nc; i++) { n[i] = sizes[(a + i) % NS]; cl[i] = clens[(b + 3 * i) % NL]; }
+                check_inflate_scratch(n, cl, segs, rounds);
+                g_case = base + " all of size " + std::to_string(sizes[a]) + " c_len " + std::to_string(clens[b]);
+                check_inflate_scratch(std::vector<ull>(nc, sizes[a]), std::vector<ull>(nc, clens[b]), segs, rounds);
+                n_scratch += 2;
+            }
+        }
+    }
     // the sub-batch cut
     for (int t = 0; t < 400; t++) {
         const int n = t < 3 ? t : 1 + (int)(rng() % 40);
@@ -639,6 +761,6 @@ int main()
         }
     }
     check_codec_plans();
-    printf("plan_check: %ld tables x pieces and the codec's plans passed\n", n_cases);
+    printf("plan_check: %ld tables x pieces and the codec's plans (%ld inflate scratch layouts) passed\n", n_cases, n_scratch);
     return 0;
 }

@@ -300,6 +300,30 @@ def test_inflate_segmented_resolver(monkeypatch, nseg):
             assert st == 0 and out == data, (len(data), level, st, _first_diff(np.frombuffer(out, np.uint8), np.frombuffer(data, np.uint8)))
 
 
+def test_inflate_where_the_segment_rule_turns(monkeypatch):
+    """The resolver cuts every chunk of a batch of fewer than 128 chunks into 256 / chunks segments (two at 127 chunks) and
+    none from 128 chunks on; the scratch plan sizes the windows, cells, flags and check sums by that rule.  One batch each of
+    127, 128 and 129 chunks of int16 x 8 channels with unequal row counts, one of them without rows, zlib level 6: the original
+    bytes and status 0, in the default environment and with four segments forced."""
+    rng = np.random.default_rng(128)
+    rows = [(37 * i + 11) % 201 for i in range(129)]
+    rows[5] = 0
+    bounds = np.concatenate(([0], np.cumsum(rows)))
+    x = np.cumsum(rng.integers(-20, 21, (int(bounds[-1]), 8)), axis=0).astype(np.int16)
+    chunks = [x[bounds[i]:bounds[i + 1]] for i in range(129)]
+    z = [O.ref_compress_chunk(c, level=6) if len(c) else zlib.compress(b'', 6) for c in chunks]
+    flags = hip.make_flags(True, False, 'F')
+    monkeypatch.delenv('MTS_LZ_SEGS', raising=False)
+    for segs in (None, '4'):
+        if segs:
+            monkeypatch.setenv('MTS_LZ_SEGS', segs)
+        for n in (127, 128, 129):
+            st, arrs = hip.decompress_chunks(z[:n], rows[:n], 8, 'int16', flags)
+            assert st == [0] * n, (segs, n, [i for i, s in enumerate(st) if s])
+            for i in range(n):
+                assert arrs[i].shape == (rows[i], 8) and np.array_equal(arrs[i], chunks[i]), (segs, n, i)
+
+
 def test_inflate_other_encoders():
     data = CASES['text_100k']
     for strategy in (zlib.Z_FILTERED, zlib.Z_HUFFMAN_ONLY, zlib.Z_RLE, zlib.Z_FIXED):
