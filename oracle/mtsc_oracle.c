@@ -29,6 +29,8 @@
  *                        the parse-independent per-position candidate tables + state machine of
  *                        SURVEY.md Appendix A.3 -- this is the shape the HIP kernels use, so the GPU
  *                        intermediates can be compared stage by stage.
+ *   orc_match_trace()    orc_match_tables()'s walk once more, reporting how each position came to its result
+ *                        (tests/match_cases.py certifies its cases with it).
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -746,6 +748,82 @@ int orc_match_tables(const uint8_t *in, long n, int level, uint32_t *t_full, uin
         if (!q_done) t_quarter[p] = SNAP();
         t_full[p] = SNAP();
 #undef SNAP
+    }
+    free(head); free(prev);
+    return ORC_OK;
+}
+
+/*
+ * orc_match_tables()'s walk once more, reporting HOW every position came to its result: what tests/match_cases.py certifies its
+ * cases with (the candidate that wins is exactly the chain-th one, the walk ended at the distance limit with budget left, ...).
+ * rec: ORC_TRACE_WORDS int32 per position:
+ *   [0] candidates visited (compared), [1] why the walk ended (ORC_END_*), [2] / [3] 1-based chain index of the candidate the
+ *   full / the quarter result is from (0: none), [4] distance of the chain head (0: none; also given when it is too far),
+ *   [5] visited candidates with the position's hash and other bytes 0..2, [6] visited candidates equal in bytes 0..2 and not in
+ *   byte 3, [7] length of the match with the chain's next element, the one NOT visited: whatever ended the walk (position 0
+ *   included when the chain ends there with the position's hash; after nice_match only an element inside the limit; 0: there
+ *   is none), [8] 1: the candidate behind the quarter budget (index chain / 4 + 1) was visited and is
+ *   longer than the quarter result, [9] / [10] t_full / t_quarter as orc_match_tables packs them.
+ * d_budget / d_limit are added to the chain budget / to MAX_DIST: 0 in every test but the one that shows that a reference off
+ * by one is caught.
+ */
+#define ORC_TRACE_WORDS 11
+#define ORC_END_NONE 0        /* no walk: fewer than 3 bytes, no chain head, or the head is too far */
+#define ORC_END_NICE 1
+#define ORC_END_BUDGET 2
+#define ORC_END_LIMIT 3       /* the next element is MAX_DIST or more away */
+#define ORC_END_CHAIN 4       /* the chain ended (NIL, which position 0 is as well) */
+int orc_match_trace(const uint8_t *in, long n, int level, int d_budget, int d_limit, int32_t *rec)
+{
+    init_tables();
+    if (level == -1) level = 6;
+    if (level < 4 || level > 9) return ORC_E_ARG;
+    level_cfg cfg = LEVELS[level];
+    const long max_dist = MAX_DIST + d_limit;
+    const int chain = cfg.chain + d_budget;
+    int32_t *head = (int32_t *)calloc(HASH_MASK + 1, sizeof(int32_t));
+    int32_t *prev = (int32_t *)calloc((size_t)(n > 0 ? n : 1), sizeof(int32_t));
+    if (!head || !prev) { free(head); free(prev); return ORC_E_MEM; }
+    for (long p = 0; p < n; p++) {
+        int32_t *r = rec + p * ORC_TRACE_WORDS;
+        memset(r, 0, sizeof(int32_t) * ORC_TRACE_WORDS);
+        if (n - p < MIN_MATCH) continue;
+        unsigned h = hash3(in + p);
+        long cur = head[h]; prev[p] = (int32_t)cur; head[h] = (int32_t)p;
+        if (cur != 0) r[4] = (int32_t)(p - cur);
+        if (cur == 0 || p - cur > max_dist) continue;
+        long lookahead = n - p;
+        int nice = cfg.nice; if ((long)nice > lookahead) nice = (int)lookahead;
+        int maxlen = lookahead < MAX_MATCH ? (int)lookahead : MAX_MATCH;
+        long limit = p > max_dist ? p - max_dist : 0;
+        int best = 2, budget = chain, qbudget = chain >> 2, k = 0, q_done = 0, qbest = 2, reason;
+        long bstart = 0, qstart = 0;
+        int bidx = 0, qidx = 0;
+        for (;;) {
+            int len = 0;
+            while (len < maxlen && in[cur + len] == in[p + len]) len++;
+            k++;
+            if (len < 3) r[5]++;
+            else if (len == 3 && maxlen > 3) r[6]++;
+            if (q_done && k == qbudget + 1 && len > qbest) r[8] = 1;
+            if (len > best) { best = len; bstart = cur; bidx = k; }
+            int stopped = best == len && bidx == k && len >= nice;
+            if (!q_done && (k == qbudget || stopped)) { qbest = best; qstart = bstart; qidx = bidx; q_done = 1; }
+            if (stopped) { reason = ORC_END_NICE; break; }
+            cur = prev[cur];
+            if (cur <= limit) { reason = cur == 0 ? ORC_END_CHAIN : ORC_END_LIMIT; break; }
+            if (--budget == 0) { reason = ORC_END_BUDGET; break; }
+        }
+        if (!q_done) { qbest = best; qstart = bstart; qidx = bidx; }
+        if (reason == ORC_END_NICE) { cur = prev[cur]; if (cur <= limit) cur = 0; }
+        if (reason == ORC_END_NICE ? cur != 0 : (cur != 0 || hash3(in) == h)) {
+            int len = 0;
+            while (len < maxlen && in[cur + len] == in[p + len]) len++;
+            r[7] = len;
+        }
+        r[0] = k; r[1] = reason; r[2] = bidx; r[3] = qidx;
+        r[9] = best >= 3 ? (int32_t)(((uint32_t)best << 16) | (uint32_t)(p - bstart)) : 0;
+        r[10] = qbest >= 3 ? (int32_t)(((uint32_t)qbest << 16) | (uint32_t)(p - qstart)) : 0;
     }
     free(head); free(prev);
     return ORC_OK;

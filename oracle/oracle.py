@@ -63,6 +63,7 @@ def lib():
         L.orc_compress_bound.restype = C.c_long
         L.orc_compress_bound.argtypes = [C.c_long]
         L.orc_match_tables.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
+        L.orc_match_trace.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.orc_parse_tables.restype = C.c_long
         L.orc_parse_tables.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]
@@ -155,6 +156,26 @@ def match_tables(data, level=6):
     rc = lib().orc_match_tables(_ptr(a), a.size, level, _ptr(tf), _ptr(tq))
     assert rc == 0, rc
     return tf[:a.size], tq[:a.size]
+
+
+TRACE_FIELDS = ('visited', 'end', 'full_idx', 'quarter_idx', 'head_dist', 'collisions', 'fail3', 'beyond_len', 'quarter_missed',
+                't_full', 't_quarter')
+END_NONE, END_NICE, END_BUDGET, END_LIMIT, END_CHAIN = range(5)
+END_NAMES = ('no walk', 'nice_match reached', 'budget spent', 'distance limit passed', 'chain exhausted')
+
+
+def match_trace(data, level=6, d_budget=0, d_limit=0):
+    """orc_match_trace: name -> int32 array over the positions (TRACE_FIELDS; t_full / t_quarter as uint32).  d_budget and
+    d_limit make a deliberately wrong reference (chain budget / MAX_DIST off by that much)."""
+    a = _bytes_arr(data)
+    rec = np.zeros((max(a.size, 1), len(TRACE_FIELDS)), dtype=np.int32)
+    rc = lib().orc_match_trace(_ptr(a), a.size, level, d_budget, d_limit, _ptr(rec))
+    assert rc == 0, rc
+    rec = rec[:a.size]
+    out = {f: np.ascontiguousarray(rec[:, i]) for i, f in enumerate(TRACE_FIELDS)}
+    out['t_full'] = out['t_full'].view(np.uint32)
+    out['t_quarter'] = out['t_quarter'].view(np.uint32)
+    return out
 
 
 def parse_tables(data, tf, tq, level=6):

@@ -80,6 +80,14 @@ def test_match_tables_other_levels(level):
     tf, tq = O.match_tables(data, level)
     gf, gq = hip.debug_match_tables(data, level)
     assert np.array_equal(gf, tf) and np.array_equal(gq, tq)
+    # two tiles: 300 owned positions behind the seam, a 258-byte match across it, a winner in the halo (tests/match_cases.py)
+    from tests import match_cases
+    data = match_cases.cases()['seam_+300'].data
+    assert len(data) > match_cases.TILE
+    tf, tq = O.match_tables(data, level)
+    gf, gq = hip.debug_match_tables(data, level)
+    assert np.array_equal(gf, tf), ('t_full', _first_diff(gf, tf))
+    assert np.array_equal(gq, tq), ('t_quarter', _first_diff(gq, tq))
 
 
 @pytest.mark.parametrize('name', TABLE_CASES + ['empty', 'one', 'two'])
