@@ -59,6 +59,8 @@ extern "C" {
 #define MTS_DETECT_MAX_SPREAD 32        /* ... and column positions either side */
 #define MTS_WAVEFORMS_MAX_ROWS 4096     /* mts_waveforms: rows of a snippet (before + after) */
 #define MTS_WAVEFORMS_MAX_WIDTH 1024    /* ... and its column positions */
+#define MTS_MEAN_MAX_LABELS 4096       /* mts_mean_waveforms: labels of a call */
+#define MTS_MEAN_MAX_ENTRIES (1L << 27) /* ... and n_labels * T * width, the entries of its sums */
 #define MTS_DETECT_MAX_REF_COLS 1024    /* columns of a median reference: a row's order keys are sorted in 4 KiB of LDS by one wave */
 #define MTS_CORRELATE_MAX_T 256         /* mts_correlate: rows of a template (its taus) */
 #define MTS_CORRELATE_MAX_OUT 1024      /* ... the templates of a call */
@@ -347,6 +349,42 @@ int mts_waveforms(int device, long cache_id, int n_chunks, const long *chunk_key
                   const long *ev_row, const int *ev_col0, int before, int after, int width,
                   float *out_wave /* (n_events, T, width) C order or null */, float *out_min, int *out_argmin, float *out_max, int *out_argmax,
                   int *chunk_status);
+
+/*
+ * Per-label sums of the snippets of mts_waveforms, in fixed point (an extension: the reference has no such call; its users average the
+ * snippets on the host).  What crosses the bus is n_labels * T * width sums and counts, not n_events * T * width floats.  A
+ * definition, not a tolerance:
+ *   z, T, entry    exactly mts_waveforms': z is mts_detect's z; the entry (e, tau, w), 0 <= tau < T = before + after, 0 <= w < width,
+ *                  has the row r = ev_row[e] - before + tau and the column position c = ev_col0[e] + w
+ *   clipping       an entry whose r lies outside [valid_begin, valid_end) or whose c lies outside [0, n_cols) contributes nothing and
+ *                  is counted nowhere
+ *   sum            every other entry takes d = (double)z[r, c] * (1 / resolution); resolution is a power of two in [2^-60, 2^60], so the
+ *                  product is exact.  If z is a NaN or |d| >= 2^42 (+-inf included): out_skipped[ev_label[e]] += 1.  Otherwise
+ *                  out_sum[ev_label[e], tau, w] += (int64)rint(d) and out_count[ev_label[e], tau, w] += 1; rint rounds to nearest,
+ *                  ties to even
+ *   events         as mts_waveforms: n_events file rows on the host, ascending (repeats allowed), each in [valid_begin, valid_end);
+ *                  ev_col0 any int; 0 <= ev_label[e] < n_labels; at most 2^21 events of one label in a call, so that |sum| < 2^63
+ *   outputs        out_sum (n_labels, T, width) int64, out_count (n_labels, T, width) int32, out_skipped (n_labels) int64, C order:
+ *                  written whole by the call, zero where nothing was added.  Integer addition is associative: the same bytes whatever
+ *                  the call, its pieces, its slabs, the gap setting, the split of a label's events into parts
+ *                  (MTS_MEAN_PART_EVENTS), the cache or the device -- and the sums of several calls over a split event list add up
+ *                  to the sums of one
+ *   limits         T and width as mts_waveforms; 1 <= n_labels <= MTS_MEAN_MAX_LABELS; n_labels * T * width <= MTS_MEAN_MAX_ENTRIES;
+ *                  taps and columns as mts_detect; with a reference n_cols <= MTS_DETECT_MAX_REF_COLS
+ *   chunks, chunk_status   as mts_waveforms; the sums of labels with events near a failed chunk are undefined
+ * mts_mean_waveforms: host cdata; cache_id 0 or a decoded-chunk cache, read in place and never inserted into, as mts_waveforms; the
+ * same pieces (MTS_PIPE_BYTES) and slabs (MTS_WAVEFORMS_SLAB_BYTES, MTS_WAVEFORMS_GAP_ROWS).  The outputs are host memory.
+ * mts_dev_mean_waveforms: device d_cdata and d_* outputs on `device`; ev_row, ev_col0, ev_label and chunk_status on the host; no cache.
+ * MTS_E_ARG with a message before anything is allocated or launched: what mts_waveforms refuses, a label outside [0, n_labels), a label
+ * with more than 2^21 events, a resolution that is not a power of two in range, any argument outside the limits above, no output
+ * buffers.  n_events == 0 writes zeros and launches no gather.
+ */
+int mts_mean_waveforms(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                       const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                       long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                       const long *ev_row, const int *ev_col0, const int *ev_label, int n_labels, int before, int after, int width,
+                       double resolution, long long *out_sum /* (n_labels, T, width) */, int *out_count /* (n_labels, T, width) */,
+                       long *out_skipped /* (n_labels) */, int *chunk_status);
 
 /*
  * Spatio-temporal template scores of filtered rows (an extension: the reference has no such call; its users pull Reader[...] across the
@@ -660,6 +698,11 @@ int mts_dev_waveforms(int device, void *stream, const unsigned char *d_cdata, co
                       const long *ev_row /* host */, const int *ev_col0 /* host */, int before, int after, int width,
                       float *d_wave /* (n_events, T, width) C order or null */, float *d_min, int *d_argmin, float *d_max, int *d_argmax,
                       int *chunk_status /* host */);
+int mts_dev_mean_waveforms(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                           const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                           long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                           const long *ev_row /* host */, const int *ev_col0 /* host */, const int *ev_label /* host */, int n_labels, int before,
+                           int after, int width, double resolution, long long *d_sum, int *d_count, long *d_skipped, int *chunk_status /* host */);
 int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                       const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
                       long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
@@ -717,7 +760,7 @@ int mts_dev_compare(int device, void *stream, const void *d_a, const void *d_b, 
  * fills up to `cap` entries of (name, ms); returns the number of stages.  For bench.py / profiling. */
 int mts_last_stage_times(int device, const char **names, float *ms, int cap);
 
-/* What the last successful mts_waveforms / mts_dev_waveforms call on `device` did, for the tests and the benchmark: out[0] its pieces,
+/* What the last successful mts_waveforms / mts_dev_waveforms (or mts_mean_waveforms / mts_dev_mean_waveforms) call on `device` did, for the tests and the benchmark: out[0] its pieces,
  * out[1] its slabs, out[2] the slabs among them that were begun at a gap, out[3] the microseconds of its gather kernels (measured,
  * with a wait per slab, only while MTS_WAVEFORMS_TIME is set; else 0). */
 int mts_waveforms_last_plan(int device, long *out /* 4 */);

@@ -70,6 +70,7 @@ DETECT_GUESS_SAMPLES = 256             # a call that finds more says how many an
 DECIMATE_CALL_BYTES = 1 << 30          # Reader.decimate: compressed bytes per device call (a longer range is split at output-row boundaries)
 WAVEFORMS_CALL_BYTES = 1 << 30         # Reader.waveforms: compressed bytes per device call (a longer event list is split between events) ...
 WAVEFORMS_OUT_BYTES = 1 << 30          # ... and the bytes of a call's result
+MEAN_WAVEFORMS_EVENT_BYTES = 1 << 28   # Reader.mean_waveforms: the bytes of a call's event list (row, position, label and their order: 24 an event)
 CORRELATE_CALL_BYTES = 1 << 30         # Reader.correlate: compressed bytes per device call (a longer range is split at chunk boundaries) ...
 CORRELATE_OUT_BYTES = 1 << 30          # ... and the bytes of a call's result
 TMATCH_CALL_BYTES = 1 << 30            # Reader.match_templates: compressed bytes per device call (a longer range is split at chunk boundaries)
@@ -485,6 +486,7 @@ class HipCodec:
         _lane_reduction, ('window_stats', 'rank_hist', 'decimate', 'detect', 'welch', 'gram'))
     project = _lane_reduction('project')
     waveforms = _lane_reduction('waveforms')
+    mean_waveforms = _lane_reduction('mean_waveforms')
     correlate = _lane_reduction('correlate')
     match_templates = _lane_reduction('match_templates')
     residual = _lane_reduction('residual')
@@ -2126,26 +2128,9 @@ class Reader:
         base.append(n)
         return [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, max_events)] + [n]
 
-    def waveforms(self, sample, channel=None, before=20, after=41, neighbours=None, channels=slice(None), taps=None, reference=None,
-                  waveforms=True):
-        """Snippets of the filtered rows around events, and their extrema, on the device: only they cross the bus.  All in float32.
-        z is detect's z: the bytes of decimate(1, taps=taps, edge='recording', dtype=float32) on `channels` (taps=None is [1.0]),
-        minus, with reference='median', the float32 median over all selected columns of each row.  Event e at file row sample[e]:
-        waveforms[e, tau, w] = z[sample[e] - before + tau, position[e] + w] for tau < T = before + after and w < W.
-        neighbours=None: W is the number of selected channels and position 0 (`channel` is not needed); neighbours=k >= 0: W =
-        2 k + 1 and position[e] = pos - k, pos the first position in `channels` that holds channel[e] (file channel numbers, as
-        detect returns them; a channel that is not selected is a ValueError).  An entry whose row lies outside the recording or
-        whose position lies outside the selection is NaN (every NaN entry, fill or data, has the bits 0x7fc00000).  trough / peak: the minimum / maximum over the entries that are not NaN
-        (the first one in (tau, w) order; -0 == +0), each a Bunch of value (float32; NaN for none), offset (int64, tau - before; 0
-        for none), channel (int64, the entry of `channels`; -1 for none) and index (int64, tau * W + w; -1 for none).  So
-        waveforms[e, before, pos - position[e]] is detect's amplitude of the event, bit for bit.  sample: ints in [0, n_samples),
-        any order, repeats allowed; the results come in that order.  waveforms=False: the extrema alone (the same bytes),
-        `waveforms` is None.  Returns a Bunch: waveforms (n, T, W), trough, peak, sample, position, before, after, channels.  T <=
-        4096, W <= 1024, a median over at most 1024 columns.  The same bytes whatever the lanes, calls, pieces or cache residency.
-        Only the chunks that the events' snippets and their filter support read are decoded: resident chunks are read where they
-        lie, the others in a transient workspace and NOT kept.  A damaged chunk in an event's support raises the IOError of
-        Reader[...]."""
-        self._need_codec('waveforms', 'waveforms', 'gathers')
+    def _snippet_args(self, what, sample, channel, before, after, neighbours, channels, taps, reference):
+        """The arguments that waveforms and mean_waveforms share, checked -> (before, after, T, W, taps, cols, reference code, the
+        events' rows as int64, their first positions)."""
         for name, v in (('before', before), ('after', after)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0:
                 raise ValueError("%s must be an int >= 0, got %r" % (name, v))
@@ -2157,7 +2142,7 @@ class Reader:
             raise ValueError("neighbours must be None or an int >= 0, got %r" % (neighbours,))
         def width(cols):
             if not cols.size:
-                raise ValueError("waveforms needs at least one channel")
+                raise ValueError("%s needs at least one channel" % what)
             W = int(cols.size) if neighbours is None else 2 * int(neighbours) + 1
             if W > hip.WAVEFORMS_MAX_WIDTH:
                 raise ValueError("a snippet holds at most %d positions, got %d" % (hip.WAVEFORMS_MAX_WIDTH, W))
@@ -2184,6 +2169,31 @@ class Reader:
             if n and (ch.min() < 0 or ch.max() >= self.n_channels or (first[ch] < 0).any()):
                 raise ValueError("channel holds a channel that is not among `channels`")
             col0 = first[ch] - int(neighbours)
+        return before, after, T, W, taps, cols, ref_code, rows, col0
+
+    def waveforms(self, sample, channel=None, before=20, after=41, neighbours=None, channels=slice(None), taps=None, reference=None,
+                  waveforms=True):
+        """Snippets of the filtered rows around events, and their extrema, on the device: only they cross the bus.  All in float32.
+        z is detect's z: the bytes of decimate(1, taps=taps, edge='recording', dtype=float32) on `channels` (taps=None is [1.0]),
+        minus, with reference='median', the float32 median over all selected columns of each row.  Event e at file row sample[e]:
+        waveforms[e, tau, w] = z[sample[e] - before + tau, position[e] + w] for tau < T = before + after and w < W.
+        neighbours=None: W is the number of selected channels and position 0 (`channel` is not needed); neighbours=k >= 0: W =
+        2 k + 1 and position[e] = pos - k, pos the first position in `channels` that holds channel[e] (file channel numbers, as
+        detect returns them; a channel that is not selected is a ValueError).  An entry whose row lies outside the recording or
+        whose position lies outside the selection is NaN (every NaN entry, fill or data, has the bits 0x7fc00000).  trough / peak: the minimum / maximum over the entries that are not NaN
+        (the first one in (tau, w) order; -0 == +0), each a Bunch of value (float32; NaN for none), offset (int64, tau - before; 0
+        for none), channel (int64, the entry of `channels`; -1 for none) and index (int64, tau * W + w; -1 for none).  So
+        waveforms[e, before, pos - position[e]] is detect's amplitude of the event, bit for bit.  sample: ints in [0, n_samples),
+        any order, repeats allowed; the results come in that order.  waveforms=False: the extrema alone (the same bytes),
+        `waveforms` is None.  Returns a Bunch: waveforms (n, T, W), trough, peak, sample, position, before, after, channels.  T <=
+        4096, W <= 1024, a median over at most 1024 columns.  The same bytes whatever the lanes, calls, pieces or cache residency.
+        Only the chunks that the events' snippets and their filter support read are decoded: resident chunks are read where they
+        lie, the others in a transient workspace and NOT kept.  A damaged chunk in an event's support raises the IOError of
+        Reader[...]."""
+        self._need_codec('waveforms', 'waveforms', 'gathers')
+        before, after, T, W, taps, cols, ref_code, rows, col0 = self._snippet_args('waveforms', sample, channel, before, after, neighbours, channels,
+                                                                                  taps, reference)
+        n, N = int(rows.size), self.n_samples
         order = np.argsort(rows, kind='stable')
         s_rows, s_col0 = rows[order], col0[order]
         n_taps = int(taps.size)
@@ -2211,6 +2221,72 @@ class Reader:
             pos = np.where(some, col0 + index % W, 0)
             out[name] = Bunch(value=value, offset=np.where(some, index // W - before, 0), channel=np.where(some, cols[pos], -1), index=index)
         return Bunch(waveforms=wave, trough=out['trough'], peak=out['peak'], sample=rows, position=col0, before=before, after=after,
+                     channels=cols)
+
+    # -- per-unit mean snippets on the device (an extension: the reference's users average the snippets on the host)
+    def mean_waveforms(self, sample, label, channel=None, before=20, after=41, neighbours=None, channels=slice(None), taps=None, reference=None,
+                       n_labels=None, resolution=2.0 ** -16):
+        """The mean snippet of every label (a unit's template), summed on the device in fixed point: K * T * W numbers cross the
+        bus, not one snippet per event.  sample, channel, neighbours, channels, taps, reference, before and after mean what they
+        mean for `waveforms`; label holds one int per sample, events with label < 0 are ignored (the usual noise cluster); n_labels
+        = K, None: max(label) + 1.  sample may come in any order.  Over the entries (e, tau, w) of waveforms(...).waveforms that are
+        not fill entries, with d = float64(entry) / resolution (resolution a power of two in [2^-60, 2^60]: exact): a NaN entry or
+        |d| >= 2^42 adds 1 to skipped[label[e]]; every other adds rint(d) (ties to even) to sum[label[e], tau, w] and 1 to
+        count[label[e], tau, w].  Returns a Bunch: mean (K, T, W) float32 = float32(float64(sum) * resolution / count), NaN (bits
+        0x7fc00000) where count is 0; sum, count (K, T, W) int64; skipped (K) int64; events (K) int64, the events of each label;
+        resolution, before, after, channels.  Integer sums do not depend on the order: the same bytes whatever the order of sample,
+        the lanes, calls, pieces or cache residency, and equal to the sums formed from waveforms' own snippets.  With
+        neighbours=None, np.nan_to_num(mean) is a valid `templates` argument of correlate and match_templates.  At most 2^21 events
+        of one label, K <= 4096, K * T * W <= 2^27; T, W and the median's columns as waveforms.  Chunks are read as waveforms reads
+        them, and a damaged chunk in an event's support raises the IOError of Reader[...]."""
+        self._need_codec('mean_waveforms', 'mean_waveforms', 'sums snippets')
+        before, after, T, W, taps, cols, ref_code, rows, col0 = self._snippet_args('mean_waveforms', sample, channel, before, after, neighbours,
+                                                                                  channels, taps, reference)
+        lab = np.asarray(label)
+        if lab.shape != rows.shape or (lab.size and lab.dtype.kind not in 'iu'):
+            raise ValueError("label must hold one int per sample")
+        lab = lab.astype(np.int64)
+        top = int(lab.max()) + 1 if lab.size else 0
+        if n_labels is None:
+            n_labels = max(top, 0)
+        elif not isinstance(n_labels, (int, np.integer)) or isinstance(n_labels, bool) or n_labels < 0:
+            raise ValueError("n_labels must be None or an int >= 0, got %r" % (n_labels,))
+        K = int(n_labels)
+        if top > K:
+            raise ValueError("label holds %d, n_labels is %d" % (top - 1, K))
+        if K > hip.MEAN_MAX_LABELS or K * T * W > hip.MEAN_MAX_ENTRIES:
+            raise ValueError("at most %d labels and %d sums (labels x rows x positions), got %d and %d"
+                             % (hip.MEAN_MAX_LABELS, hip.MEAN_MAX_ENTRIES, K, K * T * W))
+        if not isinstance(resolution, (int, float, np.integer, np.floating)) or isinstance(resolution, bool) or not hip.mean_resolution_ok(resolution):
+            raise ValueError("resolution must be a power of two in [2^-60, 2^60], got %r" % (resolution,))
+        resolution = float(resolution)
+        keep = lab >= 0
+        rows, col0, lab = rows[keep], col0[keep], lab[keep]
+        events = np.bincount(lab, minlength=K).astype(np.int64)
+        if events.size and int(events.max()) > hip.MEAN_MAX_LABEL_EVENTS:
+            raise ValueError("label %d has %d events (at most %d)" % (int(events.argmax()), int(events.max()), hip.MEAN_MAX_LABEL_EVENTS))
+        total, count, skipped = np.zeros((K, T, W), np.int64), np.zeros((K, T, W), np.int64), np.zeros(K, np.int64)
+        n, N = int(rows.size), self.n_samples
+        if n:
+            order = np.argsort(rows, kind='stable')
+            s_rows, s_col0, s_lab = rows[order], col0[order], lab[order]
+            n_taps = int(taps.size)
+            half = (n_taps - 1) // 2
+            lo = np.maximum(0, s_rows - before + half - (n_taps - 1))  # the file rows an event reads
+            hi = np.minimum(N, s_rows + after + half)
+            cuts = self._waveform_cuts(lo, hi, WAVEFORMS_CALL_BYTES, max(1, MEAN_WAVEFORMS_EVENT_BYTES // 24))
+
+            def part(a, b):
+                return (self._chunk_span(int(lo[a]), int(hi[b - 1])),
+                        (0, N, taps, cols, ref_code, s_rows[a:b], s_col0[a:b], s_lab[a:b], K, before, after, W, resolution))
+            for _, _, (s, c, k) in self._halo_parts(self.codec.mean_waveforms, cuts, part):     # (integers: any cut adds up to the same)
+                total += s
+                count += c
+                skipped += k
+        with np.errstate(divide='ignore', invalid='ignore'):
+            mean = (total.astype(np.float64) * resolution / count).astype(np.float32)
+        mean[count == 0] = np.frombuffer(np.uint32(0x7fc00000).tobytes(), np.float32)[0]
+        return Bunch(mean=mean, sum=total, count=count, skipped=skipped, events=events, resolution=resolution, before=before, after=after,
                      channels=cols)
 
     # -- power spectral density on the device (an extension: the reference's users run scipy.signal.welch on Reader[...])

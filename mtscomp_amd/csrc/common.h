@@ -138,6 +138,16 @@ int launch_waveforms(hipStream_t st, const float *d_z, long ws_row0, long ws_row
                      const int *d_ev_col0, long e0, long e1, int before, int after, int width, float *d_wave, float *d_min, int *d_argmin,
                      float *d_max, int *d_argmax);
 
+// meanwave.hip: per-label fixed-point sums of the same snippets (mts_mean_waveforms).  d_parts[0 .. n_parts): the parts of a slab's
+// events (MeanParts, reduce_plan.h) into d_perm.  For every event e of a part with label l and every entry (tau, w) whose row lies in
+// [vb, ve) and the workspace and whose column position lies in [0, n_cols): d = (double)z * (1 / resolution); a NaN or |d| >= 2^42 adds 1
+// to d_skipped[l], every other d adds rint(d) to d_sum[l, tau, w] and 1 to d_count[l, tau, w] -- integer atomics on buffers that the
+// caller zeroed before the first slab
+struct MeanPart;
+int launch_mean_waveforms(hipStream_t st, const float *d_z, long ws_row0, long ws_rows, int n_cols, long vb, long ve, const long *d_ev_row,
+                          const int *d_ev_col0, const long *d_perm, const MeanPart *d_parts, long n_parts, int before, int after, int width,
+                          double resolution, long long *d_sum, int *d_count, long *d_skipped);
+
 // correlate.hip: template scores on the same workspace (mts_correlate).  out[(t - r_begin) * n_out + k] for file rows t of [r_begin,
 // r_end) = the chain of matrix steps over (g, tau), g = 0, 4, .. < n4 outermost and tau < T inside, of z[t - before + tau, g .. g + 3]
 // against the templates; z = +0 for a row outside [vb, ve) or the workspace; a NaN is stored as 0x7fc00000.  d_tpl: the templates

@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, correlate, match_templates, residual, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, correlate, match_templates, residual, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -26,10 +26,10 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, waveforms, correlate, match_templates, residual, welch, gram): a unit of output (outputs, rows,
+//   halo (decimate, project, detect, waveforms, mean_waveforms, correlate, match_templates, residual, welch, gram): a unit of output (outputs, rows,
 //        events, blocks, groups -- the op gives HaloPlan its map from units to rows) reads rows of several adjacent chunks, so a piece
 //        reads chunks [c0, c1] through a table of segment bases and first rows, and decodes the missing ones among them -- a boundary
-//        chunk in both pieces (HaloPlan, HaloFeed).  Five of them (detect, waveforms, correlate, match_templates, residual) start from
+//        chunk in both pieces (HaloPlan, HaloFeed).  Six of them (detect, waveforms, mean_waveforms, correlate, match_templates, residual) start from
 //        one filtered signal z: their checks, uploads, filter stage and tails are the z family's shared parts below.
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
 //   - An allocation that fails empties this device's caches before it tries again (DBuf::ensure -> drop_device_caches: hipFree,
@@ -134,11 +134,11 @@ int check_taps(const char *op, int n_taps, const double *taps)
     return MTS_OK;
 }
 
-// what the z family (detect, waveforms, correlate, match_templates, residual) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
+// what the z family (detect, waveforms, mean_waveforms, correlate, match_templates, residual) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
 // in float32, x = 0 outside [vb, ve), minus the row's median over the columns with reference 1.  `op` names the entry in every message.
 struct ZArgs { const char *op; long vb, ve; int n_taps; const double *taps; int n_cols; const int *cols; int reference; };
 
-// the first checks of the z family.  max_cols 0: as many columns as a grid holds, in one message with the table (detect, waveforms);
+// the first checks of the z family.  max_cols 0: as many columns as a grid holds, in one message with the table (detect, waveforms, mean_waveforms);
 // else that many, the count named (the template ops)
 int check_zargs(const ChunkTable &T, const ZArgs &Z, int max_cols = 0)
 {
@@ -339,12 +339,12 @@ struct HaloFeed {
     }
 };
 
-// ---- z family: what detect, waveforms, correlate, match_templates and residual share around their own slab loops.  Each run reads
+// ---- z family: what detect, waveforms, mean_waveforms, correlate, match_templates and residual share around their own slab loops.  Each run reads
 // top to bottom as the halo family's sequence: plan -> regions (ZStage first, the op's, EventTail's) -> StreamGuard -> place ->
 // uploads -> run -> tail.
 //
-// The rule for leaving early, for all five: from the first asynchronous upload out of host memory that the call owns (HaloFeed::seg,
-// ZStage::h_taps, the repacked templates, SubEvents::namp) no path returns before the stream has been waited for -- a failed
+// The rule for leaving early, for all of them: from the first asynchronous upload out of host memory that the call owns (HaloFeed::seg,
+// ZStage::h_taps, the repacked templates, SubEvents::namp, the parts of mean_waveforms) no path returns before the stream has been waited for -- a failed
 // H.run, a failed MTS_HIP.  The guard is declared after those vectors and before H.place, so it goes before they do; the tails'
 // own wait() disarms it, so the normal path waits no more often than it has to.
 struct StreamGuard {
@@ -848,62 +848,138 @@ static long waveforms_gap_rows()                                     // (negativ
     return e && *e ? (long)atoll(e) : WAVEFORMS_GAP_ROWS;
 }
 
+// ---- what waveforms and mean_waveforms share: the snippet arguments and their checks, the events' pieces and slabs, the slab loop
+struct SnipArgs { long n_events; const long *ev_row; const int *ev_col0; int before, after, width; };
+
+// the first checks, in order: the filter's, the snippet's shape, the event list's pointers
+static int check_snippet_shape(const ChunkTable &T, const ZArgs &Z, const SnipArgs &A)
+{
+    if (const int rc = check_zargs(T, Z)) return rc;
+    const long n_snip = (long)A.before + (long)A.after;
+    if (A.before < 0 || A.after < 0 || n_snip < 1 || n_snip > MTS_WAVEFORMS_MAX_ROWS) {
+        set_error("%s: before %d, after %d (both >= 0, 1 .. %d rows in all)", Z.op, A.before, A.after, MTS_WAVEFORMS_MAX_ROWS); return MTS_E_ARG;
+    }
+    if (A.width < 1 || A.width > MTS_WAVEFORMS_MAX_WIDTH) { set_error("%s: width %d (1 .. %d)", Z.op, A.width, MTS_WAVEFORMS_MAX_WIDTH); return MTS_E_ARG; }
+    if (A.n_events < 0 || A.n_events > (1l << 40)) { set_error("%s: %ld events (0 .. 2^40)", Z.op, A.n_events); return MTS_E_ARG; }
+    if (A.n_events && (!A.ev_row || !A.ev_col0)) { set_error("%s: no events", Z.op); return MTS_E_ARG; }
+    return MTS_OK;
+}
+
+// the rows that the events [u0, u1) read: their snippets' support ∩ valid range
+struct SnipRows {
+    const ZArgs &Z;
+    const SnipArgs &A;
+    void operator()(long u0, long u1, long *lo, long *hi) const
+    {
+        const long half = (Z.n_taps - 1) / 2;
+        *lo = std::max(Z.vb, A.ev_row[u0] - A.before + half - (Z.n_taps - 1)); *hi = std::min(Z.ve, A.ev_row[u1 - 1] + A.after + half);
+    }
+};
+
+// the last checks: the events' rows, the columns, the chunk table and what it covers
+static int check_snippet_events(const ChunkTable &T, const ZArgs &Z, const SnipArgs &A)
+{
+    int rc;
+    for (long e = 0; e < A.n_events; e++) {
+        if (A.ev_row[e] < Z.vb || A.ev_row[e] >= Z.ve) { set_error("%s: event %ld at row %ld outside [%ld, %ld)", Z.op, e, A.ev_row[e], Z.vb, Z.ve); return MTS_E_ARG; }
+        if (e && A.ev_row[e] < A.ev_row[e - 1]) { set_error("%s: event %ld: the rows must ascend", Z.op, e); return MTS_E_ARG; }
+    }
+    if ((rc = check_columns(Z.cols, Z.n_cols, T.nc))) return rc;
+    if ((rc = check_chunk_table(true, T))) return rc;
+    long need_lo = 0, need_hi = 0;
+    if (A.n_events) SnipRows{Z, A}(0, A.n_events, &need_lo, &need_hi);
+    return check_cover(Z.op, T, need_lo, need_hi);
+}
+
+// the events' pieces (HaloFeed) and every piece's slabs (SnippetPlan), then the slab loop: filter -> median -> the op's gather.
+// report: what mts_waveforms_last_plan tells
+struct SnippetFeed {
+    HaloFeed H;
+    std::vector<SnippetPlan> slabs;
+    std::vector<long> slab0;                                  // piece p's slabs are the call's slabs [slab0[p], slab0[p + 1])
+    long max_rows = 0, report[4] = {0, 0, 0, 0};
+    bool timed = false;
+    double gather_ms = 0;
+
+    SnippetFeed(const ChunkTable &T, bool out_on_host) : H(T, out_on_host) {}
+
+    int plan(Engine &E, const ZArgs &Z, const SnipArgs &A)
+    {
+        // the first event at or after row r
+        const int rc = H.plan(A.n_events, [&](long r) { return (long)(std::lower_bound(A.ev_row, A.ev_row + A.n_events, r) - A.ev_row); }, SnipRows{Z, A});
+        if (rc) return rc;
+        // every piece's slabs: the workspace holds the longest
+        const long cap_rows = (long)std::min<u64>(env_bytes("MTS_WAVEFORMS_SLAB_BYTES", WAVEFORMS_SLAB_BYTES) / (4 * (u64)Z.n_cols), (u64)1 << 40);
+        const long gap_rows = waveforms_gap_rows();
+        report[0] = (long)H.P->pieces.size();
+        slab0.push_back(0);
+        for (const FeedPiece &Pc : H.P->pieces) {
+            slabs.emplace_back(A.ev_row, Pc.u0, Pc.u1, A.before, A.after, Z.vb, Z.ve, cap_rows, gap_rows);
+            max_rows = std::max(max_rows, slabs.back().max_rows);
+            report[1] += (long)slabs.back().slabs.size(); report[2] += slabs.back().gap_cuts;
+            slab0.push_back(report[1]);
+        }
+        timed = getenv("MTS_WAVEFORMS_TIME") != nullptr;          // the gather kernel's time, slab by slab (tools/waveforms_bench.py)
+        if (timed && !E.wav_ev[0]) { MTS_HIP(hipEventCreate(&E.wav_ev[0])); MTS_HIP(hipEventCreate(&E.wav_ev[1])); }
+        return MTS_OK;
+    }
+
+    // gather(slab, its number in the call) after the slab's rows are filtered into d_y
+    template <class Gather>
+    int run(Engine &E, hipStream_t st, const ChunkTable &T, const ZStage &F, float *d_y, int *status, Gather &&gather)
+    {
+        return H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
+            int r = MTS_OK;
+            const size_t p = (size_t)(&Pc - H.P->pieces.data());
+            long k = slab0[p];
+            for (const SnippetSlab &S : slabs[p].slabs) {
+                r = F.filter(st, T, Sg, S.a, S.b, d_y);
+                if (!r && timed) (void)hipEventRecord(E.wav_ev[0], st);
+                if (!r) r = gather(S, k++);
+                if (!r && timed) {
+                    float ms = 0;
+                    (void)hipEventRecord(E.wav_ev[1], st);
+                    (void)hipEventSynchronize(E.wav_ev[1]);
+                    (void)hipEventElapsedTime(&ms, E.wav_ev[0], E.wav_ev[1]);
+                    gather_ms += ms;
+                }
+                if (r) break;
+            }
+            return r;
+        });
+    }
+
+    void done(Engine &E)
+    {
+        report[3] = (long)(gather_ms * 1e3);
+        memcpy(E.wav_plan, report, sizeof report);
+    }
+};
+
 static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long n_events, const long *ev_row, const int *ev_col0,
                          int before, int after, int width, float *out_wave, float *out_min, int *out_argmin, float *out_max, int *out_argmax,
                          bool out_on_host, int *status)
 {
     // ---- arguments: everything is checked before anything is allocated or launched
     const long vb = Z.vb, ve = Z.ve;
-    const int n_cols = Z.n_cols, n_taps = Z.n_taps;
+    const int n_cols = Z.n_cols;
+    const SnipArgs A{n_events, ev_row, ev_col0, before, after, width};
     int rc;
-    if ((rc = check_zargs(T, Z))) return rc;
-    const long n_snip = (long)before + (long)after;
-    if (before < 0 || after < 0 || n_snip < 1 || n_snip > MTS_WAVEFORMS_MAX_ROWS) {
-        set_error("waveforms: before %d, after %d (both >= 0, 1 .. %d rows in all)", before, after, MTS_WAVEFORMS_MAX_ROWS); return MTS_E_ARG;
-    }
-    if (width < 1 || width > MTS_WAVEFORMS_MAX_WIDTH) { set_error("waveforms: width %d (1 .. %d)", width, MTS_WAVEFORMS_MAX_WIDTH); return MTS_E_ARG; }
-    if (n_events < 0 || n_events > (1l << 40)) { set_error("waveforms: %ld events (0 .. 2^40)", n_events); return MTS_E_ARG; }
-    if (n_events && (!ev_row || !ev_col0)) { set_error("waveforms: no events"); return MTS_E_ARG; }
+    if ((rc = check_snippet_shape(T, Z, A))) return rc;
     if (!out_min || !out_argmin || !out_max || !out_argmax) { set_error("waveforms: no extrema buffers"); return MTS_E_ARG; }
-    for (long e = 0; e < n_events; e++) {
-        if (ev_row[e] < vb || ev_row[e] >= ve) { set_error("waveforms: event %ld at row %ld outside [%ld, %ld)", e, ev_row[e], vb, ve); return MTS_E_ARG; }
-        if (e && ev_row[e] < ev_row[e - 1]) { set_error("waveforms: event %ld: the rows must ascend", e); return MTS_E_ARG; }
-    }
-    if ((rc = check_columns(Z.cols, n_cols, T.nc))) return rc;
-    if ((rc = check_chunk_table(true, T))) return rc;
-    const long half = (n_taps - 1) / 2;
-    // the rows that the events [u0, u1) read: their snippets' support ∩ valid range
-    auto rows = [&](long u0, long u1, long *lo, long *hi) {
-        *lo = std::max(vb, ev_row[u0] - before + half - (n_taps - 1)); *hi = std::min(ve, ev_row[u1 - 1] + after + half);
-    };
-    long need_lo = 0, need_hi = 0;
-    if (n_events) rows(0, n_events, &need_lo, &need_hi);
-    if ((rc = check_cover("waveforms", T, need_lo, need_hi))) return rc;
+    if ((rc = check_snippet_events(T, Z, A))) return rc;
     status_ok(T, status);
     if (n_events == 0) return MTS_OK;
 
-    HaloFeed H(T, out_on_host);
-    // the first event at or after row r
-    if ((rc = H.plan(n_events, [&](long r) { return (long)(std::lower_bound(ev_row, ev_row + n_events, r) - ev_row); }, rows))) return rc;
-    // every piece's slabs: the workspace holds the longest
-    const long cap_rows = (long)std::min<u64>(env_bytes("MTS_WAVEFORMS_SLAB_BYTES", WAVEFORMS_SLAB_BYTES) / (4 * (u64)n_cols), (u64)1 << 40);
-    const long gap_rows = waveforms_gap_rows();
-    std::vector<SnippetPlan> slabs;
-    long max_rows = 0, report[4] = {(long)H.P->pieces.size(), 0, 0, 0};
-    for (const FeedPiece &Pc : H.P->pieces) {
-        slabs.emplace_back(ev_row, Pc.u0, Pc.u1, before, after, vb, ve, cap_rows, gap_rows);
-        max_rows = std::max(max_rows, slabs.back().max_rows);
-        report[1] += (long)slabs.back().slabs.size(); report[2] += slabs.back().gap_cuts;
-    }
-    const bool timed = getenv("MTS_WAVEFORMS_TIME") != nullptr;   // the gather kernel's time, slab by slab (tools/waveforms_bench.py)
-    if (timed && !E.wav_ev[0]) { MTS_HIP(hipEventCreate(&E.wav_ev[0])); MTS_HIP(hipEventCreate(&E.wav_ev[1])); }
-    double gather_ms = 0;
+    SnippetFeed S(T, out_on_host);
+    HaloFeed &H = S.H;
+    if ((rc = S.plan(E, Z, A))) return rc;
     // ---- workspace
-    const u64 n_item = (u64)n_snip * width;
+    const u64 n_item = (u64)((long)before + after) * width;
     WsLayout &L = H.L;
     ZStage F(Z, L);
     const size_t o_seg = L.take(H.table_bytes()), o_erow = L.take(8 * (u64)n_events), o_ecol = L.take(4 * (u64)n_events),
-                 o_y = L.take(4 * (u64)max_rows * n_cols), o_wave = out_wave ? L.take_out(4 * (u64)n_events * n_item) : 0,
+                 o_y = L.take(4 * (u64)S.max_rows * n_cols), o_wave = out_wave ? L.take_out(4 * (u64)n_events * n_item) : 0,
                  o_min = L.take_out(4 * (u64)n_events), o_amin = L.take_out(4 * (u64)n_events), o_max = L.take_out(4 * (u64)n_events),
                  o_amax = L.take_out(4 * (u64)n_events);
     StreamGuard G{st};
@@ -916,23 +992,9 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, const Z
     float *d_min = L.out(ws, o_min, out_min), *d_max = L.out(ws, o_max, out_max);
     int *d_amin = L.out(ws, o_amin, out_argmin), *d_amax = L.out(ws, o_amax, out_argmax);
     float *d_y = (float *)(ws + o_y);
-    rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
-        int r = MTS_OK;
-        for (const SnippetSlab &S : slabs[&Pc - H.P->pieces.data()].slabs) {
-            r = F.filter(st, T, Sg, S.a, S.b, d_y);
-            if (!r && timed) (void)hipEventRecord(E.wav_ev[0], st);
-            if (!r) r = launch_waveforms(st, d_y, S.a, S.b - S.a, n_cols, vb, ve, (const long *)(ws + o_erow), (const int *)(ws + o_ecol), S.e0, S.e1,
-                                         before, after, width, d_wave, d_min, d_amin, d_max, d_amax);
-            if (!r && timed) {
-                float ms = 0;
-                (void)hipEventRecord(E.wav_ev[1], st);
-                (void)hipEventSynchronize(E.wav_ev[1]);
-                (void)hipEventElapsedTime(&ms, E.wav_ev[0], E.wav_ev[1]);
-                gather_ms += ms;
-            }
-            if (r) break;
-        }
-        return r;
+    rc = S.run(E, st, T, F, d_y, status, [&](const SnippetSlab &B, long) {
+        return launch_waveforms(st, d_y, B.a, B.b - B.a, n_cols, vb, ve, (const long *)(ws + o_erow), (const int *)(ws + o_ecol), B.e0, B.e1, before,
+                                after, width, d_wave, d_min, d_amin, d_max, d_amax);
     });
     if (rc) return rc;
     if (out_on_host) {
@@ -943,8 +1005,116 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, const Z
         MTS_HIP(hipMemcpyAsync(out_argmax, d_amax, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
     }
     if ((rc = G.wait())) return rc;
-    report[3] = (long)(gather_ms * 1e3);
-    memcpy(E.wav_plan, report, sizeof report);
+    S.done(E);
+    return MTS_OK;
+}
+
+// ---- per-label sums of snippets (mts_mean_waveforms, mts_dev_mean_waveforms) -----------------------------------------------------
+// waveforms' events, pieces, slabs and filter stage; the gather is a segmented reduction: every slab's events are grouped by label and
+// cut into parts of MTS_MEAN_PART_EVENTS events (MeanParts: a plan made for all slabs before the first upload), and k_mean_waveforms
+// adds each part's entries in fixed point to the label's sums and counts with integer atomics (meanwave.hip).  Integer sums do not
+// depend on the order: the same bytes whatever the pieces, slabs, gap and parts.
+static const long MEAN_PART_EVENTS = 64;                            // (swept at 16 / 64 / 256: profiles/mean_waveforms.json)
+static const long MEAN_MAX_LABEL_EVENTS = 1l << 21;                 // of one label in a call: |sum| < 2^21 * 2^42
+
+static long mean_part_events()
+{
+    const char *e = getenv("MTS_MEAN_PART_EVENTS");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (long)std::min<long long>(v, 1 << 20) : MEAN_PART_EVENTS;
+}
+
+static int mean_waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long n_events, const long *ev_row, const int *ev_col0,
+                              const int *ev_label, int n_labels, int before, int after, int width, double resolution, long long *out_sum,
+                              int *out_count, long *out_skipped, bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols;
+    const SnipArgs A{n_events, ev_row, ev_col0, before, after, width};
+    int rc;
+    if ((rc = check_snippet_shape(T, Z, A))) return rc;
+    const u64 n_item = (u64)((long)before + after) * width;
+    if (n_labels < 1 || n_labels > MTS_MEAN_MAX_LABELS) { set_error("mean_waveforms: %d labels (1 .. %d)", n_labels, MTS_MEAN_MAX_LABELS); return MTS_E_ARG; }
+    if ((u64)n_labels * n_item > (u64)MTS_MEAN_MAX_ENTRIES) {
+        set_error("mean_waveforms: %d labels x %llu entries (<= %ld in all)", n_labels, (unsigned long long)n_item, (long)MTS_MEAN_MAX_ENTRIES); return MTS_E_ARG;
+    }
+    int expo = 0;
+    if (!(resolution > 0) || !std::isfinite(resolution) || std::frexp(resolution, &expo) != 0.5 || expo - 1 < -60 || expo - 1 > 60) {
+        set_error("mean_waveforms: resolution %g (a power of two in [2^-60, 2^60])", resolution); return MTS_E_ARG;
+    }
+    if (!out_sum || !out_count || !out_skipped) { set_error("mean_waveforms: no output buffers"); return MTS_E_ARG; }
+    if (n_events && !ev_label) { set_error("mean_waveforms: no labels"); return MTS_E_ARG; }
+    {
+        std::vector<long> per((size_t)n_labels, 0);
+        for (long e = 0; e < n_events; e++) {
+            if (ev_label[e] < 0 || ev_label[e] >= n_labels) { set_error("mean_waveforms: event %ld: label %d outside [0, %d)", e, ev_label[e], n_labels); return MTS_E_ARG; }
+            if (++per[(size_t)ev_label[e]] > MEAN_MAX_LABEL_EVENTS) {
+                set_error("mean_waveforms: label %d has more than %ld events", ev_label[e], MEAN_MAX_LABEL_EVENTS); return MTS_E_ARG;
+            }
+        }
+    }
+    if ((rc = check_snippet_events(T, Z, A))) return rc;
+    status_ok(T, status);
+    const size_t n_sum = (size_t)n_labels * (size_t)n_item;
+    if (n_events == 0) {                                           // zeros, and no gather
+        if (out_on_host) { memset(out_sum, 0, 8 * n_sum); memset(out_count, 0, 4 * n_sum); memset(out_skipped, 0, 8 * (size_t)n_labels); return MTS_OK; }
+        MTS_HIP(hipMemsetAsync(out_sum, 0, 8 * n_sum, st));
+        MTS_HIP(hipMemsetAsync(out_count, 0, 4 * n_sum, st));
+        MTS_HIP(hipMemsetAsync(out_skipped, 0, 8 * (size_t)n_labels, st));
+        MTS_HIP(hipStreamSynchronize(st));
+        return MTS_OK;
+    }
+
+    SnippetFeed S(T, out_on_host);
+    HaloFeed &H = S.H;
+    if ((rc = S.plan(E, Z, A))) return rc;
+    // every slab's parts, one behind the other: slab k's are parts [part0[k], part0[k + 1]); the perms make one array of n_events
+    std::vector<long> perm((size_t)n_events), part0 = {0};
+    std::vector<MeanPart> parts;
+    const long part_events = mean_part_events();
+    for (const SnippetPlan &Sp : S.slabs)
+        for (const SnippetSlab &B : Sp.slabs) {
+            const MeanParts M(ev_label, B.e0, B.e1, part_events);
+            std::copy(M.perm.begin(), M.perm.end(), perm.begin() + B.e0);
+            parts.insert(parts.end(), M.parts.begin(), M.parts.end());
+            part0.push_back((long)parts.size());
+        }
+    // ---- workspace
+    WsLayout &L = H.L;
+    ZStage F(Z, L);
+    const size_t o_seg = L.take(H.table_bytes()), o_erow = L.take(8 * (u64)n_events), o_ecol = L.take(4 * (u64)n_events),
+                 o_perm = L.take(8 * (u64)n_events), o_parts = L.take(sizeof(MeanPart) * (u64)parts.size()), o_y = L.take(4 * (u64)S.max_rows * n_cols),
+                 o_sum = L.take_out(8 * (u64)n_sum), o_count = L.take_out(4 * (u64)n_sum), o_skip = L.take_out(8 * (u64)n_labels);
+    StreamGuard G{st};
+    if ((rc = H.place(E, st, E.wav, o_seg))) return rc;
+    u8 *ws = E.wav.as<u8>();
+    if ((rc = F.upload(st, ws))) return rc;
+    MTS_HIP(hipMemcpyAsync(ws + o_erow, ev_row, 8 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_ecol, ev_col0, 4 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_perm, perm.data(), 8 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_parts, parts.data(), sizeof(MeanPart) * parts.size(), hipMemcpyHostToDevice, st));
+    long long *d_sum = L.out(ws, o_sum, out_sum);
+    int *d_count = L.out(ws, o_count, out_count);
+    long *d_skip = L.out(ws, o_skip, out_skipped);
+    MTS_HIP(hipMemsetAsync(d_sum, 0, 8 * n_sum, st));
+    MTS_HIP(hipMemsetAsync(d_count, 0, 4 * n_sum, st));
+    MTS_HIP(hipMemsetAsync(d_skip, 0, 8 * (size_t)n_labels, st));
+    float *d_y = (float *)(ws + o_y);
+    const MeanPart *d_parts = (const MeanPart *)(ws + o_parts);
+    rc = S.run(E, st, T, F, d_y, status, [&](const SnippetSlab &B, long k) {
+        return launch_mean_waveforms(st, d_y, B.a, B.b - B.a, n_cols, vb, ve, (const long *)(ws + o_erow), (const int *)(ws + o_ecol),
+                                     (const long *)(ws + o_perm), d_parts + part0[(size_t)k], part0[(size_t)k + 1] - part0[(size_t)k], before, after,
+                                     width, resolution, d_sum, d_count, d_skip);
+    });
+    if (rc) return rc;
+    if (out_on_host) {
+        MTS_HIP(hipMemcpyAsync(out_sum, d_sum, 8 * n_sum, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_count, d_count, 4 * n_sum, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_skipped, d_skip, 8 * (size_t)n_labels, hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = G.wait())) return rc;
+    S.done(E);
     return MTS_OK;
 }
 
@@ -1591,6 +1761,26 @@ int mts_dev_waveforms(int device, void *stream, const unsigned char *d_cdata, co
 {
     return DEV_ENTRY(waveforms_run(E, (hipStream_t)stream, T, Z_ARGS("waveforms"), n_events, ev_row, ev_col0, before, after, width, d_wave, d_min,
                      d_argmin, d_max, d_argmax, false, chunk_status));
+}
+
+int mts_mean_waveforms(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                       const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                       long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                       const long *ev_row, const int *ev_col0, const int *ev_label, int n_labels, int before, int after, int width,
+                       double resolution, long long *out_sum, int *out_count, long *out_skipped, int *chunk_status)
+{
+    return HOST_ENTRY(mean_waveforms_run(E, nullptr, T, Z_ARGS("mean_waveforms"), n_events, ev_row, ev_col0, ev_label, n_labels, before, after, width,
+                      resolution, out_sum, out_count, out_skipped, true, chunk_status));
+}
+
+int mts_dev_mean_waveforms(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                           const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                           long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                           const long *ev_row, const int *ev_col0, const int *ev_label, int n_labels, int before, int after, int width,
+                           double resolution, long long *d_sum, int *d_count, long *d_skipped, int *chunk_status)
+{
+    return DEV_ENTRY(mean_waveforms_run(E, (hipStream_t)stream, T, Z_ARGS("mean_waveforms"), n_events, ev_row, ev_col0, ev_label, n_labels, before,
+                     after, width, resolution, d_sum, d_count, d_skipped, false, chunk_status));
 }
 
 int mts_waveforms_last_plan(int device, long *out)

@@ -1,8 +1,9 @@
 // How a reduction is fed: the part that decides and touches no device.  Which chunks go into which piece, where the compressed
 // bytes of the missing chunks lie in the staging buffer, where each of them is decoded to, which chunks a piece of the halo family
 // reads and what its segment table holds, how the tile family cuts and orders its tiles, how the events of waveforms and the rows of match_templates
-// are cut into slabs.  Addresses are plain integers here: the header includes the C++ standard library only, so tests/plan_check.cpp,
-// tests/snippet_plan_check.cpp and tests/tmatch_plan_check.cpp sweep these plans on the CPU.  reduce.hip puts the
+// are cut into slabs, how mean_waveforms groups a slab's events by label.  Addresses are plain integers here: the header includes the
+// C++ standard library only, so tests/plan_check.cpp, tests/snippet_plan_check.cpp, tests/tmatch_plan_check.cpp and
+// tests/mean_plan_check.cpp sweep these plans on the CPU.  reduce.hip puts the
 // device side around them (ChunkFeed, feed_pieces, HaloFeed, TileFeed) and says there what every caller keeps to.
 #pragma once
 
@@ -177,6 +178,31 @@ struct SnippetPlan {
             slabs.push_back({e, e + 1, a, b});
         }
         for (const SnippetSlab &S : slabs) max_rows = std::max(max_rows, S.b - S.a);
+    }
+};
+
+// ---- per-label sums of snippets (mean_waveforms): the events [e0, e1) of one slab grouped by label.  perm holds the slab's events, a
+// label's events together and in list order (stable); each label's run is cut into parts of at most part_events events.  Part
+// { label, count, first } is perm[first - e0 .. first - e0 + count): `first` counts from the call's first event, so that the perms of
+// a call's slabs, one behind the other, are one array of n_events entries.  The parts partition the slab's events; none is empty.
+struct MeanPart { int label, count; long first; };
+
+struct MeanParts {
+    std::vector<long> perm;
+    std::vector<MeanPart> parts;
+
+    MeanParts(const int *label, long e0, long e1, long part_events)
+    {
+        const long cap = std::max(1l, part_events);
+        perm.resize((size_t)(e1 > e0 ? e1 - e0 : 0));
+        for (long e = e0; e < e1; e++) perm[(size_t)(e - e0)] = e;
+        std::stable_sort(perm.begin(), perm.end(), [&](long a, long b) { return label[a] < label[b]; });
+        for (long k = 0, n = (long)perm.size(); k < n;) {
+            long run = k + 1;
+            while (run < n && label[perm[(size_t)run]] == label[perm[(size_t)k]]) run++;
+            for (long j = k; j < run; j += cap) parts.push_back({label[perm[(size_t)k]], (int)std::min(cap, run - j), e0 + j});
+            k = run;
+        }
     }
 };
 

@@ -5,6 +5,7 @@ the shared library has not been built (``python -c "import __graft_entry__ as g;
 ``make -C mtscomp_amd/csrc``) and every compute call raises ``HipError`` when no MI355X is visible.
 """
 import ctypes as C
+import math
 import os
 import warnings
 from pathlib import Path
@@ -108,6 +109,7 @@ def lib():
             ('project', [cl, cl, ci, ip, dp, ci, dp, ci], [vp, ip], None),
             ('detect', [cl, cl, cl, cl, ci, dp, ci, ip, fp, ci, ci, ci, ci, cl], [vp, vp, vp, lp, ip], None),
             ('waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci], [vp, vp, vp, vp, vp, ip], None),
+            ('mean_waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ip, ci, ci, ci, ci, C.c_double], [vp, vp, vp, ip], None),
             ('correlate', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp], [vp, ip], None),
             ('match_templates', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, fp, ci, cl], [vp, vp, vp, lp, ip], None),
             ('residual', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, cl, lp, ip, fp], [vp, ip], None),
@@ -131,7 +133,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
            'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_project', 'mts_dev_project', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
-           'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan', 'mts_correlate', 'mts_dev_correlate',
+           'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan', 'mts_mean_waveforms', 'mts_dev_mean_waveforms', 'mts_correlate', 'mts_dev_correlate',
            'mts_match_templates', 'mts_dev_match_templates',
            'mts_residual', 'mts_dev_residual', 'mts_match_residual', 'mts_dev_match_residual',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
@@ -800,6 +802,58 @@ def waveforms_last_plan(device=0):
     out = np.zeros(4, np.int64)
     _check(lib().mts_waveforms_last_plan(int(device), _lp(out)), 'mts_waveforms_last_plan')
     return dict(zip(('pieces', 'slabs', 'gap_cuts', 'gather_us'), (int(v) for v in out)))
+
+
+# -- per-label fixed-point sums of those snippets
+MEAN_MAX_LABELS = 4096                 # MTS_MEAN_MAX_LABELS
+MEAN_MAX_ENTRIES = 1 << 27             # MTS_MEAN_MAX_ENTRIES
+MEAN_MAX_LABEL_EVENTS = 1 << 21        # events of one label in a call
+_MEAN_DTYPES = (np.int64, np.int32, np.int64)                           # sum, count, skipped
+
+
+def mean_resolution_ok(resolution):
+    """A power of two in [2^-60, 2^60]: what mts_mean_waveforms takes for its fixed point."""
+    try:
+        m, e = math.frexp(float(resolution))
+    except (TypeError, ValueError, OverflowError):
+        return False
+    return m == 0.5 and -60 <= e - 1 <= 60
+
+
+def _mean_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, ev_label, n_labels, before, after, width, resolution):
+    """-> (the op's own arguments of mts_mean_waveforms, the shapes of its three results)."""
+    wav, _, item = _wav_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width)
+    ev_label = np.ascontiguousarray(np.asarray(ev_label, dtype=np.int32))
+    assert ev_label.ndim == 1 and ev_label.size == wav[7]
+    mid = wav[:10] + (_ip(ev_label), int(n_labels)) + wav[10:] + (float(resolution),)
+    K = max(int(n_labels), 0)
+    shape = (K, int(before) + int(after), int(width)) if item else (K, 0, 0)
+    return mid, (shape, shape, (K,))
+
+
+def mean_waveforms(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference,
+                   ev_row, ev_col0, ev_label, n_labels, before, after, width, resolution, device=0):
+    """mts_mean_waveforms: the fixed-point sums over each label's events of the snippets that mts_waveforms would return for them
+    (include/mtscomp_hip.h), from the adjacent chunks `keys`.  ev_label: ints in [0, n_labels).  cache_id as waveforms.  Returns
+    (status list, sum int64 (n_labels, T, width), count int32 (n_labels, T, width), skipped int64 (n_labels))."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, shapes = _mean_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, ev_label, n_labels, before, after, width, resolution)
+    res = [np.empty(sh, t) for sh, t in zip(shapes, _MEAN_DTYPES)]
+    _check(lib().mts_mean_waveforms(*head, *mid, *(_ptr(a) for a in res), _ip(status)), 'mts_mean_waveforms')
+    return (_status(status, n),) + tuple(res)
+
+
+def dev_mean_waveforms(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0,
+                       ev_label, n_labels, before, after, width, resolution, out=None, download=True):
+    """mts_dev_mean_waveforms on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the three results (made
+    when None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, (sum, count, skipped) or
+    None, out)."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, shapes = _mean_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, ev_label, n_labels, before, after, width, resolution)
+    res = [np.empty(sh, t) for sh, t in zip(shapes, _MEAN_DTYPES)]
+    out, ptrs, at = _dev_results(out, cbuf.device, [a.nbytes for a in res])
+    _check(lib().mts_dev_mean_waveforms(*head, *mid, *ptrs, _ip(status)), 'mts_dev_mean_waveforms')
+    return _status(status, n), tuple(_dev_fetch(out, at, res)) if download else None, out
 
 
 # -- spatio-temporal template scores
