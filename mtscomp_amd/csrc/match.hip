@@ -107,9 +107,12 @@ constexpr int M6_SLICES = 64;
 constexpr int M5_RING = 256;
 constexpr int M5_ROWS = 32;
 constexpr int M5_LEVELS = 4;                         // tables for prefix lengths 4, 5, 6, 7
-constexpr int M5_ROW_WORDS = M5_RING / 32 + 1;       // a row is 8 words of bits + 1 of padding, so that rows start in different LDS banks (32-byte rows whose word
+constexpr int M5_ROW_WORDS = M5_RING / 32 + 1;       // a row is 8 words of bits + a ninth, so that rows start in different LDS banks (32-byte rows whose word
                                                      // addresses are (offset & 28) | row save ten instructions per group and cost 1.8 ms in bank conflicts; whole rows read
-                                                     // from one address -- four ds_read2_b32 -- and the five words picked in registers save fourteen and cost 0.5 ms: round 4)
+                                                     // from one address -- four ds_read2_b32 -- and the five words picked in registers save fourteen and cost 0.5 ms: round 4).
+                                                     // k_match5: word 8 is DATA, a copy of word 0 (kept by commit() in the phase that writes word 0; the zero fill covers it):
+                                                     // the upper half-wave reads "the word behind the lower half's", and behind word 7 that is word 8 -- no wrap of its own.
+                                                     // (k_match6 has its own M6_ROW_WORDS, whose last word is padding.)
 constexpr int M5_TABLE = M5_ROWS * M5_ROW_WORDS * 4; // bytes per table
 constexpr int M5_SLOTS = M5_LEVELS + 1;                // the first table has 64 rows (a 6-bit key of byte 3): two table slots
 constexpr int M5_SX_BYTES = MTS_M5_SX == 1 ? 8 : MTS_M5_SX == 2 ? 4 : 0;      // per slot, of its bytes 7..
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(M5W * 64) void k_match5(const u8 *__restrict__ stre
     const u8 *gwin = stream + td.stream_off + td.w;
     auto wread = [&](u32 addr) -> u32 { return gld_u32_unaligned(gwin, addr); };
     u64 *SE = (u64 *)(smem + wave * (M5_RING * 8));
-    u64 *SX = (u64 *)(smem + M5W * M5_RING * 8 + wave * (M5_RING * 8));      // bytes 7..12 of every slot: matches up to 13 never leave the LDS
+    // (behind the entry rings, at the same offset + M5W * 2 KB: bytes 7..12 of every slot -- matches up to 13 never leave the LDS)
     u32 *TB = (u32 *)(smem + M5W * M5_RING * (8 + M5_SX_BYTES) + M5_VLUT + wave * (M5_SLOTS * M5_TABLE));      // [level][row][8 words + 1]
     const uint4 *VLUT = (const uint4 *)(smem + M5W * M5_RING * (8 + M5_SX_BYTES));      // [0 .. 128]: the newest n of 128 bits (one table per workgroup; behind the rings, where its offset fits a ds instruction's)
     typedef __attribute__((address_space(3))) const u64 *lds_u64p;
@@ -258,17 +261,39 @@ __global__ __launch_bounds__(M5W * 64) void k_match5(const u8 *__restrict__ stre
     u32 inv[6];                                                    // lane r builds row r of the first table: bit j of r clear -> all ones
 #pragma unroll
     for (int j = 0; j < 6; j++) inv[j] = ((lane >> j) & 1) ? 0u : 0xffffffffu;
-    // slot idx -> position -> its 13 bytes -> entry; enters the ring at idx & 255, replacing slot idx - 256.  The ring
+    // The ring has 256 slots and a group 64: a group's ring positions are PH * 64 + lane with PH = group & 3, the same for the whole
+    // wave, and every ring or table address of the group is a per-lane constant plus one of four constants.  What makes such
+    // addresses -- commit() and the mask phase of a group -- exists once per phase, PH a compile-time constant, behind a wave-uniform
+    // switch: every LDS access in there is one of these base registers and an instruction immediate (as run-time data the phase
+    // cost ~13 vector instructions of shifts, masks and adds per commit and 29 per mask phase).  The walks exist once: they take the
+    // phase through `lo8`.  (The empty asm at the top of the group loop keeps base + constant from being hoisted into a register each.)
+    typedef __attribute__((address_space(3))) u32 *lds_w32p;
+    typedef __attribute__((address_space(3))) u64 *lds_w64p;
+    auto lds32 = [](u32 a) -> lds_w32p { return (lds_w32p)(size_t)a; };       // (byte addresses in LDS)
+    auto lds64 = [](u32 a) -> lds_w64p { return (lds_w64p)(size_t)a; };
+    const u32 tb_base = (u32)(size_t)(__attribute__((address_space(3))) u8 *)(u8 *)TB;
+    u32 a_ring = se_base + (u32)lane * 8;                          // this lane's slot of ring quarter 0
+    u32 a_row0 = tb_base + (u32)lane * (M5_ROW_WORDS * 4);        // row `lane` of the first table (64 rows),
+    u32 a_row1 = a_row0 + 2 * M5_TABLE;                            // of tables 1..3 (their 96 rows are contiguous),
+    u32 a_row2 = a_row1 + 64 * (M5_ROW_WORDS * 4);                 // and row 64 + lane of those (lanes 0..31)
+    // addends of key * 36, per table: the rows of table d from the word of this lane's half-wave on (the upper half reads and sets the word behind the lower half's)
+    u32 a_tab0 = tb_base + ((u32)lane >> 5) * 4, a_tab1 = a_tab0 + m5_slot(1) * M5_TABLE, a_tab2 = a_tab0 + m5_slot(2) * M5_TABLE, a_tab3 = a_tab0 + m5_slot(3) * M5_TABLE;
+    auto a_tab = [&](const int d) __attribute__((always_inline)) -> u32 { return d == 0 ? a_tab0 : d == 1 ? a_tab1 : d == 2 ? a_tab2 : a_tab3; };
+    const u32 lane_bit = 1u << (lane & 31), lane_sh = (u32)lane & 31;
+    const bool lower = lane < 32;
+    // slot idx -> position -> its 13 bytes -> entry; enters the ring at idx & 255 = PH * 64 + lane, replacing slot idx - 256.  The ring
     // positions of a 64-slot group are two whole words of every table row: they are cleared and set again (the first table,
     // whose keys repeat most -- 32 lanes adding the same bit to the same word would be serialised by the LDS -- is rebuilt
-    // from five ballots by the lane that owns the row; the others take one atomic OR per slot).  `nbv` = the chain behind
+    // from five ballots by the lane that owns the row; the others take one atomic OR per slot).  Word 8 of a row mirrors word 0
+    // (M5_ROW_WORDS): the phase whose word pair is {0, 1} writes both.  `nbv` = the chain behind
     // the slot = the slots back to the start of its hash run (at most 128 matter), from the ballot of the run starts.
-    auto commit = [&](int idx, u32 rc, u32 lo, u32 hi, u64 x, u32 (&key)[M5_LEVELS], u32 &nbv, u64 &vm) -> u64 {
-        const u32 rp = (u32)idx & (M5_RING - 1), word = rp >> 5, bit = 1u << (rp & 31);
+    // (valid = idx < wlen as unsigned numbers, vm = its ballot: made by the caller, in front of the switch -- a ballot of a comparison in another
+    //  block goes through a 0 / 1 register and a second comparison)
+    auto commit = [&](auto phase, const bool valid, const u64 vm, u32 rc, u32 lo, u32 hi, u64 x, u32 (&key)[M5_LEVELS], u32 &nbv) __attribute__((always_inline)) -> u64 {
+        constexpr u32 PH = decltype(phase)::value;
+        constexpr u32 WP = 2 * PH;                                 // the group's word pair: words WP (lanes 0..31) and WP + 1
         // (lane masks are made by single comparisons and combined as scalars: the ballot of a compound condition goes through a
         //  0 / 1 register and a second comparison)
-        const bool valid = (u32)idx < wlen;                        // (a negative index is a huge one)
-        vm = ballot64(valid);
         const u64 ce = valid ? make_entry(rc, lo, hi) : ~0ull;
         // a slot starts a run when its hash differs from its predecessor's (slots are committed in order)
         const u32 h = valid ? hash_of(lo) : 0xfffffffeu;
@@ -291,11 +316,11 @@ __global__ __launch_bounds__(M5W * 64) void k_match5(const u8 *__restrict__ stre
         nbv = nbv < 128u ? nbv : 128u;
         run_carry = sr ? (u32)__builtin_clzll(sr) + 1u : (run_carry + 64u < 128u ? run_carry + 64u : 128u);
         m5_keys((u32)(ce >> 32), key);
-        const u32 wp = word & ~1u;                                 // the group's word pair
         {
-            u32 *t1 = TB + 2 * (M5_TABLE / 4) + lane * M5_ROW_WORDS + wp;   // rows of tables 1..3 are contiguous: 96 rows
+            lds_w32p t1 = lds32(a_row1 + WP * 4), t2 = lds32(a_row2 + WP * 4);
             t1[0] = 0; t1[1] = 0;
-            if (lane < 32) { t1[64 * M5_ROW_WORDS] = 0; t1[64 * M5_ROW_WORDS + 1] = 0; }
+            if (PH == 0) t1[8] = 0;
+            if (lower) { t2[0] = 0; t2[1] = 0; if (PH == 0) t2[8] = 0; }
             // (atomic ORs for this table as well take 42 vector instructions off a group -- 8 % of the kernel's -- and give them back
             //  as LDS waits: byte 3 of an even position is the high byte of a small delta, two values, 32 lanes per word;
             //  SQ_WAIT_INST_LDS x5, the same 25.2 ms)
@@ -313,38 +338,55 @@ __global__ __launch_bounds__(M5W * 64) void k_match5(const u8 *__restrict__ stre
 #endif
                 m0 = and_xor(m0, (u32)B, inv[j]); m1 = and_xor(m1, (u32)(B >> 32), inv[j]);
             }
-            { u32 *t0 = TB + lane * M5_ROW_WORDS + wp; t0[0] = m0; t0[1] = m1; }
+            { lds_w32p t0 = lds32(a_row0 + WP * 4); t0[0] = m0; t0[1] = m1; if (PH == 0) t0[8] = m0; }
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int d = 1; d < M5_LEVELS; d++)
-            if (valid) atomicOr(&TB[m5_slot(d) * (M5_TABLE / 4) + key[d] * M5_ROW_WORDS + word], bit);
-        SE[rp] = ce;
+            if (valid) __hip_atomic_fetch_or(lds32(key[d] * (M5_ROW_WORDS * 4) + a_tab(d) + WP * 4), lane_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (PH == 0) {                                             // word 0 was set by the lower half-wave: so is its copy
+#pragma unroll
+            for (int d = 1; d < M5_LEVELS; d++)
+                if (valid && lower) __hip_atomic_fetch_or(lds32(key[d] * (M5_ROW_WORDS * 4) + a_tab(d) + 8 * 4), lane_bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        *lds64(a_ring + PH * 512) = ce;
 #if MTS_M5_SX == 1
-        SX[rp] = x;
+        *lds64(a_ring + (M5W * M5_RING * 8 + PH * 512)) = x;
 #elif MTS_M5_SX == 2
-        ((u32 *)(smem + M5W * M5_RING * 8))[wave * M5_RING + rp] = (u32)x;
+        *lds32((a_ring >> 1) + (M5W * M5_RING * 8 + PH * 256)) = (u32)x;
 #endif
         return ce;
+    };
+    // the copy for a phase that is only known at run time (the same in every lane: a scalar branch)
+    auto by_phase = [&](u32 ph, auto &&f) __attribute__((always_inline)) {
+        switch (ph) {
+        case 0: return f(std::integral_constant<u32, 0>{});
+        case 1: return f(std::integral_constant<u32, 1>{});
+        case 2: return f(std::integral_constant<u32, 2>{});
+        default: return f(std::integral_constant<u32, 3>{});
+        }
     };
     // bytes 0..12 of the string at window offset r with ONE 16-byte load (the four dwords around it): the lanes are each
     // somewhere else in the window, and the address unit charges by the instruction
     typedef u32 u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-    auto load16 = [&](u32 r, u32 &lo, u32 &hi, u64 &x) {
-        const u8 *q = gwin + (r & ~3u);
-        const u32x4_a4 w = *(const u32x4_a4 *)q;
+    // (in two halves: the group loop issues the load in the middle of a group and takes the bytes apart at its end, behind the walks)
+    auto fetch16 = [&](u32 r) -> u32x4_a4 { return *(const u32x4_a4 *)(gwin + (r & ~3u)); };
+    auto unpack16 = [&](const u32x4_a4 w, u32 r, u32 &lo, u32 &hi, u64 &x) {
         lo = alignbyte(w.y, w.x, r);
         hi = alignbyte(w.z, w.y, r);
         const u32 b8 = alignbyte(w.w, w.z, r), b12 = alignbyte(0u, w.w, r);
         x = (u64)__builtin_amdgcn_alignbit(b8, hi, 24) | ((u64)(__builtin_amdgcn_alignbit(b12, b8, 24) & 0xffffu) << 32);      // bytes 7..10, 11..12
     };
+    auto load16 = [&](u32 r, u32 &lo, u32 &hi, u64 &x) { unpack16(fetch16(r), r, lo, hi, x); };
+    u32 ph = (u32)__builtin_amdgcn_readfirstlane((int)(g_begin & 3));      // the phase of the group about to be walked: a scalar
     // pipeline: (rc, lo, hi) of the group about to be walked, rc of the one after
     u32 rc_c = r_0, rc_n = r_1;
     u32 lo_c, hi_c;
     u64 x_c;
     {
         u32 kk[M5_LEVELS], nb;
-        u64 vmm;
+        const bool va = (u32)(i_first - 128) < wlen, vb = (u32)(i_first - 64) < wlen;      // (a negative index is a huge one)
+        const u64 vma = ballot64(va), vmb = ballot64(vb);
         const u32 ra = r_ha, rb = r_hb;
         u32 la, ha, lb, hb;
         u64 xa, xb;
@@ -352,34 +394,76 @@ __global__ __launch_bounds__(M5W * 64) void k_match5(const u8 *__restrict__ stre
         load16(rb, lb, hb, xb);
         load16(rc_c, lo_c, hi_c, x_c);
         *sink = 0;                                                 // (a store behind the loads, as at the end of every iteration)
-        commit(i_first - 128, ra, la, ha, xa, kk, nb, vmm);
+        by_phase(ph ^ 2, [&](auto phase) { commit(phase, va, vma, ra, la, ha, xa, kk, nb); });
         __builtin_amdgcn_wave_barrier();
-        commit(i_first - 64, rb, lb, hb, xb, kk, nb, vmm);
+        by_phase((ph + 3) & 3, [&](auto phase) { commit(phase, vb, vmb, rb, lb, hb, xb, kk, nb); });
     }
-    for (u32 g = g_begin; g < g_end; g++) {
+    for (u32 g = g_begin; g < g_end; g++, ph = (ph + 1) & 3) {
         const u32 i0 = g * 64, i = i0 + lane;
         u32 key[M5_LEVELS], nbv;
+        asm volatile("" : "+v"(a_ring), "+v"(a_row0), "+v"(a_row1), "+v"(a_row2), "+v"(a_tab0), "+v"(a_tab1), "+v"(a_tab2), "+v"(a_tab3));      // (registers: see above)
         __builtin_amdgcn_wave_barrier();
 #if MTS_M5_STATS == 2
         st_mark = (u64)clock64();
 #endif
-        u64 vm;
-        const u64 e = commit((int)i, rc_c, lo_c, hi_c, x_c, key, nbv, vm);
-        const u64 ex = x_c;
-        __builtin_amdgcn_wave_barrier();
-        // next group's words, and the position of the one after
-        rc_c = rc_n;
-        load16(rc_c, lo_c, hi_c, x_c);
-        rc_n = slot_fwd(i + 128);
-        const u32 e0 = (u32)e, e1 = (u32)(e >> 32);
-        const u32 rel_p = e0 & REL_MASK;
-        const bool own = i < wlen && rel_p >= halo;
-        const u64 ownm = vm & ballot64(rel_p >= halo);             // (the same as a lane mask, without the ballot of a compound condition)
+        const bool valid = i < wlen;
+        const u64 vm = ballot64(valid);
+        u64 e, ex, ownm;
+        u32x4_a4 w_n;                                              // the four dwords around the next group's strings
+        // The next group's bytes are taken out of them at the END of this group, on either path: inside the phase's copy (where the load
+        // is issued) the values would be wanted at the join behind it, and the wave would sit out the load's round trip in front of
+        // its walks instead of behind them (measured: k_match5 18.6-18.9 ms against 18.1-18.3, with 9 % fewer vector instructions).
+        auto next_bytes = [&]() __attribute__((always_inline)) { unpack16(w_n, rc_c, lo_c, hi_c, x_c); };
+        u32 e0, e1, rel_p, lo8;
+        bool own;
+        u32 V[4], A4[4], A5[4], A6[4], A7[4];                     // V = inside the budget; A_d = V & "first d bytes may match"
+        // what depends on the group's phase: the commit and the four filter masks (false: no lane of the group owns its position)
+        auto front = [&](auto phase) __attribute__((always_inline)) -> bool {
+            constexpr u32 PH = decltype(phase)::value;
+            e = commit(phase, valid, vm, rc_c, lo_c, hi_c, x_c, key, nbv);
+            ex = x_c;
+            __builtin_amdgcn_wave_barrier();
+            // next group's words, and the position of the one after
+            rc_c = rc_n;
+            w_n = fetch16(rc_c);
+            rc_n = slot_fwd(i + 128);
+            e0 = (u32)e; e1 = (u32)(e >> 32);
+            rel_p = e0 & REL_MASK;
+            own = valid && rel_p >= halo;
+            ownm = vm & ballot64(rel_p >= halo);         // (the same as a lane mask, without the ballot of a compound condition)
+            if (!ownm) return false;
 #if MTS_M5_STATS == 2
-        if (!ownm) { *sink = 0; M5_MARK(5); continue; }
-        M5_MARK(0);
+            M5_MARK(0);
+#endif
+            // the 128 slots before this lane's own are ring positions lo .. lo + 127 (mod 256), lo = ((PH + 2) & 3) * 64 + lane; candidate j
+            // (1 = newest) is bit 128 - j of the masks.  V = the candidates inside this lane's chain budget.
+            constexpr u32 PL = (PH + 2) & 3, W = 2 * PL;          // lo's ring quarter; its word in lanes 0..31 (W + 1 in lanes 32..63)
+            lo8 = a_ring + PL * 512;                               // (ring_e() takes the low 11 bits: the wave's base in a_ring drops out)
+            nbv = own ? (nbv < chain ? nbv : chain) : 0;
+            {   // the newest nbv of the 128 bits: one 16-byte read of a table of the 129 masks (24 instructions of shifts and selects otherwise)
+                const uint4 v = VLUT[nbv];
+                V[0] = v.x; V[1] = v.y; V[2] = v.z; V[3] = v.w;
+            }
+            auto rowmask = [&](const int d, const u32 (&in)[4], u32 (&out)[4]) __attribute__((always_inline)) {
+                // words (W + k) & 7 in the lower half-wave, the word behind each in the upper one (a_tab): behind word 7 that is word 8, the copy of word 0
+                const u32 row = key[d] * (M5_ROW_WORDS * 4) + a_tab(d);
+                auto word = [&](const u32 k) -> u32 { return *lds32(row + ((W + k) & 7) * 4); };
+                const u32 W0 = word(0), W1 = word(1), W2 = word(2), W3 = word(3), W4 = word(4);
+                out[0] = in[0] & __builtin_amdgcn_alignbit(W1, W0, lane_sh);
+                out[1] = in[1] & __builtin_amdgcn_alignbit(W2, W1, lane_sh);
+                out[2] = in[2] & __builtin_amdgcn_alignbit(W3, W2, lane_sh);
+                out[3] = in[3] & __builtin_amdgcn_alignbit(W4, W3, lane_sh);
+            };
+            rowmask(0, V, A4);
+            rowmask(1, A4, A5);
+            rowmask(2, A5, A6);
+            rowmask(3, A6, A7);
+            return true;
+        };
+#if MTS_M5_STATS == 2
+        if (!by_phase(ph, front)) { *sink = 0; next_bytes(); M5_MARK(5); continue; }
 #else
-        if (!ownm) { *sink = 0; continue; }                             // (the store every path has: see the end of the loop)
+        if (!by_phase(ph, front)) { *sink = 0; next_bytes(); continue; }      // (the store every path has: see the end of the loop)
 #endif
         const u32 p_abs = td.w + rel_p;
         const u32 look = n - p_abs;
@@ -388,29 +472,6 @@ __global__ __launch_bounds__(M5W * 64) void k_match5(const u8 *__restrict__ stre
         // window offsets a candidate must lie above: the head of the chain, the others
         const int lim1 = (int)(p_abs > (u32)MAX_DIST + 1 ? p_abs - MAX_DIST - 1 : 0) - (int)td.w;
         const int limn = (int)(p_abs > (u32)MAX_DIST ? p_abs - MAX_DIST : 0) - (int)td.w;
-        // the 128 slots before this lane's own are ring positions lo .. lo + 127 (mod 256); candidate j
-        // (1 = newest) is bit 128 - j of the masks.  V = the candidates inside this lane's chain budget.
-        const u32 lo = (i + 128) & (M5_RING - 1), w0 = lo >> 5, sh = lo & 31, lo8 = lo << 3;
-        nbv = own ? (nbv < chain ? nbv : chain) : 0;
-        u32 V[4], A4[4], A5[4], A6[4], A7[4];                     // V = inside the budget; A_d = V & "first d bytes may match"
-        {   // the newest nbv of the 128 bits: one 16-byte read of a table of the 129 masks (24 instructions of shifts and selects otherwise)
-            const uint4 v = VLUT[nbv];
-            V[0] = v.x; V[1] = v.y; V[2] = v.z; V[3] = v.w;
-        }
-        auto rowmask = [&](const int d, const u32 (&in)[4], u32 (&out)[4]) __attribute__((always_inline)) {
-            const u8 *row = (const u8 *)(TB + m5_slot(d) * (M5_TABLE / 4) + key[d] * M5_ROW_WORDS);
-            // (byte offsets ((w0 + k) << 2) & 28: an add-shift and an AND per word; as (w0 + k) & 7 first it was an add, an AND and a shift)
-            auto word = [&](const u32 k) -> u32 { return *(const u32 *)(row + (((w0 + k) << 2) & 28u)); };
-            const u32 W0 = word(0), W1 = word(1), W2 = word(2), W3 = word(3), W4 = word(4);
-            out[0] = in[0] & __builtin_amdgcn_alignbit(W1, W0, sh);
-            out[1] = in[1] & __builtin_amdgcn_alignbit(W2, W1, sh);
-            out[2] = in[2] & __builtin_amdgcn_alignbit(W3, W2, sh);
-            out[3] = in[3] & __builtin_amdgcn_alignbit(W4, W3, sh);
-        };
-        rowmask(0, V, A4);
-        rowmask(1, A4, A5);
-        rowmask(2, A5, A6);
-        rowmask(3, A6, A7);
 #if MTS_M5_STATS == 2
         asm volatile("" :: "v"(A7[0]), "v"(A7[1]), "v"(A7[2]), "v"(A7[3]));
         M5_MARK(1);
@@ -614,6 +675,7 @@ __global__ __launch_bounds__(M5W * 64) void k_match5(const u8 *__restrict__ stre
             u32 *dst = own ? T + p_abs : sink;
             *dst = e;
         }
+        next_bytes();
 #if MTS_M5_STATS
         st_groups++;
 #if MTS_M5_STATS == 2
