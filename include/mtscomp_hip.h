@@ -45,7 +45,7 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_correlate, mts_match_templates, mts_welch, mts_gram and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_waveform_features, mts_correlate, mts_match_templates, mts_welch, mts_gram and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
 #define MTS_PROJECT_MAX_COLS 1024
 #define MTS_PROJECT_MAX_OUT  1024
@@ -61,6 +61,8 @@ extern "C" {
 #define MTS_WAVEFORMS_MAX_WIDTH 1024    /* ... and its column positions */
 #define MTS_MEAN_MAX_LABELS 4096       /* mts_mean_waveforms: labels of a call */
 #define MTS_MEAN_MAX_ENTRIES (1L << 27) /* ... and n_labels * T * width, the entries of its sums */
+#define MTS_FEATURES_MAX_COMPONENTS 32  /* mts_waveform_features: rows of its basis (the components) */
+#define MTS_FEATURES_MAX_BASIS 8192     /* ... and n_comp * T, the entries of the basis: 32 KiB of LDS */
 #define MTS_DETECT_MAX_REF_COLS 1024    /* columns of a median reference: a row's order keys are sorted in 4 KiB of LDS by one wave */
 #define MTS_CORRELATE_MAX_T 256         /* mts_correlate: rows of a template (its taus) */
 #define MTS_CORRELATE_MAX_OUT 1024      /* ... the templates of a call */
@@ -387,6 +389,34 @@ int mts_mean_waveforms(int device, long cache_id, int n_chunks, const long *chun
                        long *out_skipped /* (n_labels) */, int *chunk_status);
 
 /*
+ * The snippets of mts_waveforms projected on a small temporal basis: the "PC features" that clustering reads (an extension: the reference
+ * has no such call; its users pull the snippets across the bus and run an einsum on the host).  What crosses the bus is n_events *
+ * n_comp * width floats, not n_events * T * width.  Everything is float32 and a definition, not a tolerance:
+ *   z, events, snippet, fill   exactly mts_waveforms': s[e, tau, w] is the entry that mts_waveforms returns, the quiet NaN 0x7fc00000
+ *                  where its row lies outside [valid_begin, valid_end) or its column position outside [0, n_cols)
+ *   basis          (n_comp, T) float32 in C order on the host, T = before + after; every entry finite
+ *   features       out_feat[e, p, w] is the chain acc = +0; for tau = 0 .. T - 1: acc = fmaf(s[e, tau, w], basis[p, tau], acc), bit for
+ *                  bit; a NaN result is stored as 0x7fc00000.  Zero basis entries are not skipped (inf * 0 is NaN), so one fill or NaN
+ *                  entry in the column (e, ., w) makes out_feat[e, :, w] NaN.  From +0 the chain never ends at -0
+ *   outputs        out_feat (n_events, n_comp, width) C order.  One chain is one thread's from +0 to its store: the same bytes
+ *                  whatever the call, its pieces, its slabs, the gap setting, the cache or the device, and the bytes of the chain
+ *                  applied on the host to mts_waveforms' own snippets
+ *   limits         T, width, n_events, taps, columns and the reference's columns as mts_waveforms; 1 <= n_comp <=
+ *                  MTS_FEATURES_MAX_COMPONENTS; n_comp * T <= MTS_FEATURES_MAX_BASIS
+ *   chunks, chunk_status   as mts_waveforms; the features near a failed chunk are undefined
+ * mts_waveform_features: host cdata; cache_id 0 or a decoded-chunk cache, read in place and never inserted into, as mts_waveforms; the
+ * same pieces (MTS_PIPE_BYTES) and slabs (MTS_WAVEFORMS_SLAB_BYTES, MTS_WAVEFORMS_GAP_ROWS).  The output is host memory.
+ * mts_dev_waveform_features: device d_cdata and d_feat on `device`; ev_row, ev_col0, basis and chunk_status on the host; no cache.
+ * MTS_E_ARG with a message before anything is allocated or launched: what mts_waveforms refuses, n_comp or n_comp * T outside the
+ * limits, no basis, no output buffer, a basis entry that is not finite.  n_events == 0 is MTS_OK without a launch.
+ */
+int mts_waveform_features(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                          const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                          long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                          const long *ev_row, const int *ev_col0, int before, int after, int width, int n_comp,
+                          const float *basis /* (n_comp, T) C order */, float *out_feat /* (n_events, n_comp, width) C order */, int *chunk_status);
+
+/*
  * Spatio-temporal template scores of filtered rows (an extension: the reference has no such call; its users pull Reader[...] across the
  * bus, filter it and run a matched filter on the host).  Only the scores cross the bus.  Everything is float32 and a definition, not a
  * tolerance:
@@ -703,6 +733,11 @@ int mts_dev_mean_waveforms(int device, void *stream, const unsigned char *d_cdat
                            long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
                            const long *ev_row /* host */, const int *ev_col0 /* host */, const int *ev_label /* host */, int n_labels, int before,
                            int after, int width, double resolution, long long *d_sum, int *d_count, long *d_skipped, int *chunk_status /* host */);
+int mts_dev_waveform_features(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                              const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                              long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                              const long *ev_row /* host */, const int *ev_col0 /* host */, int before, int after, int width, int n_comp,
+                              const float *basis /* host */, float *d_feat, int *chunk_status /* host */);
 int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                       const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
                       long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
@@ -760,7 +795,7 @@ int mts_dev_compare(int device, void *stream, const void *d_a, const void *d_b, 
  * fills up to `cap` entries of (name, ms); returns the number of stages.  For bench.py / profiling. */
 int mts_last_stage_times(int device, const char **names, float *ms, int cap);
 
-/* What the last successful mts_waveforms / mts_dev_waveforms (or mts_mean_waveforms / mts_dev_mean_waveforms) call on `device` did, for the tests and the benchmark: out[0] its pieces,
+/* What the last successful mts_waveforms / mts_dev_waveforms (or mts_mean_waveforms / mts_dev_mean_waveforms, mts_waveform_features / mts_dev_waveform_features) call on `device` did, for the tests and the benchmark: out[0] its pieces,
  * out[1] its slabs, out[2] the slabs among them that were begun at a gap, out[3] the microseconds of its gather kernels (measured,
  * with a wait per slab, only while MTS_WAVEFORMS_TIME is set; else 0). */
 int mts_waveforms_last_plan(int device, long *out /* 4 */);

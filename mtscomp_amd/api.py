@@ -281,6 +281,37 @@ def whitening_weights(cov, eps=0.0):
     return 0.5 * (w + w.T)
 
 
+def waveform_basis(waveforms, n_components=3):
+    """The temporal basis of Reader.waveform_features from snippets: the n_components leading eigenvectors of the temporal Gram
+    matrix, as float32 (P, T).  waveforms: any (..., T, W) array of numbers -- the snippets of Reader.waveforms, or the mean of
+    Reader.mean_waveforms; every column (..., :, w) is one T-vector v, and a column that holds a NaN is dropped.  G = sum v v^T in
+    float64, not centred (as Kilosort does); np.linalg.eigh(G); the eigenvectors of the P largest eigenvalues in descending order,
+    each signed so that its entry of largest magnitude (the first on a tie) is positive.  ValueError for an array of fewer than
+    two axes, an n_components that is not an int in [1, T], or fewer than n_components columns without a NaN."""
+    w = np.asarray(waveforms)
+    if w.ndim < 2 or w.dtype.kind not in 'fiu' or not w.shape[-2]:
+        raise ValueError("waveforms must be a (..., T, W) array of numbers")
+    T = int(w.shape[-2])
+    if not isinstance(n_components, (int, np.integer)) or isinstance(n_components, bool) or not 1 <= n_components <= T:
+        raise ValueError("n_components must be an int in [1, %d], got %r" % (T, n_components))
+    P = int(n_components)
+    cols = np.moveaxis(w, -2, -1).reshape(-1, T)                      # one column a row
+    gram, kept = np.zeros((T, T), np.float64), 0
+    for a in range(0, cols.shape[0], 1 << 16):                        # (float64 copies of 2^16 columns at a time)
+        v = cols[a:a + (1 << 16)].astype(np.float64)
+        v = v[~np.isnan(v).any(axis=1)]
+        if not np.isfinite(v).all():
+            raise ValueError("waveforms must be finite or NaN")
+        gram += v.T @ v
+        kept += v.shape[0]
+    if kept < P:
+        raise ValueError("%d components need at least as many columns without a NaN, got %d" % (P, kept))
+    _, vec = np.linalg.eigh(gram)                                     # (ascending eigenvalues)
+    basis = vec[:, ::-1][:, :P].T.astype(np.float32)
+    top = np.abs(basis).argmax(axis=1)                                # (the first of equal magnitudes, as float32)
+    return np.ascontiguousarray(basis * np.where(basis[np.arange(P), top] < 0, np.float32(-1), np.float32(1))[:, None])
+
+
 _DETECT_CAP_AT = 11                     # where max_events stands among the op's own arguments of codec.detect ...
 _TMATCH_CAP_AT = 11                     # ... and of codec.match_templates / match_residual (the subtracted events follow it)
 
@@ -487,6 +518,7 @@ class HipCodec:
     project = _lane_reduction('project')
     waveforms = _lane_reduction('waveforms')
     mean_waveforms = _lane_reduction('mean_waveforms')
+    waveform_features = _lane_reduction('waveform_features')
     correlate = _lane_reduction('correlate')
     match_templates = _lane_reduction('match_templates')
     residual = _lane_reduction('residual')
@@ -2129,7 +2161,7 @@ class Reader:
         return [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, max_events)] + [n]
 
     def _snippet_args(self, what, sample, channel, before, after, neighbours, channels, taps, reference):
-        """The arguments that waveforms and mean_waveforms share, checked -> (before, after, T, W, taps, cols, reference code, the
+        """The arguments that waveforms, mean_waveforms and waveform_features share, checked -> (before, after, T, W, taps, cols, reference code, the
         events' rows as int64, their first positions)."""
         for name, v in (('before', before), ('after', after)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0:
@@ -2288,6 +2320,56 @@ class Reader:
         mean[count == 0] = np.frombuffer(np.uint32(0x7fc00000).tobytes(), np.float32)[0]
         return Bunch(mean=mean, sum=total, count=count, skipped=skipped, events=events, resolution=resolution, before=before, after=after,
                      channels=cols)
+
+    # -- snippets projected on a temporal basis on the device (an extension: the reference's users run an einsum on the snippets)
+    def waveform_features(self, sample, basis, channel=None, before=20, after=41, neighbours=None, channels=slice(None), taps=None,
+                          reference=None):
+        """The snippets of `waveforms` projected on a small temporal basis -- the "PC features" that clustering reads -- on the
+        device: P numbers of every T cross the bus.  sample, channel, neighbours, channels, taps, reference, before and after mean
+        what they mean for `waveforms`.  basis: (P, T) numbers, T = before + after (api.waveform_basis makes one from snippets),
+        rounded once to float32; every entry must be finite, also after the rounding.  All in float32, with s =
+        waveforms(...).waveforms: features[e, p, w] is the chain acc = +0; for tau = 0 .. T - 1: acc = fmaf(s[e, tau, w],
+        basis[p, tau], acc), bit for bit; every NaN result has the bits 0x7fc00000.  Zero basis entries are not skipped (inf * 0 is
+        NaN), so one NaN entry -- fill or data -- in the column s[e, :, w] makes features[e, :, w] NaN: an event near the
+        recording's ends is NaN throughout, a position outside the selection is NaN for its events.  A 1-D basis (T,) gives features
+        (n, W), without the P axis.  sample: ints in [0, n_samples), any order, repeats allowed; the results come in that order.
+        Returns a Bunch: features (n, P, W) float32, sample, position, basis (the float32 (P, T) array used), before, after,
+        channels.  P <= 32, P * T <= 8192; T, W and the median's columns as waveforms.  The same bytes whatever the order of sample,
+        the lanes, calls, pieces or cache residency, and the bytes of that chain run on the host over waveforms' own snippets.
+        Chunks are read as waveforms reads them, and a damaged chunk in an event's support raises the IOError of Reader[...]."""
+        self._need_codec('waveform_features', 'waveform_features', 'projects snippets')
+        before, after, T, W, taps, cols, ref_code, rows, col0 = self._snippet_args('waveform_features', sample, channel, before, after,
+                                                                                  neighbours, channels, taps, reference)
+        b = np.asarray(basis)
+        if b.dtype.kind not in 'fiu' or b.ndim not in (1, 2) or b.shape[-1] != T:
+            raise ValueError("basis must be a (P, %d) or (%d,) array of numbers (before + after = %d), got shape %r" % (T, T, T, b.shape))
+        flat = b.ndim == 1
+        with np.errstate(over='ignore'):
+            b = np.ascontiguousarray(np.atleast_2d(b).astype(np.float32))
+        P = int(b.shape[0])
+        if not 1 <= P <= hip.FEATURES_MAX_COMPONENTS or P * T > hip.FEATURES_MAX_BASIS:
+            raise ValueError("at most %d components and %d basis entries (components x rows), got %d and %d"
+                             % (hip.FEATURES_MAX_COMPONENTS, hip.FEATURES_MAX_BASIS, P, P * T))
+        if not np.isfinite(b).all():
+            raise ValueError("basis must be finite as float32")
+        n, N = int(rows.size), self.n_samples
+        feat = np.empty((n, P, W), np.float32)
+        if n:
+            order = np.argsort(rows, kind='stable')
+            s_rows, s_col0 = rows[order], col0[order]
+            n_taps = int(taps.size)
+            half = (n_taps - 1) // 2
+            lo = np.maximum(0, s_rows - before + half - (n_taps - 1))  # the file rows an event reads
+            hi = np.minimum(N, s_rows + after + half)
+            cuts = self._waveform_cuts(lo, hi, WAVEFORMS_CALL_BYTES, max(1, WAVEFORMS_OUT_BYTES // (4 * P * W)))
+
+            def part(a, b_):
+                return (self._chunk_span(int(lo[a]), int(hi[b_ - 1])),
+                        (0, N, taps, cols, ref_code, s_rows[a:b_], s_col0[a:b_], before, after, W, b))
+            in_order = bool((order[1:] > order[:-1]).all())          # (detect's events are: plain copies then)
+            for a, b_, got in self._halo_parts(self.codec.waveform_features, cuts, part):
+                feat[slice(a, b_) if in_order else order[a:b_]] = got[0]
+        return Bunch(features=feat[:, 0] if flat else feat, sample=rows, position=col0, basis=b, before=before, after=after, channels=cols)
 
     # -- power spectral density on the device (an extension: the reference's users run scipy.signal.welch on Reader[...])
     def welch(self, nperseg=256, start=0, stop=None, channels=slice(None), noverlap=None, window='hann', detrend='constant',

@@ -148,6 +148,25 @@ int launch_mean_waveforms(hipStream_t st, const float *d_z, long ws_row0, long w
                           const int *d_ev_col0, const long *d_perm, const MeanPart *d_parts, long n_parts, int before, int after, int width,
                           double resolution, long long *d_sum, int *d_count, long *d_skipped);
 
+// features.hip: the same snippets projected on a temporal basis (mts_waveform_features).  For the events e of [e0, e1), p < n_comp and
+// w < width: feat[e, p, w] = the chain acc = fmaf(z[ev_row[e] - before + tau, ev_col0[e] + w], basis[p, tau], acc) over tau = 0 .. T - 1
+// from +0; the quiet NaN 0x7fc00000 when the column position lies outside [0, n_cols), when one of the T rows lies outside [vb, ve)
+// or the workspace, and for a NaN result.  d_basis: the image that features_basis_image made, n_comp * T floats
+constexpr int FEAT_PB = 8;                                         // components of a register block
+int launch_waveform_features(hipStream_t st, const float *d_z, long ws_row0, long ws_rows, int n_cols, long vb, long ve, const long *d_ev_row,
+                             const int *d_ev_col0, long e0, long e1, int before, int after, int width, int n_comp, const float *d_basis,
+                             float *d_feat);
+// basis (P, T) C order -> the kernel's image: blocks of FEAT_PB components one behind the other, the last of the P % FEAT_PB that
+// remain; component p0 + k of a block of nb components from p0 lies at p0 * T + tau * nb + k
+inline void features_basis_image(const float *basis, int P, int T, float *image)
+{
+    for (int p0 = 0; p0 < P; p0 += FEAT_PB) {
+        const int nb = P - p0 < FEAT_PB ? P - p0 : FEAT_PB;
+        for (int tau = 0; tau < T; tau++)
+            for (int k = 0; k < nb; k++) image[(size_t)p0 * T + (size_t)tau * nb + k] = basis[(size_t)(p0 + k) * T + tau];
+    }
+}
+
 // correlate.hip: template scores on the same workspace (mts_correlate).  out[(t - r_begin) * n_out + k] for file rows t of [r_begin,
 // r_end) = the chain of matrix steps over (g, tau), g = 0, 4, .. < n4 outermost and tau < T inside, of z[t - before + tau, g .. g + 3]
 // against the templates; z = +0 for a row outside [vb, ve) or the workspace; a NaN is stored as 0x7fc00000.  d_tpl: the templates

@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, correlate, match_templates, residual, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates, residual, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -26,10 +26,10 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, waveforms, mean_waveforms, correlate, match_templates, residual, welch, gram): a unit of output (outputs, rows,
+//   halo (decimate, project, detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates, residual, welch, gram): a unit of output (outputs, rows,
 //        events, blocks, groups -- the op gives HaloPlan its map from units to rows) reads rows of several adjacent chunks, so a piece
 //        reads chunks [c0, c1] through a table of segment bases and first rows, and decodes the missing ones among them -- a boundary
-//        chunk in both pieces (HaloPlan, HaloFeed).  Six of them (detect, waveforms, mean_waveforms, correlate, match_templates, residual) start from
+//        chunk in both pieces (HaloPlan, HaloFeed).  Seven of them (detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates, residual) start from
 //        one filtered signal z: their checks, uploads, filter stage and tails are the z family's shared parts below.
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
 //   - An allocation that fails empties this device's caches before it tries again (DBuf::ensure -> drop_device_caches: hipFree,
@@ -134,7 +134,7 @@ int check_taps(const char *op, int n_taps, const double *taps)
     return MTS_OK;
 }
 
-// what the z family (detect, waveforms, mean_waveforms, correlate, match_templates, residual) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
+// what the z family (detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates, residual) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
 // in float32, x = 0 outside [vb, ve), minus the row's median over the columns with reference 1.  `op` names the entry in every message.
 struct ZArgs { const char *op; long vb, ve; int n_taps; const double *taps; int n_cols; const int *cols; int reference; };
 
@@ -339,12 +339,12 @@ struct HaloFeed {
     }
 };
 
-// ---- z family: what detect, waveforms, mean_waveforms, correlate, match_templates and residual share around their own slab loops.  Each run reads
+// ---- z family: what detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates and residual share around their own slab loops.  Each run reads
 // top to bottom as the halo family's sequence: plan -> regions (ZStage first, the op's, EventTail's) -> StreamGuard -> place ->
 // uploads -> run -> tail.
 //
 // The rule for leaving early, for all of them: from the first asynchronous upload out of host memory that the call owns (HaloFeed::seg,
-// ZStage::h_taps, the repacked templates, SubEvents::namp, the parts of mean_waveforms) no path returns before the stream has been waited for -- a failed
+// ZStage::h_taps, the repacked templates, SubEvents::namp, the parts of mean_waveforms, the basis image of waveform_features) no path returns before the stream has been waited for -- a failed
 // H.run, a failed MTS_HIP.  The guard is declared after those vectors and before H.place, so it goes before they do; the tails'
 // own wait() disarms it, so the normal path waits no more often than it has to.
 struct StreamGuard {
@@ -848,7 +848,7 @@ static long waveforms_gap_rows()                                     // (negativ
     return e && *e ? (long)atoll(e) : WAVEFORMS_GAP_ROWS;
 }
 
-// ---- what waveforms and mean_waveforms share: the snippet arguments and their checks, the events' pieces and slabs, the slab loop
+// ---- what waveforms, mean_waveforms and waveform_features share: the snippet arguments and their checks, the events' pieces and slabs, the slab loop
 struct SnipArgs { long n_events; const long *ev_row; const int *ev_col0; int before, after, width; };
 
 // the first checks, in order: the filter's, the snippet's shape, the event list's pointers
@@ -1004,6 +1004,68 @@ static int waveforms_run(Engine &E, hipStream_t st, const ChunkTable &T, const Z
         MTS_HIP(hipMemcpyAsync(out_max, d_max, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
         MTS_HIP(hipMemcpyAsync(out_argmax, d_amax, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
     }
+    if ((rc = G.wait())) return rc;
+    S.done(E);
+    return MTS_OK;
+}
+
+// ---- snippets projected on a temporal basis (mts_waveform_features, mts_dev_waveform_features) ---------------------------------------
+// waveforms' events, pieces, slabs and filter stage; the gather is k_waveform_features (features.hip), which reads the same entries of z
+// and keeps n_comp numbers of every T: one thread owns a chain from +0 to its store, so the bytes depend on no cut made here.
+static int waveform_features_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long n_events, const long *ev_row,
+                                 const int *ev_col0, int before, int after, int width, int n_comp, const float *basis, float *out_feat,
+                                 bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols;
+    const SnipArgs A{n_events, ev_row, ev_col0, before, after, width};
+    int rc;
+    if ((rc = check_snippet_shape(T, Z, A))) return rc;
+    const long n_snip = (long)before + after;
+    if (n_comp < 1 || n_comp > MTS_FEATURES_MAX_COMPONENTS) {
+        set_error("waveform_features: %d components (1 .. %d)", n_comp, MTS_FEATURES_MAX_COMPONENTS); return MTS_E_ARG;
+    }
+    if ((long)n_comp * n_snip > MTS_FEATURES_MAX_BASIS) {
+        set_error("waveform_features: %d components x %ld rows (<= %d entries in all)", n_comp, n_snip, MTS_FEATURES_MAX_BASIS); return MTS_E_ARG;
+    }
+    if (!basis) { set_error("waveform_features: no basis"); return MTS_E_ARG; }
+    if (!out_feat) { set_error("waveform_features: no output buffer"); return MTS_E_ARG; }
+    const size_t n_basis = (size_t)n_comp * (size_t)n_snip;
+    for (size_t k = 0; k < n_basis; k++)
+        if (!std::isfinite(basis[k])) {
+            set_error("waveform_features: basis[%d, %ld] is not finite", (int)(k / (size_t)n_snip), (long)(k % (size_t)n_snip)); return MTS_E_ARG;
+        }
+    if ((rc = check_snippet_events(T, Z, A))) return rc;
+    status_ok(T, status);
+    if (n_events == 0) return MTS_OK;
+
+    SnippetFeed S(T, out_on_host);
+    HaloFeed &H = S.H;
+    if ((rc = S.plan(E, Z, A))) return rc;
+    std::vector<float> image(n_basis);                             // the basis as the kernel stages it
+    features_basis_image(basis, n_comp, (int)n_snip, image.data());
+    // ---- workspace
+    const u64 n_item = (u64)n_comp * width;
+    WsLayout &L = H.L;
+    ZStage F(Z, L);
+    const size_t o_seg = L.take(H.table_bytes()), o_erow = L.take(8 * (u64)n_events), o_ecol = L.take(4 * (u64)n_events),
+                 o_basis = L.take(4 * (u64)n_basis), o_y = L.take(4 * (u64)S.max_rows * n_cols), o_feat = L.take_out(4 * (u64)n_events * n_item);
+    StreamGuard G{st};
+    if ((rc = H.place(E, st, E.wav, o_seg))) return rc;
+    u8 *ws = E.wav.as<u8>();
+    if ((rc = F.upload(st, ws))) return rc;
+    MTS_HIP(hipMemcpyAsync(ws + o_erow, ev_row, 8 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_ecol, ev_col0, 4 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_basis, image.data(), 4 * n_basis, hipMemcpyHostToDevice, st));
+    float *d_feat = L.out(ws, o_feat, out_feat);
+    float *d_y = (float *)(ws + o_y);
+    rc = S.run(E, st, T, F, d_y, status, [&](const SnippetSlab &B, long) {
+        return launch_waveform_features(st, d_y, B.a, B.b - B.a, n_cols, vb, ve, (const long *)(ws + o_erow), (const int *)(ws + o_ecol), B.e0, B.e1,
+                                        before, after, width, n_comp, (const float *)(ws + o_basis), d_feat);
+    });
+    if (rc) return rc;
+    if (out_on_host) MTS_HIP(hipMemcpyAsync(out_feat, d_feat, 4 * (size_t)n_events * n_item, hipMemcpyDeviceToHost, st));
     if ((rc = G.wait())) return rc;
     S.done(E);
     return MTS_OK;
@@ -1781,6 +1843,26 @@ int mts_dev_mean_waveforms(int device, void *stream, const unsigned char *d_cdat
 {
     return DEV_ENTRY(mean_waveforms_run(E, (hipStream_t)stream, T, Z_ARGS("mean_waveforms"), n_events, ev_row, ev_col0, ev_label, n_labels, before,
                      after, width, resolution, d_sum, d_count, d_skipped, false, chunk_status));
+}
+
+int mts_waveform_features(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                          const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                          long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                          const long *ev_row, const int *ev_col0, int before, int after, int width, int n_comp, const float *basis, float *out_feat,
+                          int *chunk_status)
+{
+    return HOST_ENTRY(waveform_features_run(E, nullptr, T, Z_ARGS("waveform_features"), n_events, ev_row, ev_col0, before, after, width, n_comp, basis,
+                      out_feat, true, chunk_status));
+}
+
+int mts_dev_waveform_features(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                              const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                              long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                              const long *ev_row, const int *ev_col0, int before, int after, int width, int n_comp, const float *basis,
+                              float *d_feat, int *chunk_status)
+{
+    return DEV_ENTRY(waveform_features_run(E, (hipStream_t)stream, T, Z_ARGS("waveform_features"), n_events, ev_row, ev_col0, before, after, width,
+                     n_comp, basis, d_feat, false, chunk_status));
 }
 
 int mts_waveforms_last_plan(int device, long *out)

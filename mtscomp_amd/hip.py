@@ -110,6 +110,7 @@ def lib():
             ('detect', [cl, cl, cl, cl, ci, dp, ci, ip, fp, ci, ci, ci, ci, cl], [vp, vp, vp, lp, ip], None),
             ('waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci], [vp, vp, vp, vp, vp, ip], None),
             ('mean_waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ip, ci, ci, ci, ci, C.c_double], [vp, vp, vp, ip], None),
+            ('waveform_features', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci, ci, fp], [vp, ip], None),
             ('correlate', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp], [vp, ip], None),
             ('match_templates', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, fp, ci, cl], [vp, vp, vp, lp, ip], None),
             ('residual', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, cl, lp, ip, fp], [vp, ip], None),
@@ -133,7 +134,8 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_debug_inflate', 'mts_release', 'mts_cache_create', 'mts_cache_destroy', 'mts_cache_query',
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
            'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_project', 'mts_dev_project', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
-           'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan', 'mts_mean_waveforms', 'mts_dev_mean_waveforms', 'mts_correlate', 'mts_dev_correlate',
+           'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan', 'mts_mean_waveforms', 'mts_dev_mean_waveforms',
+           'mts_waveform_features', 'mts_dev_waveform_features', 'mts_correlate', 'mts_dev_correlate',
            'mts_match_templates', 'mts_dev_match_templates',
            'mts_residual', 'mts_dev_residual', 'mts_match_residual', 'mts_dev_match_residual',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
@@ -854,6 +856,44 @@ def dev_mean_waveforms(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags,
     out, ptrs, at = _dev_results(out, cbuf.device, [a.nbytes for a in res])
     _check(lib().mts_dev_mean_waveforms(*head, *mid, *ptrs, _ip(status)), 'mts_dev_mean_waveforms')
     return _status(status, n), tuple(_dev_fetch(out, at, res)) if download else None, out
+
+
+# -- those snippets projected on a temporal basis
+FEATURES_MAX_COMPONENTS = 32           # MTS_FEATURES_MAX_COMPONENTS
+FEATURES_MAX_BASIS = 8192              # MTS_FEATURES_MAX_BASIS
+
+
+def _feat_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width, basis):
+    """-> (the op's own arguments of mts_waveform_features, the shape of its result, the basis that the pointer among them points into)."""
+    wav, n_ev, item = _wav_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width)
+    basis = np.ascontiguousarray(np.asarray(basis, dtype=np.float32))
+    assert basis.ndim == 2 and basis.shape[1] == int(before) + int(after)
+    mid = wav + (int(basis.shape[0]), basis.ctypes.data_as(C.POINTER(C.c_float)))
+    return mid, ((n_ev, int(basis.shape[0]), int(width)) if item else (n_ev, 0, 0)), basis
+
+
+def waveform_features(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference,
+                      ev_row, ev_col0, before, after, width, basis, device=0):
+    """mts_waveform_features: the snippets that mts_waveforms would return for the events, each column (e, ., w) projected on the rows of
+    basis (n_comp, before + after) float32 by a chain of fmaf (include/mtscomp_hip.h), from the adjacent chunks `keys`.  cache_id as
+    waveforms.  Returns (status list, features float32 (n, n_comp, width))."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, shape, basis = _feat_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width, basis)
+    feat = np.empty(shape, np.float32)
+    _check(lib().mts_waveform_features(*head, *mid, _ptr(feat), _ip(status)), 'mts_waveform_features')
+    return _status(status, n), feat
+
+
+def dev_waveform_features(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0,
+                          before, after, width, basis, out=None, download=True):
+    """mts_dev_waveform_features on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the features (made when
+    None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, features or None, out)."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, shape, basis = _feat_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width, basis)
+    feat = np.empty(shape, np.float32)
+    out, ptrs, at = _dev_results(out, cbuf.device, [feat.nbytes])
+    _check(lib().mts_dev_waveform_features(*head, *mid, *ptrs, _ip(status)), 'mts_dev_waveform_features')
+    return _status(status, n), _dev_fetch(out, at, [feat])[0] if download else None, out
 
 
 # -- spatio-temporal template scores
