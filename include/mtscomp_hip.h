@@ -45,7 +45,7 @@ extern "C" {
 #define MTS_FLAG_SPATIAL_DIFF 2
 #define MTS_FLAG_ORDER_F 4
 #define MTS_FLAG_FLOAT 8          /* items are IEEE floats (itemsize 4 or 8): np.diff / np.cumsum in that type, bit for bit */
-#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_waveform_features, mts_correlate, mts_match_templates, mts_welch, mts_gram and their device variants only; the codec does not care) */
+#define MTS_FLAG_UNSIGNED 16      /* integer items are unsigned (mts_window_stats, mts_decimate, mts_project, mts_detect, mts_waveforms, mts_waveform_features, mts_localize, mts_correlate, mts_match_templates, mts_welch, mts_gram and their device variants only; the codec does not care) */
 #define MTS_DECIMATE_MAX_TAPS 8192
 #define MTS_PROJECT_MAX_COLS 1024
 #define MTS_PROJECT_MAX_OUT  1024
@@ -63,6 +63,11 @@ extern "C" {
 #define MTS_MEAN_MAX_ENTRIES (1L << 27) /* ... and n_labels * T * width, the entries of its sums */
 #define MTS_FEATURES_MAX_COMPONENTS 32  /* mts_waveform_features: rows of its basis (the components) */
 #define MTS_FEATURES_MAX_BASIS 8192     /* ... and n_comp * T, the entries of the basis: 32 KiB of LDS */
+#define MTS_LOCALIZE_MAX_DIMS 4         /* mts_localize: coordinates of a channel position */
+#define MTS_LOCALIZE_PTP 0              /* ... its amplitude modes: maximum - minimum of a column */
+#define MTS_LOCALIZE_NEG 1              /* ... -minimum (detect's sign 'neg') */
+#define MTS_LOCALIZE_POS 2              /* ... maximum ('pos') */
+#define MTS_LOCALIZE_ABS 3              /* ... maximum of the absolute values ('abs') */
 #define MTS_DETECT_MAX_REF_COLS 1024    /* columns of a median reference: a row's order keys are sorted in 4 KiB of LDS by one wave */
 #define MTS_CORRELATE_MAX_T 256         /* mts_correlate: rows of a template (its taus) */
 #define MTS_CORRELATE_MAX_OUT 1024      /* ... the templates of a call */
@@ -417,6 +422,48 @@ int mts_waveform_features(int device, long cache_id, int n_chunks, const long *c
                           const float *basis /* (n_comp, T) C order */, float *out_feat /* (n_events, n_comp, width) C order */, int *chunk_status);
 
 /*
+ * Where on the probe a spike happened, and its amplitude on every channel of the snippet (an extension: the reference has no such call;
+ * its users pull the snippets across the bus and run nanmax - nanmin and a weighted mean on the host).  What crosses the bus is
+ * n_events * (width + n_dims + 2) numbers, not n_events * T * width.  Everything is float32 and a definition, not a tolerance:
+ *   z, events, snippet, fill   exactly mts_waveforms': s[e, tau, w] is the entry that mts_waveforms returns, the quiet NaN 0x7fc00000
+ *                  where its row lies outside [valid_begin, valid_end) or its column position outside [0, n_cols), and for a NaN of
+ *                  the data
+ *   extrema        of the column (e, ., w), over the entries that are not NaN: lo the first minimum, hi the first maximum, each with
+ *                  its own bits (-0 == +0: the first wins, as mts_waveforms' extrema).  A column without such an entry has none
+ *   amplitude      a[e, w] by mode: MTS_LOCALIZE_PTP hi - lo (one subtraction), MTS_LOCALIZE_NEG -lo (exact: +0 gives -0),
+ *                  MTS_LOCALIZE_POS hi, MTS_LOCALIZE_ABS the first maximum of fabsf(entry); 0x7fc00000 for a column without extrema
+ *                  and for a NaN result.  NaN entries are skipped (mts_waveforms' rule, not mts_waveform_features'): an event near
+ *                  the recording's ends keeps the amplitudes of the rows it has
+ *   weight         g[e, w] = a[e, w] if a[e, w] > 0, else +0 (NaN, negative and zero amplitudes: +0; +inf stays)
+ *   sums           one chain per event over w = 0 .. width - 1 in ascending order, c = ev_col0[e] + w, a w with c outside [0, n_cols)
+ *                  left out: out_weight[e] = (.. + g[e, w]), one addition a step, and out_moment[e, d] = fmaf(g[e, w],
+ *                  positions[c, d], ..), one fmaf a step, both from +0; a NaN result is stored as 0x7fc00000.  Skipping a step with
+ *                  g = +0 yields the same bits (the positions are finite, the chains start at +0: such a step adds +-0 and an
+ *                  accumulator is never -0), so whether an implementation takes those steps is not part of the definition
+ *   best           out_best[e] = the lowest w whose a[e, w] is the largest among those that are not NaN (-0 == +0); -1 for none
+ *   location       moment / weight is the caller's: no division and no reciprocal on the device enters the definition
+ *   positions      (n_cols, n_dims) float32 in C order on the host, one row per entry of cols; every entry finite
+ *   outputs        out_amp (n_events, width) C order or null (the other outputs are the same bytes), out_weight (n_events),
+ *                  out_moment (n_events, n_dims) C order, out_best (n_events).  One thread owns an event's chains from +0 to their
+ *                  stores, no atomics: the same bytes whatever the call, its pieces, its slabs, the gap setting, the cache or the
+ *                  device, and the bytes of the definition applied on the host to mts_waveforms' own snippets
+ *   limits         T, width, n_events, taps, columns and the reference's columns as mts_waveforms; 1 <= n_dims <= MTS_LOCALIZE_MAX_DIMS
+ *   chunks, chunk_status   as mts_waveforms; the results near a failed chunk are undefined
+ * mts_localize: host cdata; cache_id 0 or a decoded-chunk cache, read in place and never inserted into, as mts_waveforms; the same
+ * pieces (MTS_PIPE_BYTES) and slabs (MTS_WAVEFORMS_SLAB_BYTES, MTS_WAVEFORMS_GAP_ROWS).  The outputs are host memory.
+ * mts_dev_localize: device d_cdata and d_* outputs on `device`; ev_row, ev_col0, positions and chunk_status on the host; no cache.
+ * MTS_E_ARG with a message before anything is allocated or launched: what mts_waveforms refuses, a mode outside 0 .. 3, n_dims outside
+ * the limit, no positions, a position that is not finite (its row and dimension are named), no out_weight, out_moment or out_best.
+ * n_events == 0 is MTS_OK without a launch.
+ */
+int mts_localize(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                 const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                 long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                 const long *ev_row, const int *ev_col0, int before, int after, int width, int mode, int n_dims,
+                 const float *positions /* (n_cols, n_dims) C order */, float *out_amp /* (n_events, width) or null */,
+                 float *out_weight /* (n_events) */, float *out_moment /* (n_events, n_dims) */, int *out_best /* (n_events) */, int *chunk_status);
+
+/*
  * Spatio-temporal template scores of filtered rows (an extension: the reference has no such call; its users pull Reader[...] across the
  * bus, filter it and run a matched filter on the host).  Only the scores cross the bus.  Everything is float32 and a definition, not a
  * tolerance:
@@ -738,6 +785,12 @@ int mts_dev_waveform_features(int device, void *stream, const unsigned char *d_c
                               long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
                               const long *ev_row /* host */, const int *ev_col0 /* host */, int before, int after, int width, int n_comp,
                               const float *basis /* host */, float *d_feat, int *chunk_status /* host */);
+int mts_dev_localize(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                     const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                     long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                     const long *ev_row /* host */, const int *ev_col0 /* host */, int before, int after, int width, int mode, int n_dims,
+                     const float *positions /* host */, float *d_amp /* or null */, float *d_weight, float *d_moment, int *d_best,
+                     int *chunk_status /* host */);
 int mts_dev_correlate(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                       const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
                       long valid_end, long row_begin, long row_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
@@ -795,7 +848,7 @@ int mts_dev_compare(int device, void *stream, const void *d_a, const void *d_b, 
  * fills up to `cap` entries of (name, ms); returns the number of stages.  For bench.py / profiling. */
 int mts_last_stage_times(int device, const char **names, float *ms, int cap);
 
-/* What the last successful mts_waveforms / mts_dev_waveforms (or mts_mean_waveforms / mts_dev_mean_waveforms, mts_waveform_features / mts_dev_waveform_features) call on `device` did, for the tests and the benchmark: out[0] its pieces,
+/* What the last successful mts_waveforms / mts_dev_waveforms (or mts_mean_waveforms / mts_dev_mean_waveforms, mts_waveform_features / mts_dev_waveform_features, mts_localize / mts_dev_localize) call on `device` did, for the tests and the benchmark: out[0] its pieces,
  * out[1] its slabs, out[2] the slabs among them that were begun at a gap, out[3] the microseconds of its gather kernels (measured,
  * with a wait per slab, only while MTS_WAVEFORMS_TIME is set; else 0). */
 int mts_waveforms_last_plan(int device, long *out /* 4 */);

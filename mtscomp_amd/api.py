@@ -519,6 +519,7 @@ class HipCodec:
     waveforms = _lane_reduction('waveforms')
     mean_waveforms = _lane_reduction('mean_waveforms')
     waveform_features = _lane_reduction('waveform_features')
+    localize = _lane_reduction('localize')
     correlate = _lane_reduction('correlate')
     match_templates = _lane_reduction('match_templates')
     residual = _lane_reduction('residual')
@@ -2161,7 +2162,7 @@ class Reader:
         return [u for a, b in zip(base[:-1], base[1:]) for u in range(a, b, max_events)] + [n]
 
     def _snippet_args(self, what, sample, channel, before, after, neighbours, channels, taps, reference):
-        """The arguments that waveforms, mean_waveforms and waveform_features share, checked -> (before, after, T, W, taps, cols, reference code, the
+        """The arguments that waveforms, mean_waveforms, waveform_features and localize share, checked -> (before, after, T, W, taps, cols, reference code, the
         events' rows as int64, their first positions)."""
         for name, v in (('before', before), ('after', after)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0:
@@ -2370,6 +2371,80 @@ class Reader:
             for a, b_, got in self._halo_parts(self.codec.waveform_features, cuts, part):
                 feat[slice(a, b_) if in_order else order[a:b_]] = got[0]
         return Bunch(features=feat[:, 0] if flat else feat, sample=rows, position=col0, basis=b, before=before, after=after, channels=cols)
+
+    # -- spike positions and channel amplitudes on the device (an extension: the reference's users reduce the snippets on the host)
+    def localize(self, sample, positions, channel=None, before=20, after=41, neighbours=None, channels=slice(None), taps=None,
+                 reference=None, amplitude='ptp', amplitudes=True):
+        """Where on the probe every spike happened -- the amplitude-weighted mean of the channel positions, the "centre of mass"
+        of drift maps and motion estimation -- and its amplitude on every channel of the snippet, on the device: W + D + 2 numbers
+        an event cross the bus, not T * W.  sample, channel, neighbours, channels, taps, reference, before and after mean what they
+        mean for `waveforms`.  positions: (n_selected, D) numbers, 1 <= D <= 4, the probe geometry in the caller's units, one row
+        per entry of `channels` in selection order (not per file channel), rounded once to float32; every entry must be finite,
+        also after the rounding.  A 1-D positions (n_selected,) is D = 1 and gives location and moment without the D axis.
+        amplitude: 'ptp', 'neg', 'pos' or 'abs'.  All in float32 and bit for bit, with s = waveforms(...).waveforms: over the
+        entries s[e, tau, w], tau = 0 .. T - 1, that are not NaN, lo is the first minimum and hi the first maximum (-0 == +0: the
+        first wins); amplitude[e, w] is hi - lo ('ptp', one subtraction), -lo ('neg'; +0 gives -0), hi ('pos') or the first maximum
+        of abs(entry) ('abs'), and NaN (every NaN has the bits 0x7fc00000) for a column without such an entry -- a position outside
+        the selection, an event whose rows all lie outside the recording, all-NaN data -- and for a NaN result.  NaN entries are
+        skipped (waveforms' extrema rule, not waveform_features' contamination rule): a spike near the recording's ends keeps the
+        amplitudes of the rows it has.  g[e, w] = amplitude[e, w] where that is > 0, else +0.  One chain per event over w = 0 ..
+        W - 1 in ascending order, c = position[e] + w, a w with c outside the selection left out, from +0: weight = weight +
+        g[e, w] (one addition), moment[d] = fmaf(g[e, w], positions[c, d], moment[d]) (one fmaf); a step with g = +0 changes no bit
+        whether taken or not.  best[e] is the lowest w whose amplitude is the largest among those that are not NaN, -1 for none.
+        location[e, d] = float32(float64(moment[e, d]) / float64(weight[e])), formed on the host, NaN where weight is 0 or the
+        quotient is NaN.  sample: ints in [0, n_samples), any order, repeats allowed; the results come in that order.  Returns a
+        Bunch: location (n, D) float32, amplitude (n, W) float32 (None with amplitudes=False; everything else is the same bytes),
+        weight (n) float32, moment (n, D) float32, best (n) int64, channel (n) int64 (the entry of `channels` at position + best,
+        -1 for none), sample, position, positions (the float32 (n_selected, D) array used), before, after, channels, mode.  The
+        same bytes whatever the order of sample, the lanes, calls, pieces or cache residency, and the bytes of the definition run
+        on the host over waveforms' own snippets.  T, W and the median's columns as waveforms.  Chunks are read as waveforms reads
+        them, and a damaged chunk in an event's support raises the IOError of Reader[...]."""
+        self._need_codec('localize', 'localize', 'localizes spikes')
+        before, after, T, W, taps, cols, ref_code, rows, col0 = self._snippet_args('localize', sample, channel, before, after, neighbours,
+                                                                                  channels, taps, reference)
+        if not isinstance(amplitude, str) or amplitude not in hip.LOCALIZE_MODES:
+            raise ValueError("amplitude must be 'ptp', 'neg', 'pos' or 'abs', got %r" % (amplitude,))
+        mode = hip.LOCALIZE_MODES[amplitude]
+        p = np.asarray(positions)
+        if p.dtype.kind not in 'fiu' or p.ndim not in (1, 2) or p.shape[0] != cols.size:
+            raise ValueError("positions must be a (%d, D) or (%d,) array of numbers, one row per selected channel, got shape %r"
+                             % (cols.size, cols.size, p.shape))
+        flat = p.ndim == 1
+        with np.errstate(over='ignore'):
+            p = np.ascontiguousarray(p.reshape(cols.size, -1).astype(np.float32))
+        D = int(p.shape[1])
+        if not 1 <= D <= hip.LOCALIZE_MAX_DIMS:
+            raise ValueError("positions must have 1 to %d coordinates a channel, got %d" % (hip.LOCALIZE_MAX_DIMS, D))
+        if not np.isfinite(p).all():
+            raise ValueError("positions must be finite as float32")
+        n, N = int(rows.size), self.n_samples
+        amp = np.empty((n, W), np.float32) if amplitudes else None
+        weight, moment, best = np.empty(n, np.float32), np.empty((n, D), np.float32), np.empty(n, np.int64)
+        if n:
+            order = np.argsort(rows, kind='stable')
+            s_rows, s_col0 = rows[order], col0[order]
+            n_taps = int(taps.size)
+            half = (n_taps - 1) // 2
+            lo = np.maximum(0, s_rows - before + half - (n_taps - 1))  # the file rows an event reads
+            hi = np.minimum(N, s_rows + after + half)
+            cuts = self._waveform_cuts(lo, hi, WAVEFORMS_CALL_BYTES, max(1, WAVEFORMS_OUT_BYTES // (4 * (W + D + 2))))
+
+            def part(a, b):
+                return (self._chunk_span(int(lo[a]), int(hi[b - 1])),
+                        (0, N, taps, cols, ref_code, s_rows[a:b], s_col0[a:b], before, after, W, mode, p, bool(amplitudes)))
+            in_order = bool((order[1:] > order[:-1]).all())          # (detect's events are: plain copies then)
+            for a, b, got in self._halo_parts(self.codec.localize, cuts, part):
+                where = slice(a, b) if in_order else order[a:b]
+                if amplitudes:
+                    amp[where] = got[0]
+                weight[where], moment[where], best[where] = got[1], got[2], got[3]
+        with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+            location = (moment.astype(np.float64) / weight.astype(np.float64)[:, None]).astype(np.float32)
+        location[np.isnan(location) | (weight == 0)[:, None]] = np.frombuffer(np.uint32(0x7fc00000).tobytes(), np.float32)[0]
+        some = best >= 0
+        chan = np.where(some, cols[np.where(some, col0 + best, 0)], -1)
+        return Bunch(location=location[:, 0] if flat else location, amplitude=amp, weight=weight, moment=moment[:, 0] if flat else moment,
+                     best=best, channel=chan, sample=rows, position=col0, positions=p, before=before, after=after, channels=cols, mode=amplitude)
 
     # -- power spectral density on the device (an extension: the reference's users run scipy.signal.welch on Reader[...])
     def welch(self, nperseg=256, start=0, stop=None, channels=slice(None), noverlap=None, window='hann', detrend='constant',

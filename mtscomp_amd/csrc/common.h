@@ -167,6 +167,16 @@ inline void features_basis_image(const float *basis, int P, int T, float *image)
     }
 }
 
+// localize.hip: the same snippets reduced to channel amplitudes and amplitude-weighted position sums (mts_localize).  For the events e of
+// [e0, e1) and w < width: amp[e, w] (when d_amp is given) = the amplitude (mode: MTS_LOCALIZE_PTP / NEG / POS / ABS) of the column
+// z[ev_row[e] - before + tau, ev_col0[e] + w], tau < T, over its entries that are not NaN and whose row lies in [vb, ve) and the
+// workspace; the quiet NaN 0x7fc00000 when there is none, when the column position lies outside [0, n_cols), and for a NaN result.
+// weight[e], moment[e, d < n_dims]: the chains over w upwards of g = amp > 0 ? amp : +0 and fmaf(g, pos[ev_col0[e] + w, d], .) from +0;
+// best[e]: the first w of the largest amplitude that is not NaN, -1 for none.  d_pos: (n_cols, n_dims) C order, finite
+int launch_localize(hipStream_t st, const float *d_z, long ws_row0, long ws_rows, int n_cols, long vb, long ve, const long *d_ev_row,
+                    const int *d_ev_col0, long e0, long e1, int before, int after, int width, int mode, int n_dims, const float *d_pos,
+                    float *d_amp, float *d_weight, float *d_moment, int *d_best);
+
 // correlate.hip: template scores on the same workspace (mts_correlate).  out[(t - r_begin) * n_out + k] for file rows t of [r_begin,
 // r_end) = the chain of matrix steps over (g, tau), g = 0, 4, .. < n4 outermost and tau < T inside, of z[t - before + tau, g .. g + 3]
 // against the templates; z = +0 for a row outside [vb, ve) or the workspace; a NaN is stored as 0x7fc00000.  d_tpl: the templates

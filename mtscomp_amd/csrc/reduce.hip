@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates, residual, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -26,10 +26,10 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates, residual, welch, gram): a unit of output (outputs, rows,
+//   halo (decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, welch, gram): a unit of output (outputs, rows,
 //        events, blocks, groups -- the op gives HaloPlan its map from units to rows) reads rows of several adjacent chunks, so a piece
 //        reads chunks [c0, c1] through a table of segment bases and first rows, and decodes the missing ones among them -- a boundary
-//        chunk in both pieces (HaloPlan, HaloFeed).  Seven of them (detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates, residual) start from
+//        chunk in both pieces (HaloPlan, HaloFeed).  Eight of them (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual) start from
 //        one filtered signal z: their checks, uploads, filter stage and tails are the z family's shared parts below.
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
 //   - An allocation that fails empties this device's caches before it tries again (DBuf::ensure -> drop_device_caches: hipFree,
@@ -134,7 +134,7 @@ int check_taps(const char *op, int n_taps, const double *taps)
     return MTS_OK;
 }
 
-// what the z family (detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates, residual) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
+// what the z family (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
 // in float32, x = 0 outside [vb, ve), minus the row's median over the columns with reference 1.  `op` names the entry in every message.
 struct ZArgs { const char *op; long vb, ve; int n_taps; const double *taps; int n_cols; const int *cols; int reference; };
 
@@ -339,7 +339,7 @@ struct HaloFeed {
     }
 };
 
-// ---- z family: what detect, waveforms, mean_waveforms, waveform_features, correlate, match_templates and residual share around their own slab loops.  Each run reads
+// ---- z family: what detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates and residual share around their own slab loops.  Each run reads
 // top to bottom as the halo family's sequence: plan -> regions (ZStage first, the op's, EventTail's) -> StreamGuard -> place ->
 // uploads -> run -> tail.
 //
@@ -848,7 +848,7 @@ static long waveforms_gap_rows()                                     // (negativ
     return e && *e ? (long)atoll(e) : WAVEFORMS_GAP_ROWS;
 }
 
-// ---- what waveforms, mean_waveforms and waveform_features share: the snippet arguments and their checks, the events' pieces and slabs, the slab loop
+// ---- what waveforms, mean_waveforms, waveform_features and localize share: the snippet arguments and their checks, the events' pieces and slabs, the slab loop
 struct SnipArgs { long n_events; const long *ev_row; const int *ev_col0; int before, after, width; };
 
 // the first checks, in order: the filter's, the snippet's shape, the event list's pointers
@@ -1066,6 +1066,69 @@ static int waveform_features_run(Engine &E, hipStream_t st, const ChunkTable &T,
     });
     if (rc) return rc;
     if (out_on_host) MTS_HIP(hipMemcpyAsync(out_feat, d_feat, 4 * (size_t)n_events * n_item, hipMemcpyDeviceToHost, st));
+    if ((rc = G.wait())) return rc;
+    S.done(E);
+    return MTS_OK;
+}
+
+// ---- channel amplitudes and amplitude-weighted position sums of snippets (mts_localize, mts_dev_localize) ---------------------------
+// waveforms' events, pieces, slabs and filter stage; the gather is k_localize (localize.hip), which reads the same entries of z and keeps
+// width + n_dims + 2 numbers of an event: one thread owns an event's chains from +0 to their stores, so the bytes depend on no cut made here.
+static int localize_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long n_events, const long *ev_row, const int *ev_col0,
+                        int before, int after, int width, int mode, int n_dims, const float *positions, float *out_amp, float *out_weight,
+                        float *out_moment, int *out_best, bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols;
+    const SnipArgs A{n_events, ev_row, ev_col0, before, after, width};
+    int rc;
+    if ((rc = check_snippet_shape(T, Z, A))) return rc;
+    if (mode < MTS_LOCALIZE_PTP || mode > MTS_LOCALIZE_ABS) { set_error("localize: mode %d (0 .. 3)", mode); return MTS_E_ARG; }
+    if (n_dims < 1 || n_dims > MTS_LOCALIZE_MAX_DIMS) { set_error("localize: %d dimensions (1 .. %d)", n_dims, MTS_LOCALIZE_MAX_DIMS); return MTS_E_ARG; }
+    if (!positions) { set_error("localize: no positions"); return MTS_E_ARG; }
+    if (!out_weight || !out_moment || !out_best) { set_error("localize: no weight, moment or best buffer"); return MTS_E_ARG; }
+    const size_t n_pos = (size_t)n_cols * (size_t)n_dims;
+    for (size_t k = 0; k < n_pos; k++)
+        if (!std::isfinite(positions[k])) {
+            set_error("localize: positions[%ld, %d] is not finite", (long)(k / (size_t)n_dims), (int)(k % (size_t)n_dims)); return MTS_E_ARG;
+        }
+    if ((rc = check_snippet_events(T, Z, A))) return rc;
+    status_ok(T, status);
+    if (n_events == 0) return MTS_OK;
+
+    SnippetFeed S(T, out_on_host);
+    HaloFeed &H = S.H;
+    if ((rc = S.plan(E, Z, A))) return rc;
+    // ---- workspace
+    WsLayout &L = H.L;
+    ZStage F(Z, L);
+    const size_t o_seg = L.take(H.table_bytes()), o_erow = L.take(8 * (u64)n_events), o_ecol = L.take(4 * (u64)n_events),
+                 o_pos = L.take(4 * (u64)n_pos), o_y = L.take(4 * (u64)S.max_rows * n_cols),
+                 o_amp = out_amp ? L.take_out(4 * (u64)n_events * width) : 0, o_wgt = L.take_out(4 * (u64)n_events),
+                 o_mom = L.take_out(4 * (u64)n_events * n_dims), o_best = L.take_out(4 * (u64)n_events);
+    StreamGuard G{st};
+    if ((rc = H.place(E, st, E.wav, o_seg))) return rc;
+    u8 *ws = E.wav.as<u8>();
+    if ((rc = F.upload(st, ws))) return rc;
+    MTS_HIP(hipMemcpyAsync(ws + o_erow, ev_row, 8 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_ecol, ev_col0, 4 * (size_t)n_events, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_pos, positions, 4 * n_pos, hipMemcpyHostToDevice, st));
+    float *d_amp = out_amp ? L.out(ws, o_amp, out_amp) : nullptr;
+    float *d_wgt = L.out(ws, o_wgt, out_weight), *d_mom = L.out(ws, o_mom, out_moment);
+    int *d_best = L.out(ws, o_best, out_best);
+    float *d_y = (float *)(ws + o_y);
+    rc = S.run(E, st, T, F, d_y, status, [&](const SnippetSlab &B, long) {
+        return launch_localize(st, d_y, B.a, B.b - B.a, n_cols, vb, ve, (const long *)(ws + o_erow), (const int *)(ws + o_ecol), B.e0, B.e1, before,
+                               after, width, mode, n_dims, (const float *)(ws + o_pos), d_amp, d_wgt, d_mom, d_best);
+    });
+    if (rc) return rc;
+    if (out_on_host) {
+        if (out_amp) MTS_HIP(hipMemcpyAsync(out_amp, d_amp, 4 * (size_t)n_events * width, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_weight, d_wgt, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_moment, d_mom, 4 * (size_t)n_events * n_dims, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_best, d_best, 4 * (size_t)n_events, hipMemcpyDeviceToHost, st));
+    }
     if ((rc = G.wait())) return rc;
     S.done(E);
     return MTS_OK;
@@ -1863,6 +1926,26 @@ int mts_dev_waveform_features(int device, void *stream, const unsigned char *d_c
 {
     return DEV_ENTRY(waveform_features_run(E, (hipStream_t)stream, T, Z_ARGS("waveform_features"), n_events, ev_row, ev_col0, before, after, width,
                      n_comp, basis, d_feat, false, chunk_status));
+}
+
+int mts_localize(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                 const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                 long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                 const long *ev_row, const int *ev_col0, int before, int after, int width, int mode, int n_dims, const float *positions,
+                 float *out_amp, float *out_weight, float *out_moment, int *out_best, int *chunk_status)
+{
+    return HOST_ENTRY(localize_run(E, nullptr, T, Z_ARGS("localize"), n_events, ev_row, ev_col0, before, after, width, mode, n_dims, positions,
+                      out_amp, out_weight, out_moment, out_best, true, chunk_status));
+}
+
+int mts_dev_localize(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                     const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                     long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long n_events,
+                     const long *ev_row, const int *ev_col0, int before, int after, int width, int mode, int n_dims, const float *positions,
+                     float *d_amp, float *d_weight, float *d_moment, int *d_best, int *chunk_status)
+{
+    return DEV_ENTRY(localize_run(E, (hipStream_t)stream, T, Z_ARGS("localize"), n_events, ev_row, ev_col0, before, after, width, mode, n_dims,
+                     positions, d_amp, d_weight, d_moment, d_best, false, chunk_status));
 }
 
 int mts_waveforms_last_plan(int device, long *out)

@@ -111,6 +111,7 @@ def lib():
             ('waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci], [vp, vp, vp, vp, vp, ip], None),
             ('mean_waveforms', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ip, ci, ci, ci, ci, C.c_double], [vp, vp, vp, ip], None),
             ('waveform_features', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci, ci, fp], [vp, ip], None),
+            ('localize', [cl, cl, ci, dp, ci, ip, ci, cl, lp, ip, ci, ci, ci, ci, ci, fp], [vp, vp, vp, vp, ip], None),
             ('correlate', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp], [vp, ip], None),
             ('match_templates', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, fp, ci, cl], [vp, vp, vp, lp, ip], None),
             ('residual', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, cl, lp, ip, fp], [vp, ip], None),
@@ -135,7 +136,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_cache_read_rows', 'mts_cache_read_slices', 'mts_cache_read_slices_leading',
            'mts_window_stats', 'mts_dev_window_stats', 'mts_decimate', 'mts_dev_decimate', 'mts_project', 'mts_dev_project', 'mts_detect', 'mts_dev_detect', 'mts_welch', 'mts_dev_welch',
            'mts_waveforms', 'mts_dev_waveforms', 'mts_waveforms_last_plan', 'mts_mean_waveforms', 'mts_dev_mean_waveforms',
-           'mts_waveform_features', 'mts_dev_waveform_features', 'mts_correlate', 'mts_dev_correlate',
+           'mts_waveform_features', 'mts_dev_waveform_features', 'mts_localize', 'mts_dev_localize', 'mts_correlate', 'mts_dev_correlate',
            'mts_match_templates', 'mts_dev_match_templates',
            'mts_residual', 'mts_dev_residual', 'mts_match_residual', 'mts_dev_match_residual',
            'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
@@ -894,6 +895,55 @@ def dev_waveform_features(cbuf, offs, lens, row0, n_rows, n_channels, dtype, fla
     out, ptrs, at = _dev_results(out, cbuf.device, [feat.nbytes])
     _check(lib().mts_dev_waveform_features(*head, *mid, *ptrs, _ip(status)), 'mts_dev_waveform_features')
     return _status(status, n), _dev_fetch(out, at, [feat])[0] if download else None, out
+
+
+# -- those snippets reduced to channel amplitudes and amplitude-weighted position sums
+LOCALIZE_MAX_DIMS = 4                  # MTS_LOCALIZE_MAX_DIMS
+LOCALIZE_MODES = {'ptp': 0, 'neg': 1, 'pos': 2, 'abs': 3}               # MTS_LOCALIZE_PTP, _NEG, _POS, _ABS
+_LOCALIZE_DTYPES = (np.float32, np.float32, np.int32)                   # weight, moment, best of an event
+
+
+def _loc_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width, mode, positions):
+    """-> (the op's own arguments of mts_localize, the shapes of its four results, the positions that the pointer among them points
+    into)."""
+    wav, n_ev, _ = _wav_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width)
+    positions = np.ascontiguousarray(np.asarray(positions, dtype=np.float32))
+    assert positions.ndim == 2 and positions.shape[0] == wav[4]
+    D = int(positions.shape[1])
+    mid = wav + (int(mode), D, positions.ctypes.data_as(C.POINTER(C.c_float)))
+    return mid, ((n_ev, max(int(width), 0)), (n_ev,), (n_ev, D), (n_ev,)), positions
+
+
+def localize(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference, ev_row,
+             ev_col0, before, after, width, mode, positions, want_amp=True, device=0):
+    """mts_localize: the snippets that mts_waveforms would return for the events reduced to the amplitude of every column (mode 0 .. 3:
+    LOCALIZE_MODES) and the chains weight = sum g, moment = sum g * positions[c] over the amplitudes g > 0 (include/mtscomp_hip.h), from
+    the adjacent chunks `keys`.  positions: (n_cols, n_dims) float32.  cache_id as waveforms.  Returns (status list, amplitude float32
+    (n, width) or None without want_amp, weight float32 (n), moment float32 (n, n_dims), best int32 (n))."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, shapes, positions = _loc_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width, mode, positions)
+    amp = np.empty(shapes[0], np.float32) if want_amp else None
+    res = [np.empty(sh, t) for sh, t in zip(shapes[1:], _LOCALIZE_DTYPES)]
+    _check(lib().mts_localize(*head, *mid, _ptr(amp) if want_amp else None, *(_ptr(a) for a in res), _ip(status)), 'mts_localize')
+    return (_status(status, n), amp) + tuple(res)
+
+
+def dev_localize(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0,
+                 before, after, width, mode, positions, want_amp=True, out=None, download=True):
+    """mts_dev_localize on a DevBuffer of compressed chunks (offsets into it).  `out`: a DevBuffer for the four results (made when
+    None; returned so that a caller timing repeated calls can pass it again).  Returns (status list, (amplitude or None, weight,
+    moment, best) or None, out)."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, shapes, positions = _loc_args(valid_begin, valid_end, taps, cols, reference, ev_row, ev_col0, before, after, width, mode, positions)
+    amp = np.empty(shapes[0] if want_amp else 0, np.float32)
+    res = [amp] + [np.empty(sh, t) for sh, t in zip(shapes[1:], _LOCALIZE_DTYPES)]
+    out, ptrs, at = _dev_results(out, cbuf.device, [a.nbytes for a in res])
+    _check(lib().mts_dev_localize(*head, *mid, ptrs[0] if want_amp else None, *ptrs[1:], _ip(status)), 'mts_dev_localize')
+    got = None
+    if download:
+        got = _dev_fetch(out, at, res)
+        got = (got[0] if want_amp else None,) + tuple(got[1:])
+    return _status(status, n), got, out
 
 
 # -- spatio-temporal template scores

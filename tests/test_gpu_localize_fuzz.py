@@ -1,0 +1,27 @@
+"""Randomised parity of Reader.localize under -m gpu: tools/fuzz_localize_gpu.py for MTS_FUZZ_SECONDS (default 5) with a fixed seed
+(MTS_FUZZ_SEED overrides it; the seed is printed): amplitude, weight, moment, best and location against the numpy restatement, byte
+for byte.  Replay a failure with
+    MTS_FUZZ_SEED=<seed> MTS_FUZZ_SECONDS=30 python -m pytest tests/test_gpu_localize_fuzz.py -m gpu -s
+"""
+import os
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parent.parent
+pytestmark = pytest.mark.gpu
+
+SEED = int(os.environ.get('MTS_FUZZ_SEED', 20261020))
+SECONDS = float(os.environ.get('MTS_FUZZ_SECONDS', 5))
+
+
+def test_fuzz_localize(tmp_path):
+    env = dict(os.environ, PYTHONWARNINGS='ignore', HOME=str(tmp_path))
+    env.pop('MTSCOMP_DEVICE_CACHE_GB', None)
+    print('fuzz_localize_gpu seed %d' % SEED)
+    p = subprocess.run([sys.executable, str(ROOT / 'tools' / 'fuzz_localize_gpu.py'), str(SEED), str(SECONDS)], env=env, cwd=str(ROOT),
+                       capture_output=True, text=True, timeout=SECONDS + 600)
+    print(p.stdout[-3000:], p.stderr[-3000:])
+    assert p.returncode == 0, 'seed %d: %s' % (SEED, (p.stdout + p.stderr)[-3000:])
