@@ -733,6 +733,36 @@ int mts_rank_hist(int device, long cache_id, int n_chunks, const long *chunk_key
                   const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *out_hist, unsigned long long *out_kmin,
                   unsigned long long *out_kmax, long *out_count, int *chunk_status);
 
+/*
+ * The same round over the filtered signal z of mts_detect instead of the decoded items (an extension, as mts_rank_hist): what
+ * Reader.quantile / median / mad order when taps= or reference= is given.  The chunks (adjacent), valid_begin .. reference and
+ * chunk_status are those of mts_detect: z[t, j] is float32, the FIR of the selected columns inside [valid_begin, valid_end) minus, with
+ * reference 1, the row's median over them.  z never leaves the device: it is made slab by slab (at most MTS_ZRANK_SLAB_BYTES of
+ * float32, default 256 MiB) and counted where it lies.
+ *   items          the float32 z[t, j]: mode, center, the order key (key_bits = 32 in mode 0, 64 in modes 1 and 2), the digits and the
+ *                  selectors are mts_rank_hist's for a float32 recording
+ *   grid           row_begin, row_end, window_rows as mts_rank_hist, inside [valid_begin, valid_end): window w is the rows
+ *                  [row_begin + w * window_rows, min(row_end, row_begin + (w + 1) * window_rows))
+ *   count range    row_begin <= count_begin <= count_end <= row_end.  Only the rows of [count_begin, count_end) are counted, so that a
+ *                  caller cuts a grid over calls wherever it likes and adds the partials; the chunks cover the filter's support of
+ *                  the count range, [count_begin + half - (n_taps - 1), count_end + half) inside the valid range, half = (n_taps - 1) / 2
+ *   outputs        hist, kmin, kmax of mts_rank_hist's shapes for the grid, zeroed / initialised once per call and accumulated with
+ *                  integer atomics across slabs and pieces: the same bits whatever the slabs, pieces, calls and cache residency.
+ *                  count (n_windows): the rows of window w inside the count range
+ * When a chunk of the call did not decode, chunk_status says so and the outputs are to be discarded (as the events of mts_detect).
+ * mts_filtered_rank_hist: host cdata and outputs; cache_id 0 or a decoded-chunk cache, resident chunks are read where they lie and
+ * nothing is inserted.  mts_dev_filtered_rank_hist: device d_cdata and d_* outputs; the small arrays on the host; no cache.
+ * MTS_E_ARG before anything is allocated or launched: what mts_detect refuses of its filter arguments, what mts_rank_hist refuses of
+ * mode, center and the selectors (key_bits of a float32 item), a grid outside the valid range, a count range outside the grid, or
+ * chunks that do not cover the support.
+ */
+int mts_filtered_rank_hist(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                           const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags,
+                           long valid_begin, long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                           long row_begin, long row_end, long window_rows, long count_begin, long count_end, int mode, const double *center,
+                           const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *out_hist, unsigned long long *out_kmin,
+                           unsigned long long *out_kmax, long *out_count, int *chunk_status);
+
 /* ---------------------------------------------------------------------------------------------
  * Device-resident variants (inputs and outputs already in HBM; used by bench.py and by callers that
  * keep recordings on the GPU).  Pointers are device pointers on `device`; `stream` is a hipStream_t
@@ -825,6 +855,13 @@ int mts_dev_rank_hist(int device, void *stream, const unsigned char *d_cdata, co
                       long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center /* host */,
                       const unsigned long long *sel_prefix /* host */, const int *sel_shift /* host */, unsigned int *d_hist,
                       unsigned long long *d_kmin, unsigned long long *d_kmax, long *count /* host */, int *chunk_status /* host */);
+int mts_dev_filtered_rank_hist(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                               const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags,
+                               long valid_begin, long valid_end, int n_taps, const double *taps /* host */, int n_cols,
+                               const int *cols /* host */, int reference, long row_begin, long row_end, long window_rows, long count_begin,
+                               long count_end, int mode, const double *center /* host */, const unsigned long long *sel_prefix /* host */,
+                               const int *sel_shift /* host */, unsigned int *d_hist, unsigned long long *d_kmin,
+                               unsigned long long *d_kmax, long *count /* host */, int *chunk_status /* host */);
 /* integer-exact synthetic recording, rows [t0, t1) of n_channels int16, on device */
 int mts_dev_synth_int16(int device, void *stream, void *d_out, long t0, long t1, int n_channels,
                         long seed);

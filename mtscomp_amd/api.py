@@ -524,6 +524,7 @@ class HipCodec:
     match_templates = _lane_reduction('match_templates')
     residual = _lane_reduction('residual')
     match_residual = _lane_reduction('match_residual')
+    filtered_rank_hist = _lane_reduction('filtered_rank_hist')
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -1585,8 +1586,8 @@ class Reader:
                 present = [False] * len(keys)                       # dropped since the query: send everything
 
     # -- exact order statistics on the device (an extension: the reference's users sort Reader[...] on the host)
-    def _rank_setup(self, what, start, stop, window, channels):
-        self._need_codec(what, 'rank_hist', 'selects')
+    def _rank_setup(self, what, start, stop, window, channels, filtered=False):
+        self._need_codec(what, 'filtered_rank_hist' if filtered else 'rank_hist', 'selects in the filtered rows' if filtered else 'selects')
         i0, i1 = self._row_range(start, stop)
         window = _window_rows(window, i0, i1)
         if min(window, i1 - i0) >= 1 << 32:
@@ -1605,9 +1606,10 @@ class Reader:
         except ValueError:
             raise ValueError("center of shape %r does not broadcast to (n_windows, n_channels) = %r" % (c.shape, (n_win, n_cols))) from None
 
-    def _rank_scan(self, i0, i1, window, cols, ranks, mode=0, center=None):
+    def _rank_scan(self, i0, i1, window, cols, ranks, mode=0, center=None, filt=None):
         """The order statistics `ranks` (n_windows, R) int64, 0 <= rank < rows of the window, of every (window, column) cell of the
-        grid: a most-significant-digit radix select whose rounds are mts_rank_hist calls.  -> (keys (n_windows, R, C) uint64 --
+        grid: a most-significant-digit radix select whose rounds are mts_rank_hist calls.  filt = (taps, reference code): the items
+        are the float32 filtered rows z of detect instead of the decoded ones, and the rounds mts_filtered_rank_hist calls.  -> (keys (n_windows, R, C) uint64 --
         hip.rank_values turns them into items --, has_nan (n_windows, C), rounds: the mts_rank_hist passes made).  The windows are scanned in runs whose histograms fit
         QUANTILE_SLAB_BYTES, RANK_SELECTORS ranks at a time; a run is at most ceil(key_bits / 8) rounds, each one pass over its
         chunks."""
@@ -1618,29 +1620,33 @@ class Reader:
         rounds = 0
         if not n_win or not cols.size or not R:
             return out, has_nan, rounds
-        nan_key = hip.rank_key_nan(self.dtype, mode)
-        floats = bool(mode) or self.dtype.kind == 'f'
+        dtype = np.dtype(np.float32) if filt else self.dtype       # the items' type: what the keys are made of
+        nan_key = hip.rank_key_nan(dtype, mode)
+        floats = bool(mode) or dtype.kind == 'f'
         per_win = S * (4 * nb + 16) * cols.size
         run_wins = max(1, QUANTILE_SLAB_BYTES // per_win)
         status = {}
         for ws in range(0, n_win, run_wins):
             we = min(n_win, ws + run_wins)
             rb, re = i0 + ws * window, min(i1, i0 + we * window)
-            calls = self._chunk_runs(self._chunks_in(rb, re), QUANTILE_CALL_BYTES)
+            if filt:                                                # (the cut list of the run's rows: every [cuts[i], cuts[i + 1]) a round of calls)
+                calls = self._halo_cuts(rb, re, QUANTILE_CALL_BYTES, rb, re, lambda row: row)
+            else:
+                calls = self._chunk_runs(self._chunks_in(rb, re), QUANTILE_CALL_BYTES)
             cen = center[ws:we] if mode else None
             for r0 in range(0, R, S):
                 rk = ranks[ws:we, r0:r0 + S]
                 got = rk.shape[1]
                 if got < S:                                         # (an odd rank out: the second selector repeats it and shares its histogram)
                     rk = np.concatenate([rk] + [rk[:, -1:]] * (S - got), axis=1)
-                keys, kmax0, n_rounds = self._rank_rounds(calls, rb, re, window, cols, mode, cen, rk, status)
+                keys, kmax0, n_rounds = self._rank_rounds(calls, rb, re, window, cols, mode, cen, rk, status, dtype, filt)
                 rounds += n_rounds
                 out[ws:we, r0:r0 + got] = keys[:, :got]
                 if r0 == 0 and floats:
                     has_nan[ws:we] = kmax0 == nan_key
         return out, has_nan, rounds
 
-    def _rank_rounds(self, calls, rb, re, window, cols, mode, center, ranks, status):
+    def _rank_rounds(self, calls, rb, re, window, cols, mode, center, ranks, status, dtype, filt=None):
         """The rounds of one run of windows [rb, re) for RANK_SELECTORS ranks per cell.  State per (window, selector, column): the
         candidates are the items with key >> (shift + 8) == pref, the rank `rel` counts among them.  A round's histogram picks the
         digit; the candidates' kmin / kmax (known one round late) tell down to which bit they all agree (bit_length(kmin ^ kmax)): the next digit
@@ -1649,7 +1655,7 @@ class Reader:
         selectors are always disjoint.  -> (keys (n_windows, S, C) uint64, kmax of the first, prefix-free round (n_windows, C), the rounds made)."""
         S, B = hip.RANK_SELECTORS, hip.RANK_BITS
         nw, C = ranks.shape[0], cols.size
-        kb = hip.rank_key_bits(self.dtype, mode)
+        kb = hip.rank_key_bits(dtype, mode)
         u64 = np.uint64
         rel = np.repeat(ranks[:, :, None].astype(np.int64), C, axis=2)
         shift = np.full((nw, S, C), kb - B, u64)
@@ -1667,7 +1673,7 @@ class Reader:
             share = ~done[:, 0] & ~done[:, 1] & (pref[:, 0] == pref[:, 1]) & (shift[:, 0] == shift[:, 1])
             sel_shift = np.where(done, -1, shift.astype(np.int64)).astype(np.int32)
             sel_shift[:, 1][share] = -1
-            hist, kmin, kmax = self._rank_call(calls, rb, re, window, cols, mode, center, pref, sel_shift, status)
+            hist, kmin, kmax = self._rank_call(calls, rb, re, window, cols, mode, center, pref, sel_shift, status, filt)
             if rnd == 0:
                 kmax0 = kmax[:, 0].copy()
             for s in range(S):
@@ -1707,29 +1713,58 @@ class Reader:
             rnd += 1
         return val, kmax0, rnd
 
-    def _rank_call(self, calls, rb, re, window, cols, mode, center, pref, sel_shift, status):
-        """One round over the chunks of `calls` (lists of chunk indices): every call's chunks on their owner lanes, the integer
-        partials added (the order does not matter).  A chunk that did not decode raises the error of Reader[...]."""
+    def _rank_call(self, calls, rb, re, window, cols, mode, center, pref, sel_shift, status, filt=None):
+        """One round, the integer partials of its calls added (the order does not matter).  A chunk that did not decode raises the
+        error of Reader[...].  The feed -- unfiltered: `calls` are lists of chunk indices (the tile family), every call's chunks on
+        their owner lanes.  filt = (taps, reference code): `calls` is the cut list of the rows [rb, re) (the halo family), every part
+        (a, b) one mts_filtered_rank_hist call that counts its rows on the grid of the windows it meets, with the adjacent chunks
+        of its filter support."""
         S, nb = hip.RANK_SELECTORS, 1 << hip.RANK_BITS
         nw, C = pref.shape[0], cols.size
         hist = np.zeros((nw, S, nb, C), np.uint32)
         kmin = np.full((nw, S, C), hip.RANK_KEY_NONE, np.uint64)
         kmax = np.zeros((nw, S, C), np.uint64)
-        for run in calls:
-            lo, hi = max(rb, self.chunk_bounds[run[0]]), min(re, self.chunk_bounds[run[-1] + 1])
+
+        def grid(lo, hi):
+            """The windows that hold the rows [lo, hi): (their slice, the grid's rows, its center and selectors)."""
             w0, w1 = (lo - rb) // window, -(-(hi - rb) // window)
-            cb, ce = rb + w0 * window, min(re, rb + w1 * window)
             sl = slice(w0, w1)
             cen = None if center is None else np.ascontiguousarray(center[sl])
-            pre, shf = np.ascontiguousarray(pref[sl]), np.ascontiguousarray(sel_shift[sl])
-            for res in self._on_owner_lanes(self.codec.rank_hist, run, status, cb, ce, window, cols, mode, cen, pre, shf):
-                hist[sl] += res['hist']
-                kmin[sl] = np.minimum(kmin[sl], res['kmin'])
-                kmax[sl] = np.maximum(kmax[sl], res['kmax'])
+            return sl, (rb + w0 * window, min(re, rb + w1 * window)), (mode, cen, np.ascontiguousarray(pref[sl]), np.ascontiguousarray(sel_shift[sl]))
+
+        def unfiltered():
+            for run in calls:
+                sl, (cb, ce), sel = grid(max(rb, self.chunk_bounds[run[0]]), min(re, self.chunk_bounds[run[-1] + 1]))
+                for res in self._on_owner_lanes(self.codec.rank_hist, run, status, cb, ce, window, cols, *sel):
+                    yield sl, res
+
+        def filtered():
+            taps, ref_code = filt
+
+            def part(a, b):
+                _, (cb, ce), sel = grid(a, b)
+                keys = self._chunk_span(*self._support(a, b, 0, 0, 1, int(taps.size)))
+                return keys, (0, self.n_samples, taps, cols, ref_code, cb, ce, window, a, b) + sel
+            for a, b, (res,) in self._halo_parts(self.codec.filtered_rank_hist, calls, part):
+                yield grid(a, b)[0], res
+
+        for sl, res in (filtered() if filt else unfiltered()):
+            hist[sl] += res['hist']
+            kmin[sl] = np.minimum(kmin[sl], res['kmin'])
+            kmax[sl] = np.maximum(kmax[sl], res['kmax'])
         self._raise_for(status)
         return hist, kmin, kmax
 
-    def quantile(self, q, start=0, stop=None, channels=slice(None), window=None, method='linear', center=None, absolute=False):
+    def _rank_filter(self, taps, reference, channels):
+        """taps= / reference= of quantile, median and mad -> None when neither is given (the decoded items are ordered), else (taps as
+        float64, reference as the library's code), checked as detect checks them."""
+        if taps is None and reference is None:
+            return None
+        taps, _, ref_code, _ = self._filter_args(taps, reference, channels)
+        return taps, ref_code
+
+    def quantile(self, q, start=0, stop=None, channels=slice(None), window=None, method='linear', center=None, absolute=False, taps=None,
+                 reference=None):
         """Exact per-window, per-channel quantiles of rows [start, stop), selected on the device: only digit histograms cross the
         bus.  start / stop / window / channels as window_stats (window=None: one window over the range).  q: a float or a 1-D
         sequence of floats in [0, 1].  For a window of n rows the position v = q * (n - 1) is computed exactly (as a fraction), index
@@ -1747,7 +1782,15 @@ class Reader:
         (mts_rank_hist rounds: what a cold scan decodes).  A scalar q drops the n_q axis, an int channel
         the C axis.  Chunks resident in the device cache are read where they lie; the others are decoded in a transient workspace
         and NOT kept.  Every window costs a histogram however few rows it has: small windows are correct, not fast.  A damaged chunk
-        raises the IOError of Reader[...]."""
+        raises the IOError of Reader[...].
+        taps= / reference= (as detect takes them; either given): what is ordered is z[t, j], the filtered rows of detect -- float32,
+        the bytes of decimate(1, taps=taps, edge='recording', dtype=float32) on `channels` (taps=None is [1.0]) minus, with
+        reference='median', the float32 median over the selected columns of each row; the bytes of residual([], ...).  z is made
+        and counted on the device slab by slab and never crosses the bus.  The items are float32: lower / upper are float32 without
+        center / absolute, everything else is the contract above for a float32 recording (a NaN in a row makes, with the median
+        reference, every column's window NaN).  The Bunch then also carries taps (the float64 array used) and reference; rounds
+        counts mts_filtered_rank_hist rounds.  The same bits whatever the lanes, calls, pieces, slabs or cache residency; a damaged
+        chunk in the filter's support raises the IOError of Reader[...]."""
         if method not in QUANTILE_METHODS:
             raise ValueError("method must be one of %r, got %r" % (QUANTILE_METHODS, method))
         try:
@@ -1758,7 +1801,8 @@ class Reader:
         qa = qa.reshape(-1) if qa.ndim <= 1 else qa
         if qa.ndim != 1 or np.asarray(q).dtype.kind not in 'fiu' or not ((qa >= 0) & (qa <= 1)).all():
             raise ValueError("q must be a float or a 1-D sequence of floats in [0, 1], got %r" % (q,))
-        i0, i1, window, cols, squeeze, count = self._rank_setup('quantile', start, stop, window, channels)
+        filt = self._rank_filter(taps, reference, channels)
+        i0, i1, window, cols, squeeze, count = self._rank_setup('quantile', start, stop, window, channels, filt is not None)
         n_win, nq = count.size, qa.size
         mode = 2 if absolute else 1 if center is not None else 0
         cen = self._rank_center(center, n_win, cols.size) if mode else None
@@ -1783,8 +1827,8 @@ class Reader:
             w = int(np.argmax(rows))
             rk[rows] = np.concatenate((u, np.repeat(u[-1:], R - u.size)))
             pos_lo[rows], pos_hi[rows] = np.searchsorted(u, index[w]), np.searchsorted(u, upper_i[w])
-        keys, has_nan, rounds = self._rank_scan(i0, i1, window, cols, rk, mode, cen)
-        vals = hip.rank_values(keys, self.dtype, mode)              # (n_win, R, C)
+        keys, has_nan, rounds = self._rank_scan(i0, i1, window, cols, rk, mode, cen, filt)
+        vals = hip.rank_values(keys, np.float32 if filt else self.dtype, mode)      # (n_win, R, C)
         if n_win:
             lower, upper = np.take_along_axis(vals, pos_lo[:, :, None], axis=1), np.take_along_axis(vals, pos_hi[:, :, None], axis=1)
         else:
@@ -1805,6 +1849,8 @@ class Reader:
         res = np.where(has_nan[:, None, :], np.nan, res)
         out = Bunch(count=count, q=qa, quantile=res, lower=lower, upper=upper, index=index, frac=frac, start=i0, stop=i1, window=window,
                     channels=cols, method=method, rounds=rounds)
+        if filt:
+            out.taps, out.reference = filt[0], reference
         if squeeze:
             for key in ('quantile', 'lower', 'upper'):
                 out[key] = out[key][:, :, 0]
@@ -1813,32 +1859,39 @@ class Reader:
                 out[key] = out[key][:, 0]
         return out
 
-    def median(self, start=0, stop=None, channels=slice(None), window=None):
+    def median(self, start=0, stop=None, channels=slice(None), window=None, taps=None, reference=None):
         """Per-window, per-channel median of rows [start, stop) as float64, (n_windows, C) (an int channel drops C): quantile(0.5)
         with method='midpoint' -- (float64(lower) + float64(upper)) / 2 over the two middle order statistics of a window of an even
         number of rows, the middle one of an odd number --, the value of np.median(r[w0:w1, channels].astype(np.float64), axis=0),
-        NaN for a window that holds one.  Ordering rules, cache use and errors as quantile."""
-        return self.quantile(0.5, start, stop, channels=channels, window=window, method='midpoint').quantile
+        NaN for a window that holds one.  Ordering rules, cache use and errors as quantile.  taps= / reference= as quantile: the
+        median of the filtered rows z, np.median(z.astype(np.float64), axis=0)."""
+        return self.quantile(0.5, start, stop, channels=channels, window=window, method='midpoint', taps=taps, reference=reference).quantile
 
-    def mad(self, start=0, stop=None, channels=slice(None), window=None, center='median'):
+    def mad(self, start=0, stop=None, channels=slice(None), window=None, center='median', taps=None, reference=None):
         """Per-window, per-channel median absolute deviation median(|float64(x) - center|) of rows [start, stop): two scans on the
         device, the median, then the median of the absolute deviations from it.  center: 'median', or an array that broadcasts to
         (n_windows, C) (zeros: the spike-band noise estimate median(|x|); divide by 0.6745 for a standard deviation).  Returns a
         Bunch: count, center, mad (n_windows, C) float64 (an int channel drops C), start, stop, window, channels, rounds (the passes
         over the chunks of both scans).  Per window it
         equals scipy.stats.median_abs_deviation(x.astype(np.float64), axis=0), NaN for a window that holds one.  Ordering rules,
-        cache use and errors as quantile."""
-        i0, i1, window, cols, squeeze, count = self._rank_setup('mad', start, stop, window, channels)
+        cache use and errors as quantile.  taps= / reference= as quantile: x is the filtered rows z, and the Bunch also carries taps and
+        reference -- mad(center=0.0, taps=highpass_taps(300, sample_rate), reference='median').mad / 0.6745 is the spike-band noise
+        level that detect's thresholds are set from."""
+        filt = self._rank_filter(taps, reference, channels)
+        i0, i1, window, cols, squeeze, count = self._rank_setup('mad', start, stop, window, channels, filt is not None)
+        taps = None if filt is None else filt[0]
         if isinstance(center, str):
             if center != 'median':
                 raise ValueError("center must be 'median' or an array, got %r" % (center,))
-            med = self.quantile(0.5, i0, i1, channels=cols, window=window, method='midpoint')
+            med = self.quantile(0.5, i0, i1, channels=cols, window=window, method='midpoint', taps=taps, reference=reference)
             cen, rounds = med.quantile.reshape(count.size, cols.size), med.rounds
         else:
             cen, rounds = self._rank_center(center, count.size, cols.size), 0
-        res = self.quantile(0.5, i0, i1, channels=cols, window=window, method='midpoint', center=cen, absolute=True)
+        res = self.quantile(0.5, i0, i1, channels=cols, window=window, method='midpoint', center=cen, absolute=True, taps=taps, reference=reference)
         dev = res.quantile
         out = Bunch(count=count, center=cen, mad=dev, start=i0, stop=i1, window=window, channels=cols, rounds=rounds + res.rounds)
+        if filt:
+            out.taps, out.reference = taps, reference
         if squeeze:
             out.center, out.mad = cen[:, 0], dev[:, 0]
         return out

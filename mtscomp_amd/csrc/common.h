@@ -108,6 +108,14 @@ int launch_rank_hist(hipStream_t st, int itemsize, int flags, int mode, const St
                      int n_launch, const int *d_ok, const int *d_cols, int n_cols, int n_channels, const double *d_center, const u64 *d_prefix,
                      const int *d_shift, u32 *d_hist, u64 *d_kmin, u64 *d_kmax);
 
+// zselect.hip: the same round over a float32 workspace z that launch_decimate (q = 1) and launch_row_median filled
+// (mts_filtered_rank_hist).  d_y holds the file rows [s0, s1), n_cols items a row, and every one of them is counted on the window grid
+// (row_begin, window_rows); selectors, centers and outputs as launch_rank_hist, accumulated the same way.  One workgroup per
+// block_rows rows and 64 columns, its rows cut at the grid's windows by arithmetic alone (zrank_segment, reduce_plan.h)
+constexpr long ZSEL_BLOCK_ROWS = 4096;                                  // H: as SEL_TILE_ROWS, one LDS histogram flush per 64 columns and window
+int launch_zrank_hist(hipStream_t st, int mode, const float *d_y, long s0, long s1, long block_rows, int n_cols, long row_begin, long window_rows,
+                      const double *d_center, const u64 *d_prefix, const int *d_shift, u32 *d_hist, u64 *d_kmin, u64 *d_kmax);
+
 // decimate.hip: FIR + keep every q-th row of decoded chunks (mts_decimate).  Outputs k in [k_begin, k_end) of the call:
 // out[(k - k_begin) * n_cols + c] = sum_j taps[j] * x[first_row + k * q - j, cols[c]] in the out_itemsize float type, j ascending,
 // x = 0 outside [valid_begin, valid_end) and outside the segments; segment s holds file rows [seg_row0[s], seg_row0[s + 1]) at

@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -26,10 +26,10 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, welch, gram): a unit of output (outputs, rows,
+//   halo (decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist, welch, gram): a unit of output (outputs, rows,
 //        events, blocks, groups -- the op gives HaloPlan its map from units to rows) reads rows of several adjacent chunks, so a piece
 //        reads chunks [c0, c1] through a table of segment bases and first rows, and decodes the missing ones among them -- a boundary
-//        chunk in both pieces (HaloPlan, HaloFeed).  Eight of them (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual) start from
+//        chunk in both pieces (HaloPlan, HaloFeed).  Nine of them (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist) start from
 //        one filtered signal z: their checks, uploads, filter stage and tails are the z family's shared parts below.
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
 //   - An allocation that fails empties this device's caches before it tries again (DBuf::ensure -> drop_device_caches: hipFree,
@@ -134,7 +134,7 @@ int check_taps(const char *op, int n_taps, const double *taps)
     return MTS_OK;
 }
 
-// what the z family (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
+// what the z family (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
 // in float32, x = 0 outside [vb, ve), minus the row's median over the columns with reference 1.  `op` names the entry in every message.
 struct ZArgs { const char *op; long vb, ve; int n_taps; const double *taps; int n_cols; const int *cols; int reference; };
 
@@ -339,7 +339,7 @@ struct HaloFeed {
     }
 };
 
-// ---- z family: what detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates and residual share around their own slab loops.  Each run reads
+// ---- z family: what detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual and filtered_rank_hist share around their own slab loops.  Each run reads
 // top to bottom as the halo family's sequence: plan -> regions (ZStage first, the op's, EventTail's) -> StreamGuard -> place ->
 // uploads -> run -> tail.
 //
@@ -1438,6 +1438,117 @@ static int residual_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZA
     return dense_tail(G, out_on_host, out, d_out, n_items);
 }
 
+// ---- one round of a radix select over the filtered signal (mts_filtered_rank_hist, mts_dev_filtered_rank_hist) -----------------
+// The unit is a row of the count range [count_begin, count_end), a part of the window grid (row_begin, row_end, window_rows).  Piece p
+// owns the rows in its chunks; they read their filter support and nothing else (no exclusion radius: a slab is the rows it owns).  A
+// piece's rows go through the float32 workspace in slabs (filter -> median -> k_zrank_hist on the stream).  The histograms, kmin and
+// kmax are zeroed / initialised once per call, accumulated with integer atomics across slabs and pieces on the device and copied out
+// once: the same bytes whatever the pieces and slabs.  The items are float32, so the keys have 32 bits in mode 0.
+static const u64 ZRANK_SLAB_BYTES = 256ull << 20;
+
+static int filtered_rank_hist_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long row_begin, long row_end, long window_rows,
+                                  long count_begin, long count_end, int mode, const double *center, const unsigned long long *sel_prefix,
+                                  const int *sel_shift, unsigned int *o_hist, unsigned long long *o_kmin, unsigned long long *o_kmax,
+                                  bool out_on_host, long *count, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols, n_taps = Z.n_taps;
+    int rc;
+    if ((rc = check_zargs(T, Z))) return rc;
+    if (window_rows < 1) { set_error("window_rows %ld < 1", window_rows); return MTS_E_ARG; }
+    if (row_begin < vb || row_end < row_begin || row_end > ve) { set_error("filtered rank hist: rows invalid"); return MTS_E_ARG; }
+    if (count_begin < row_begin || count_end < count_begin || count_end > row_end) {
+        set_error("filtered rank hist: count range [%ld, %ld) outside the grid [%ld, %ld)", count_begin, count_end, row_begin, row_end); return MTS_E_ARG;
+    }
+    if (mode < 0 || mode > 2) { set_error("filtered rank hist: mode %d (0, 1 or 2)", mode); return MTS_E_ARG; }
+    const long span = row_end - row_begin;
+    if ((window_rows < span ? window_rows : span) >= (1l << 32)) { set_error("windows of 2^32 rows or more"); return MTS_E_ARG; }
+    const long n_win = (span + window_rows - 1) / window_rows;
+    if (n_win && (!o_hist || !o_kmin || !o_kmax || !count || !sel_prefix || !sel_shift || (mode && !center))) {
+        set_error("filtered rank hist: selectors, center or outputs missing"); return MTS_E_ARG;
+    }
+    const int key_bits = mode ? 64 : 32;                     // (a float32 item)
+    const u64 n_sel = (u64)n_win * MTS_RANK_SELECTORS * n_cols;
+    for (u64 e = 0; e < n_sel; e++) {
+        const int sh = sel_shift[e];
+        if (sh < 0) continue;
+        const int above = key_bits - sh - MTS_RANK_BITS;     // bits of the key above the digit
+        if (above < 0) { set_error("filtered rank hist: shift %d above key_bits - %d", sh, MTS_RANK_BITS); return MTS_E_ARG; }
+        if (above < 64 && (sel_prefix[e] >> above)) { set_error("filtered rank hist: a prefix of more than %d bits at shift %d", above, sh); return MTS_E_ARG; }
+    }
+    if ((rc = check_columns(Z.cols, n_cols, T.nc))) return rc;
+    if ((rc = check_chunk_table(true, T))) return rc;
+    const long half = (n_taps - 1) / 2, n_units = count_end - count_begin;
+    // the rows that the rows [u0, u1) read: their filter support ∩ valid range
+    auto rows = [&](long u0, long u1, long *lo, long *hi) {
+        *lo = std::max(vb, count_begin + u0 + half - (n_taps - 1)); *hi = std::min(ve, count_begin + u1 + half);
+    };
+    long need_lo = 0, need_hi = 0;
+    if (n_units) rows(0, n_units, &need_lo, &need_hi);
+    if ((rc = check_cover("filtered rank hist", T, need_lo, need_hi))) return rc;
+    status_ok(T, status);
+    for (long w = 0; w < n_win; w++) count[w] = 0;
+    if (!n_win) return MTS_OK;
+    const u64 n_cells = (u64)n_win * n_cols, hist_bytes = n_sel * (4ull << MTS_RANK_BITS), k_bytes = n_sel * 8;
+    if (!n_units) {                                          // nothing to count: the identities
+        if (out_on_host) { memset(o_hist, 0, (size_t)hist_bytes); memset(o_kmin, 0xff, (size_t)k_bytes); memset(o_kmax, 0, (size_t)k_bytes); return MTS_OK; }
+        MTS_HIP(hipMemsetAsync(o_hist, 0, (size_t)hist_bytes, st));
+        MTS_HIP(hipMemsetAsync(o_kmin, 0xff, (size_t)k_bytes, st));
+        MTS_HIP(hipMemsetAsync(o_kmax, 0, (size_t)k_bytes, st));
+        MTS_HIP(hipStreamSynchronize(st));
+        return MTS_OK;
+    }
+
+    HaloFeed H(T, out_on_host);
+    if ((rc = H.plan(n_units, [&](long r) { return r - count_begin; }, rows))) return rc;
+    // rows a slab owns: the workspace holds them and nothing else
+    const u64 cap_rows = std::min<u64>(env_bytes("MTS_ZRANK_SLAB_BYTES", ZRANK_SLAB_BYTES) / (4 * (u64)n_cols), (u64)1 << 40);
+    const long own = std::min(n_units, std::max(1l, (long)cap_rows));
+    const long block_rows = (long)std::min<u64>(env_bytes("MTS_ZRANK_BLOCK_ROWS", (u64)ZSEL_BLOCK_ROWS), (u64)1 << 40);      // (the bench sweeps it)
+    // ---- workspace: taps, columns, segment tables, centers, selectors, the filtered slab, the outputs
+    WsLayout &L = H.L;
+    ZStage F(Z, L);
+    const size_t o_seg = L.take(H.table_bytes()), o_cen = L.take(mode ? 8 * n_cells : 0), o_pre = L.take(k_bytes), o_shf = L.take(n_sel * 4),
+                 o_y = L.take(4 * (u64)own * n_cols), w_hist = L.take_out(hist_bytes), w_kmin = L.take_out(k_bytes), w_kmax = L.take_out(k_bytes);
+    StreamGuard G{st};
+    if ((rc = H.place(E, st, E.zrank, o_seg))) return rc;
+    u8 *ws = E.zrank.as<u8>();
+    if ((rc = F.upload(st, ws))) return rc;
+    double *d_cen = (double *)(ws + o_cen);
+    u64 *d_pre = (u64 *)(ws + o_pre);
+    int *d_shf = (int *)(ws + o_shf);
+    float *d_y = (float *)(ws + o_y);
+    u32 *d_hist = L.out(ws, w_hist, (u32 *)o_hist);
+    u64 *d_kmin = L.out(ws, w_kmin, (u64 *)o_kmin), *d_kmax = L.out(ws, w_kmax, (u64 *)o_kmax);
+    if (mode) MTS_HIP(hipMemcpyAsync(d_cen, center, 8 * (size_t)n_cells, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_pre, sel_prefix, (size_t)k_bytes, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(d_shf, sel_shift, 4 * (size_t)n_sel, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemsetAsync(d_hist, 0, (size_t)hist_bytes, st));
+    MTS_HIP(hipMemsetAsync(d_kmin, 0xff, (size_t)k_bytes, st));
+    MTS_HIP(hipMemsetAsync(d_kmax, 0, (size_t)k_bytes, st));
+    rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
+        const long p0 = count_begin + Pc.u0, p1 = count_begin + Pc.u1;
+        int r = MTS_OK;
+        for (long s0 = p0; !r && s0 < p1; s0 += own) {
+            const long s1 = std::min(p1, s0 + own);
+            r = F.filter(st, T, Sg, s0, s1, d_y);
+            if (!r) r = launch_zrank_hist(st, mode, d_y, s0, s1, block_rows, n_cols, row_begin, window_rows, d_cen, d_pre, d_shf, d_hist, d_kmin, d_kmax);
+        }
+        return r;
+    });
+    if (rc) return rc;
+    if (out_on_host) {                                        // the histograms, and nothing else, cross the bus
+        MTS_HIP(hipMemcpyAsync(o_hist, d_hist, (size_t)hist_bytes, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(o_kmin, d_kmin, (size_t)k_bytes, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(o_kmax, d_kmax, (size_t)k_bytes, hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = G.wait())) return rc;
+    for (long w = (count_begin - row_begin) / window_rows; w < n_win && row_begin + w * window_rows < count_end; w++)      // (after the last wait)
+        count[w] = std::min(count_end, row_begin + std::min(span, (w + 1) * window_rows)) - std::max(count_begin, row_begin + w * window_rows);
+    return MTS_OK;
+}
+
 // ---- template events (mts_match_templates, mts_dev_match_templates) ------------------------------------------------------------
 // The unit is a row of [row_begin, row_end).  Piece p owns the rows in its chunks; their events need the scores R rows either side,
 // those z from `before` rows before to T - before - 1 rows after, and that the filter's support: the rows [u0, u1) read the file rows
@@ -1812,6 +1923,28 @@ int mts_dev_rank_hist(int device, void *stream, const unsigned char *d_cdata, co
 {
     return DEV_ENTRY(rank_hist_run(E, (hipStream_t)stream, T, row_begin, row_end, window_rows, n_cols, cols, mode, center, sel_prefix, sel_shift,
                      d_hist, d_kmin, d_kmax, false, count, chunk_status));
+}
+
+int mts_filtered_rank_hist(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                           const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags,
+                           long valid_begin, long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                           long row_begin, long row_end, long window_rows, long count_begin, long count_end, int mode, const double *center,
+                           const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *out_hist, unsigned long long *out_kmin,
+                           unsigned long long *out_kmax, long *out_count, int *chunk_status)
+{
+    return HOST_ENTRY(filtered_rank_hist_run(E, nullptr, T, Z_ARGS("filtered rank hist"), row_begin, row_end, window_rows, count_begin, count_end,
+                      mode, center, sel_prefix, sel_shift, out_hist, out_kmin, out_kmax, true, out_count, chunk_status));
+}
+
+int mts_dev_filtered_rank_hist(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                               const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags,
+                               long valid_begin, long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference,
+                               long row_begin, long row_end, long window_rows, long count_begin, long count_end, int mode,
+                               const double *center, const unsigned long long *sel_prefix, const int *sel_shift, unsigned int *d_hist,
+                               unsigned long long *d_kmin, unsigned long long *d_kmax, long *count, int *chunk_status)
+{
+    return DEV_ENTRY(filtered_rank_hist_run(E, (hipStream_t)stream, T, Z_ARGS("filtered rank hist"), row_begin, row_end, window_rows, count_begin,
+                     count_end, mode, center, sel_prefix, sel_shift, d_hist, d_kmin, d_kmax, false, count, chunk_status));
 }
 
 int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,

@@ -1,9 +1,10 @@
 // How a reduction is fed: the part that decides and touches no device.  Which chunks go into which piece, where the compressed
 // bytes of the missing chunks lie in the staging buffer, where each of them is decoded to, which chunks a piece of the halo family
 // reads and what its segment table holds, how the tile family cuts and orders its tiles, how the events of waveforms and the rows of match_templates
-// are cut into slabs, how mean_waveforms groups a slab's events by label.  Addresses are plain integers here: the header includes the
-// C++ standard library only, so tests/plan_check.cpp, tests/snippet_plan_check.cpp, tests/tmatch_plan_check.cpp and
-// tests/mean_plan_check.cpp sweep these plans on the CPU.  reduce.hip puts the
+// are cut into slabs, how mean_waveforms groups a slab's events by label, which rows and windows a workgroup of the filtered select
+// counts.  Addresses are plain integers here: the header includes the C++ standard library only, so tests/plan_check.cpp,
+// tests/snippet_plan_check.cpp, tests/tmatch_plan_check.cpp, tests/mean_plan_check.cpp and tests/zrank_plan_check.cpp sweep these
+// plans on the CPU.  reduce.hip puts the
 // device side around them (ChunkFeed, feed_pieces, HaloFeed, TileFeed) and says there what every caller keeps to.
 #pragma once
 
@@ -15,6 +16,13 @@
 #include <vector>
 
 #include "codec_plan.h"
+
+// (what a kernel runs too: no HIP in here beyond the function attributes, as op_rank.h)
+#ifdef __HIPCC__
+#define MTS_PLAN_FN __host__ __device__ inline
+#else
+#define MTS_PLAN_FN inline
+#endif
 
 namespace mts {
 
@@ -237,6 +245,28 @@ struct TmatchSlabs {
         return S;
     }
 };
+
+// ---- filtered select (k_zrank_hist, zselect.hip): the rows [s0, s1) that one launch counts, on the window grid (row_begin,
+// window_rows).  Block b owns the rows [s0 + b * H, min(s1, s0 + (b + 1) * H)) and walks them in segments that end at the window
+// boundaries of the grid: the segments of all blocks partition [s0, s1), none crosses a window and each names its own.  Arithmetic
+// alone -- the kernel and tests/zrank_plan_check.cpp run the same functions.
+struct ZrankSeg { long r0, r1, win; };                        // the rows [r0, r1) of window `win`
+
+MTS_PLAN_FN long zrank_blocks(long s0, long s1, long H) { return s1 > s0 ? (s1 - s0 + H - 1) / H : 0; }
+// the rows of block b
+MTS_PLAN_FN ZrankSeg zrank_block_rows(long s0, long s1, long H, long b)
+{
+    const long r0 = s0 + b * H;
+    return {r0, s1 - r0 < H ? s1 : r0 + H, -1};
+}
+// the segment that starts at row r of a block that ends at `end` (r < end; row_begin <= r)
+MTS_PLAN_FN ZrankSeg zrank_segment(long r, long end, long row_begin, long window_rows)
+{
+    const long win = (r - row_begin) / window_rows;
+    // (rows to the window's end, not its last row + 1: row_begin + (win + 1) * window_rows may pass 2^63 for a window of 2^62 rows)
+    const long left = window_rows - (r - row_begin - win * window_rows);
+    return {r, end - r < left ? end : r + left, win};
+}
 
 // ---- tile family: the rows of every (chunk ∩ window) segment cut into tiles of tile_rows rows, in row order; a chunk's rows are
 // reduced on their own, so each piece decodes exactly its own missing chunks.  Tile is the kernels' descriptor

@@ -118,7 +118,9 @@ def lib():
             ('match_residual', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, fp, ci, cl, cl, lp, ip, fp], [vp, vp, vp, lp, ip], None),
             ('welch', [cl, cl, cl, ci, cl, dp, ci, ci, ci, ip], [vp, ip], None),
             ('gram', [cl, cl, cl, cl, cl, ci, ip], [vp, vp, ip], None),
-            ('rank_hist', [cl, cl, cl, ci, ip, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip], [vp, vp, vp, lp, ip])):
+            ('rank_hist', [cl, cl, cl, ci, ip, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip], [vp, vp, vp, lp, ip]),
+            ('filtered_rank_hist', [cl, cl, ci, dp, ci, ip, ci, cl, cl, cl, cl, cl, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip],
+             [vp, vp, vp, lp, ip])):
         getattr(L, 'mts_' + name).argtypes = host + mid + tail
         getattr(L, 'mts_dev_' + name).argtypes = dev + mid + (dev_tail or tail)
     L.mts_waveforms_last_plan.argtypes = [C.c_int, lp]
@@ -139,7 +141,7 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_waveform_features', 'mts_dev_waveform_features', 'mts_localize', 'mts_dev_localize', 'mts_correlate', 'mts_dev_correlate',
            'mts_match_templates', 'mts_dev_match_templates',
            'mts_residual', 'mts_dev_residual', 'mts_match_residual', 'mts_dev_match_residual',
-           'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist']
+           'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist', 'mts_filtered_rank_hist', 'mts_dev_filtered_rank_hist']
 
 
 def _check(rc, what):
@@ -627,6 +629,49 @@ def dev_rank_hist(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, row_
     mid, res, cnt, nw = _rank_args(row_begin, row_end, window_rows, cols, mode, center, sel_prefix, sel_shift)
     out, ptrs, at = _dev_results(out, cbuf.device, [a.nbytes for a in res])
     _check(lib().mts_dev_rank_hist(*head, *mid, *ptrs, _lp(cnt), _ip(status)), 'mts_dev_rank_hist')
+    if fetch:
+        _dev_fetch(out, at, res)
+    return _status(status, n), dict(zip(('hist', 'kmin', 'kmax'), res), count=cnt[:nw]), out
+
+
+# -- the same round over the filtered signal z of detect
+ZRANK_BLOCK_ROWS = 4096      # rows of z that one workgroup of k_zrank_hist counts (ZSEL_BLOCK_ROWS)
+
+
+def _frank_args(valid_begin, valid_end, taps, cols, reference, row_begin, row_end, window_rows, count_begin, count_end, mode, center, sel_prefix,
+                sel_shift):
+    """-> (the op's own arguments of mts_filtered_rank_hist, the arrays hist, kmin, kmax, the count array, n_windows)."""
+    taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).ravel())
+    grid, res, cnt, nw = _rank_args(row_begin, row_end, window_rows, cols, mode, center, sel_prefix, sel_shift)
+    mid = (int(valid_begin), int(valid_end), int(taps.size), _dp(taps)) + grid[3:5] + (int(reference),) + grid[:3] + (
+        int(count_begin), int(count_end)) + grid[5:]
+    return mid, res, cnt, nw
+
+
+def filtered_rank_hist(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference,
+                       row_begin, row_end, window_rows, count_begin, count_end, mode, center, sel_prefix, sel_shift, device=0):
+    """mts_filtered_rank_hist: one round of the radix select over z, the filtered rows of mts_detect (taps, cols, reference 0 / 1,
+    float32 items), from the adjacent chunks `keys`.  The grid (row_begin, row_end, window_rows), mode, center and the selectors as
+    rank_hist for a float32 recording; only the rows of [count_begin, count_end), inside the grid, are counted, and the chunks cover
+    their filter support.  cache_id 0: no cache, every chunk comes with its bytes; else chunks with lens[i] == 0 must be resident
+    (HipError E_MISS).  Returns (status list, dict hist, kmin, kmax, count as rank_hist): partials to be added and combined in any
+    order, to be discarded when a status is not CHUNK_OK."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, (hist, kmin, kmax), cnt, nw = _frank_args(valid_begin, valid_end, taps, cols, reference, row_begin, row_end, window_rows, count_begin,
+                                                   count_end, mode, center, sel_prefix, sel_shift)
+    _check(lib().mts_filtered_rank_hist(*head, *mid, hist.ctypes.data_as(C.POINTER(C.c_uint)), _ullp(kmin), _ullp(kmax), _lp(cnt), _ip(status)),
+           'mts_filtered_rank_hist')
+    return _status(status, n), dict(hist=hist, kmin=kmin, kmax=kmax, count=cnt[:nw])
+
+
+def dev_filtered_rank_hist(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference, row_begin,
+                           row_end, window_rows, count_begin, count_end, mode, center, sel_prefix, sel_shift, out=None, fetch=True):
+    """mts_dev_filtered_rank_hist on a DevBuffer of compressed chunks (offsets into it).  `out`, fetch and the result as dev_rank_hist."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, res, cnt, nw = _frank_args(valid_begin, valid_end, taps, cols, reference, row_begin, row_end, window_rows, count_begin, count_end, mode,
+                                    center, sel_prefix, sel_shift)
+    out, ptrs, at = _dev_results(out, cbuf.device, [a.nbytes for a in res])
+    _check(lib().mts_dev_filtered_rank_hist(*head, *mid, *ptrs, _lp(cnt), _ip(status)), 'mts_dev_filtered_rank_hist')
     if fetch:
         _dev_fetch(out, at, res)
     return _status(status, n), dict(zip(('hist', 'kmin', 'kmax'), res), count=cnt[:nw]), out
