@@ -691,6 +691,42 @@ int mts_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, co
              int *chunk_status);
 
 /*
+ * The same Gram matrices and column sums over the filtered signal z of mts_detect instead of the decoded items (an extension, as
+ * mts_gram): what Reader.cov forms when taps= or reference= is given, the covariance a spike sorter whitens with.  By definition the
+ * result is mts_gram of a float32 recording whose items are z.
+ *   z              mts_detect's: the chunks (adjacent), valid_begin .. reference and chunk_status are those of mts_detect.  z[t, j] is
+ *                  float32, the FIR of the selected columns with x = 0 outside [valid_begin, valid_end), minus, with reference 1, the
+ *                  row's median over them.  The arguments are checked as mts_detect checks them; with a reference n_cols <=
+ *                  MTS_DETECT_MAX_REF_COLS, without one n_cols <= MTS_GRAM_MAX_COLS.  z never leaves the device: it is made z slab by
+ *                  z slab (at most MTS_ZGRAM_SLAB_BYTES of float32, default 256 MiB, rounded down to whole slabs of
+ *                  MTS_GRAM_SLAB_ROWS rows and never less than one) and reduced where it lies.
+ *   grid           range_begin, range_end, window_rows, group_begin, group_end as mts_gram, inside [valid_begin, valid_end): the
+ *                  windows, the groups of MTS_GRAM_GROUP_ROWS rows and their numbering are mts_gram's
+ *   the tree       mts_gram's, word for word: a group is cut into slabs of MTS_GRAM_SLAB_ROWS rows aligned to its start; the items
+ *                  are widened to double once (exact); a slab's entry (i, j) is the chain of v_mfma_f64_16x16x4_f64 steps over its
+ *                  rows 4 at a time in row order, from +0 (rows past the slab's end read as 0); a group's entry is its slabs' entries
+ *                  added in slab order from +0; one triangle is mirrored.  Column sums: per slab, the items added in row order in
+ *                  double from +0, slabs in slab order.  The error bound of mts_gram holds with z for x.  The result is the same
+ *                  bits whatever the lanes, calls, pieces, z slabs and cache residency.  Unlike mts_gram it is NOT independent of
+ *                  the column set when reference is 1: the median is taken over the selected columns, so another set is another z.
+ *                  A NaN in a row of x makes, with reference 1, every item of that row of z NaN.
+ *   out_gram       (group_end - group_begin, n_cols, n_cols) float64
+ *   out_sum        (group_end - group_begin, n_cols) float64
+ *   chunks         adjacent, covering the filter support of the call's groups: with [lo, hi) the rows of groups [group_begin,
+ *                  group_end) and half = (n_taps - 1) / 2, the rows [lo + half - (n_taps - 1), hi + half) inside the valid range
+ * When a chunk of the call did not decode, chunk_status says so and the outputs are to be discarded.
+ * mts_filtered_gram: host cdata and outputs; cache_id 0 or a decoded-chunk cache, resident chunks are read where they lie and
+ * nothing is inserted; pieces (MTS_PIPE_BYTES) are cut at group boundaries.  mts_dev_filtered_gram: device d_cdata, d_gram and d_sum;
+ * the small arrays on the host; no cache.
+ * MTS_E_ARG before anything is allocated or launched: what mts_detect refuses of its filter arguments, what mts_gram refuses of the
+ * grid, a range outside the valid rows, or chunks that do not cover the support.
+ */
+int mts_filtered_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                      const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                      long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long range_begin, long range_end,
+                      long window_rows, long group_begin, long group_end, double *out_gram, double *out_sum, int *chunk_status);
+
+/*
  * One round of a radix select over the windows of mts_window_stats (an extension: the reference has no such call; its users sort
  * Reader[...] on the host).  Order statistics do not combine across chunks; digit histograms of candidates do.  Only the histograms
  * cross the bus.  The range, the windows, the chunks (ascending, not necessarily adjacent), cols, flags and chunk_status are those of
@@ -855,6 +891,11 @@ int mts_dev_rank_hist(int device, void *stream, const unsigned char *d_cdata, co
                       long row_end, long window_rows, int n_cols, const int *cols, int mode, const double *center /* host */,
                       const unsigned long long *sel_prefix /* host */, const int *sel_shift /* host */, unsigned int *d_hist,
                       unsigned long long *d_kmin, unsigned long long *d_kmax, long *count /* host */, int *chunk_status /* host */);
+int mts_dev_filtered_gram(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                          const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                          long valid_end, int n_taps, const double *taps /* host */, int n_cols, const int *cols /* host */, int reference,
+                          long range_begin, long range_end, long window_rows, long group_begin, long group_end, double *d_gram, double *d_sum,
+                          int *chunk_status /* host */);
 int mts_dev_filtered_rank_hist(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
                                const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags,
                                long valid_begin, long valid_end, int n_taps, const double *taps /* host */, int n_cols,

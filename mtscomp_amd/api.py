@@ -525,6 +525,7 @@ class HipCodec:
     residual = _lane_reduction('residual')
     match_residual = _lane_reduction('match_residual')
     filtered_rank_hist = _lane_reduction('filtered_rank_hist')
+    filtered_gram = _lane_reduction('filtered_gram')
 
     cache_destroy = staticmethod(hip.cache_destroy)
     cache_query = staticmethod(hip.cache_query)
@@ -2577,7 +2578,7 @@ class Reader:
         return f, (psd[:, 0] if squeeze else psd)
 
     # -- channel covariance on the device (an extension: the reference's users form x.T @ x of Reader[...] on the host)
-    def cov(self, start=0, stop=None, channels=slice(None), window=None, ddof=1):
+    def cov(self, start=0, stop=None, channels=slice(None), window=None, ddof=1, taps=None, reference=None):
         """Per-window channel x channel covariance of rows [start, stop), on the device: only one Gram matrix and one row of sums per
         group of rows cross the bus.  Per window this is np.cov(self[w0:w1, channels], rowvar=False, ddof=ddof) up to rounding.
         Windows are [start + w * window, min(start + (w + 1) * window, stop)); window=None is one window over the range.  start / stop
@@ -2592,8 +2593,28 @@ class Reader:
         a multiple of 2^-1074 like any IEEE product (the error bound in the header has an absolute term n * 2^-1074 for it).  The
         raw-moment formula loses relative accuracy on float data whose mean is large compared with its spread (no centred two-pass
         form).  Chunks resident in the device cache are read where they lie; the others are decoded in a transient workspace and NOT
-        kept.  A damaged chunk raises the IOError of Reader[...]."""
-        self._need_codec('cov', 'gram', 'forms Gram matrices')
+        kept.  A damaged chunk raises the IOError of Reader[...].
+        taps= / reference= (as detect takes them; either given): the rows are z[t, j], the filtered rows of detect -- float32, the
+        bytes of decimate(1, taps=taps, edge='recording', dtype=float32) on `channels` (taps=None is [1.0]) minus, with
+        reference='median', the float32 median over the selected columns of each row; the bytes of residual([], ...).  z is made
+        and reduced on the device slab by slab and never crosses the bus (mts_filtered_gram).  Everything above is then the contract
+        for a float32 recording whose items are z: gram and sum are float64, the summation tree is the same.  With the median
+        reference the result is NOT independent of the column set (the median is over the selected columns), and a NaN in a row
+        poisons every entry of that row's window, not only those of its own column.  The Bunch then also carries taps (the float64
+        array used) and reference.  The same bits whatever the lanes, calls, pieces, slabs or cache residency; a damaged chunk in
+        the filter's support raises the IOError of Reader[...].  Whitening in the spike band, z never leaving the device:
+            hp = highpass_taps(300, r.sample_rate, 101)
+            c = r.cov(taps=hp, reference='median')
+            W = whitening_weights(c.cov[0], 1e-6)
+            white = r.correlate(W.T[:, None, :], before=0, taps=hp, reference='median')     # T = 1 templates: project applied to z
+        and a matched filter in whitened space is correlate on z with the whitening folded into the templates on the host,
+        K'[k, tau, i] = sum_j W[i, j] * Kw[k, tau, j]."""
+        filt = self._rank_filter(taps, reference, channels)
+        if filt:
+            self._need_codec('cov', 'filtered_gram', 'forms Gram matrices of the filtered rows')
+        else:
+            self._need_codec('cov', 'gram', 'forms Gram matrices')
+        n_taps = int(filt[0].size) if filt else 1
         i0, i1 = self._row_range(start, stop)
         window = _window_rows(window, i0, i1)
         if not isinstance(ddof, (int, np.integer)) or isinstance(ddof, bool) or ddof < 0:
@@ -2602,7 +2623,7 @@ class Reader:
         cols, _ = self._stats_channels(channels)
         nc = int(cols.size)
         n_win = -(-(i1 - i0) // window)
-        g_dt, s_dt = hip.gram_dtypes(self.dtype)
+        g_dt, s_dt = hip.gram_dtypes(np.float32 if filt else self.dtype)       # (z is float32)
         gram = np.zeros((n_win, nc, nc), g_dt)
         sm = np.zeros((n_win, nc), s_dt)
         cnt = np.minimum(window, i1 - i0 - window * np.arange(n_win, dtype=np.int64)).astype(np.int64)
@@ -2614,8 +2635,10 @@ class Reader:
             glo = w0 + (g % K) * hip.GRAM_GROUP_ROWS
             ghi = np.minimum(np.minimum(glo + hip.GRAM_GROUP_ROWS, w0 + window), i1)
             bounds, offsets = np.asarray(self.chunk_bounds, np.int64), np.asarray(self.chunk_offsets, np.int64)
-            gc0 = np.searchsorted(bounds, glo, 'right') - 1
-            gc1 = np.searchsorted(bounds, ghi - 1, 'right') - 1
+            # the chunks a group reads: those of its rows' filter support (_support; one tap: the rows themselves)
+            half = (n_taps - 1) // 2
+            gc0 = np.searchsorted(bounds, np.maximum(0, glo + half - (n_taps - 1)), 'right') - 1
+            gc1 = np.searchsorted(bounds, np.minimum(self.n_samples, ghi + half) - 1, 'right') - 1
             # calls: whole groups, cut where the compressed bytes of their chunks pass GRAM_CALL_BYTES or their results GRAM_SLAB_BYTES
             cum = np.concatenate(([0], np.cumsum(offsets[gc1 + 1] - offsets[gc0])))
             per_call = max(1, GRAM_SLAB_BYTES // (8 * (nc * nc + nc)))
@@ -2626,8 +2649,12 @@ class Reader:
                 cuts.append(min(n_groups, a + per_call, max(b, a + 1)))
 
             def part(a, b):
-                return list(range(int(gc0[a]), int(gc1[b - 1]) + 1)), (i0, i1, window, a, b, cols)
-            for a, b, (gp, sp) in self._halo_parts(self.codec.gram, cuts, part):      # groups in order: the float sums are the same every time
+                keys = list(range(int(gc0[a]), int(gc1[b - 1]) + 1))
+                if filt:
+                    return keys, (0, self.n_samples, filt[0], cols, filt[1], i0, i1, window, a, b)
+                return keys, (i0, i1, window, a, b, cols)
+            fn = self.codec.filtered_gram if filt else self.codec.gram
+            for a, b, (gp, sp) in self._halo_parts(fn, cuts, part):      # groups in order: the float sums are the same every time
                 if K == 1:
                     gram[a:b] += gp
                     sm[a:b] += sp
@@ -2641,7 +2668,10 @@ class Reader:
             denom = cnt - ddof
             cov = (gram.astype(np.float64) - sf[:, :, None] * mean[:, None, :]) / denom[:, None, None]
         cov[denom <= 0] = np.nan
-        return Bunch(count=cnt, sum=sm, gram=gram, mean=mean, cov=cov, start=i0, stop=i1, window=window, channels=cols)
+        out = Bunch(count=cnt, sum=sm, gram=gram, mean=mean, cov=cov, start=i0, stop=i1, window=window, channels=cols)
+        if filt:
+            out.update(taps=filt[0], reference=reference)
+        return out
 
     def _read_range(self, b0, b1):
         """The compressed bytes of chunks b0 .. b1-1 in one read."""

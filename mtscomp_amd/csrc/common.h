@@ -252,6 +252,12 @@ int launch_gram_combine(hipStream_t st, const double *d_part, const u64 *d_psum,
                         int float_sum, double *d_gram, u64 *d_sum);
 int launch_gram_finish(hipStream_t st, double *d_gram, long n);
 
+// zgram.hip: the same partials from a float32 workspace z that launch_decimate (q = 1) and launch_row_median filled
+// (mts_filtered_gram).  d_y holds the file rows from z_row0 on, n_cols items a row; the slabs [slab0, slab0 + n_slabs) of d_slab_rows lie
+// inside them.  d_part and d_psum as launch_gram's for a float32 recording (the sums as double bits), bit for bit: one launch for both
+int launch_zgram(hipStream_t st, const float *d_y, long z_row0, int n_cols, const long *d_slab_rows, long slab0, long n_slabs, double *d_part,
+                 u64 *d_psum);
+
 // project.hip: channel-mixing products (mts_project).  out[(t - r_begin) * n_out + k] = the chain of 4-column MFMA steps over
 // (x[t, cols[j]] - offs[j]) * w[j, k], j ascending, for file rows t of [r_begin, r_end) in the out_itemsize float type.  d_offs: n_cols
 // values and d_w: (n_cols rounded up to PROJECT_PAD, w_pitch) values of that type, zeros past n_cols and n_out; w_pitch: n_out rounded

@@ -113,6 +113,8 @@ struct Engine {
     // filtered select: taps, columns, segment tables, centers, selectors, the filtered slab, the histograms and keys of the host entry
     // point
     DBuf zrank;
+    // filtered Gram: taps, columns, slab and segment tables, the filtered slab, the partials, the accumulators of the host entry point
+    DBuf zgram;
     // geometry of the last compress batch whose per-segment / per-block / per-tile descriptors are on the device (a recording is
     // compressed batch after batch of the same shape: the 10 MB of index arrays need not be rebuilt and copied every call)
     // (valid while the three buffers are the allocations the arrays were copied into: DBuf::gen, not the address -- a buffer
@@ -162,7 +164,7 @@ struct Engine {
     void release_all()
     {
         DBuf *all[] = {&stream, &sort_a, &sort_b, &sort_ws, &tables, &tokens, &segbuf, &blk, &blkcodes, &blkhdr, &desc,
-                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &wav, &cor, &tm, &res, &welch, &gram, &proj, &zrank};
+                       &adler, &misc, &h_in, &h_out, &inf_scratch, &inf_desc, &segsums, &fast_lists, &fast_state, &stats, &dec, &det, &wav, &cor, &tm, &res, &welch, &gram, &proj, &zrank, &zgram};
         for (DBuf *b : all) b->release();
         arena_reset();                                   // (every piece of it has just been let go)
         geo_n.clear();

@@ -1,4 +1,4 @@
-// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist, welch, gram) and their C entries.
+// The host side of the device reductions (window_stats, rank_hist, decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist, filtered_gram, welch, gram) and their C entries.
 // The plans -- what goes into which piece, and where -- are in reduce_plan.h and know no device; this file allocates, copies,
 // decodes and launches around them.
 #include <stdio.h>
@@ -26,10 +26,10 @@ using namespace mts;
 // the compressed bytes of piece p + 1 cross the bus on a helper thread.  Two families share this code:
 //   tiles (window_stats, rank_hist): a chunk's rows are cut into tiles that are reduced on their own, so the resident chunks go first
 //        and each piece decodes exactly its own missing chunks (TilePlan, TileFeed);
-//   halo (decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist, welch, gram): a unit of output (outputs, rows,
+//   halo (decimate, project, detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist, filtered_gram, welch, gram): a unit of output (outputs, rows,
 //        events, blocks, groups -- the op gives HaloPlan its map from units to rows) reads rows of several adjacent chunks, so a piece
 //        reads chunks [c0, c1] through a table of segment bases and first rows, and decodes the missing ones among them -- a boundary
-//        chunk in both pieces (HaloPlan, HaloFeed).  Nine of them (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist) start from
+//        chunk in both pieces (HaloPlan, HaloFeed).  Ten of them (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist, filtered_gram) start from
 //        one filtered signal z: their checks, uploads, filter stage and tails are the z family's shared parts below.
 // What every caller keeps to, and TileFeed, HaloFeed, feed_pieces and ChunkFeed hold up:
 //   - An allocation that fails empties this device's caches before it tries again (DBuf::ensure -> drop_device_caches: hipFree,
@@ -134,7 +134,7 @@ int check_taps(const char *op, int n_taps, const double *taps)
     return MTS_OK;
 }
 
-// what the z family (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
+// what the z family (detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist, filtered_gram) filters: z[t, j] = sum_k taps[k] * x[t + half - k, cols[j]]
 // in float32, x = 0 outside [vb, ve), minus the row's median over the columns with reference 1.  `op` names the entry in every message.
 struct ZArgs { const char *op; long vb, ve; int n_taps; const double *taps; int n_cols; const int *cols; int reference; };
 
@@ -339,7 +339,7 @@ struct HaloFeed {
     }
 };
 
-// ---- z family: what detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual and filtered_rank_hist share around their own slab loops.  Each run reads
+// ---- z family: what detect, waveforms, mean_waveforms, waveform_features, localize, correlate, match_templates, residual, filtered_rank_hist and filtered_gram share around their own slab loops.  Each run reads
 // top to bottom as the halo family's sequence: plan -> regions (ZStage first, the op's, EventTail's) -> StreamGuard -> place ->
 // uploads -> run -> tail.
 //
@@ -1873,6 +1873,113 @@ static int gram_run(Engine &E, hipStream_t st, const ChunkTable &T, long range_b
     return MTS_OK;
 }
 
+// ---- Gram matrices of the filtered signal (mts_filtered_gram, mts_dev_filtered_gram) --------------------------------------------
+// mts_gram of a float32 recording whose items are z.  The grid, the groups, the Gram slabs and the accumulators are gram_run's; the
+// unit is a group, and piece p owns the groups whose first row lies in its chunks.  Their rows read their filter support.  A piece's
+// Gram slabs go through the float32 workspace in z slabs (filter -> median -> k_zgram -> the combine, on the stream): a z slab holds
+// whole Gram slabs of one or more groups (zgram_slabs, reduce_plan.h), at most MTS_ZGRAM_SLAB_BYTES of z and GRAM_SLAB_BYTES of
+// partials.  The combine adds a z slab's partials to their groups' accumulators in slab order, so every group sum is the same
+// sequence of additions whatever the z slabs, pieces and calls.
+static const u64 ZGRAM_SLAB_BYTES = 256ull << 20;
+
+static int filtered_gram_run(Engine &E, hipStream_t st, const ChunkTable &T, const ZArgs &Z, long range_begin, long range_end, long window_rows,
+                             long group_begin, long group_end, double *out_gram, double *out_sum, bool out_on_host, int *status)
+{
+    // ---- arguments: everything is checked before anything is allocated or launched
+    const long vb = Z.vb, ve = Z.ve;
+    const int n_cols = Z.n_cols, n_taps = Z.n_taps;
+    int rc;
+    if ((rc = check_zargs(T, Z, MTS_GRAM_MAX_COLS))) return rc;
+    if (window_rows < 1) { set_error("filtered gram: window_rows %ld < 1", window_rows); return MTS_E_ARG; }
+    if (range_begin < vb || range_end <= range_begin || range_end > ve) {
+        set_error("filtered gram: range [%ld, %ld) empty or outside the valid rows [%ld, %ld)", range_begin, range_end, vb, ve); return MTS_E_ARG;
+    }
+    const long GR = GRAM_GROUP_ROWS, SR = GRAM_SLAB_ROWS;
+    const long K = (window_rows + GR - 1) / GR;                   // groups per whole window
+    const long n_range = range_end - range_begin, n_full = n_range / window_rows, tail = n_range % window_rows;
+    const long total_groups = n_full * K + (tail + GR - 1) / GR;
+    if (group_begin < 0 || group_end <= group_begin || group_end > total_groups) {
+        set_error("filtered gram: groups [%ld, %ld) empty or outside the %ld groups of the range", group_begin, group_end, total_groups); return MTS_E_ARG;
+    }
+    if (!out_gram || !out_sum) { set_error("filtered gram: no output buffer"); return MTS_E_ARG; }
+    if ((rc = check_columns(Z.cols, n_cols, T.nc))) return rc;
+    if ((rc = check_chunk_table(true, T))) return rc;
+    const long n_groups = group_end - group_begin;
+    if (n_groups > (1l << 31)) { set_error("filtered gram: too many groups in one call"); return MTS_E_ARG; }
+    const long half = (n_taps - 1) / 2;
+    // the rows that groups [u0, u1) (call-local) read: the filter support of theirs ∩ valid range
+    auto rows = [&](long u0, long u1, long *lo, long *hi) {
+        long a, b, tmp;
+        gram_group_rows(range_begin, range_end, window_rows, GR, group_begin + u0, &a, &tmp);
+        gram_group_rows(range_begin, range_end, window_rows, GR, group_begin + u1 - 1, &tmp, &b);
+        *lo = std::max(vb, a + half - (n_taps - 1)); *hi = std::min(ve, b + half);
+    };
+    long need_lo, need_hi;
+    rows(0, n_groups, &need_lo, &need_hi);
+    if ((rc = check_cover("filtered gram", T, need_lo, need_hi))) return rc;
+    status_ok(T, status);
+    // Gram slabs of the call: slab_rows (2 per slab), gfirst[g] the first slab of call group g
+    std::vector<long> gfirst(n_groups + 1, 0), glo(n_groups), slab_rows;
+    for (long g = 0; g < n_groups; g++) {
+        long hi;
+        gram_group_rows(range_begin, range_end, window_rows, GR, group_begin + g, &glo[g], &hi);
+        gfirst[g] = (long)slab_rows.size() / 2;
+        gram_cut_slabs(glo[g], hi, SR, slab_rows);
+    }
+    const long n_slabs = gfirst[n_groups] = (long)slab_rows.size() / 2;
+
+    HaloFeed H(T, out_on_host);
+    // the first group whose first row is at or after row r
+    if ((rc = H.plan(n_groups, [&](long r) { return std::lower_bound(glo.begin(), glo.end(), r) - glo.begin(); }, rows))) return rc;
+    // a z slab: whole Gram slabs, z <= MTS_ZGRAM_SLAB_BYTES (never less than one Gram slab), their partials <= GRAM_SLAB_BYTES
+    const long cap_rows = zgram_cap_rows(env_bytes("MTS_ZGRAM_SLAB_BYTES", ZGRAM_SLAB_BYTES), n_cols, SR);
+    const long cap_slabs = std::min(n_slabs, std::min(65535l, (long)std::max<u64>(1, GRAM_SLAB_BYTES / (u64)gram_slab_bytes(n_cols))));
+    const long z_rows = std::min(cap_rows, std::min(cap_slabs * SR, slab_rows[2 * n_slabs - 1] - slab_rows[0]));
+    const u64 nn = (u64)n_cols * n_cols;
+    // ---- workspace: taps, columns, the slab tables, the segment tables, the filtered slab, the partials, the accumulators
+    WsLayout &L = H.L;
+    ZStage F(Z, L);
+    const size_t o_slab = L.take(16 * (u64)n_slabs), o_gf = L.take(8 * (u64)(n_groups + 1)), o_seg = L.take(H.table_bytes()),
+                 o_y = L.take(4 * (u64)z_rows * n_cols), o_part = L.take((u64)cap_slabs * gram_pairs(n_cols) * 64 * 64 * 8),
+                 o_psum = L.take((u64)cap_slabs * 8 * n_cols), o_acc = L.take_out(8 * (u64)n_groups * nn),
+                 o_accs = L.take_out(8 * (u64)n_groups * n_cols);
+    StreamGuard G{st};
+    if ((rc = H.place(E, st, E.zgram, o_seg))) return rc;
+    u8 *ws = E.zgram.as<u8>();
+    if ((rc = F.upload(st, ws))) return rc;
+    MTS_HIP(hipMemcpyAsync(ws + o_slab, slab_rows.data(), 16 * (size_t)n_slabs, hipMemcpyHostToDevice, st));
+    MTS_HIP(hipMemcpyAsync(ws + o_gf, gfirst.data(), 8 * (size_t)(n_groups + 1), hipMemcpyHostToDevice, st));
+    double *d_gram = L.out(ws, o_acc, out_gram);
+    u64 *d_sum = L.out(ws, o_accs, (u64 *)out_sum);
+    MTS_HIP(hipMemsetAsync(d_gram, 0, 8 * (size_t)n_groups * nn, st));
+    MTS_HIP(hipMemsetAsync(d_sum, 0, 8 * (size_t)n_groups * n_cols, st));
+    float *d_y = (float *)(ws + o_y);
+    double *d_part = (double *)(ws + o_part);
+    u64 *d_psum = (u64 *)(ws + o_psum);
+    const long *d_slab = (const long *)(ws + o_slab), *d_gf = (const long *)(ws + o_gf);
+    rc = H.run(E, st, status, [&](const FeedPiece &Pc, const PieceSegs &Sg) {
+        int r = MTS_OK;
+        for (const ZgramSlab &zs : zgram_slabs(slab_rows.data(), gfirst[Pc.u0], gfirst[Pc.u1], cap_rows, cap_slabs)) {
+            const long a = slab_rows[2 * zs.s0], b = slab_rows[2 * zs.s1 - 1];
+            if ((r = F.filter(st, T, Sg, a, b, d_y))) break;
+            if ((r = launch_zgram(st, d_y, a, n_cols, d_slab, zs.s0, zs.s1 - zs.s0, d_part, d_psum))) break;
+            // the groups the slabs [s0, s1) belong to
+            const long g0 = std::upper_bound(gfirst.begin(), gfirst.end(), zs.s0) - gfirst.begin() - 1;
+            const long g1 = std::lower_bound(gfirst.begin(), gfirst.end(), zs.s1) - gfirst.begin();
+            for (long ga = g0; !r && ga < g1; ga += 65535)
+                r = launch_gram_combine(st, d_part, d_psum, zs.s0, zs.s1, ga, std::min(g1, ga + 65535), d_gf, n_cols, 1, d_gram, d_sum);
+            if (r) break;
+        }
+        return r;
+    });
+    if (rc) return rc;
+    if (out_on_host) {                                        // the accumulators, and nothing else, cross the bus
+        MTS_HIP(hipMemcpyAsync(out_gram, d_gram, 8 * (size_t)n_groups * nn, hipMemcpyDeviceToHost, st));
+        MTS_HIP(hipMemcpyAsync(out_sum, d_sum, 8 * (size_t)n_groups * n_cols, hipMemcpyDeviceToHost, st));
+    }
+    return G.wait();
+}
+
 // The chunk table has the same names in every host entry and in every device entry of include/mtscomp_hip.h: `call` is the op's run
 // on (Engine &E, const ChunkTable &T).
 #define HOST_ENTRY(call)                                                                                                                     \
@@ -1945,6 +2052,24 @@ int mts_dev_filtered_rank_hist(int device, void *stream, const unsigned char *d_
 {
     return DEV_ENTRY(filtered_rank_hist_run(E, (hipStream_t)stream, T, Z_ARGS("filtered rank hist"), row_begin, row_end, window_rows, count_begin,
                      count_end, mode, center, sel_prefix, sel_shift, d_hist, d_kmin, d_kmax, false, count, chunk_status));
+}
+
+int mts_filtered_gram(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,
+                      const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels, int itemsize, int flags, long valid_begin,
+                      long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long range_begin, long range_end,
+                      long window_rows, long group_begin, long group_end, double *out_gram, double *out_sum, int *chunk_status)
+{
+    return HOST_ENTRY(filtered_gram_run(E, nullptr, T, Z_ARGS("filtered gram"), range_begin, range_end, window_rows, group_begin, group_end, out_gram,
+                      out_sum, true, chunk_status));
+}
+
+int mts_dev_filtered_gram(int device, void *stream, const unsigned char *d_cdata, const long *c_offsets, const long *c_lengths,
+                          const long *chunk_row0, const long *n_rows, int n_chunks, int n_channels, int itemsize, int flags, long valid_begin,
+                          long valid_end, int n_taps, const double *taps, int n_cols, const int *cols, int reference, long range_begin,
+                          long range_end, long window_rows, long group_begin, long group_end, double *d_gram, double *d_sum, int *chunk_status)
+{
+    return DEV_ENTRY(filtered_gram_run(E, (hipStream_t)stream, T, Z_ARGS("filtered gram"), range_begin, range_end, window_rows, group_begin,
+                     group_end, d_gram, d_sum, false, chunk_status));
 }
 
 int mts_decimate(int device, long cache_id, int n_chunks, const long *chunk_keys, const long *chunk_row0, const unsigned char *cdata,

@@ -2,9 +2,9 @@
 // bytes of the missing chunks lie in the staging buffer, where each of them is decoded to, which chunks a piece of the halo family
 // reads and what its segment table holds, how the tile family cuts and orders its tiles, how the events of waveforms and the rows of match_templates
 // are cut into slabs, how mean_waveforms groups a slab's events by label, which rows and windows a workgroup of the filtered select
-// counts.  Addresses are plain integers here: the header includes the C++ standard library only, so tests/plan_check.cpp,
-// tests/snippet_plan_check.cpp, tests/tmatch_plan_check.cpp, tests/mean_plan_check.cpp and tests/zrank_plan_check.cpp sweep these
-// plans on the CPU.  reduce.hip puts the
+// counts, how the Gram slabs of the filtered Gram are gathered into z slabs.  Addresses are plain integers here: the header includes
+// the C++ standard library only, so tests/plan_check.cpp, tests/snippet_plan_check.cpp, tests/tmatch_plan_check.cpp,
+// tests/mean_plan_check.cpp, tests/zrank_plan_check.cpp and tests/zgram_plan_check.cpp sweep these plans on the CPU.  reduce.hip puts the
 // device side around them (ChunkFeed, feed_pieces, HaloFeed, TileFeed) and says there what every caller keeps to.
 #pragma once
 
@@ -266,6 +266,45 @@ MTS_PLAN_FN ZrankSeg zrank_segment(long r, long end, long row_begin, long window
     // (rows to the window's end, not its last row + 1: row_begin + (win + 1) * window_rows may pass 2^63 for a window of 2^62 rows)
     const long left = window_rows - (r - row_begin - win * window_rows);
     return {r, end - r < left ? end : r + left, win};
+}
+
+// ---- filtered Gram (filtered_gram_run, reduce.hip): the groups of mts_gram's grid, their Gram slabs, and the z slabs that a piece's
+// Gram slabs go through.  The groups of a grid are adjacent in the file (a window begins where the one before it ends), so a run of
+// Gram slabs is a run of rows.
+// group g of the grid (range, window_rows) in groups of GR rows: its file rows [lo, hi)
+inline void gram_group_rows(long range_begin, long range_end, long window_rows, long GR, long g, long *lo, long *hi)
+{
+    const long K = (window_rows + GR - 1) / GR;                   // groups per whole window
+    const long w = g / K, k = g % K, w0 = range_begin + w * window_rows;
+    const long w1 = window_rows < range_end - w0 ? w0 + window_rows : range_end;
+    *lo = w0 + k * GR;
+    *hi = GR < w1 - *lo ? *lo + GR : w1;
+}
+// the Gram slabs of a group's rows [lo, hi): SR rows each from lo, the last may be short; 2 entries (begin, end) per slab
+inline void gram_cut_slabs(long lo, long hi, long SR, std::vector<long> &slab_rows)
+{
+    for (long r = lo; r < hi; r += SR) { slab_rows.push_back(r); slab_rows.push_back(SR < hi - r ? r + SR : hi); }
+}
+// the rows of z that a bound of `bytes` holds (n_cols float32 a row), rounded down to whole Gram slabs and never less than one
+inline long zgram_cap_rows(uint64_t bytes, int n_cols, long SR)
+{
+    const uint64_t rows = bytes / (4 * (uint64_t)n_cols), most = (uint64_t)1 << 40;
+    return std::max(SR, (long)(std::min(rows, most) / (uint64_t)SR) * SR);
+}
+// Gram slabs [s0, s1) of the call make one z slab: the rows [slab_rows[2 s0], slab_rows[2 s1 - 1])
+struct ZgramSlab { long s0, s1; };
+// the Gram slabs [s_begin, s_end) (adjacent rows, in order) in z slabs of at most cap_rows rows and cap_slabs Gram slabs: each takes
+// whole Gram slabs while they fit, at least one (cap_rows >= SR holds any one of them)
+inline std::vector<ZgramSlab> zgram_slabs(const long *slab_rows, long s_begin, long s_end, long cap_rows, long cap_slabs)
+{
+    std::vector<ZgramSlab> out;
+    for (long s = s_begin; s < s_end;) {
+        long e = s + 1;
+        while (e < s_end && e - s < cap_slabs && slab_rows[2 * e + 1] - slab_rows[2 * s] <= cap_rows) e++;
+        out.push_back({s, e});
+        s = e;
+    }
+    return out;
 }
 
 // ---- tile family: the rows of every (chunk ∩ window) segment cut into tiles of tile_rows rows, in row order; a chunk's rows are

@@ -118,6 +118,7 @@ def lib():
             ('match_residual', [cl, cl, cl, cl, ci, dp, ci, ip, ci, ci, ci, ci, fp, fp, ci, cl, cl, lp, ip, fp], [vp, vp, vp, lp, ip], None),
             ('welch', [cl, cl, cl, ci, cl, dp, ci, ci, ci, ip], [vp, ip], None),
             ('gram', [cl, cl, cl, cl, cl, ci, ip], [vp, vp, ip], None),
+            ('filtered_gram', [cl, cl, ci, dp, ci, ip, ci, cl, cl, cl, cl, cl], [dp, dp, ip], [vp, vp, ip]),
             ('rank_hist', [cl, cl, cl, ci, ip, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip], [vp, vp, vp, lp, ip]),
             ('filtered_rank_hist', [cl, cl, ci, dp, ci, ip, ci, cl, cl, cl, cl, cl, ci, dp, up, ip], [C.POINTER(C.c_uint), up, up, lp, ip],
              [vp, vp, vp, lp, ip])):
@@ -141,7 +142,8 @@ EXPORTS = ['mts_version', 'mts_device_count', 'mts_strerror', 'mts_last_error', 
            'mts_waveform_features', 'mts_dev_waveform_features', 'mts_localize', 'mts_dev_localize', 'mts_correlate', 'mts_dev_correlate',
            'mts_match_templates', 'mts_dev_match_templates',
            'mts_residual', 'mts_dev_residual', 'mts_match_residual', 'mts_dev_match_residual',
-           'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist', 'mts_filtered_rank_hist', 'mts_dev_filtered_rank_hist']
+           'mts_gram', 'mts_dev_gram', 'mts_rank_hist', 'mts_dev_rank_hist', 'mts_filtered_rank_hist', 'mts_dev_filtered_rank_hist',
+           'mts_filtered_gram', 'mts_dev_filtered_gram']
 
 
 def _check(rc, what):
@@ -1236,6 +1238,40 @@ def dev_gram(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, range_beg
     mid, outs = _gram_args(dtype, range_begin, range_end, window_rows, group_begin, group_end, cols)
     out, ptrs, at = _dev_results(out, cbuf.device, [8 * int(np.prod(shape)) for shape, _ in outs])
     _check(lib().mts_dev_gram(*head, *mid, *ptrs, _ip(status)), 'mts_dev_gram')
+    g, s = _dev_fetch(out, at, [np.empty(*o) for o in outs]) if download else (None, None)
+    return _status(status, n), g, s, out
+
+
+# -- the same Gram matrices over the filtered signal z of detect
+def _fgram_args(valid_begin, valid_end, taps, cols, reference, range_begin, range_end, window_rows, group_begin, group_end):
+    """-> (the op's own arguments of mts_filtered_gram, the shapes and dtypes of the Gram entries and the sums: float64, z is float32)."""
+    taps = np.ascontiguousarray(np.asarray(taps, dtype=np.float64).ravel())
+    grid, outs = _gram_args(np.float32, range_begin, range_end, window_rows, group_begin, group_end, cols)
+    mid = (int(valid_begin), int(valid_end), int(taps.size), _dp(taps)) + grid[5:7] + (int(reference),) + grid[:5]
+    return mid, outs
+
+
+def filtered_gram(cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference,
+                  range_begin, range_end, window_rows, group_begin, group_end, device=0):
+    """mts_filtered_gram: the Gram entries and column sums of groups [group_begin, group_end) of the grid (range, window_rows) over z,
+    the filtered rows of mts_detect (taps, cols, reference 0 / 1, float32 items), from the adjacent chunks `keys`, which cover the
+    groups' filter support.  The grid and the summation tree are gram's for a float32 recording.  cache_id 0: no cache, every chunk
+    comes with its bytes; else chunks with lens[i] == 0 must be resident (HipError E_MISS).  Returns (status list, gram (n_groups,
+    n_cols, n_cols) float64, sum (n_groups, n_cols) float64), to be discarded when a status is not CHUNK_OK."""
+    head, n, status = _host_chunks(device, cache_id, keys, row0, cdata, offs, lens, n_rows, n_channels, dtype, flags)
+    mid, outs = _fgram_args(valid_begin, valid_end, taps, cols, reference, range_begin, range_end, window_rows, group_begin, group_end)
+    g, s = (np.empty(*o) for o in outs)
+    _check(lib().mts_filtered_gram(*head, *mid, _dp(g), _dp(s), _ip(status)), 'mts_filtered_gram')
+    return _status(status, n), g, s
+
+
+def dev_filtered_gram(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags, valid_begin, valid_end, taps, cols, reference, range_begin,
+                      range_end, window_rows, group_begin, group_end, out=None, download=True):
+    """mts_dev_filtered_gram on a DevBuffer of compressed chunks (offsets into it).  `out`, download and the result as dev_gram."""
+    head, n, status = _dev_chunks(cbuf, offs, lens, row0, n_rows, n_channels, dtype, flags)
+    mid, outs = _fgram_args(valid_begin, valid_end, taps, cols, reference, range_begin, range_end, window_rows, group_begin, group_end)
+    out, ptrs, at = _dev_results(out, cbuf.device, [8 * int(np.prod(shape)) for shape, _ in outs])
+    _check(lib().mts_dev_filtered_gram(*head, *mid, *ptrs, _ip(status)), 'mts_dev_filtered_gram')
     g, s = _dev_fetch(out, at, [np.empty(*o) for o in outs]) if download else (None, None)
     return _status(status, n), g, s, out
 
