@@ -168,7 +168,12 @@ int mts_cache_read_slices(long cache_id, int n_chunks, const long *chunk_keys, c
  * (about n_leading / n_channels of them plus a margin).  MTS_E_MISS: the bytes given do not reach the prefix, or a resident entry
  * holds fewer channels than asked for -- call again with more bytes.  Column ranges of the requests must end at or before
  * n_leading.  n_leading == n_channels is mts_cache_read_slices.  (The reference decodes whole chunks and drops columns on the
- * host, mtscomp.py:835-842.) */
+ * host, mtscomp.py:835-842.)
+ * How many bytes are enough: those up to and including the byte that holds the last bit of the deflate block that completes the
+ * prefix, no slack behind it (tests/test_gpu_prefix_reads.py, PREFIX_SLACK_BYTES = 0) -- also when that block is the chunk's last
+ * one: the check value behind it is never looked at, so a chunk cut inside its 4-byte trailer is as good as a whole one.  Any
+ * shorter prefix of an intact chunk, and a stream the block-parallel decoder cannot follow up to there (fixed or stored blocks the
+ * scan does not announce, beyond a short one), is MTS_E_MISS, never MTS_CHUNK_CORRUPT / MTS_CHUNK_BADSIZE and never wrong bytes. */
 int mts_cache_read_slices_leading(long cache_id, int n_chunks, const long *chunk_keys, const unsigned char *cdata,
                                   const long *c_offsets, const long *c_lengths, const long *n_rows, int n_channels,
                                   int itemsize, int flags, int n_leading, int n_requests, const long *requests,

@@ -1416,6 +1416,7 @@ __global__ __launch_bounds__(64) void k_inf_chain(const u8 *__restrict__ cdata, 
     u32 ntok = 0, ntrue = 0;
     u64 nout = 0;
     bool last = false, need_seq = cand_overflow, enough = false;      // enough: a partial decode has the bytes it wants
+    const u64 want = min(ch.n_need, ch.n_expect);                     // (a chunk without rows has n_need 1 and wants nothing)
     LaneLds L;
     L.bind(tabs, 1, 0);
     // The walk goes from block to block: where a block ends is where the next one must have been announced.  Position and result
@@ -1464,8 +1465,8 @@ __global__ __launch_bounds__(64) void k_inf_chain(const u8 *__restrict__ cdata, 
                 pos = (u64)e.x | ((u64)e.y << 32);
                 cur = i + 1;
                 last = (e.w >> 31) != 0;
+                if (ch.n_need && nout >= want) { enough = true; break; }      // (the final block included: a partial decode never looks at the check value)
                 if (last) break;
-                if (ch.n_need && nout >= ch.n_need) { enough = true; break; }
                 i = c_succ[i];
             }
         }
@@ -1532,7 +1533,7 @@ __global__ __launch_bounds__(64) void k_inf_chain(const u8 *__restrict__ cdata, 
         ntrue++;
         ntok += b_ntok; nout += b_nout;
         pos = b_end;
-        if (ch.n_need && nout >= ch.n_need) enough = true;
+        if (ch.n_need && nout >= want) enough = true;
     }
     if (enough) {
         // whole blocks up to the one that reaches the wanted prefix (the stream buffer has room for the whole chunk)
@@ -1544,8 +1545,10 @@ __global__ __launch_bounds__(64) void k_inf_chain(const u8 *__restrict__ cdata, 
         ntrue = 0;
     } else if (!need_seq) {
         const u64 tb = (pos + 7) & ~7ull;
-        if (tb + 32 > br.end) r.status = MTS_CHUNK_CORRUPT;                   // no room for the check value
-        else {
+        if (tb + 32 > br.end) {                                               // no room for the check value
+            r.status = ch.n_need ? MTS_CHUNK_NEEDMORE : MTS_CHUNK_CORRUPT;    // (a partial decode that ended short of its prefix: the caller comes back with the whole chunk)
+            if (ch.n_need) ntrue = 0;
+        } else {
             const u8 *t = (const u8 *)br.w + (tb >> 3);
             r.adler_stored = ((u32)t[0] << 24) | ((u32)t[1] << 16) | ((u32)t[2] << 8) | t[3];
             r.end_bit = tb + 32;

@@ -1,14 +1,17 @@
 """A reader of zlib streams (RFC 1950 / 1951), pure Python: which blocks a stream has and what their headers hold.
 
-It walks the blocks of a stream that stdlib ``zlib.compress`` wrote -- never the device's bytes -- and decodes no match beyond
-skipping its bits.  Its purpose is to state which edges of the block encoder and of the header decoder a test case reaches
-(tests/block_cases.py, tests/test_block_cases.py) and to name the block a differing byte lies in (tests/test_gpu_block_edges.py).
+It walks the blocks of a zlib stream -- stdlib ``zlib.compress``'s, a hand-built one, or the device's bytes once they have been
+copied to the host (any bytes-like object) -- and decodes no match beyond its length.  Its purpose is to state which edges of
+the block encoder and of the header decoder a test case reaches (tests/block_cases.py, tests/test_block_cases.py), to name the
+block a differing byte lies in (tests/test_gpu_block_edges.py), and to say where the block that completes a wanted prefix of the
+output ends (tests/prefix_cases.py).
 
 ``blocks(z)`` returns one dict per block:
 
     btype, last     0 stored / 1 fixed / 2 dynamic, BFINAL
     bit_start       bit offset of the block's first (BFINAL) bit in the stream, the two zlib header bytes included
     bit_end         bit offset behind the block (behind the end-of-block code; a stored block's last byte)
+    nout            bytes the block produces: 1 per literal, the copy length per match, LEN for a stored block
     stored:         pad (padding bits between the 3 block-type bits and LEN), len (LEN)
     dynamic:        hlit, hdist, hclen (the COUNTS: 257 .. 286, 1 .. 30, 4 .. 19),
                     bl_lens (the 19 bit-length code lengths, by symbol), bl_max,
@@ -21,6 +24,7 @@ skipping its bits.  Its purpose is to state which edges of the block encoder and
 
 BL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
 LEN_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+LEN_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
 DIST_EXTRA = (0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13)
 DIST_BASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
              8193, 12289, 16385, 24577)
@@ -95,15 +99,39 @@ def _fixed():
 
 
 def _body(bits, ldec, ddec):
-    ntok = 0
+    """(tokens, bytes produced) of a block body; the end-of-block code is consumed.  One 8-byte window per token holds all of it
+    (15 + 5 + 15 + 13 bits at most), so the loop does without _Bits' calls: the catalogues walk megabytes of streams."""
+    (lmx, ltab), (dmx, dtab) = ldec, ddec
+    if not lmx:
+        raise ValueError('no such code')
+    d, pos, n, frm = bits.d, bits.pos, bits.n, int.from_bytes
+    lmask, dmask = (1 << lmx) - 1, (1 << dmx) - 1
+    ntok = nout = 0
     while True:
-        s = _sym(bits, ldec)
-        if s == 256:
-            return ntok
-        ntok += 1
+        w = frm(d[pos >> 3:(pos >> 3) + 8], 'little') >> (pos & 7)
+        e = ltab[w & lmask]
+        if e is None:
+            raise ValueError('no such code')
+        s, used = e
         if s > 256:
-            bits.take(LEN_EXTRA[s - 257])
-            bits.take(DIST_EXTRA[_sym(bits, ddec)])
+            x = LEN_EXTRA[s - 257]
+            nout += LEN_BASE[s - 257] + ((w >> used) & ((1 << x) - 1))
+            used += x
+            e = dtab[(w >> used) & dmask] if dmx else None
+            if e is None:
+                raise ValueError('no such code')
+            bits.pos = pos + used + e[1]
+            bits.take(DIST_EXTRA[e[0]])                        # (through take(): tests count the 13-bit ones)
+            pos, used = bits.pos, 0
+        pos += used
+        if pos > n:
+            raise ValueError('stream ends inside a block')
+        if s == 256:
+            bits.pos = pos
+            return ntok, nout
+        ntok += 1
+        if s < 256:
+            nout += 1
 
 
 def blocks(z):
@@ -126,9 +154,10 @@ def blocks(z):
             if bits.pos + 8 * b['len'] > bits.n:
                 raise ValueError('stream ends inside a block')
             bits.pos += 8 * b['len']
+            b['nout'] = b['len']
         elif b['btype'] == 1:
             t0 = bits.pos
-            b['ntok'] = _body(bits, *_fixed())
+            b['ntok'], b['nout'] = _body(bits, *_fixed())
             b['body_bits'] = bits.pos - t0
         elif b['btype'] == 2:
             h0 = bits.pos
@@ -156,7 +185,7 @@ def blocks(z):
             ll, dl = lens[:b['hlit']], lens[b['hlit']:]
             b['l_max_len'], b['d_max_len'] = max(ll), max(dl)
             t0 = bits.pos
-            b['ntok'] = _body(bits, _decoder(ll), _decoder(dl))
+            b['ntok'], b['nout'] = _body(bits, _decoder(ll), _decoder(dl))
             b['body_bits'] = bits.pos - t0
         else:
             raise ValueError('reserved block type')

@@ -202,3 +202,27 @@ def test_block_report_has_the_overflow_fields():
     header.  (Where they are not zero, test_stream_reader_agrees_with_the_oracle holds them to zlib's own bytes.)"""
     _, _, _, ob = O.deflate(b'abc', 6, report=True)
     assert [(o['btype'], o['ovf_l'], o['ovf_d'], o['ovf_bl'], o['hdr_bits']) for o in ob] == [(1, 0, 0, 0, 0)]
+
+
+# ------------------------------------------------------------------------------------------------
+# bytes produced per block (tests/prefix_cases.py places the end of a wanted prefix with them)
+# ------------------------------------------------------------------------------------------------
+def _nout_streams():
+    data = CASES[sorted(CASES)[0]]
+    yield 'stored', zlib.compress(data, 0)
+    c = zlib.compressobj(6, zlib.DEFLATED, 15, 8, zlib.Z_FIXED)
+    yield 'fixed', c.compress(data) + c.flush()
+    yield 'empty', zlib.compress(b'', 6)
+
+
+def test_blocks_report_the_bytes_they_produce():
+    """sum(nout) is the length of what zlib inflates: stored-only, Z_FIXED and empty streams, and every (case, level) of the module."""
+    from tests.deflate_shape import blocks
+    for what, z in _nout_streams():
+        sh = blocks(z)
+        assert sum(b['nout'] for b in sh) == len(zlib.decompress(z)), what
+        assert all(b['nout'] == b['len'] for b in sh if b['btype'] == 0)
+        assert {b['btype'] for b in sh} == {{'stored': 0}.get(what, 1)}, what
+    for name, level in PAIRS:
+        assert sum(b['nout'] for b in B.shape(name, level)) == len(CASES[name]), (name, level)
+        assert all(b['nout'] >= b['ntok'] for b in B.shape(name, level) if b['btype'])
